@@ -2,6 +2,8 @@
 """bench.py -- headline benchmark: decompressed MB/s of the MI355X bzip2 block decoder.
 
   python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                           (also the secondary figures and checks, see below)
+  python bench.py ... --dump-outputs DIR               (what the last timed step computed, as .npy files)
 
 Workload (BASELINE.json metric, configs[3] at N = 1, 2, 4, 8): ONE single-stream `bzip2 -9` file of a seeded
 Silesia-style corpus repeated to 2 GiB (tools/silesia_like.py + tools/bz2build.py; the real Silesia corpus is not
@@ -18,6 +20,16 @@ Multi-GPU (default, "scaling": "strong"): the file's block queue is partitioned 
 compressed size (indexed_bzip2_amd.distributed.shard_blocks); rank r copies and decodes ONLY its range, and the decoded
 extents are gathered into rank 0's HBM over RCCL/xGMI (size all_gather + grouped isend/irecv, RCCL has no gatherv).
 `value` = 2 GiB x steps / max-over-ranks time.  `--weak` keeps the round-1 mode (every rank its own whole copy).
+
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and the roofline derived from
+the timed region.  `--full` adds what takes runs or checks of its own: the GPU magic scan timed, the file's stream CRC
+checked against the device-computed block CRCs, the gathered extents' checksums on rank 0, the resident-input and
+decoded-bytes-in-host-memory figures, every kernel timed alone, and the CPU baseline.
+
+`--dump-outputs DIR` (rank 0, right after the timed region): the BlockResult records of the last timed step, one float64
+file per field (`block_<field>.npy`), and `decoded_sample.npy`, float32: 2 048 windows of 4 KiB at seeded offsets of the
+decoded bytes rank 0 holds (its own extent, then the extents gathered from the other ranks), or all of them if there
+are no more than 8 MiB.
 
 Prints ONE JSON line (rank 0).
 """
@@ -40,9 +52,27 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def default_cache_dir():
+    """Where the workload is cached unless --cache-dir or BZ2_BENCH_CACHE name a folder: the user's cache directory, or a
+    folder of this user in the temporary directory if that cannot be written.  Never the source tree: the user who runs
+    the benchmark may not be allowed to write there."""
+    import tempfile
+    user_cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+    for d in (os.path.join(user_cache, "indexed_bzip2_amd_bench"),
+              os.path.join(tempfile.gettempdir(), f"indexed_bzip2_amd_bench-{os.getuid()}")):
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    raise SystemExit("bench.py: no writable folder for the workload cache, name one with --cache-dir")
+
+
 def build_workload(total_bytes, base_bytes, cache_dir, rank, world, barrier, kind="silesia"):
     """Rank 0 builds (or finds cached) the .bz2 file; everyone loads it.  kind "urandom" = config 3 of BASELINE.json
-    (seeded random bytes: incompressible), for tools/bench_configs.py."""
+    (seeded random bytes: incompressible), for tools/bench_configs.py.  Both files appear under their final names only
+    when complete (written under names of this process, then renamed), so runs that share the cache never read a part."""
     key = f"silesia_like-{base_bytes}-x{total_bytes}-l9-v3" if kind == "silesia" else f"urandom-{base_bytes}-x{total_bytes}-l9-v3"
     path = os.path.join(cache_dir, key + ".bz2")
     meta_path = path + ".json"
@@ -64,12 +94,14 @@ def build_workload(total_bytes, base_bytes, cache_dir, rank, world, barrier, kin
         enc, nblocks, offsets = bz2build.stitch(streams, repeat, 9, m.find_magic)
         t3 = time.time()
         sha = hashlib.sha256(base.tobytes()).hexdigest()
-        with open(path + ".tmp", "wb") as f:
+        tmp = f".tmp{os.getpid()}"
+        with open(path + tmp, "wb") as f:
             f.write(enc)
-        os.replace(path + ".tmp", path)
-        with open(meta_path, "w") as f:
+        os.replace(path + tmp, path)
+        with open(meta_path + tmp, "w") as f:
             json.dump({"decoded_bytes": int(len(base)) * repeat, "base_sha256": sha, "repeat": repeat,
                        "blocks": nblocks, "offsets": offsets}, f)
+        os.replace(meta_path + tmp, meta_path)
         log(f"[bench] workload built: generate {t1 - t0:.1f}s compress {t2 - t1:.1f}s stitch {t3 - t2:.1f}s "
             f"-> {len(enc) / 1e6:.1f} MB compressed, {nblocks} blocks")
     barrier()
@@ -118,6 +150,45 @@ def cpu_baseline(path, meta, budget_seconds):
             "sample": f"first {len(offs)} blocks ({n / 1e6:.0f} MB decoded) through oracle/bz2_oracle.c ({dt:.1f} s)"}
 
 
+DUMP_WINDOW = 4096          # --dump-outputs: bytes per sampled window of the decoded output
+DUMP_WINDOWS = 2048         # 8 MiB of decoded bytes = 32 MB as float32
+DUMP_SEED = 0xD1FF
+
+
+def dump_positions(total):
+    """Positions in the decoded bytes that --dump-outputs samples: DUMP_WINDOWS distinct windows of DUMP_WINDOW bytes at
+    seeded offsets, ascending; every byte if there are no more than that."""
+    import numpy as np
+    if total <= DUMP_WINDOW * DUMP_WINDOWS:
+        return np.arange(total, dtype=np.int64)
+    rng = np.random.default_rng(DUMP_SEED)
+    starts = np.sort(rng.choice(total // DUMP_WINDOW, DUMP_WINDOWS, replace=False)) * DUMP_WINDOW
+    return (starts[:, None] + np.arange(DUMP_WINDOW, dtype=np.int64)).ravel()
+
+
+def dump_outputs(out_dir, records, n_blocks, extents):
+    """Write what the timed path computed in its last step to out_dir (see the module docstring).  records: the step's
+    BlockResult ctypes array, of which the first n_blocks are its blocks; extents: 1-D uint8 tensors of the decoded
+    bytes, in order."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    rec = np.ctypeslib.as_array(records)[:n_blocks]
+    for name in rec.dtype.names:
+        np.save(os.path.join(out_dir, f"block_{name}.npy"), rec[name].astype(np.float64))
+    idx = dump_positions(sum(int(e.numel()) for e in extents))
+    sample = np.empty(len(idx), dtype=np.float32)
+    base = 0
+    for e in extents:
+        n = int(e.numel())
+        mask = (idx >= base) & (idx < base + n)          # every index is < total: each lands in exactly one extent
+        if mask.any():
+            sel = torch.from_numpy(idx[mask] - base).to(e.device)
+            sample[mask] = e[sel].float().cpu().numpy()
+        base += n
+    np.save(os.path.join(out_dir, "decoded_sample.npy"), sample)
+
+
 class _DevicePtr:
     """Zero-copy view of a raw device pointer for torch.as_tensor (plumbing for the RCCL gather)."""
 
@@ -132,10 +203,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--total-bytes", type=int, default=2 * 1024**3)
     ap.add_argument("--base-bytes", type=int, default=214_748_364)   # x10 = 2 GiB - 8 bytes
-    ap.add_argument("--cache-dir", default=os.environ.get("BZ2_BENCH_CACHE", "/tmp/indexed_bzip2_amd_bench"))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cache-dir", default=os.environ.get("BZ2_BENCH_CACHE"),
+                    help="folder of the cached workload (default: see default_cache_dir)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary figures and checks (magic scan time, stream CRC, gathered checksums, "
+                         "resident input, decoded bytes to host memory, kernels alone, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's block records and a seeded sample of its decoded bytes as .npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-gather", action="store_true")
-    ap.add_argument("--no-host-output", action="store_true", help="skip the decoded-bytes-in-host-memory figure")
+    ap.add_argument("--no-host-output", action="store_true",
+                    help="with --full: skip the decoded-bytes-in-host-memory figure")
     ap.add_argument("--workload", default="silesia", choices=["silesia", "urandom"],
                     help="silesia = the headline workload (config 4 of BASELINE.json); urandom = config 3 (2 GiB of seeded "
                          "random bytes at bzip2 -9: incompressible), used by tools/bench_configs.py")
@@ -151,6 +229,10 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 flow on ONE GPU: ranks share cuda:0 and extents travel via host memory")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.cache_dir:
+        args.cache_dir = default_cache_dir()
 
     world_env = int(os.environ.get("WORLD_SIZE", "1"))
     if args.contexts == 0:
@@ -210,15 +292,22 @@ def main():
     decs = [m.Decoder(device=device_index, max_batch_blocks=max(n_blocks, 1)) for _ in range(args.contexts)]
     dec = decs[0]
 
+    # The GPU magic scan here and the read-back of the decoded bytes below stay in every run although they are checks:
+    # the scan creates a stream of its own and the first read-back uses the null stream, and the HIP runtime assigns
+    # hardware queues to streams in creation order, so the contexts' streams created later depend on them.  Without these
+    # two steps the timed steps took 86.3-87.1 ms instead of 80.3-81.1 on one box with GPU_MAX_HW_QUEUES=4.
     # block offsets: the GPU magic scan over the resident range must find exactly the blocks the file was built from
     dec.set_input_host_async(host_ptr, my_bytes, keepalive=host_in)
-    dec.find_magic()
-    t_scan = time.perf_counter()
     gpu_offsets = dec.find_magic()
-    scan_ms = (time.perf_counter() - t_scan) * 1e3
     assert gpu_offsets == my_offsets, "GPU magic scan disagrees with the block offsets of the workload"
+    scan_ms = None
+    if args.full:
+        t_scan = time.perf_counter()
+        dec.find_magic()
+        scan_ms = (time.perf_counter() - t_scan) * 1e3
 
-    # ---- correctness gate (also the first warm-up): statuses, sizes, and the file's stream CRC over ALL ranks ----
+    # ---- first warm-up: statuses and sizes (the extent sizes of all ranks are those the gather of every step uses);
+    # with --full also the correctness gate: the file's stream CRC over ALL ranks ----
     results, my_decoded = dec.decode_batch(my_offsets)
     bad = [r for r in results if r["status"] != 0]
     assert not bad, f"{len(bad)} blocks failed: {bad[:2]}"
@@ -231,19 +320,20 @@ def main():
     else:
         parts = [(chain, n_blocks, my_decoded, None)]
     extent_sizes = [p[2] for p in parts]
-    if strong:
-        stream_crc = combine_crc_chains((p[0], p[1]) for p in parts)
-        assert sum(p[2] for p in parts) == file_decoded, (parts, file_decoded)
-    else:
-        stream_crc = chain
-        assert my_decoded == file_decoded
-    eos_bit = offsets[-1] + (results[-1]["encoded_size_bits"] if hi == n_file_blocks else 0)
-    if rank == world - 1 or not strong:
-        stored = 0
-        for i in range(32):
-            b = eos_bit + 48 + i
-            stored = (stored << 1) | ((enc[b >> 3] >> (7 - (b & 7))) & 1)
-        assert stream_crc == stored, f"checksum of block checksums {stream_crc:08x} != stream CRC in file {stored:08x}"
+    if args.full:
+        if strong:
+            stream_crc = combine_crc_chains((p[0], p[1]) for p in parts)
+            assert sum(p[2] for p in parts) == file_decoded, (parts, file_decoded)
+        else:
+            stream_crc = chain
+            assert my_decoded == file_decoded
+        eos_bit = offsets[-1] + (results[-1]["encoded_size_bits"] if hi == n_file_blocks else 0)
+        if rank == world - 1 or not strong:
+            stored = 0
+            for i in range(32):
+                b = eos_bit + 48 + i
+                stored = (stored << 1) | ((enc[b >> 3] >> (7 - (b & 7))) & 1)
+            assert stream_crc == stored, f"checksum of block checksums {stream_crc:08x} != stream CRC in file {stored:08x}"
     # (the per-block CRCs cover every decoded byte; tests/ compare full payloads against the oracle at smaller sizes)
     view = torch.as_tensor(_DevicePtr(dec.output_device_ptr(), my_decoded), device="cuda")
     assert bytes(view[:4096].cpu().numpy()) == dec.copy_output(0, 4096)
@@ -275,7 +365,7 @@ def main():
     # ---- content check of the gather, once, outside the timed region: every block of every peer, as it lies in rank 0's
     # gather buffer, has the checksum its sender computed (= the one stored in the file: status OK above) ----
     gathered_blocks_checked = 0
-    if world > 1 and strong and not args.no_gather:
+    if args.full and world > 1 and strong and not args.no_gather:
         gather(my_decoded, dec)
         pending = gather_done.pop(id(dec), None)
         if pending is not None:
@@ -373,12 +463,19 @@ def main():
 
     dt, gpu_ms = timed(args.steps, resident=args.resident)
     # per-kernel HIP-event durations of the LAST timed step (its events are still there)
-    t = decs[(args.steps - 1) % len(decs)].timings()
+    last = (args.steps - 1) % len(decs)
+    t = decs[last].timings()
     ksum = dict(t["kernels"])
     kernel_ms = t["ms_kernel_sum"]
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the contexts: the last step's output buffer and records are still as it left them
+        extents = [torch.as_tensor(_DevicePtr(decs[last].output_device_ptr(), my_decoded), device="cuda")]
+        if gather_buf is not None:
+            extents.append(gather_buf[:sum(extent_sizes[1:])])
+        dump_outputs(args.dump_outputs, res_cs[last], n_blocks, extents)
     # secondary figure: the same steps with the compressed bytes already resident in HBM (round-1's headline)
     resident_dt = None
-    if not args.resident:
+    if args.full and not args.resident:
         for d in decs:
             d.set_input_host_async(host_ptr, my_bytes, keepalive=host_in)
             d.decode_batch(my_offsets[:1])       # orders the copy; the input stays
@@ -388,7 +485,7 @@ def main():
     # second figure of SURVEY 8(d): "decoded bytes in host memory" -- every step's output copied to page-locked host memory
     # (mi355x_bz2_copy_output_begin / _end: on a copy stream, beside the context's next step); single GPU only
     host_dt = host_steps = None
-    if world == 1 and not args.resident and not args.no_host_output:
+    if args.full and world == 1 and not args.resident and not args.no_host_output:
         host_out.extend(torch.empty(my_decoded, dtype=torch.uint8).pin_memory() for _ in decs)
         run_steps(len(decs), to_host=True)
         host_steps = max(2, min(10, args.steps))
@@ -401,7 +498,7 @@ def main():
     # every kernel launched ONCE over the whole batch, nothing beside it (no block groups, one context, input resident):
     # the per-kernel durations that mean something on their own
     alone = None
-    if world == 1:
+    if args.full and world == 1:
         os.environ["MI355X_BZ2_NO_SPLIT"] = "1"
         try:
             d0 = decs[0]
@@ -451,8 +548,9 @@ def main():
                        "step": ("compressed bytes resident in HBM -> decoded bytes in HBM" if args.resident else
                                 "compressed bytes in page-locked host memory -> H2D (on the context's input stream, beside the "
                                 "kernels of the step in front of it) -> decoded bytes in HBM"),
-                       "block_offsets": "known before the timed region (index / finder thread); the same offsets from the "
-                                        "GPU magic scan k_find_magic take %.2f ms (not part of a step)" % scan_ms},
+                       "block_offsets": "known before the timed region (index / finder thread)" + (
+                           "" if scan_ms is None else "; the same offsets from the GPU magic scan k_find_magic take "
+                                                      "%.2f ms (not part of a step)" % scan_ms)},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                          "algorithmic_bytes_per_step": int(alg_bytes), "io_floor_bytes_per_step": int(io_floor),
@@ -468,9 +566,11 @@ def main():
                                        "can exceed ms_per_step)",
                          "pipeline_ms_per_step": round(pipeline_ms, 3),
                          "kernel_ms_sum_per_step": round(kernel_ms, 3), "dominant_kernel": dom,
-                         "kernels_ms": {k: round(v, 3) for k, v in (alone["kernels"] if alone else ksum).items() if v > 0},
                          "kernels_ms_in_the_crowd": {k: round(v, 3) for k, v in ksum.items() if v > 0}},
         }
+        if args.full:
+            out["roofline"]["kernels_ms"] = {k: round(v, 3) for k, v in (alone["kernels"] if alone else ksum).items()
+                                             if v > 0}
         if alone:
             out["roofline"]["kernel_ms_sum_alone"] = round(alone["ms_kernel_sum"], 3)
             out["roofline"]["dominant_kernel"] = max(alone["kernels"], key=alone["kernels"].get)
@@ -488,7 +588,7 @@ def main():
         if resident_dt is not None:
             out["config"]["resident_input_MBps"] = round(job_decoded * resident_steps / resident_dt / 1e6, 1)
             out["config"]["resident_input_ms_per_step"] = round(resident_dt / resident_steps * 1e3, 3)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(path, meta, 40.0)
         print(json.dumps(out), flush=True)
     barrier()

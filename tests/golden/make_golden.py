@@ -5,6 +5,7 @@ from tests/datagen.py + CPython bz2, outputs are the reference's) is committed, 
 For every case: sha256 of the compressed input, the block map of ParallelBZ2Reader::blockOffsets(), the serial
 BZ2Reader map, and per data block (offset, encodedSize, headerCRC, calculatedCRC, decodedSize, fnv64(data)).
 Also records the reference's verdict (exception type) for a set of corrupted / truncated inputs.
+`make_golden.py live` writes tests/golden/live_reference.bz2 and .json instead (see live()).
 """
 import hashlib
 import json
@@ -20,6 +21,7 @@ from oracle import oracle as O
 
 OUT = os.path.join(ROOT, "tests", "golden", "reference_vectors.json")
 FIX = os.path.join(ROOT, "tests", "golden", "fixtures")
+LIVE = os.path.join(ROOT, "tests", "golden", "live_reference")   # .bz2 + .json, `make_golden.py live`
 
 
 def ref_case(path):
@@ -97,5 +99,20 @@ def main():
     print("wrote", OUT, os.path.getsize(OUT), "bytes")
 
 
+def live():
+    """The input of tests/test_oracle.py::test_live_reference_agrees (stored: another libbz2 may compress it differently)
+    and the reference's answers for it: ParallelBZ2Reader's block map with 3 threads, and the block records."""
+    assert O.ref_available(), "build oracle/_ref first: make -C oracle ref"
+    raw = datagen.runs(700_000, 77) + datagen.random_bytes(100_000, 78)
+    with open(LIVE + ".bz2", "wb") as f:
+        f.write(datagen.compress(raw, 4))
+    m = [[int(a), int(b)] for a, b in (l.split() for l in O.ref_run("map", LIVE + ".bz2", 3).strip().splitlines())]
+    blocks = [[int(f[0]), int(f[1]), int(f[2], 16), int(f[3], 16), int(f[4])]
+              for f in (l.split() for l in O.ref_run("blocks", LIVE + ".bz2").strip().splitlines())]
+    with open(LIVE + ".json", "w") as f:
+        json.dump({"raw_sha256": hashlib.sha256(raw).hexdigest(), "map": m, "blocks": blocks}, f, indent=1)
+    print("wrote", LIVE + ".bz2", LIVE + ".json")
+
+
 if __name__ == "__main__":
-    main()
+    live() if sys.argv[1:] == ["live"] else main()

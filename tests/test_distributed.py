@@ -106,18 +106,29 @@ def test_bench_sharded_rehearsal_on_one_gpu(world, tmp_path):
     """bench.py's N > 1 flow on ONE GPU (gloo, ranks share cuda:0, extents travel through host memory): the block queue
     of one file partitioned over the ranks, every rank copies and decodes only its byte range, the extents are gathered
     to rank 0, and the file's stream CRC is checked against the combination of all ranks' block-CRC chains (bench.py
-    asserts it on the last rank).  A 64 MB workload keeps it short."""
+    --full asserts it on the last rank).  A 64 MB workload keeps it short.  The bytes bench.py --dump-outputs samples
+    from rank 0's own and gathered extents are those of the workload."""
     import json
     import subprocess
     import sys
+    import numpy as np
+    import bench
+    import silesia_like          # (on sys.path once bench is imported)
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", BZ2_BENCH_CACHE=str(tmp_path))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline",
-           "--total-bytes", str(64_000_000), "--base-bytes", str(16_000_000)]
+           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--no-cpu-baseline",
+           "--total-bytes", str(64_000_000), "--base-bytes", str(16_000_000), "--dump-outputs", str(tmp_path / "dump")]
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env)
     assert run.returncode == 0, run.stderr[-3000:]
     line = json.loads([l for l in run.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == world and line["scaling"] == "strong" and line["value"] > 0
     assert line["config"]["input_resident_in_hbm"] is False
     assert line["config"]["blocks_rank0"] < 80 // world + 8      # rank 0 holds its share of the ~72 blocks only
+    assert line["config"]["gathered_blocks_verified_on_rank0"] > 0
+    sizes = np.load(tmp_path / "dump" / "block_decoded_size.npy")
+    assert len(sizes) == line["config"]["blocks_rank0"] and sizes.sum() == line["config"]["decoded_bytes_rank0"]
+    assert not np.load(tmp_path / "dump" / "block_status.npy").any()
+    decoded = np.tile(silesia_like.generate(16_000_000), 4)       # bench.py's workload: the corpus repeated to 64 MB
+    assert np.array_equal(np.load(tmp_path / "dump" / "decoded_sample.npy"),
+                          decoded[bench.dump_positions(len(decoded))].astype(np.float32))

@@ -2,6 +2,7 @@
 AddressSanitizer + UBSan and under ThreadSanitizer: CPU builds only (GPU sanitizers are not available on the pool).  The
 harnesses in tests/native/ drive the classes with seeded random operations and exact-size buffers; host_known_answers
 replays the answers recorded from the reference's own classes (tests/golden/host_vectors.txt)."""
+import ctypes
 import os
 import shutil
 import subprocess
@@ -27,6 +28,17 @@ CASES = [
 ]
 
 
+ADDR_NO_RANDOMIZE = 0x0040000
+
+
+def _without_aslr():
+    """ThreadSanitizer expects the program within fixed address ranges; kernels that randomise mappings with more bits
+    place it outside them ("FATAL: ThreadSanitizer: unexpected memory mapping").  Its harnesses therefore run with address
+    randomisation off for that one process (personality(2), what `setarch -R` does)."""
+    libc = ctypes.CDLL(None, use_errno=True)
+    libc.personality(libc.personality(0xFFFFFFFF) | ADDR_NO_RANDOMIZE)
+
+
 @pytest.mark.skipif(shutil.which("g++") is None, reason="needs g++")
 @pytest.mark.parametrize("harness, sanitizer, args, expect", CASES)
 def test_host_code_under_sanitizers(tmp_path, harness, sanitizer, args, expect):
@@ -35,6 +47,7 @@ def test_host_code_under_sanitizers(tmp_path, harness, sanitizer, args, expect):
                             "-pthread", "-o", str(exe), os.path.join(NATIVE, harness), FINDER],
                            capture_output=True, text=True, timeout=600)
     assert build.returncode == 0, build.stderr[-2000:]
-    run = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=600)
+    run = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=600,
+                         preexec_fn=_without_aslr if sanitizer == "thread" else None)
     assert run.returncode == 0, (run.stdout[-500:], run.stderr[-3000:])
     assert expect in run.stdout

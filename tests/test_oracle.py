@@ -5,7 +5,8 @@
   - the RUNA/RUNB known-answer table (src/tests/indexed_bzip2/testRunAB.cpp:12-77),
   - the magic-scan known answers (src/tests/core/testBitStringFinder.cpp:119-146),
   - CPython's bz2 module (libbz2) as an independent third decoder,
-  - the live reference binary when it is present (oracle/_ref/ref_bz2).
+  - the live reference's answers for one more stream, stored, and the binary itself when it is present
+    (oracle/_ref/ref_bz2).
 """
 import bz2
 import hashlib
@@ -210,22 +211,27 @@ def test_stream_crc_matches_eos(oracle):
     assert h["is_eos"] == 1 and h["header_crc"] == s
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_bz2")),
-                    reason="compiled reference not present")
 def test_live_reference_agrees(oracle, tmp_path):
-    """When oracle/_ref/ref_bz2 exists (authoring container, GPU box snapshot) compare against it directly."""
+    """The reference's block map (3 threads) and block records for a stream of runs and random bytes, recorded from
+    oracle/_ref/ref_bz2 with its input (tests/golden/live_reference.*, `make_golden.py live`): the oracle gives the same.
+    Where oracle/_ref/ref_bz2 exists (authoring container), the live reference is asked again and must agree."""
     raw = datagen.runs(700_000, 77) + datagen.random_bytes(100_000, 78)
-    enc = datagen.compress(raw, 4)
-    p = tmp_path / "live.bz2"
-    p.write_bytes(enc)
-    ref_map = {int(a): int(b) for a, b in (l.split() for l in oracle.ref_run("map", p, 3).strip().splitlines())}
+    live = os.path.join(ROOT, "tests", "golden", "live_reference")
+    enc = open(live + ".bz2", "rb").read()
+    gold = json.load(open(live + ".json"))
+    assert hashlib.sha256(raw).hexdigest() == gold["raw_sha256"] and gold["blocks"]
+    ref_map = {a: b for a, b in gold["map"]}
     st, out, bmap, tg = oracle.decode_file(enc)
     assert st == 0 and out == raw and bmap == ref_map
-    for line in oracle.ref_run("blocks", p).strip().splitlines():
-        off, size, hcrc, ccrc, dsize, fnv = line.split()
-        d, payload = oracle.decode_block(enc, int(off))
-        assert (d["encoded_size_bits"], d["header_crc"], d["computed_crc"], d["decoded_size"]) == \
-               (int(size), int(hcrc, 16), int(ccrc, 16), int(dsize))
+    for off, size, hcrc, ccrc, dsize in gold["blocks"]:
+        d, payload = oracle.decode_block(enc, off)
+        assert (d["encoded_size_bits"], d["header_crc"], d["computed_crc"], d["decoded_size"]) == (size, hcrc, ccrc, dsize)
+    if os.path.exists(os.path.join(ROOT, "oracle", "_ref", "ref_bz2")):
+        p = tmp_path / "live.bz2"
+        p.write_bytes(enc)
+        assert {int(a): int(b) for a, b in (l.split() for l in oracle.ref_run("map", p, 3).strip().splitlines())} == ref_map
+        assert [[int(f[0]), int(f[1]), int(f[2], 16), int(f[3], 16), int(f[4])]
+                for f in (l.split() for l in oracle.ref_run("blocks", p).strip().splitlines())] == gold["blocks"]
 
 
 def _check_damaged(decode_block):

@@ -24,8 +24,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
+import bench  # noqa: E402  (plain Python at import: torch still comes first where a config needs the GPU)
+
 REF = os.path.join(ROOT, "oracle", "_ref", "ref_bz2")
-CACHE = os.environ.get("BZ2_BENCH_CACHE", "/tmp/indexed_bzip2_amd_bench")
+CACHE = os.environ.get("BZ2_BENCH_CACHE") or bench.default_cache_dir()   # bench.py's default
 CORES = os.cpu_count() or 1
 
 
@@ -44,7 +46,7 @@ def reference_bench(path, parallelization, max_bytes):
 
 
 def run_bench(extra, env=None):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"] + extra
     e = dict(os.environ)
     e.update(env or {})
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, env=e)
