@@ -27,15 +27,12 @@
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
+#include "bz2_plan.hpp"
 
 using namespace bz2gpu;
 
-constexpr uint32_t MAX_CHUNKS = 3;          /* groups of cheap blocks; one more stream than hardware queues (4 by
-                                               default) would serialize two groups */
-constexpr int MAX_GROUPS = MAX_CHUNKS + 1;   /* + the expensive group */
 /* register budgets (wavefronts per SIMD that a kernel's registers leave room for, see k_hscan) and groups per chunk of k_hsym:
  * the other values that round 3 built (2 / 5, 2 / 3, 128 / 512) made no difference for a step (profiles/r03_ab_registers.txt) */
-constexpr uint32_t BWT_SPLIT_BLOCKS = 640;   /* batches up to this size build their tables with several workgroups per block */
 constexpr uint32_t REGS_SCAN = 4, SYM_GROUPS = 256, REGS_MTF = 4;
 
 /** A host -> HBM copy of the input that runs in pieces on a thread and a stream of its own
@@ -152,7 +149,6 @@ struct mi355x_bz2_ctx
     uint32_t* hSlotOf{ nullptr };     /* pinned: original index -> slot */
     uint32_t* dSlotOf{ nullptr };
     uint64_t* dTotals{ nullptr };     /* k_offsets: {total decoded bytes, does not fit} */
-    uint32_t* dScanQueue{ nullptr };  /* [MAX_GROUPS]: block counters of k_hscan<1> launched with a capped grid */
     uint32_t* dBwtCounts{ nullptr };  /* [min( cap, BWT_SPLIT_BLOCKS )][BWT_COUNTS_PER_BLOCK]: byte counts per chunk, small batches */
     uint64_t* hTotals{ nullptr };     /* pinned */
     BlockMeta* hMeta{ nullptr };       /* pinned */
@@ -192,8 +188,8 @@ struct mi355x_bz2_ctx
     uint32_t launched[MAX_GROUPS]{};                            /* bit k: kernel k was launched for the group in this batch */
     /* a batch between mi355x_bz2_decode_batch_begin and _end */
     uint32_t pendingBlocks{ 0 };
-    int pendingGroups{ 0 }, pendingExpensive{ -1 };
-    uint32_t pendingGroupCount[MAX_GROUPS]{};
+    BatchPlan plan;                   /* of the last batch begun */
+    bool trace{ false };              /* MI355X_BZ2_TRACE=1 when it was begun */
     int timingGroups{ 0 };            /* groups of the last batch */
     bool timingsResolved{ true };     /* timings.ms_kernel[] filled in for the last batch */
     uint32_t nKernels{ 0 };
@@ -286,7 +282,7 @@ freeScratch( mi355x_bz2_ctx* c, bool now = true )
     c->dR = nullptr; c->dSegLen = nullptr; c->dSegSucc = nullptr; c->dSegCont = nullptr;
     c->dChain = nullptr; c->dStash = nullptr; c->dPlan = nullptr; c->dWalkBlk = nullptr; c->dWalkPre = nullptr;
     c->hOrder = nullptr; c->hSlotOf = nullptr; c->hMeta = nullptr; c->hOffsets = nullptr;
-    c->dSlotOf = nullptr; c->dTotals = nullptr; c->hTotals = nullptr; c->dScanQueue = nullptr; c->dBwtCounts = nullptr;
+    c->dSlotOf = nullptr; c->dTotals = nullptr; c->hTotals = nullptr; c->dBwtCounts = nullptr;
     c->capacity = 0;
 }
 
@@ -334,7 +330,6 @@ ensureScratch( mi355x_bz2_ctx* c, uint32_t nBlocks )
     const size_t oWalkPre = reserve( deviceBytes, MAX_GROUPS * ( (size_t)cap + 16 ) * sizeof( uint32_t ) );
     const size_t oSlotOf = reserve( deviceBytes, (size_t)cap * sizeof( uint32_t ) );
     const size_t oTotals = reserve( deviceBytes, 2 * sizeof( uint64_t ) );
-    const size_t oScanQueue = reserve( deviceBytes, MAX_GROUPS * sizeof( uint32_t ) );
     const size_t oBwtCounts = reserve( deviceBytes, (size_t)std::min( cap, BWT_SPLIT_BLOCKS ) * BWT_COUNTS_PER_BLOCK * sizeof( uint32_t ) );
     const size_t hOrderAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
     const size_t hSlotOfAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
@@ -377,7 +372,6 @@ ensureScratch( mi355x_bz2_ctx* c, uint32_t nBlocks )
     c->dWalkPre = reinterpret_cast<uint32_t*>( d + oWalkPre );
     c->dSlotOf = reinterpret_cast<uint32_t*>( d + oSlotOf );
     c->dTotals = reinterpret_cast<uint64_t*>( d + oTotals );
-    c->dScanQueue = reinterpret_cast<uint32_t*>( d + oScanQueue );
     c->dBwtCounts = reinterpret_cast<uint32_t*>( d + oBwtCounts );
     c->hOrder = reinterpret_cast<uint32_t*>( h + hOrderAt );
     c->hSlotOf = reinterpret_cast<uint32_t*>( h + hSlotOfAt );
@@ -428,10 +422,9 @@ constexpr uint32_t N_KERNELS = sizeof( KERNEL_NAMES ) / sizeof( KERNEL_NAMES[0] 
 static_assert( N_KERNELS <= MI355X_BZ2_MAX_KERNELS );
 }  // namespace
 
-/* record an event pair around one launch so that every kernel gets its own device duration */
 /* ONE k_walk at a time per process, whatever stream and context it comes from: every walk is ordered behind the one
- * launched before it (MI355X_BZ2_WALK_SERIAL=0 turns this off).  A walk keeps one or two 3.6 MB tables per XCD in its
- * 4 MB L2; walks of several block groups and contexts side by side push each other's tables out.  In turn, and with
+ * launched before it.  A walk keeps one or two 3.6 MB tables per XCD in its 4 MB L2; walks of several block groups and
+ * contexts side by side push each other's tables out.  In turn, and with
  * fewer workgroups each (64 per XCD instead of 256: the other kernels of the crowd fill the wave slots while the walk
  * waits for its gathers), a step of the four-context bench takes 67.5 instead of 74 ms. */
 struct WalkChain
@@ -445,13 +438,15 @@ struct WalkChain
 WalkChain g_walkChains[16];      /* by device: walks on different GPUs have nothing to do with each other */
 WalkChain& walkChainOf( int device ) { return g_walkChains[(unsigned)device % 16u]; }
 
-#define TIMED_LAUNCH( ctx, group, queue, index, ... )                                      \
+/* record an event pair around the launches of one timing slot, so that every kernel gets its own device duration */
+#define TIMED( ctx, group, queue, index, ... )                                             \
     do {                                                                                   \
         ( ctx )->launched[group] |= 1u << ( index );                                       \
         HIP_TRY( ctx, hipEventRecord( ( ctx )->ev[group][2 * ( index )], queue ) );        \
-        hipLaunchKernelGGL( __VA_ARGS__ );                                                 \
+        __VA_ARGS__;                                                                       \
         HIP_TRY( ctx, hipEventRecord( ( ctx )->ev[group][2 * ( index ) + 1], queue ) );    \
     } while ( 0 )
+#define TIMED_LAUNCH( ctx, group, queue, index, ... ) TIMED( ctx, group, queue, index, hipLaunchKernelGGL( __VA_ARGS__ ) )
 
 namespace
 {
@@ -469,6 +464,51 @@ allowLargeLds()
     allow( reinterpret_cast<const void*>( &k_mtf<MTF_SMALL_STRIDE, 1024> ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ) );
     allow( reinterpret_cast<const void*>( &k_link2 ), sizeof( LinkShared ) );
     return ok;
+}
+
+/** The environment switches a batch reads, once per batch: the forms the tests ask for whatever the batch size, NO_SPLIT
+ * (set between batches by bench.py --full) and the two traces. */
+struct BatchSwitches
+{
+    PlanOverrides plan;
+    bool trace{ false };         /* MI355X_BZ2_TRACE=1: per-group kernel timeline of every batch on stderr */
+    bool readerTrace{ false };   /* MI355X_BZ2_READER_TRACE: host time of decode_batch_begin */
+};
+
+BatchSwitches
+readSwitches()
+{
+    const auto positive = [] ( const char* name ) {
+        const char* v = std::getenv( name );
+        return v != nullptr && std::atoi( v ) > 0 ? (uint32_t)std::atoi( v ) : 0u;
+    };
+    const auto one = [] ( const char* name ) {
+        const char* v = std::getenv( name );
+        return v != nullptr && v[0] == '1';
+    };
+    BatchSwitches s;
+    s.plan.scanWaves = positive( "MI355X_BZ2_SCAN_WAVES" );   /* 1 = k_hscan<1>, 4 / 8 = k_hscan_spec<4 / 8> */
+    s.plan.bwtSplit = positive( "MI355X_BZ2_BWT_SPLIT" );     /* workgroups per block of the table build (1, 2, 4, 8) */
+    s.plan.mtfNarrow = one( "MI355X_BZ2_MTF_NARROW" );        /* 256 lanes per block in k_mtf */
+    s.plan.noSplit = one( "MI355X_BZ2_NO_SPLIT" );
+    s.trace = one( "MI355X_BZ2_TRACE" );
+    s.readerTrace = std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr;
+    return s;
+}
+
+/** Expansion and CRC of every block of the batch into c->dOut, and the records back to the host.  `overflow`: k_offsets'
+ * verdict that the output did not fit (the kernels then do nothing), or null. */
+int
+queueOutput( mi355x_bz2_ctx* c, uint32_t n, const uint64_t* overflow )
+{
+    TIMED_LAUNCH( c, 0, c->stream, 8, k_rle<true>, dim3( n ), dim3( RLE_THREADS ), 0, c->stream, c->dMeta, c->dR, c->dOut,
+                  overflow );
+    TIMED_LAUNCH( c, 0, c->stream, 9, k_crc, dim3( n ), dim3( CRC_THREADS ), 0, c->stream, c->dMeta, c->dOut, c->crc,
+                  overflow );
+    HIP_TRY( c, hipEventRecord( c->evStep[2], c->stream ) );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( c->hMeta, c->dMeta, (size_t)n * sizeof( BlockMeta ), hipMemcpyDeviceToHost, c->stream ) );
+    return MI355X_BZ2_OK;
 }
 }  // namespace
 
@@ -960,7 +1000,7 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     }
     HIP_TRY( c, hipSetDevice( c->device ) );
-    const bool traceBegin = std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr;
+    const BatchSwitches switches = readSwitches();
     const auto tBegin = std::chrono::steady_clock::now();
     int rc = ensureScratch( c, n );
     if ( rc != MI355X_BZ2_OK ) return rc;
@@ -981,83 +1021,15 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     }
     const auto tInput = std::chrono::steady_clock::now();
 
-    /* ---- plan: cost estimate, groups, slots, work order --------------------------------------------------------
-     * cost = estimated compressed size (distance to the next requested offset, or to the end of the input).
-     * The group-start scan (k_hscan<1>) is one serial chain per block: a launch lasts as long as its LARGEST block.
-     * Everything behind it (symbols, MTF, BWT, walk, RLE, CRC) is throughput work of about the same size for every block.
-     * The batch is therefore cut into groups, each with its own HIP stream, such that the throughput work starts early and
-     * never runs dry:
-     *   - the "expensive" group: blocks above 45 % of the largest cost, if they are a minority (incompressible blocks
-     *     among text).  Its scan starts at once and runs beside everything else on a high-priority stream.
-     *   - the other blocks, sorted by cost, in up to MAX_CHUNKS chunks of growing size.  All scans start together; a chunk
-     *     of cheap blocks is through early, and its MTF .. RLE kernels run while the later chunks are still being scanned.
-     * Inside a group the stage-1 kernels start their largest blocks first (LPT).
-     * Slots: group g occupies slots [groupFirst[g], +groupCount[g]) of every per-block buffer; results are mapped
-     * back to input order. */
-    std::vector<uint64_t> cost( n );
-    {
-        std::vector<uint32_t> byOffset( n );
-        for ( uint32_t i = 0; i < n; ++i ) byOffset[i] = i;
-        std::sort( byOffset.begin(), byOffset.end(), [&] ( uint32_t a, uint32_t b ) { return offsets[a] < offsets[b]; } );
-        for ( uint32_t k = 0; k < n; ++k ) {
-            const uint64_t next = k + 1 < n ? offsets[byOffset[k + 1]] : inSize * 8;
-            const uint64_t cur = offsets[byOffset[k]];
-            cost[byOffset[k]] = next > cur ? next - cur : 0;
-        }
-    }
-    uint64_t maxCost = 0;
-    for ( const auto v : cost ) maxCost = std::max( maxCost, v );
-    const char* noSplit = std::getenv( "MI355X_BZ2_NO_SPLIT" );
-    const bool split = n >= 64 && !( noSplit != nullptr && noSplit[0] == '1' );
+    /* groups, slots, work order and kernel forms: bz2_plan.hpp */
+    const bool crowd = walkChainOf( c->device ).liveContexts.load() >= 3;
+    c->plan = planBatch( offsets, n, inSize, crowd, switches.plan );
+    c->trace = switches.trace;
+    const BatchPlan& plan = c->plan;
+    std::copy( plan.slotOf.begin(), plan.slotOf.end(), c->hSlotOf );
+    std::copy( plan.offsets.begin(), plan.offsets.end(), c->hOffsets );
+    std::copy( plan.order.begin(), plan.order.end(), c->hOrder );
 
-    std::vector<uint32_t> ascending( n );   /* block indices by increasing cost */
-    for ( uint32_t i = 0; i < n; ++i ) ascending[i] = i;
-    std::stable_sort( ascending.begin(), ascending.end(), [&] ( uint32_t a, uint32_t b ) { return cost[a] < cost[b]; } );
-
-    uint32_t nExpensive = 0;
-    if ( split ) {
-        while ( nExpensive < n && cost[ascending[n - 1 - nExpensive]] * 100 > maxCost * 45 ) ++nExpensive;
-        if ( nExpensive < 16 || (uint64_t)nExpensive * 100 > (uint64_t)n * 35 ) nExpensive = 0;
-    }
-    const uint32_t nCheap = n - nExpensive;
-    uint32_t nChunks = 1;
-    if ( split ) {
-        /* measured on MI355X (round 1, and still the right proportion): a lone stage-1 wave takes about 5.5 ns per
-         * compressed bit; the kernels behind it together about 0.04 ms per block when the GPU is full */
-        const double huffMs = (double)cost[ascending[nCheap - 1]] * 5.5e-6;
-        const double restMs = (double)nCheap * 0.04;
-        const double ratio = restMs / std::max( huffMs, 1e-3 );
-        nChunks = (uint32_t)std::min<double>( { ratio, (double)MAX_CHUNKS, (double)( nCheap / 128 ) } );
-        nChunks = std::max( nChunks, 1u );
-        if ( const char* forced = std::getenv( "MI355X_BZ2_CHUNKS" ); forced != nullptr && std::atoi( forced ) > 0 ) {
-            nChunks = std::min<uint32_t>( (uint32_t)std::atoi( forced ), MAX_CHUNKS );
-        }
-    }
-    const int nGroups = (int)nChunks + ( nExpensive > 0 ? 1 : 0 );
-    const int expensiveGroup = nExpensive > 0 ? (int)nChunks : -1;
-    uint32_t groupCount[MAX_GROUPS] = {};
-    uint32_t groupFirst[MAX_GROUPS] = {};
-    {
-        /* chunk g ends at rank nCheap * (g + 1)(g + 2) / (K (K + 1)): 1/3, 1 for two chunks; 1/6, 1/2, 1 for three --
-         * a small first chunk gets the throughput kernels going early, the later ones keep them fed */
-        uint32_t begin = 0;
-        for ( uint32_t g = 0; g < nChunks; ++g ) {
-            const uint32_t end = (uint32_t)( (uint64_t)nCheap * ( g + 1 ) * ( g + 2 ) / ( (uint64_t)nChunks * ( nChunks + 1 ) ) );
-            groupCount[g] = end - begin;
-            begin = end;
-        }
-    }
-    if ( expensiveGroup >= 0 ) groupCount[expensiveGroup] = nExpensive;
-    for ( int g = 1; g < nGroups; ++g ) groupFirst[g] = groupFirst[g - 1] + groupCount[g - 1];
-    /* slot = rank by cost: group g = ranks [groupFirst[g], +groupCount[g]); LPT order inside the group = descending */
-    for ( uint32_t rank = 0; rank < n; ++rank ) {
-        c->hSlotOf[ascending[rank]] = rank;
-        c->hOffsets[rank] = offsets[ascending[rank]];
-    }
-    for ( int g = 0; g < nGroups; ++g ) {
-        uint32_t* order = c->hOrder + groupFirst[g];
-        for ( uint32_t k = 0; k < groupCount[g]; ++k ) order[k] = groupCount[g] - 1 - k;   /* group-relative slot */
-    }
     for ( auto& bits : c->launched ) bits = 0;
     if ( c->inPending ) {
         HIP_TRY( c, hipStreamWaitEvent( c->stream, c->inReady, 0 ) );
@@ -1069,50 +1041,17 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     HIP_TRY( c, hipMemcpyAsync( c->dOrder, c->hOrder, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemcpyAsync( c->dSlotOf, c->hSlotOf, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipEventRecord( c->evStep[1], c->stream ) );
-    auto streamOf = [&] ( int g ) { return g == expensiveGroup ? c->gstream[MAX_GROUPS - 1] : c->gstream[g]; };
-    for ( int g = 1; g < nGroups; ++g ) {
+    /* the expensive group runs on the high-priority stream */
+    auto streamOf = [&] ( int g ) { return g == plan.expensive ? c->gstream[MAX_GROUPS - 1] : c->gstream[g]; };
+    for ( int g = 1; g < plan.groups; ++g ) {
         HIP_TRY( c, hipStreamWaitEvent( streamOf( g ), c->evStep[1], 0 ) );
     }
 
-    /* three or more contexts alive on this device: batches run side by side (a reader, the bench), kernels are chosen for
-     * the throughput of the crowd; one or two: for the latency of the batch */
-    const bool crowd = walkChainOf( c->device ).liveContexts.load() >= 3;
-    const char* wg = std::getenv( "MI355X_BZ2_WALK_WGS" );   /* tuning knob: workgroups per XCD */
-    /* measured, walks in turn: four contexts in flight 64 workgroups 67.4 ms per step, 128: 68.6, 256: 72.8; a single context
-     * 64: 85.6 ms per batch, 128: 81.0, 256 (walks of the block groups side by side): 84.0 */
-    const uint32_t wgsPerXcd = wg != nullptr && std::atoi( wg ) > 0
-                               ? (uint32_t)std::atoi( wg )
-                               : ( crowd ? WALK_WGS_CROWD : WALK_WGS_PER_XCD );
-    const char* wc = std::getenv( "MI355X_BZ2_WALK_CHUNK" );
-    /* Segments per claim.  A lane takes a new segment whenever it has finished one, so a claim has to hold several segments
-     * per lane for the lanes to stay busy (segment lengths are geometric: with one segment per lane 22 % of the lanes of a
-     * gather instruction are alive, PMC) -- but the segments an XCD has claimed should not span more than a block or two,
-     * or its workgroups work on more tables than its L2 holds (claims of 1 024 with 128 workgroups per XCD: FETCH_SIZE of
-     * k_walk 14.8 -> 77.6 GB per step).  Workgroups x claim = 32 768 = one block's segments; measured on one box, ms per
-     * step (k_walk alone): 128 x 256: 65.1 (17.3), 64 x 256: 63.3 (22.1), 64 x 512: 61.6 (18.7), 32 x 1 024: 60.9 / 62.0 (22.2),
-     * 24 x 1 536: 61.6, 16 x 2 048: 65.4.  In a crowd: 32 workgroups per XCD (an eighth of the wave slots) with claims of 1 024. */
-    const uint32_t walkChunk = wc != nullptr && std::atoi( wc ) > 0 ? (uint32_t)std::atoi( wc ) : ( crowd && n >= 256 ? 4 * WALK_CHUNK : WALK_CHUNK );
-
-    const char* sw = std::getenv( "MI355X_BZ2_SCAN_WAVES" );   /* tuning knob: 1 = k_hscan<1>, 4 / 8 = k_hscan_spec<4 / 8>, whatever the batch size */
-    const uint32_t forcedScanWaves = sw != nullptr && std::atoi( sw ) > 0 ? (uint32_t)std::atoi( sw ) : 0u;
-    /* most workgroups of a k_hscan<1> launch (0: one per block).  Ten of them fill the LDS of a CU for as long as
-     * their blocks take (10 to 30 ms): the kernels of the other groups and contexts that need LDS wait for them */
-    const char* sg = std::getenv( "MI355X_BZ2_SCAN_GRID" );
-    const uint32_t scanGrid = sg != nullptr ? (uint32_t)std::atoi( sg ) : 0u;
-    const char* bsp = std::getenv( "MI355X_BZ2_BWT_SPLIT" );   /* tuning knob: workgroups per block of the table build (1, 2, 4, 8) */
-    const uint32_t bwtSplit = bsp != nullptr ? std::min<uint32_t>( (uint32_t)std::atoi( bsp ), BWT_SPLIT_MAX ) : 0u;
-    const char* smx = std::getenv( "MI355X_BZ2_SCAN_MIXED" );   /* 0: off; 4 / 8: that many waves per expensive block; default: by count */
-    const uint32_t scanMixed = smx != nullptr ? (uint32_t)std::atoi( smx ) : 1u;
-    const char* wsr = std::getenv( "MI355X_BZ2_WALK_SERIAL" );
-    const bool walkSerial = !( wsr != nullptr && wsr[0] == '0' );
-    const char* mn = std::getenv( "MI355X_BZ2_MTF_NARROW" );   /* 1: 256 lanes per block in k_mtf whatever the batch size */
-    const bool mtfNarrow = mn != nullptr && mn[0] == '1';
-    const char* st = std::getenv( "MI355X_BZ2_SCAN_TUNE" );
-    const uint32_t scanTune = st != nullptr ? (uint32_t)std::atoi( st ) : 0u;
-    for ( int launch = 0; launch < nGroups; ++launch ) {
+    const dim3 walkGrid( WALK_QUEUES * plan.walkWgsPerXcd );
+    for ( int launch = 0; launch < plan.groups; ++launch ) {
         /* the expensive group is queued first, then the chunks from cheap to less cheap */
-        const int g = expensiveGroup >= 0 ? ( launch == 0 ? expensiveGroup : launch - 1 ) : launch;
-        const uint32_t m = groupCount[g], first = groupFirst[g];
+        const int g = plan.expensive >= 0 ? ( launch == 0 ? plan.expensive : launch - 1 ) : launch;
+        const uint32_t m = plan.count[g], first = plan.first[g];
         hipStream_t q = streamOf( g );
         BlockMeta* const meta = c->dMeta + first;
         HuffMeta* const hmeta = c->dHmeta + first;
@@ -1128,51 +1067,24 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
         uint2* const chain = c->dChain + (size_t)first * SEG_STRIDE;
         uint32_t* const stash = c->dStash + (size_t)first * SEG_STRIDE * ( STASH_BYTES / 4 );
         const uint32_t* const order = c->dOrder + first;
-        WalkPlan* const plan = c->dPlan + g;
+        WalkPlan* const walkPlan = c->dPlan + g;
         uint32_t* const walkBlk = c->dWalkBlk + (size_t)g * ( c->capacity + 16 );
         uint32_t* const walkPre = c->dWalkPre + (size_t)g * ( c->capacity + 16 );
-        const dim3 walkGrid( WALK_QUEUES * wgsPerXcd );
 
         {
             ScanMeta* const smeta = c->dSmeta + first;
             HuffTables* const htab = c->dHtab + first;
             uint32_t* const gpos = c->dGpos + (size_t)first * GPOS_STRIDE;
-            /* wavefronts per block: one when the batch fills the GPU by itself; four or eight, each on a group of its own
-             * (k_hscan_spec, bz2_hscan.hip.h), when few blocks have to be through quickly (their LDS, one build per wave,
-             * allows 4 and 2 blocks per CU).  Measured: sixteen waves gain nothing over eight (the chain from group to
-             * group and the barriers grow with the waves); eight are faster than four for ONE batch of 320 blocks (15 vs
-             * 18 ms) but slower when four such batches run side by side (14.5 vs 13.4 ms per batch): eight up to 384
-             * blocks for a caller with one or two contexts, up to 128 in a crowd */
-            /* In a big batch the launch of one wave per block lasts as long as its largest block's chain (34 ms for an
-             * incompressible block, against 14.6 ms of average wave life): the expensive minority gets its own waves per
-             * group (MI355X_BZ2_SCAN_MIXED=0: one wave per block for them too) */
-            /* (in a crowd -- batches side by side, the scan of one under the other kernels of the rest -- one wave per block
-             * from 800 blocks on: a share of 1 270 blocks 37.5 -> 33.4 ms per step, of 960 blocks 28.1 -> 26.7, of 630 blocks
-             * 20.2 -> 20.7, profiles/r03_ab_share.txt) */
-            uint32_t scanWaves = forcedScanWaves != 0 ? forcedScanWaves
-                                                      : ( n <= ( crowd ? 128u : 384u ) ? 8u : ( n <= ( crowd ? 800u : 1280u ) ? 4u : 1u ) );
-            if ( forcedScanWaves == 0 && scanWaves == 1 && g == expensiveGroup && scanMixed != 0 ) {
-                scanWaves = scanMixed >= 4 ? scanMixed : ( m <= 128 ? 8u : 4u );
-            }
             const auto* const inWords = reinterpret_cast<const uint32_t*>( inBase );
-            if ( scanWaves >= 8 ) {
+            if ( plan.scanWaves[g] == 8 ) {
                 TIMED_LAUNCH( c, g, q, 12, k_hscan_spec<8>, dim3( m ), dim3( 512 ), 0, q, inWords, inSize, c->dOffsets + first,
-                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order, scanTune );
-            } else if ( scanWaves >= 4 ) {
+                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
+            } else if ( plan.scanWaves[g] == 4 ) {
                 TIMED_LAUNCH( c, g, q, 12, k_hscan_spec<4>, dim3( m ), dim3( 256 ), 0, q, inWords, inSize, c->dOffsets + first,
-                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order, scanTune );
+                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
             } else {
-                uint32_t* scanQueue = nullptr;
-                uint32_t grid = m;
-                if ( scanGrid != 0 && scanGrid < m ) {
-                    HIP_TRY( c, hipMemsetAsync( c->dScanQueue + g, 0, sizeof( uint32_t ), q ) );
-                    scanQueue = c->dScanQueue + g;
-                    grid = scanGrid;
-                }
-#define SCAN1( W ) TIMED_LAUNCH( c, g, q, 12, ( k_hscan<1, W> ), dim3( grid ), dim3( 64 ), sizeof( ScanShared<1> ), q, inWords, inSize, \
-                                 c->dOffsets + first, meta, hmeta, smeta, sel, stb, htab, gpos, m, order, scanTune, scanQueue )
-                SCAN1( REGS_SCAN );
-#undef SCAN1
+                TIMED_LAUNCH( c, g, q, 12, ( k_hscan<1, REGS_SCAN> ), dim3( m ), dim3( 64 ), sizeof( ScanShared<1> ), q, inWords,
+                              inSize, c->dOffsets + first, meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
             }
 #define HSYM( T ) TIMED_LAUNCH( c, g, q, 13, k_hsym<T>, dim3( ( MAX_SCAN_GROUPS + ( T ) * SYM_CHUNKS - 1 ) / ( ( T ) * SYM_CHUNKS ), m ), dim3( T ), \
                                 sizeof( SymShared<T> ), q, inWords, meta, hmeta, smeta, sel, htab, gpos, sym )
@@ -1182,9 +1094,8 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
 #define MTF256( STRIDE, STREAM, INDEX ) \
         TIMED_LAUNCH( c, g, STREAM, INDEX, ( k_mtf<STRIDE, MTF_THREADS, REGS_MTF> ), dim3( m ), dim3( MTF_THREADS ), \
                       sizeof( MtfShared<STRIDE, MTF_THREADS> ), STREAM, meta, hmeta, sym, stb, lcol, m, order )
-        /* Every block belongs to one of the two k_mtf instances (by its symbol count), the other returns at once.  In a
-         * small batch each lasts as long as its slowest block (4 and 7 ms): side by side instead of one behind the other. */
-        if ( n <= 1280 ) {
+        /* every block belongs to one of the two k_mtf instances (by its symbol count), the other returns at once */
+        if ( plan.mtfSide ) {
             if ( c->sideStream[g] == nullptr ) {
                 HIP_TRY( c, hipStreamCreateWithFlags( &c->sideStream[g], hipStreamNonBlocking ) );
                 HIP_TRY( c, hipEventCreateWithFlags( &c->evFork[g], hipEventDisableTiming ) );
@@ -1193,20 +1104,17 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
             hipStream_t side = c->sideStream[g];
             HIP_TRY( c, hipEventRecord( c->evFork[g], q ) );
             HIP_TRY( c, hipStreamWaitEvent( side, c->evFork[g], 0 ) );
-            /* (up to 640 blocks: one batch of 320 blocks 30.4 -> 28.0 ms, but four side by side 11.9 -> 12.1 ms per batch) */
-            if ( n <= ( crowd ? 256u : 640u ) && !mtfNarrow ) {
-                /* few blocks: 512 lanes per block, each with half the symbols */
-                if ( n <= 64 ) {
-                    /* (the 128-entry lists of 1 024 lanes still fit the LDS of a CU: 152 KB) */
-                    TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order );
-                } else {
-                    TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order );
-                }
-                HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
-                TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order );
+            if ( plan.mtfSmallLanes == 1024 ) {
+                TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order );
+            } else if ( plan.mtfSmallLanes == 512 ) {
+                TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order );
             } else {
                 MTF256( MTF_SMALL_STRIDE, side, 11 );
-                HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
+            }
+            HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
+            if ( plan.mtfSmallLanes > 256 ) {
+                TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order );
+            } else {
                 MTF256( MTF_LANE_STRIDE, q, 1 );
             }
             HIP_TRY( c, hipStreamWaitEvent( q, c->evJoin[g], 0 ) );
@@ -1215,33 +1123,24 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
             MTF256( MTF_LANE_STRIDE, q, 1 );
         }
 #undef MTF256
-        /* table build: one workgroup per block when the batch fills the GPU with that (1 024 threads each: 512 at a time);
-         * fewer blocks are spread over 2, 4 or 8 workgroups each (a lone block: 1.0 -> 0.3 ms) */
-        const uint32_t bwtSlices = bwtSplit != 0 ? bwtSplit : ( n > BWT_SPLIT_BLOCKS ? 1u : ( n > 256 ? 2u : ( n > 128 ? 4u : BWT_SPLIT_MAX ) ) );
-        if ( bwtSlices > 1 && n <= BWT_SPLIT_BLOCKS ) {
+        if ( plan.bwtSlices > 1 ) {
             uint32_t* const counts = c->dBwtCounts + (size_t)first * BWT_COUNTS_PER_BLOCK;
-            c->launched[g] |= 1u << 2;
-            HIP_TRY( c, hipEventRecord( c->ev[g][2 * 2], q ) );
-            hipLaunchKernelGGL( k_bwt_count, dim3( bwtSlices, m ), dim3( 1024 ), 0, q, meta, lcol, counts, bwtSlices );
-            hipLaunchKernelGGL( k_bwt_rank, dim3( bwtSlices, m ), dim3( 1024 ), 0, q, meta, lcol, tab, counts, bwtSlices );
-            HIP_TRY( c, hipEventRecord( c->ev[g][2 * 2 + 1], q ) );
+            TIMED( c, g, q, 2, hipLaunchKernelGGL( k_bwt_count, dim3( plan.bwtSlices, m ), dim3( 1024 ), 0, q, meta, lcol, counts, plan.bwtSlices );
+                               hipLaunchKernelGGL( k_bwt_rank, dim3( plan.bwtSlices, m ), dim3( 1024 ), 0, q, meta, lcol, tab, counts, plan.bwtSlices ) );
         } else {
             TIMED_LAUNCH( c, g, q, 2, k_bwt_build, dim3( m ), dim3( 1024 ), 0, q, meta, lcol, tab );
         }
-        TIMED_LAUNCH( c, g, q, 10, k_walk_plan, dim3( 1 ), dim3( 256 ), 0, q, meta, m, plan, walkBlk, walkPre );
-        if ( walkSerial ) {
+        TIMED_LAUNCH( c, g, q, 10, k_walk_plan, dim3( 1 ), dim3( 256 ), 0, q, meta, m, walkPlan, walkBlk, walkPre );
+        {
             WalkChain& walks = walkChainOf( c->device );
-            const std::scoped_lock chain( walks.mutex );
+            const std::scoped_lock walkLock( walks.mutex );
             if ( walks.last != nullptr ) HIP_TRY( c, hipStreamWaitEvent( q, walks.last, 0 ) );
             TIMED_LAUNCH( c, g, q, 3, k_walk, walkGrid, dim3( WALK_THREADS ), 0, q,
-                          meta, tab, plan, walkBlk, walkPre, segLen, segSucc, walkChunk, stash, segCont );
+                          meta, tab, walkPlan, walkBlk, walkPre, segLen, segSucc, plan.walkChunk, stash, segCont );
             hipEvent_t& slot = walks.events[walks.next++ % 64];
             if ( slot == nullptr ) HIP_TRY( c, hipEventCreateWithFlags( &slot, hipEventDisableTiming ) );
             HIP_TRY( c, hipEventRecord( slot, q ) );
             walks.last = slot;
-        } else {
-            TIMED_LAUNCH( c, g, q, 3, k_walk, walkGrid, dim3( WALK_THREADS ), 0, q,
-                          meta, tab, plan, walkBlk, walkPre, segLen, segSucc, walkChunk, stash, segCont );
         }
         TIMED_LAUNCH( c, g, q, 4, k_link2, dim3( m ), dim3( LINK_THREADS ), sizeof( LinkShared ), q, meta, segLen, segSucc, chain );
         TIMED_LAUNCH( c, g, q, 5, k_emit, dim3( ( SEG_STRIDE + EMIT_THREADS * EMIT_TILES - 1 ) / ( EMIT_THREADS * EMIT_TILES ), m ), dim3( EMIT_THREADS ), 0, q,
@@ -1255,7 +1154,7 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
         }
     }
     HIP_TRY( c, hipGetLastError() );
-    for ( int g = 1; g < nGroups; ++g ) {
+    for ( int g = 1; g < plan.groups; ++g ) {
         HIP_TRY( c, hipStreamWaitEvent( c->stream, c->evGroupDone[g], 0 ) );
     }
 
@@ -1271,19 +1170,11 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     }
     hipLaunchKernelGGL( k_offsets, dim3( 1 ), dim3( OFFSETS_THREADS ), 0, c->stream, c->dMeta, c->dSlotOf, n,
                         c->out[c->outCurrent].capacity, c->dTotals );
-    TIMED_LAUNCH( c, 0, c->stream, 8, k_rle<true>, dim3( n ), dim3( RLE_THREADS ), 0, c->stream, c->dMeta, c->dR, c->dOut,
-                  c->dTotals + 1 );
-    TIMED_LAUNCH( c, 0, c->stream, 9, k_crc, dim3( n ), dim3( CRC_THREADS ), 0, c->stream, c->dMeta, c->dOut, c->crc,
-                  c->dTotals + 1 );
-    HIP_TRY( c, hipEventRecord( c->evStep[2], c->stream ) );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( c->hMeta, c->dMeta, (size_t)n * sizeof( BlockMeta ), hipMemcpyDeviceToHost, c->stream ) );
+    rc = queueOutput( c, n, c->dTotals + 1 );
+    if ( rc != MI355X_BZ2_OK ) return rc;
     HIP_TRY( c, hipMemcpyAsync( c->hTotals, c->dTotals, 2 * sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
     c->pendingBlocks = n;
-    c->pendingGroups = nGroups;
-    c->pendingExpensive = expensiveGroup;
-    for ( int g = 0; g < MAX_GROUPS; ++g ) c->pendingGroupCount[g] = groupCount[g];
-    if ( traceBegin ) {
+    if ( switches.readerTrace ) {
         const auto ms = [] ( auto a, auto b ) { return std::chrono::duration<double, std::milli>( b - a ).count(); };
         std::fprintf( stderr, "[device] begin of %u blocks: scratch %.1f ms, input %.1f ms, plan + launches %.1f ms\n", n,
                       ms( tBegin, tScratch ), ms( tScratch, tInput ), ms( tInput, std::chrono::steady_clock::now() ) );
@@ -1301,8 +1192,7 @@ mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* c, mi355x_bz2_block_result* results
     if ( n == 0 ) return MI355X_BZ2_OK;   /* empty batch */
     if ( results == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     c->pendingBlocks = 0;
-    const int nGroups = c->pendingGroups, expensiveGroup = c->pendingExpensive;
-    const uint32_t* const groupCount = c->pendingGroupCount;
+    const BatchPlan& plan = c->plan;
     int rc = MI355X_BZ2_OK;
     HIP_TRY( c, hipSetDevice( c->device ) );
     HIP_TRY( c, hipStreamSynchronize( c->stream ) );
@@ -1319,13 +1209,8 @@ mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* c, mi355x_bz2_block_result* results
         rc = ensureOutput( c, total );
         if ( rc != MI355X_BZ2_OK ) return rc;
         HIP_TRY( c, hipMemcpyAsync( c->dMeta, c->hMeta, (size_t)n * sizeof( BlockMeta ), hipMemcpyHostToDevice, c->stream ) );
-        TIMED_LAUNCH( c, 0, c->stream, 8, k_rle<true>, dim3( n ), dim3( RLE_THREADS ), 0, c->stream, c->dMeta, c->dR, c->dOut,
-                      static_cast<const uint64_t*>( nullptr ) );
-        TIMED_LAUNCH( c, 0, c->stream, 9, k_crc, dim3( n ), dim3( CRC_THREADS ), 0, c->stream, c->dMeta, c->dOut, c->crc,
-                      static_cast<const uint64_t*>( nullptr ) );
-        HIP_TRY( c, hipEventRecord( c->evStep[2], c->stream ) );
-        HIP_TRY( c, hipGetLastError() );
-        HIP_TRY( c, hipMemcpyAsync( c->hMeta, c->dMeta, (size_t)n * sizeof( BlockMeta ), hipMemcpyDeviceToHost, c->stream ) );
+        rc = queueOutput( c, n, nullptr );
+        if ( rc != MI355X_BZ2_OK ) return rc;
         HIP_TRY( c, hipStreamSynchronize( c->stream ) );
     }
     c->outSizeHint = std::max( c->outSizeHint, total );
@@ -1356,11 +1241,11 @@ mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* c, mi355x_bz2_block_result* results
     float ms = 0;
     c->timings = {};
     c->timings.n_kernels = N_KERNELS;
-    if ( const char* trace = std::getenv( "MI355X_BZ2_TRACE" ); trace != nullptr && trace[0] == '1' ) {
+    if ( c->trace ) {
         /* per-group timeline relative to the step start: [start, end] of every kernel in ms */
-        for ( int g = 0; g < nGroups; ++g ) {
-            std::fprintf( stderr, "[mi355x_bz2] group %d%s (%u blocks):", g, g == expensiveGroup ? " expensive" : "",
-                          groupCount[g] );
+        for ( int g = 0; g < plan.groups; ++g ) {
+            std::fprintf( stderr, "[mi355x_bz2] group %d%s (%u blocks):", g, g == plan.expensive ? " expensive" : "",
+                          plan.count[g] );
             for ( uint32_t k = 0; k < N_KERNELS; ++k ) {
                 if ( !( c->launched[g] & ( 1u << k ) ) ) continue;
                 float t0 = 0, t1 = 0;
@@ -1374,7 +1259,7 @@ mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* c, mi355x_bz2_block_result* results
     if ( hipEventElapsedTime( &ms, c->evStep[0], c->evStep[2] ) == hipSuccess ) c->timings.ms_total = ms;   /* wall */
     /* the per-kernel durations are read from the events on demand (mi355x_bz2_last_timings): ~90 event queries per
      * batch cost milliseconds of host time that a caller who does not ask should not pay */
-    c->timingGroups = nGroups;
+    c->timingGroups = plan.groups;
     c->timingsResolved = false;
     return MI355X_BZ2_OK;
 }

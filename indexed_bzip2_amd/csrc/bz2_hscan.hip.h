@@ -698,21 +698,12 @@ k_hscan( const uint32_t* __restrict__ in_words,
          HuffTables* __restrict__     tab_buf,
          uint32_t* __restrict__       gpos_buf,
          uint32_t                     n_blocks,
-         const uint32_t* __restrict__ order,
-         uint32_t                     tune,    /* debugging: 1 = one group per build, 2 = always the full span */
-         uint32_t*                    queue )  /* K == 1 only: not null = the workgroups take blocks from this counter (zeroed by
-                                                  the host) until none is left, so that a grid smaller than the batch -- one
-                                                  that leaves LDS to the kernels of other streams -- still decodes all of it */
+         const uint32_t* __restrict__ order )
 {
     static_assert( K == 1, "one wavefront per block: the forms with shared rows were measured and dropped (DESIGN.md)" );
     extern __shared__ __attribute__( ( aligned( 16 ) ) ) uint8_t ldsAtLaunch[];     /* sizeof( ScanShared<K> ) */
     ScanShared<K>& sh = *reinterpret_cast<ScanShared<K>*>( ldsAtLaunch );
-    for ( uint32_t slotIndex = blockIdx.x;; slotIndex += gridDim.x ) {
-    if ( K == 1 && queue != nullptr ) {
-        uint32_t taken = 0;
-        if ( threadIdx.x == 0 ) taken = atomicAdd( queue, 1u );
-        slotIndex = sfl( taken );
-    }
+    const uint32_t slotIndex = blockIdx.x;
     if ( slotIndex >= n_blocks ) return;
     const uint32_t b = sfl( order[slotIndex] );
     const uint32_t lane = threadIdx.x & 63;
@@ -796,10 +787,9 @@ k_hscan( const uint32_t* __restrict__ in_words,
             const uint32_t est = (uint32_t)__builtin_amdgcn_readlane( (int)estV, t );
             const bool nearEnd = p + SCAN_MAX_SPAN + 32 > sizeBits;
             uint32_t rows = SCAN_ROWS, m = 1;
-            if ( est != 0 && !forceFull && !nearEnd && !( tune & 2u ) ) {
+            if ( est != 0 && !forceFull && !nearEnd ) {
                 const uint32_t need = est + ( est >> 3 ) + 16;   /* a group of this table: last one + 12 % + 16 bits */
                 m = ( SCAN_MAX_SPAN - 24 ) / need;
-                if ( tune & 1u ) m = 1;
                 if ( m > runLen ) m = runLen;
                 if ( m < 1 ) m = 1;
                 rows = ( m * need + 24 + 63 ) >> 6;
@@ -900,8 +890,6 @@ k_hscan( const uint32_t* __restrict__ in_words,
         sm.pad[0] = sm.pad[1] = 0;
         smeta[b] = sm;
     }
-    if ( K != 1 || queue == nullptr ) return;
-    }
 }
 
 /* =============================================================================================================
@@ -950,8 +938,7 @@ k_hscan_spec( const uint32_t* __restrict__ in_words,
               HuffTables* __restrict__     tab_buf,
               uint32_t* __restrict__       gpos_buf,
               uint32_t                     n_blocks,
-              const uint32_t* __restrict__ order,
-              uint32_t                     tune )   /* debugging: 1 = one group per unit */
+              const uint32_t* __restrict__ order )
 {
     __shared__ SpecShared<K> shared;
     ScanShared<1>& sh = shared.s;
@@ -1033,7 +1020,7 @@ k_hscan_spec( const uint32_t* __restrict__ in_words,
                 loV = accLo;
                 widthV = accHi - accLo;
                 rowsV = scan_rows_per_wave<1>( ( widthV + need + 24 + 63 ) >> 6 );
-                const bool ok = ( lane < K ) && ( gw < nSel ) && ( gw < MAX_SCAN_GROUPS ) && !( ( tune & 1u ) && lane > 0 )
+                const bool ok = ( lane < K ) && ( gw < nSel ) && ( gw < MAX_SCAN_GROUPS )
                                 && ( est != 0 ) && ( widthV + need + 24 <= SCAN_MAX_SPAN ) && ( accHi <= SPEC_REACH<K> )
                                 && ( p + accLo + SCAN_MAX_SPAN + 32 <= sizeBits );
                 const uint64_t okMask = __ballot( ok );

@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bz2_plan.hpp"   /* BWT_SPLIT_MAX */
+
 namespace bz2gpu
 {
 constexpr uint32_t MAX_N = 900000;            /* bzip2.hpp:416 dbuf size */
@@ -354,7 +356,6 @@ k_bwt_build( const BlockMeta* __restrict__ meta,
  * (s, b) turns the counts of all chunks in front of its own into the first rank of every byte value in each of its
  * chunks, then ranks its slice exactly as k_bwt_build's second pass does.
  * ------------------------------------------------------------------------------------------------------------- */
-constexpr uint32_t BWT_SPLIT_MAX = 8;                                   /* most slices per block */
 constexpr uint32_t BWT_COUNTS_PER_BLOCK = BWT_SPLIT_MAX * BWT_WAVES * 256;   /* u32 */
 
 __device__ __forceinline__ void

@@ -1,4 +1,4 @@
-"""Host-side C++ (magic finder, block index, run cache, access-pattern tracker, block finder thread) under
+"""Host-side C++ (magic finder, block index, run cache, access-pattern tracker, block finder thread, batch plan) under
 AddressSanitizer + UBSan and under ThreadSanitizer: CPU builds only (GPU sanitizers are not available on the pool).  The
 harnesses in tests/native/ drive the classes with seeded random operations and exact-size buffers; host_known_answers
 replays the answers recorded from the reference's own classes (tests/golden/host_vectors.txt)."""
@@ -25,6 +25,7 @@ CASES = [
     # scan behind a complete list: this harness shows that within ten rounds on that code)
     ("finder_race.cpp", "thread", ["60"], "finder race ok"),
     ("finder_race.cpp", "address,undefined", ["120"], "finder race ok"),
+    ("plan_cases.cpp", "address,undefined", [], "plan ok"),           # how a batch is cut into groups and kernel forms
 ]
 
 
