@@ -225,6 +225,18 @@ int mi355x_bz2_debug_copy_stage( mi355x_bz2_ctx* ctx, uint32_t index, int stage,
 int mi355x_bz2_crc32_device( mi355x_bz2_ctx* ctx, const void* device_bytes, const uint64_t* sizes, uint32_t n_pieces,
                              uint32_t* crcs );
 
+/* Pieces of the last batch's output (mi355x_bz2_output_device) copied into `dst` by the k_gather kernel: piece i is
+ * [src_offset, src_offset + size) of the output, written to dst + dst_offset.  `dst` is device memory on the context's
+ * device (dst_is_device = 1) or host memory (dst_is_device = 0: the pieces are gathered back to back into a context-owned
+ * device staging buffer, copied to the host in one D2H and put in place; bytes of `dst` that no piece covers are not
+ * written).  Offsets and sizes may have any alignment.  Runs on the context's stream and returns when done; no batch may
+ * be in flight.  The read_ranges path of the reader; no reference counterpart. */
+typedef struct mi355x_bz2_gather_piece {
+    uint64_t src_offset, dst_offset, size;
+} mi355x_bz2_gather_piece;
+int mi355x_bz2_gather_output( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, uint32_t n_pieces,
+                              void* dst, int dst_is_device );
+
 /* ------------------------------------------------------------------------------------------------ 2. magic scan */
 
 #define MI355X_BZ2_MAGIC_BLOCK 0x314159265359ULL   /* bzip2.hpp:103 */
@@ -270,6 +282,16 @@ int      mi355x_bz2_reader_closed( const mi355x_bz2_reader* r );              /*
 int      mi355x_bz2_reader_size( const mi355x_bz2_reader* r, uint64_t* size );
 uint64_t mi355x_bz2_reader_tell_compressed( const mi355x_bz2_reader* r );     /* tellCompressed :385-393 */
 int      mi355x_bz2_reader_block_offsets_complete( const mi355x_bz2_reader* r ); /*             :329-333 */
+
+/* pread of many ranges at once: range i is [offsets[i], offsets[i] + sizes[i]) of the decoded file, and its bytes go to
+ * dst + sizes[0] + ... + sizes[i - 1]; n_read[i] = bytes produced (short only at the end of the file; the bytes of dst
+ * behind them are not written).  Every block that some range needs is decoded once, in launches of at most
+ * `parallelization` blocks, and only the requested bytes are copied out of HBM (k_gather).  dst_is_device: dst is device
+ * memory on the reader's device.  Does not move the read position or eof(); ranges behind the indexed part of the file
+ * are indexed first, as a forward seek would.  A block that fails to decode fails the call with its status (dst is then
+ * unspecified).  No reference counterpart (ParallelBZ2Reader reads one range at a time). */
+int mi355x_bz2_reader_read_ranges( mi355x_bz2_reader* r, const uint64_t* offsets, const uint64_t* sizes, uint32_t n,
+                                   void* dst, int dst_is_device, uint64_t* n_read );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

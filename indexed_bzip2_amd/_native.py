@@ -83,6 +83,10 @@ class ReaderStats(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class GatherPiece(ctypes.Structure):
+    _fields_ = [("src_offset", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("size", ctypes.c_uint64)]
+
+
 # every symbol include/mi355x_bz2.h declares: (name, restype, argtypes)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
@@ -117,6 +121,7 @@ SYMBOLS = [
     ("mi355x_bz2_share_input", ctypes.c_int, [_vp, _vp]),
     ("mi355x_bz2_find_magic_device", ctypes.c_int, [_vp, ctypes.c_uint64, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_crc32_device", ctypes.c_int, [_vp, _vp, _u64p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    ("mi355x_bz2_gather_output", ctypes.c_int, [_vp, ctypes.POINTER(GatherPiece), ctypes.c_uint32, _vp, ctypes.c_int]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -135,6 +140,7 @@ SYMBOLS = [
     ("mi355x_bz2_reader_block_offsets", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_available_block_offsets", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_set_block_offsets", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_read_ranges", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint32, _vp, ctypes.c_int, _u64p]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -320,6 +326,26 @@ class Decoder:
         out = (ctypes.c_uint32 * max(1, n))()
         self._check(lib().mi355x_bz2_crc32_device(self._h, ctypes.c_void_p(device_ptr), arr, n, out))
         return list(out[:n])
+
+    @staticmethod
+    def _pieces(pieces):
+        pieces = [(int(s), int(d), int(n)) for s, d, n in pieces]
+        arr = (GatherPiece * max(1, len(pieces)))(*[GatherPiece(s, d, n) for s, d, n in pieces])
+        return pieces, arr
+
+    def gather_output(self, pieces) -> bytes:
+        """k_gather on the host path: `pieces` = [(src_offset, dst_offset, size)] of the last batch's output; returns the
+        destination, max(dst_offset + size) bytes long (bytes no piece covers are zero)."""
+        pieces, arr = self._pieces(pieces)
+        total = max((d + n for _, d, n in pieces), default=0)
+        buf = ctypes.create_string_buffer(max(1, total))
+        self._check(lib().mi355x_bz2_gather_output(self._h, arr, len(pieces), buf, 0))
+        return buf.raw[:total]
+
+    def gather_output_to_device(self, pieces, device_ptr: int):
+        """The same into device memory at `device_ptr` (on the decoder's device): each piece written in place."""
+        pieces, arr = self._pieces(pieces)
+        self._check(lib().mi355x_bz2_gather_output(self._h, arr, len(pieces), ctypes.c_void_p(device_ptr), 1))
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

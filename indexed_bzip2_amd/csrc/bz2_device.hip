@@ -181,6 +181,15 @@ struct mi355x_bz2_ctx
     uint64_t outSize{ 0 };
     uint32_t lastBlocks{ 0 };
 
+    /* mi355x_bz2_gather_output: grow-only, so that a call allocates nothing once the sizes have been seen.  The tile
+     * list (page-locked and on the device) and, for a host destination, the packed pieces (device and page-locked) */
+    GatherTile* hGatherTiles{ nullptr };
+    GatherTile* dGatherTiles{ nullptr };
+    uint64_t gatherTileCap{ 0 };
+    uint8_t* dGatherStage{ nullptr };
+    uint8_t* hGatherStage{ nullptr };
+    uint64_t gatherStageCap{ 0 };
+
     CrcConsts crc{};
     hipEvent_t ev[MAX_GROUPS][2 * MI355X_BZ2_MAX_KERNELS]{};   /* [group][2 * kernel + {start, end}] */
     hipEvent_t evStep[3]{};                                     /* step start, inputs uploaded, step end */
@@ -684,6 +693,10 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     }
     (void)hipFree( c->dScanFound );
     (void)hipFree( c->dScanCounter );
+    (void)hipFree( c->dGatherTiles );
+    (void)hipHostFree( c->hGatherTiles );
+    (void)hipFree( c->dGatherStage );
+    (void)hipHostFree( c->hGatherStage );
     if ( c->copyStream ) (void)hipStreamSynchronize( c->copyStream );
     for ( auto& buffer : c->out ) {
         (void)hipFree( buffer.bytes );
@@ -1496,6 +1509,86 @@ mi355x_bz2_crc32_device( mi355x_bz2_ctx* c, const void* deviceBytes, const uint6
         return rc;
     }
     for ( uint32_t i = 0; i < nPieces; ++i ) crcs[i] = records[i].computed_crc;
+    return MI355X_BZ2_OK;
+}
+
+int
+mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst,
+                          int dstIsDevice )
+{
+    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = "gather_output: a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    /* every piece inside the last batch's output; tiles of at most GATHER_TILE bytes */
+    uint64_t nTiles = 0, total = 0;
+    for ( uint32_t i = 0; i < nPieces; ++i ) {
+        const auto& p = pieces[i];
+        if ( p.size > c->outSize || p.src_offset > c->outSize - p.size || p.dst_offset > ~uint64_t( 0 ) - p.size ) {
+            c->lastError = "gather_output: piece " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        nTiles += ( p.size + GATHER_TILE - 1 ) / GATHER_TILE;
+        total += p.size;
+    }
+    if ( total == 0 ) return MI355X_BZ2_OK;
+    if ( dst == nullptr || nTiles > 0x7FFFFFFFu ) {
+        c->lastError = "gather_output: no destination, or too many pieces";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    /* the previous call's tile list has been consumed (every call waits for its kernel) */
+    if ( nTiles > c->gatherTileCap ) {
+        const uint64_t cap = std::max<uint64_t>( 2 * c->gatherTileCap, nTiles );
+        retire( c, c->hGatherTiles, c->gatherTileCap * sizeof( GatherTile ), true, cap * sizeof( GatherTile ) );
+        retire( c, c->dGatherTiles, c->gatherTileCap * sizeof( GatherTile ), false, cap * sizeof( GatherTile ) );
+        c->hGatherTiles = nullptr;
+        c->dGatherTiles = nullptr;
+        c->gatherTileCap = 0;
+        HIP_TRY( c, hipHostMalloc( reinterpret_cast<void**>( &c->hGatherTiles ), cap * sizeof( GatherTile ), hipHostMallocDefault ) );
+        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &c->dGatherTiles ), cap * sizeof( GatherTile ) ) );
+        c->gatherTileCap = cap;
+    }
+    const bool toHost = dstIsDevice == 0;
+    if ( toHost && total > c->gatherStageCap ) {
+        const uint64_t cap = std::max<uint64_t>( c->gatherStageCap + c->gatherStageCap / 2, total );
+        retire( c, c->hGatherStage, c->gatherStageCap, true, cap );
+        retire( c, c->dGatherStage, c->gatherStageCap, false, cap );
+        c->hGatherStage = nullptr;
+        c->dGatherStage = nullptr;
+        c->gatherStageCap = 0;
+        HIP_TRY( c, hipHostMalloc( reinterpret_cast<void**>( &c->hGatherStage ), cap, hipHostMallocDefault ) );
+        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &c->dGatherStage ), cap ) );
+        c->gatherStageCap = cap;
+    }
+    /* a host destination gets the pieces packed back to back in the staging buffer, one D2H copy of exactly the requested
+     * bytes, and then each piece copied to its place: bytes of `dst` between the pieces are never written */
+    uint64_t tile = 0, staged = 0;
+    for ( uint32_t i = 0; i < nPieces; ++i ) {
+        const auto& p = pieces[i];
+        const uint64_t at = toHost ? staged : p.dst_offset;
+        for ( uint64_t k = 0; k < p.size; k += GATHER_TILE ) {
+            c->hGatherTiles[tile++] = { p.src_offset + k, at + k, std::min<uint64_t>( GATHER_TILE, p.size - k ) };
+        }
+        staged += p.size;
+    }
+    HIP_TRY( c, hipMemcpyAsync( c->dGatherTiles, c->hGatherTiles, nTiles * sizeof( GatherTile ), hipMemcpyHostToDevice, c->stream ) );
+    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, c->dGatherTiles, c->dOut,
+                        toHost ? c->dGatherStage : static_cast<uint8_t*>( dst ) );
+    HIP_TRY( c, hipGetLastError() );
+    if ( toHost ) {
+        HIP_TRY( c, hipMemcpyAsync( c->hGatherStage, c->dGatherStage, total, hipMemcpyDeviceToHost, c->stream ) );
+    }
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    if ( toHost ) {
+        staged = 0;
+        for ( uint32_t i = 0; i < nPieces; ++i ) {
+            std::memcpy( static_cast<uint8_t*>( dst ) + pieces[i].dst_offset, c->hGatherStage + staged, pieces[i].size );
+            staged += pieces[i].size;
+        }
+    }
     return MI355X_BZ2_OK;
 }
 

@@ -912,4 +912,59 @@ k_crc( BlockMeta*                  meta,
         if ( crc != mt.header_crc ) meta[b].status = ST_CRC;
     }
 }
+
+/* -------------------------------------------------------------------------------------------------------------
+ * k_gather: pieces of a batch's ragged output into a destination (mi355x_bz2_gather_output, the read_ranges path).  The
+ * host cuts every piece into tiles of at most GATHER_TILE bytes, one workgroup per tile, so that a long range does not
+ * serialise on one workgroup.  Both ends may have any alignment: the bytes in front of the first 16-byte aligned
+ * destination address and behind the last one are written one by one (at most 15 each), the stretch between with one
+ * 16-byte store per lane.  A misaligned source is read as aligned dwords, five per 16 bytes, and shifted into place
+ * with v_alignbyte_b32; those loads reach up to 3 bytes behind the piece, which the output buffer's 256 bytes of slack
+ * behind the batch's last byte cover.
+ * ------------------------------------------------------------------------------------------------------------- */
+constexpr uint32_t GATHER_THREADS = 256;
+constexpr uint64_t GATHER_TILE = 32768;
+
+struct GatherTile
+{
+    uint64_t src, dst, size;   /* size <= GATHER_TILE */
+};
+
+__global__ __launch_bounds__( GATHER_THREADS ) void
+k_gather( const GatherTile* __restrict__ tiles, const uint8_t* __restrict__ src, uint8_t* __restrict__ dst )
+{
+    const GatherTile t = tiles[blockIdx.x];
+    const uint8_t* const s = src + t.src;
+    uint8_t* const d = dst + t.dst;
+    const uint32_t n = (uint32_t)t.size;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t toAligned = ( 16u - (uint32_t)( reinterpret_cast<uintptr_t>( d ) & 15u ) ) & 15u;
+    const uint32_t head = toAligned < n ? toAligned : n;
+    const uint32_t vectors = ( n - head ) >> 4;
+    const uint32_t tail = head + 16u * vectors;
+    if ( tid < head ) d[tid] = s[tid];
+    if ( tail + tid < n ) d[tail + tid] = s[tail + tid];
+
+    const uint8_t* const sb = s + head;
+    uint4* const dv = reinterpret_cast<uint4*>( d + head );
+    const uint32_t shift = (uint32_t)( reinterpret_cast<uintptr_t>( sb ) & 3u );
+    if ( ( reinterpret_cast<uintptr_t>( sb ) & 15u ) == 0 ) {
+        const uint4* const sv = reinterpret_cast<const uint4*>( sb );
+        for ( uint32_t k = tid; k < vectors; k += GATHER_THREADS ) dv[k] = sv[k];
+    } else if ( shift == 0 ) {
+        const uint32_t* const sw = reinterpret_cast<const uint32_t*>( sb );
+        for ( uint32_t k = tid; k < vectors; k += GATHER_THREADS ) {
+            const uint32_t* const w = sw + 4 * k;
+            dv[k] = make_uint4( w[0], w[1], w[2], w[3] );
+        }
+    } else {
+        const uint32_t* const sw = reinterpret_cast<const uint32_t*>( sb - shift );
+        for ( uint32_t k = tid; k < vectors; k += GATHER_THREADS ) {
+            const uint32_t* const w = sw + 4 * k;
+            const uint32_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3], w4 = w[4];
+            dv[k] = make_uint4( __builtin_amdgcn_alignbyte( w1, w0, shift ), __builtin_amdgcn_alignbyte( w2, w1, shift ),
+                                __builtin_amdgcn_alignbyte( w3, w2, shift ), __builtin_amdgcn_alignbyte( w4, w3, shift ) );
+        }
+    }
+}
 }  // namespace bz2gpu

@@ -38,6 +38,7 @@
 
 #include "../../include/mi355x_bz2.h"
 #include "bz2_host.hpp"
+#include "bz2_ranges.hpp"
 
 namespace mi355x
 {
@@ -51,14 +52,20 @@ struct Bz2Exception : public std::runtime_error
     int status;
 };
 
-[[noreturn]] static void
-fail( int status, const std::string& detail = {} )
+static Bz2Exception
+error( int status, const std::string& detail = {} )
 {
     std::string message = mi355x_bz2_status_string( status );
     if ( !detail.empty() ) {
         message += ": " + detail;
     }
-    throw Bz2Exception( status, message );
+    return Bz2Exception( status, message );
+}
+
+[[noreturn]] static void
+fail( int status, const std::string& detail = {} )
+{
+    throw error( status, detail );
 }
 
 /* ------------------------------------------------------------------------------------------------ compressed source */
@@ -471,6 +478,30 @@ public:
         return run;
     }
 
+    /** One launch of read_ranges: blocks that need not be consecutive, decoded once and gathered straight into the
+     * caller's destination.  It goes ahead of everything queued (somebody waits for it), publishes no run and is not a
+     * flight: the runs, flights and look-ahead of the sequential reader are not disturbed. */
+    struct RangesWork
+    {
+        const bz2gpu::RangeLaunch* launch{ nullptr };
+        std::vector<mi355x_bz2_gather_piece> pieces;
+        void* dst{ nullptr };
+        bool dstIsDevice{ false };
+        std::promise<void> done;     /* a Bz2Exception if a block or the device failed */
+    };
+
+    [[nodiscard]] std::future<void>
+    launchRanges( std::unique_ptr<RangesWork> ranges )
+    {
+        auto work = std::make_unique<Launch>();
+        auto result = ranges->done.get_future();
+        work->ranges = std::move( ranges );
+        const std::scoped_lock lock( m_queueMutex );
+        m_queue.push_front( std::move( work ) );
+        m_queueChanged.notify_all();
+        return result;
+    }
+
     [[nodiscard]] mi355x_bz2_reader_stats
     statistics() const
     {
@@ -492,6 +523,7 @@ private:
         bool lookAhead{ false };
         std::promise<RunPtr> promise;
         std::shared_ptr<std::atomic<bool> > done;
+        std::unique_ptr<RangesWork> ranges;    /* set: a read_ranges launch, none of the fields above are used */
     };
 
     struct Flight
@@ -735,6 +767,78 @@ private:
         };
 
         std::optional<Step> copying;    /* decoded, on its way to the host */
+
+        /* A read_ranges launch.  Ordering against the run of this context that may still be on its way to the host
+         * (`copying`): that copy reads the output buffer of the context's previous batch, on the context's copy stream.
+         * decode_batch_begin sees the copy and puts this batch into the context's other output buffer; while this batch
+         * decodes, the copy is waited for and its run published; decode_batch_end then leaves this batch's buffer as the
+         * context's output, which k_gather reads on the context's stream, and mi355x_bz2_gather_output returns only when
+         * the bytes are in the caller's destination.  Nothing reads this buffer afterwards, so the context's next batch
+         * may write into it at once. */
+        const auto runRanges = [&] ( RangesWork& work ) {
+            const auto t0 = std::chrono::steady_clock::now();
+            const auto& launch = *work.launch;
+            const auto n = (uint32_t)launch.bits.size();
+            std::vector<mi355x_bz2_block_result> results( n );
+            std::shared_ptr<const uint8_t> staging;   /* bounded residency: the packed windows, page-locked */
+            int rc = MI355X_BZ2_OK;
+            if ( m_resident ) {
+                rc = mi355x_bz2_decode_batch_begin( ctx, launch.bits.data(), n );
+            } else {
+                staging = m_hostBuffers->get( (size_t)launch.packedBytes, m_hostBuffers );
+                if ( !staging ) {
+                    rc = MI355X_BZ2_ERR_DEVICE;
+                } else {
+                    auto* const bytes = const_cast<uint8_t*>( staging.get() );
+                    uint64_t end = 0;
+                    for ( const auto& window : launch.windows ) {
+                        std::memset( bytes + end, 0, window.at - end );
+                        std::memcpy( bytes + window.at, m_source->bytes() + window.from, window.to - window.from );
+                        end = window.at + ( window.to - window.from );
+                    }
+                    rc = mi355x_bz2_set_input_host_async( ctx, bytes, launch.packedBytes );
+                    if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_decode_batch_begin( ctx, launch.packedBits.data(), n );
+                    m_uploadedBytes.fetch_add( launch.packedBytes, std::memory_order_relaxed );
+                }
+            }
+            if ( copying ) {
+                publish( *copying );
+                copying.reset();
+            }
+            uint64_t total = 0;
+            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_decode_batch_end( ctx, results.data(), &total );
+            std::exception_ptr failure;
+            if ( rc != MI355X_BZ2_OK ) {
+                failure = std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+            }
+            for ( uint32_t k = 0; !failure && k < n; ++k ) {
+                const auto& r = results[k];
+                if ( r.status != MI355X_BZ2_OK ) {
+                    failure = std::make_exception_ptr( error( r.status, "block at bit offset " + std::to_string( launch.bits[k] ) ) );
+                } else if ( r.decoded_size != launch.sizes[k] || r.data_offset != launch.outOffsets[k] ) {
+                    failure = std::make_exception_ptr(
+                        error( MI355X_BZ2_ERR_LOGIC, "the block index promises more bytes than the block decodes to" ) );
+                }
+            }
+            if ( !failure ) {
+                rc = mi355x_bz2_gather_output( ctx, work.pieces.data(), (uint32_t)work.pieces.size(), work.dst,
+                                               work.dstIsDevice ? 1 : 0 );
+                if ( rc != MI355X_BZ2_OK ) failure = std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+            }
+            staging.reset();
+            {
+                const std::scoped_lock lock( m_queueMutex );
+                ++m_batches;
+                m_blocksDecoded += n;
+                m_decodeSeconds += std::chrono::duration<double>( std::chrono::steady_clock::now() - t0 ).count();
+            }
+            if ( failure ) {
+                work.done.set_exception( failure );
+            } else {
+                work.done.set_value();
+            }
+        };
+
         while ( true ) {
             Step step;
             {
@@ -752,6 +856,10 @@ private:
                 }
                 step.work = std::move( m_queue.front() );
                 m_queue.pop_front();
+            }
+            if ( step.work->ranges ) {
+                runRanges( *step.work->ranges );
+                continue;
             }
             step.t0 = std::chrono::steady_clock::now();
             const auto n = (uint32_t)step.work->offsets.size();
@@ -1005,6 +1113,80 @@ public:
             read( Sink(), goal - m_position );
         }
         return tell();
+    }
+
+    /**
+     * pread of n ranges into `dst` (mi355x_bz2_reader_read_ranges): the blocks the ranges need are decoded once, in
+     * launches of at most a batch, and k_gather copies just the requested bytes.  The position, eof() and the runs of the
+     * sequential reader stay as they were; ranges behind the indexed part of the file are indexed first, as a forward
+     * seek would.
+     */
+    void
+    readRanges( const uint64_t* offsets, const uint64_t* sizes, size_t n, void* dst, bool dstIsDevice, uint64_t* nRead )
+    {
+        if ( closed() ) {
+            fail( MI355X_BZ2_ERR_CLOSED, "read_ranges on a closed reader" );
+        }
+        uint64_t furthest = 0;
+        for ( size_t i = 0; i < n; ++i ) {
+            if ( sizes[i] > 0 ) furthest = std::max( furthest, offsets[i] + std::min( sizes[i], ~uint64_t( 0 ) - offsets[i] ) );
+        }
+        if ( !m_index.sealed() && ( furthest > m_index.frontier() ) ) {
+            const size_t position = m_position;
+            const bool atEnd = m_atEnd;
+            try {
+                m_position = (size_t)m_index.frontier();
+                m_atEnd = false;
+                read( Sink(), (size_t)( furthest - m_position ) );
+            } catch ( ... ) {
+                m_position = position;
+                m_atEnd = atEnd;
+                throw;
+            }
+            m_position = position;
+            m_atEnd = atEnd;
+        }
+
+        /* the map as far as it is known; while it is not complete, its last entry is followed by the end of the open block */
+        auto map = m_index.snapshot();
+        if ( !m_index.sealed() && !map.empty() ) {
+            const auto open = m_index.locate( map.back().second );
+            if ( open.bitLength > 0 ) map.emplace_back( map.back().first + open.bitLength, map.back().second + open.byteLength );
+        }
+        auto plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, false, m_source->size() );
+        if ( plan.distinctBlocks > 0 && !scheduler().inputResident() ) {
+            plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, true, m_source->size() );
+        }
+        if ( !plan.pieces.empty() && dst == nullptr ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "read_ranges: no destination" );
+        }
+
+        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
+        for ( size_t l = 0; l < works.size(); ++l ) {
+            works[l] = std::make_unique<BatchScheduler::RangesWork>();
+            works[l]->launch = &plan.launches[l];
+            works[l]->dst = dst;
+            works[l]->dstIsDevice = dstIsDevice;
+        }
+        for ( const auto& piece : plan.pieces ) {
+            works[piece.launch]->pieces.push_back( { piece.src, piece.dst, piece.size } );
+        }
+        /* each to the front of the queue: the last one first, so that the first launch is taken first */
+        std::vector<std::future<void> > pending( works.size() );
+        for ( size_t l = works.size(); l-- > 0; ) {
+            pending[l] = scheduler().launchRanges( std::move( works[l] ) );
+        }
+        /* all of them are waited for (they write into dst) before the first failure in file order is reported */
+        std::exception_ptr failure;
+        for ( auto& launch : pending ) {
+            try {
+                launch.get();
+            } catch ( ... ) {
+                if ( !failure ) failure = std::current_exception();
+            }
+        }
+        if ( failure ) std::rethrow_exception( failure );
+        std::copy( plan.nRead.begin(), plan.nRead.end(), nRead );
     }
 
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
@@ -1394,6 +1576,16 @@ mi355x_bz2_reader_set_block_offsets( mi355x_bz2_reader* r, const uint64_t* bits,
             offsets.emplace( bits[i], bytes[i] );
         }
         reader.setBlockOffsets( offsets );
+    } );
+}
+
+int
+mi355x_bz2_reader_read_ranges( mi355x_bz2_reader* r, const uint64_t* offsets, const uint64_t* sizes, uint32_t n, void* dst,
+                               int dstIsDevice, uint64_t* nRead )
+{
+    if ( n > 0 && ( offsets == nullptr || sizes == nullptr || nRead == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.readRanges( offsets, sizes, n, dst, dstIsDevice != 0, nRead );
     } );
 }
 

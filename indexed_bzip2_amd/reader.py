@@ -163,6 +163,57 @@ class _IndexedBzip2FileParallel:
         self._require()
         self._check(N.lib().mi355x_bz2_reader_join_threads(self._h))
 
+    def read_ranges_into(self, offsets, sizes, out):
+        """pread of many ranges at once: range i = `sizes[i]` bytes at decoded offset `offsets[i]`, written to `out` at
+        sum(sizes[:i]).  `out` is a writable contiguous host buffer, or a contiguous torch.uint8 tensor on the reader's
+        device (the bytes then never pass through the host).  Every block the ranges need is decoded once; the read
+        position is not moved.  Returns the bytes read per range (numpy uint64; short only at the end of the file; the
+        bytes of `out` behind them are left as they were)."""
+        import numpy as np
+        self._require()
+        offsets = [int(o) for o in offsets]
+        sizes = [int(s) for s in sizes]
+        if len(offsets) != len(sizes):
+            raise ValueError(f"{len(offsets)} offsets but {len(sizes)} sizes")
+        if any(o < 0 for o in offsets) or any(s < 0 for s in sizes):
+            raise ValueError("offsets and sizes must not be negative")
+        n = len(offsets)
+        total = sum(sizes)
+        if getattr(out, "is_cuda", False):
+            import torch
+            if out.dtype != torch.uint8 or not out.is_contiguous():
+                raise ValueError("a device destination must be a contiguous torch.uint8 tensor")
+            capacity, device = out.numel(), 1
+            # the tensor may still be written by work queued on torch's stream (a fill): the gather comes after it
+            torch.cuda.current_stream(out.device).synchronize()
+            dst = ctypes.c_void_p(out.data_ptr())
+        else:
+            view = memoryview(out).cast("B")
+            if view.readonly:
+                raise ValueError("the destination buffer is read-only")
+            capacity, device = len(view), 0
+            dst = (ctypes.c_char * max(1, capacity)).from_buffer(view) if capacity > 0 else None
+        if capacity < total:
+            raise ValueError(f"the destination holds {capacity} bytes, the ranges need {total}")
+        offs = (ctypes.c_uint64 * max(1, n))(*offsets)
+        lens = (ctypes.c_uint64 * max(1, n))(*sizes)
+        got = (ctypes.c_uint64 * max(1, n))()
+        self._check(N.lib().mi355x_bz2_reader_read_ranges(self._h, offs, lens, n, dst, device, got))
+        return np.frombuffer(got, dtype=np.uint64, count=n).copy()
+
+    def read_ranges(self, ranges):
+        """[(offset, size), ...] -> one bytes object per range, as long as what the file holds of it."""
+        ranges = [(int(o), int(s)) for o, s in ranges]
+        if any(o < 0 or s < 0 for o, s in ranges):
+            raise ValueError("offsets and sizes must not be negative")
+        out = bytearray(sum(s for _, s in ranges))
+        got = self.read_ranges_into([o for o, _ in ranges], [s for _, s in ranges], out)
+        result, at = [], 0
+        for (_, size), n in zip(ranges, got):
+            result.append(bytes(out[at:at + int(n)]))
+            at += size
+        return result
+
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
         like the reference, whose serial reader checks and whose parallel reader does not)."""
@@ -223,6 +274,19 @@ class IndexedBzip2File(io.BufferedReader):
         self.streams_verified = self.bz2reader.streams_verified
 
         super().__init__(fobj, buffer_size=1024**2)
+
+    # positionless: the buffered reader's position and read-ahead stay valid
+    def read_ranges(self, ranges):
+        """See _IndexedBzip2FileParallel.read_ranges."""
+        if self.closed:
+            raise ValueError("I/O operation on closed file.")
+        return self.bz2reader.read_ranges(ranges)
+
+    def read_ranges_into(self, offsets, sizes, out):
+        """See _IndexedBzip2FileParallel.read_ranges_into."""
+        if self.closed:
+            raise ValueError("I/O operation on closed file.")
+        return self.bz2reader.read_ranges_into(offsets, sizes, out)
 
 
 builtins_open = builtins.open
