@@ -176,10 +176,10 @@ int mi355x_bz2_decode_batch( mi355x_bz2_ctx* ctx, const uint64_t* block_bit_offs
  * One batch per context can be in flight; contexts used in turn (begin(A), begin(B), end(A), begin(A'), end(B), ...)
  * overlap the latency-bound first kernels of one batch with the throughput kernels of the others.  The input of the NEXT
  * batch may be queued while one is in flight (mi355x_bz2_set_input_host_async: second input buffer, stream of its own).
- * A context drives up to nine HIP streams (up to four block groups and, for small batches, a side stream each for the
- * second k_mtf instance; one stream each for input copies, output copies and the device magic scan): set
- * GPU_MAX_HW_QUEUES (16 measured best for four contexts) before the HIP runtime starts, or streams share hardware queues
- * and serialize. */
+ * Block groups and, for small batches, the second k_mtf instance of a group run on streams of their own as far as the
+ * context's share of the hardware queues allows: GPU_MAX_HW_QUEUES (as the runtime reads it, 4 by default) divided by the
+ * contexts alive on the device.  A context whose share is one queue runs a batch as one group on its own stream.  Input
+ * copies, output copies and the device magic scan have a stream each. */
 int mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* ctx, const uint64_t* block_bit_offsets, uint32_t n_blocks );
 int mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* ctx, mi355x_bz2_block_result* results, uint64_t* total_decoded );
 

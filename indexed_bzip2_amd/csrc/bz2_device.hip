@@ -28,6 +28,7 @@
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
 #include "bz2_plan.hpp"
+#include "bz2_lanes.hpp"
 
 using namespace bz2gpu;
 
@@ -82,9 +83,11 @@ struct mi355x_bz2_ctx
     int device{ 0 };
     uint32_t flags{ 0 };
     hipStream_t stream{ nullptr };
-    hipStream_t gstream[MAX_GROUPS]{};   /* gstream[0] == stream; higher groups = more expensive blocks, higher priority */
+    /* the lanes of a batch (bz2_lanes.hpp), created when a layout first uses them: lane[0] == stream; highStream serves
+     * the expensive group's lane */
+    hipStream_t lane[MAX_LANES]{};
+    hipStream_t highStream{ nullptr };
     /* small batches: the two k_mtf instances of a group (each block belongs to one of them) side by side, see begin */
-    hipStream_t sideStream[MAX_GROUPS]{};
     hipEvent_t evFork[MAX_GROUPS]{}, evJoin[MAX_GROUPS]{};
     std::string lastError;
     mutable std::mutex mutex;
@@ -435,7 +438,9 @@ static_assert( N_KERNELS <= MI355X_BZ2_MAX_KERNELS );
  * launched before it.  A walk keeps one or two 3.6 MB tables per XCD in its 4 MB L2; walks of several block groups and
  * contexts side by side push each other's tables out.  In turn, and with
  * fewer workgroups each (64 per XCD instead of 256: the other kernels of the crowd fill the wave slots while the walk
- * waits for its gathers), a step of the four-context bench takes 67.5 instead of 74 ms. */
+ * waits for its gathers), a step of the four-context bench takes 67.5 instead of 74 ms.  With one hardware queue per
+ * context (bz2_lanes.hpp) the wait stops only the waiting context's queue, and the chain still pays: 65.3-66.1 ms per step
+ * with it, 101.0-101.6 without. */
 struct WalkChain
 {
     std::mutex mutex;
@@ -446,6 +451,22 @@ struct WalkChain
 };
 WalkChain g_walkChains[16];      /* by device: walks on different GPUs have nothing to do with each other */
 WalkChain& walkChainOf( int device ) { return g_walkChains[(unsigned)device % 16u]; }
+
+/** The hardware queues the HIP runtime of this process gives its streams: GPU_MAX_HW_QUEUES as the runtime read it when it
+ * started.  Read once, never set. */
+uint32_t
+queueBudget()
+{
+    static const uint32_t budget = queueBudgetOf( std::getenv( "GPU_MAX_HW_QUEUES" ) );
+    return budget;
+}
+
+/** This context's share of the queues now (bz2_lanes.hpp). */
+uint32_t
+lanesNow( const mi355x_bz2_ctx* c )
+{
+    return laneBudget( queueBudget(), (uint32_t)std::max( 1, walkChainOf( c->device ).liveContexts.load() ) );
+}
 
 /* record an event pair around the launches of one timing slot, so that every kernel gets its own device duration */
 #define TIMED( ctx, group, queue, index, ... )                                             \
@@ -517,6 +538,30 @@ queueOutput( mi355x_bz2_ctx* c, uint32_t n, const uint64_t* overflow )
     HIP_TRY( c, hipEventRecord( c->evStep[2], c->stream ) );
     HIP_TRY( c, hipGetLastError() );
     HIP_TRY( c, hipMemcpyAsync( c->hMeta, c->dMeta, (size_t)n * sizeof( BlockMeta ), hipMemcpyDeviceToHost, c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
+/** The streams and events of the lanes a batch uses, created the first time a layout asks for them. */
+int
+ensureLanes( mi355x_bz2_ctx* c, const LaneLayout& layout )
+{
+    for ( uint32_t l = 1; l < layout.lanes; ++l ) {
+        if ( (int)l == layout.highLane ) {
+            if ( c->highStream == nullptr ) {
+                /* numerically lower = higher priority: the expensive group's scan is the longest chain of a batch */
+                int leastPriority = 0, greatestPriority = 0;
+                (void)hipDeviceGetStreamPriorityRange( &leastPriority, &greatestPriority );
+                HIP_TRY( c, hipStreamCreateWithPriority( &c->highStream, hipStreamNonBlocking, greatestPriority ) );
+            }
+        } else if ( c->lane[l] == nullptr ) {
+            HIP_TRY( c, hipStreamCreateWithFlags( &c->lane[l], hipStreamNonBlocking ) );
+        }
+    }
+    for ( int g = 0; g < MAX_GROUPS; ++g ) {
+        if ( layout.sideLaneOf[g] < 0 || c->evFork[g] != nullptr ) continue;
+        HIP_TRY( c, hipEventCreateWithFlags( &c->evFork[g], hipEventDisableTiming ) );
+        HIP_TRY( c, hipEventCreateWithFlags( &c->evJoin[g], hipEventDisableTiming ) );
+    }
     return MI355X_BZ2_OK;
 }
 }  // namespace
@@ -625,17 +670,16 @@ mi355x_bz2_create( const mi355x_bz2_config* config, mi355x_bz2_ctx** out )
         mi355x_bz2_destroy( c );   /* releases whatever exists so far */
         return MI355X_BZ2_ERR_DEVICE;
     }
-    c->gstream[0] = c->stream;
+    c->lane[0] = c->stream;
     {
-        int leastPriority = 0, greatestPriority = 0;   /* numerically lower = higher priority */
-        (void)hipDeviceGetStreamPriorityRange( &leastPriority, &greatestPriority );
-        for ( int g = 1; g < MAX_GROUPS; ++g ) {
-            /* gstream[MAX_GROUPS - 1] serves the expensive group: its scan is the longest chain of a batch */
-            const int priority = g == MAX_GROUPS - 1 ? greatestPriority : ( leastPriority + greatestPriority ) / 2;
-            if ( hipStreamCreateWithPriority( &c->gstream[g], hipStreamNonBlocking, priority ) != hipSuccess ) {
-                mi355x_bz2_destroy( c );
-                return MI355X_BZ2_ERR_DEVICE;
-            }
+        /* the other lanes come with the first batch that uses them (ensureLanes), or now: see lanesAtCreation */
+        BatchPlan widest;
+        widest.groups = MAX_GROUPS;
+        widest.expensive = MAX_GROUPS - 1;
+        const uint32_t lanes = lanesAtCreation( queueBudget(), (uint32_t)walkChainOf( device ).liveContexts.load() );
+        if ( ensureLanes( c, layLanes( lanes, widest ) ) != MI355X_BZ2_OK ) {
+            mi355x_bz2_destroy( c );
+            return MI355X_BZ2_ERR_DEVICE;
         }
     }
     for ( auto& e : c->evGroupDone ) {
@@ -677,9 +721,10 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     walkChainOf( c->device ).liveContexts.fetch_sub( 1 );
     (void)hipSetDevice( c->device );
     if ( c->stream ) (void)hipStreamSynchronize( c->stream );
-    for ( int g = 1; g < MAX_GROUPS; ++g ) {
-        if ( c->gstream[g] ) (void)hipStreamSynchronize( c->gstream[g] );
+    for ( uint32_t l = 1; l < MAX_LANES; ++l ) {
+        if ( c->lane[l] ) (void)hipStreamSynchronize( c->lane[l] );
     }
+    if ( c->highStream ) (void)hipStreamSynchronize( c->highStream );
     freeScratch( c );
     freeRetired( c );
     c->upload.reset();   /* joins the copy thread (of the owner; sharers only drop their reference) before the memory goes */
@@ -712,14 +757,11 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
         if ( e ) (void)hipEventDestroy( e );
     }
     if ( c->stream ) (void)hipStreamDestroy( c->stream );
-    for ( int g = 1; g < MAX_GROUPS; ++g ) {
-        if ( c->gstream[g] ) (void)hipStreamDestroy( c->gstream[g] );
+    for ( uint32_t l = 1; l < MAX_LANES; ++l ) {
+        if ( c->lane[l] ) (void)hipStreamDestroy( c->lane[l] );
     }
+    if ( c->highStream ) (void)hipStreamDestroy( c->highStream );
     for ( int g = 0; g < MAX_GROUPS; ++g ) {
-        if ( c->sideStream[g] ) {
-            (void)hipStreamSynchronize( c->sideStream[g] );
-            (void)hipStreamDestroy( c->sideStream[g] );
-        }
         if ( c->evFork[g] ) (void)hipEventDestroy( c->evFork[g] );
         if ( c->evJoin[g] ) (void)hipEventDestroy( c->evJoin[g] );
     }
@@ -792,7 +834,8 @@ awaitInput( mi355x_bz2_ctx* c, uint64_t needed, const uint8_t** base, uint64_t* 
 /** Queue `size` bytes (host or device source) into a ctx-owned input copy, zero padded, on the input stream; no wait.
  * The next decode_batch_begin is ordered behind the copy.  While a batch is in flight the copy goes into the buffer
  * that batch does not read.  Copies of more than 64 MiB go in pieces, so that what other streams move is not queued
- * behind one long transfer. */
+ * behind one long transfer.  The copy keeps its stream also when the context has one lane (bz2_lanes.hpp): on the
+ * context's stream, behind its batch, the four-context bench took 76.4 ms per step instead of 65.3-66.1. */
 int
 queueInput( mi355x_bz2_ctx* c, const void* bytes, uint64_t size, hipMemcpyKind kind )
 {
@@ -1034,11 +1077,18 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     }
     const auto tInput = std::chrono::steady_clock::now();
 
-    /* groups, slots, work order and kernel forms: bz2_plan.hpp */
+    /* groups, slots, work order and kernel forms: bz2_plan.hpp; the streams they run on: bz2_lanes.hpp.  With one lane
+     * block groups would only run one after the other: the batch is one group */
     const bool crowd = walkChainOf( c->device ).liveContexts.load() >= 3;
-    c->plan = planBatch( offsets, n, inSize, crowd, switches.plan );
+    const uint32_t lanes = lanesNow( c );
+    PlanOverrides knobs = switches.plan;
+    if ( lanes == 1 ) knobs.noSplit = true;
+    c->plan = planBatch( offsets, n, inSize, crowd, knobs );
     c->trace = switches.trace;
     const BatchPlan& plan = c->plan;
+    const LaneLayout layout = layLanes( lanes, plan );
+    rc = ensureLanes( c, layout );
+    if ( rc != MI355X_BZ2_OK ) return rc;
     std::copy( plan.slotOf.begin(), plan.slotOf.end(), c->hSlotOf );
     std::copy( plan.offsets.begin(), plan.offsets.end(), c->hOffsets );
     std::copy( plan.order.begin(), plan.order.end(), c->hOrder );
@@ -1054,11 +1104,19 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     HIP_TRY( c, hipMemcpyAsync( c->dOrder, c->hOrder, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemcpyAsync( c->dSlotOf, c->hSlotOf, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipEventRecord( c->evStep[1], c->stream ) );
-    /* the expensive group runs on the high-priority stream */
-    auto streamOf = [&] ( int g ) { return g == plan.expensive ? c->gstream[MAX_GROUPS - 1] : c->gstream[g]; };
-    for ( int g = 1; g < plan.groups; ++g ) {
-        HIP_TRY( c, hipStreamWaitEvent( streamOf( g ), c->evStep[1], 0 ) );
+    /* the expensive group's lane is the high-priority stream */
+    auto streamOfLane = [&] ( int l ) { return l == layout.highLane ? c->highStream : c->lane[l]; };
+    auto streamOf = [&] ( int g ) { return streamOfLane( layout.laneOf[g] ); };
+    {
+        bool waits[MAX_LANES]{};   /* lanes other than the context's stream start behind the uploads, once each */
+        for ( int g = 0; g < plan.groups; ++g ) {
+            const int l = layout.laneOf[g];
+            if ( l != 0 && !waits[l] ) HIP_TRY( c, hipStreamWaitEvent( streamOfLane( l ), c->evStep[1], 0 ) );
+            waits[l] = true;
+        }
     }
+    int lastGroupOfLane[MAX_LANES];   /* in launch order: the join below waits for it */
+    for ( auto& g : lastGroupOfLane ) g = -1;
 
     const dim3 walkGrid( WALK_QUEUES * plan.walkWgsPerXcd );
     for ( int launch = 0; launch < plan.groups; ++launch ) {
@@ -1107,34 +1165,27 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
 #define MTF256( STRIDE, STREAM, INDEX ) \
         TIMED_LAUNCH( c, g, STREAM, INDEX, ( k_mtf<STRIDE, MTF_THREADS, REGS_MTF> ), dim3( m ), dim3( MTF_THREADS ), \
                       sizeof( MtfShared<STRIDE, MTF_THREADS> ), STREAM, meta, hmeta, sym, stb, lcol, m, order )
-        /* every block belongs to one of the two k_mtf instances (by its symbol count), the other returns at once */
-        if ( plan.mtfSide ) {
-            if ( c->sideStream[g] == nullptr ) {
-                HIP_TRY( c, hipStreamCreateWithFlags( &c->sideStream[g], hipStreamNonBlocking ) );
-                HIP_TRY( c, hipEventCreateWithFlags( &c->evFork[g], hipEventDisableTiming ) );
-                HIP_TRY( c, hipEventCreateWithFlags( &c->evJoin[g], hipEventDisableTiming ) );
-            }
-            hipStream_t side = c->sideStream[g];
+        /* every block belongs to one of the two k_mtf instances (by its symbol count), the other returns at once.  Small
+         * batches (plan.mtfSide) run them side by side when the layout gives the second one a lane */
+        const hipStream_t side = layout.sideLaneOf[g] >= 0 ? streamOfLane( layout.sideLaneOf[g] ) : q;
+        if ( side != q ) {
             HIP_TRY( c, hipEventRecord( c->evFork[g], q ) );
             HIP_TRY( c, hipStreamWaitEvent( side, c->evFork[g], 0 ) );
-            if ( plan.mtfSmallLanes == 1024 ) {
-                TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order );
-            } else if ( plan.mtfSmallLanes == 512 ) {
-                TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order );
-            } else {
-                MTF256( MTF_SMALL_STRIDE, side, 11 );
-            }
-            HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
-            if ( plan.mtfSmallLanes > 256 ) {
-                TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order );
-            } else {
-                MTF256( MTF_LANE_STRIDE, q, 1 );
-            }
-            HIP_TRY( c, hipStreamWaitEvent( q, c->evJoin[g], 0 ) );
+        }
+        if ( plan.mtfSmallLanes == 1024 ) {
+            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order );
+        } else if ( plan.mtfSmallLanes == 512 ) {
+            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order );
         } else {
-            MTF256( MTF_SMALL_STRIDE, q, 11 );
+            MTF256( MTF_SMALL_STRIDE, side, 11 );
+        }
+        if ( side != q ) HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
+        if ( plan.mtfSmallLanes > 256 ) {
+            TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order );
+        } else {
             MTF256( MTF_LANE_STRIDE, q, 1 );
         }
+        if ( side != q ) HIP_TRY( c, hipStreamWaitEvent( q, c->evJoin[g], 0 ) );
 #undef MTF256
         if ( plan.bwtSlices > 1 ) {
             uint32_t* const counts = c->dBwtCounts + (size_t)first * BWT_COUNTS_PER_BLOCK;
@@ -1162,12 +1213,14 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
         TIMED_LAUNCH( c, g, q, 6, k_replicate, dim3( m ), dim3( 256 ), 0, q, meta, rbuf, reinterpret_cast<uint8_t*>( stash ),
                       (size_t)SEG_STRIDE * STASH_BYTES );
         TIMED_LAUNCH( c, g, q, 7, k_rle<false>, dim3( m ), dim3( RLE_THREADS ), 0, q, meta, rbuf, (uint8_t*)nullptr );
-        if ( g >= 1 ) {
-            HIP_TRY( c, hipEventRecord( c->evGroupDone[g], q ) );
-        }
+        lastGroupOfLane[layout.laneOf[g]] = g;
     }
     HIP_TRY( c, hipGetLastError() );
-    for ( int g = 1; g < plan.groups; ++g ) {
+    /* the join: the output kernels on the context's stream wait for the last group of every other lane */
+    for ( uint32_t l = 1; l < MAX_LANES; ++l ) {
+        const int g = lastGroupOfLane[l];
+        if ( g < 0 ) continue;
+        HIP_TRY( c, hipEventRecord( c->evGroupDone[g], streamOfLane( (int)l ) ) );
         HIP_TRY( c, hipStreamWaitEvent( c->stream, c->evGroupDone[g], 0 ) );
     }
 

@@ -5,8 +5,8 @@
  * cost = estimated compressed size (distance to the next requested offset, or to the end of the input).
  * The group-start scan (k_hscan<1>) is one serial chain per block: a launch lasts as long as its LARGEST block.
  * Everything behind it (symbols, MTF, BWT, walk, RLE, CRC) is throughput work of about the same size for every block.
- * The batch is therefore cut into groups, each with its own HIP stream, such that the throughput work starts early and
- * never runs dry:
+ * The batch is therefore cut into groups, each on a HIP stream of its own where the queues allow it (bz2_lanes.hpp),
+ * such that the throughput work starts early and never runs dry:
  *   - the "expensive" group: blocks above 45 % of the largest cost, if they are a minority (incompressible blocks
  *     among text).  Its scan starts at once and runs beside everything else on a high-priority stream.
  *   - the other blocks, sorted by cost, in up to MAX_CHUNKS chunks of growing size.  All scans start together; a chunk
@@ -22,8 +22,8 @@
 
 namespace bz2gpu
 {
-constexpr uint32_t MAX_CHUNKS = 3;          /* groups of cheap blocks; one more stream than hardware queues (4 by
-                                               default) would serialize two groups */
+constexpr uint32_t MAX_CHUNKS = 3;          /* groups of cheap blocks; each gets a stream only if the context's share
+                                               of the hardware queues allows it (bz2_lanes.hpp) */
 constexpr int MAX_GROUPS = MAX_CHUNKS + 1;   /* + the expensive group */
 constexpr uint32_t BWT_SPLIT_BLOCKS = 640;   /* batches up to this size build their tables with several workgroups per block */
 constexpr uint32_t BWT_SPLIT_MAX = 8;        /* most slices per block */
