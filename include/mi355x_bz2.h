@@ -183,12 +183,14 @@ int mi355x_bz2_decode_batch( mi355x_bz2_ctx* ctx, const uint64_t* block_bit_offs
 int mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* ctx, const uint64_t* block_bit_offsets, uint32_t n_blocks );
 int mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* ctx, mi355x_bz2_block_result* results, uint64_t* total_decoded );
 
-/* Device pointer of the last batch's ragged output buffer (block i at data_offset). */
+/* Device pointer of the last batch's ragged output buffer (block i at data_offset).  After mi355x_bz2_decompress_buffers
+ * this function, mi355x_bz2_copy_output and mi355x_bz2_gather_output address that call's result instead (the buffers'
+ * bytes back to back), until the next batch or call on the context. */
 const void* mi355x_bz2_output_device( const mi355x_bz2_ctx* ctx );
 /* Copy [offset, offset+size) of the last batch's output to host memory (D2H). */
 int mi355x_bz2_copy_output( mi355x_bz2_ctx* ctx, uint64_t offset, uint64_t size, void* host_dst );
 /* The same copy in the background, on a stream of its own: _begin (after decode_batch_end, before the next
- * decode_batch_begin) queues it and returns, _end waits for the copy started last.  The context then writes its next
+ * decode_batch_begin; not for the result of mi355x_bz2_decompress_buffers: MI355X_BZ2_ERR_INVALID_ARGUMENT) queues it and returns, _end waits for the copy started last.  The context then writes its next
  * batch into a second output buffer, so the next decode_batch_begin may follow at once: the copy of batch k overlaps the
  * kernels of batch k + 1 (the reader's per-context loop; ParallelBZ2Reader gets the same overlap from its thread pool,
  * BlockFetcher.hpp:620-642).  `host_dst` should be page-locked and must stay valid until _end has returned.
@@ -236,6 +238,44 @@ typedef struct mi355x_bz2_gather_piece {
 } mi355x_bz2_gather_piece;
 int mi355x_bz2_gather_output( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, uint32_t n_pieces,
                               void* dst, int dst_is_device );
+
+/* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
+ * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
+ * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
+ * the status it fails with and error_offset_bits the bit offset (in the buffer) of the block or header where it does;
+ * n_blocks and n_streams then count the blocks and streams that decoded in front of the failure (decoded_size is 0).
+ * One bad buffer never fails the others; the return value is non-OK only for argument or device failures.
+ * The buffers are copied (pageable memory is fine) in upload windows of up to 1 GiB, cut between buffers, into the
+ * context's input: the call REPLACES the input made resident with mi355x_bz2_set_input_*, so a caller that also runs
+ * decode_batch on this context sets its input again afterwards.  A window that does not fit on the device fails the call
+ * with MI355X_BZ2_ERR_INVALID_ARGUMENT (a single buffer that large is for the reader, which streams).  Blocks are decoded in launches of at most max_launch_blocks (0 = 512; 10.1 MB of scratch per block), each
+ * block bounded by its own buffer's end, so a damaged or truncated buffer reads none of its neighbour's bytes.
+ * The output: buffer i's bytes are [output_offset, output_offset + decoded_size) of mi355x_bz2_output_device (read with
+ * mi355x_bz2_copy_output / mi355x_bz2_gather_output; mi355x_bz2_copy_output_begin refuses it), in input order, back to
+ * back; a failed buffer takes 0 bytes.  The
+ * context keeps that buffer (grown, never shrunk) and it is valid until the next batch or call on the context.
+ * *total_decoded = the sum of decoded_size.
+ * One difference from the reader: a non-empty buffer that does not start with a stream header ("BZh1".."BZh9") fails
+ * with MI355X_BZ2_ERR_STREAM_HEADER; the reader checks the header only once its magic scan has found a block, and reads
+ * such bytes as an empty file if it finds none.  A 0-byte buffer decodes to 0 bytes, as in both.
+ * Differences from CPython's bz2.decompress, which are the reader's:
+ *   - bytes behind the last end-of-stream block that do not start a stream header are ignored and flagged in
+ *     trailing_garbage (bz2.decompress raises OSError);
+ *   - a stream header with no block magic behind it ("BZh9" alone) decodes to 0 bytes (bz2.decompress raises EOFError);
+ *   - randomised blocks fail with MI355X_BZ2_ERR_RANDOMIZED (bz2.decompress decodes them).
+ * No reference counterpart. */
+typedef struct mi355x_bz2_buffer_result {
+    uint64_t output_offset;      /* of this buffer's bytes in the context's output */
+    uint64_t decoded_size;
+    uint64_t error_offset_bits;  /* magic of the failing block, relative to the buffer (0 if OK) */
+    uint32_t n_blocks, n_streams;
+    int32_t  trailing_garbage;   /* bytes behind the last end-of-stream block were ignored */
+    int32_t  status;             /* mi355x_bz2_status, as the reader would raise it for these bytes */
+} mi355x_bz2_buffer_result;
+
+int mi355x_bz2_decompress_buffers( mi355x_bz2_ctx* ctx, const uint8_t* const* buffers, const uint64_t* sizes,
+                                   uint32_t n, uint32_t max_launch_blocks /* 0 = 512 */,
+                                   mi355x_bz2_buffer_result* results, uint64_t* total_decoded );
 
 /* ------------------------------------------------------------------------------------------------ 2. magic scan */
 

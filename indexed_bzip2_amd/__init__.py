@@ -15,6 +15,7 @@ import os as _os
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
 from ._native import Bz2Error, Decoder, find_magic, lib, status_string, warmup  # noqa: F401
+from .buffers import decompress, decompress_many, decompress_many_to_tensor  # noqa: F401
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401
                      write_block_offsets)
 

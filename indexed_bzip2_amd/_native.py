@@ -87,6 +87,15 @@ class GatherPiece(ctypes.Structure):
     _fields_ = [("src_offset", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("size", ctypes.c_uint64)]
 
 
+class BufferResult(ctypes.Structure):
+    _fields_ = [("output_offset", ctypes.c_uint64), ("decoded_size", ctypes.c_uint64),
+                ("error_offset_bits", ctypes.c_uint64), ("n_blocks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
+                ("trailing_garbage", ctypes.c_int32), ("status", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
 # every symbol include/mi355x_bz2.h declares: (name, restype, argtypes)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
@@ -145,6 +154,8 @@ SYMBOLS = [
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
     ("mi355x_bz2_reader_statistics", ctypes.c_int, [_vp, ctypes.POINTER(ReaderStats)]),
+    ("mi355x_bz2_decompress_buffers", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_uint32,
+                                                      ctypes.c_uint32, ctypes.POINTER(BufferResult), _u64p]),
     ("mi355x_bz2_decode_chunk", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                ctypes.c_uint64, ctypes.POINTER(ChunkResult), ctypes.POINTER(BlockResult),
                                                ctypes.c_uint32, ctypes.POINTER(ChunkBoundary), ctypes.c_uint32]),
@@ -204,6 +215,14 @@ def find_magic(data: bytes, magic: int = MAGIC_BLOCK, threads: int = 0):
     arr = (ctypes.c_uint64 * max(1, n))()
     L.mi355x_bz2_find_magic(data, len(data), magic, arr, n, threads)
     return list(arr[:n])
+
+
+def _byte_view(obj) -> memoryview:
+    """A flat unsigned-byte view of any C-contiguous buffer-protocol object (bytes, bytearray, memoryview, numpy)."""
+    view = memoryview(obj)
+    if not view.c_contiguous:
+        raise ValueError("buffers must be C-contiguous")
+    return view.cast("B") if view.format != "B" or view.ndim != 1 else view
 
 
 class _KeptInputs(tuple):
@@ -310,6 +329,21 @@ class Decoder:
         return (d, [blocks[i].as_dict() for i in range(min(cap, d["n_blocks"]))],
                 [(footers[i].encoded_offset_bits, footers[i].decoded_offset) for i in range(min(cap, d["n_footers"]))],
                 payload)
+
+    def decompress_buffers(self, buffers, max_launch_blocks: int = 0):
+        """mi355x_bz2_decompress_buffers over C-contiguous byte buffers: returns (list of BufferResult dicts, total).
+        The bytes are then [output_offset, output_offset + decoded_size) of the output: copy_output, gather_output,
+        output_device_ptr (copy_output_begin refuses it).  Replaces the decoder's input (set_input)."""
+        import numpy as np
+        arrays = [np.frombuffer(_byte_view(b), dtype=np.uint8) for b in buffers]   # no copy, read-only is fine
+        n = len(arrays)
+        ptrs = (ctypes.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrays])
+        sizes = (ctypes.c_uint64 * max(1, n))(*[a.size for a in arrays])
+        res = (BufferResult * max(1, n))()
+        total = ctypes.c_uint64()
+        self._check(lib().mi355x_bz2_decompress_buffers(self._h, ptrs, sizes, n, max_launch_blocks, res,
+                                                        ctypes.byref(total)))
+        return [res[i].as_dict() for i in range(n)], total.value
 
     def find_magic(self, magic: int = MAGIC_BLOCK):
         """Magic-bit scan of the resident input on the GPU (k_find_magic)."""

@@ -1,0 +1,34 @@
+/**
+ * bz2_ctx.hpp -- entry points of the decoder context (bz2_device.hip) that other host code of the library uses but the
+ * C ABI does not export.
+ */
+#pragma once
+
+#include <cstdint>
+#include <string>
+
+#include "../../include/mi355x_bz2.h"
+
+namespace mi355x
+{
+/** mi355x_bz2_decode_batch_begin with an optional end of the input per block: the scan kernels read block i's bits only
+ * up to min( input size, endBytes[i] ) bytes, as if the input ended there.  nullptr: the whole input (the public form). */
+int decodeBatchBegin( mi355x_bz2_ctx* ctx, const uint64_t* offsets, const uint64_t* endBytes, uint32_t n );
+
+/** A context-owned device buffer of at least `size` bytes, grown (its first `keep` bytes copied along) and kept across
+ * calls. */
+int resultBuffer( mi355x_bz2_ctx* ctx, uint64_t size, uint64_t keep, uint8_t** device );
+
+/** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
+ * `size` bytes of the result buffer. */
+int publishResult( mi355x_bz2_ctx* ctx, uint64_t size );
+
+/** The device ordinal the context was created on. */
+int deviceOf( const mi355x_bz2_ctx* ctx );
+
+/** Bytes of the larger of the context's own input copies (reused by the next mi355x_bz2_set_input_host). */
+uint64_t inputCapacity( const mi355x_bz2_ctx* ctx );
+
+/** What mi355x_bz2_last_error returns from now on. */
+void setLastError( mi355x_bz2_ctx* ctx, const std::string& message );
+}  // namespace mi355x

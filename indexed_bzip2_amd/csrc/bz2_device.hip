@@ -29,6 +29,7 @@
 #include "bz2_walk.hip.h"
 #include "bz2_plan.hpp"
 #include "bz2_lanes.hpp"
+#include "bz2_ctx.hpp"
 
 using namespace bz2gpu;
 
@@ -156,6 +157,8 @@ struct mi355x_bz2_ctx
     uint64_t* hTotals{ nullptr };     /* pinned */
     BlockMeta* hMeta{ nullptr };       /* pinned */
     uint64_t* hOffsets{ nullptr };     /* pinned */
+    uint64_t* dEnds{ nullptr };       /* per-block end of the input in bytes, by slot (decodeBatchBegin with ends only) */
+    uint64_t* hEnds{ nullptr };       /* pinned */
 
     /* output: dOut holds the last finished batch.  A caller that copies it out in the background
      * (mi355x_bz2_copy_output_begin) gets the next batch written into a second buffer, so that the copy and the next
@@ -192,6 +195,10 @@ struct mi355x_bz2_ctx
     uint8_t* dGatherStage{ nullptr };
     uint8_t* hGatherStage{ nullptr };
     uint64_t gatherStageCap{ 0 };
+
+    /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back, grow-only (mi355x::resultBuffer) */
+    uint8_t* dResult{ nullptr };
+    uint64_t resultCap{ 0 };
 
     CrcConsts crc{};
     hipEvent_t ev[MAX_GROUPS][2 * MI355X_BZ2_MAX_KERNELS]{};   /* [group][2 * kernel + {start, end}] */
@@ -293,7 +300,7 @@ freeScratch( mi355x_bz2_ctx* c, bool now = true )
     c->dHmeta = nullptr; c->dSmeta = nullptr; c->dHtab = nullptr; c->dGpos = nullptr; c->dL = nullptr; c->dTab = nullptr;
     c->dR = nullptr; c->dSegLen = nullptr; c->dSegSucc = nullptr; c->dSegCont = nullptr;
     c->dChain = nullptr; c->dStash = nullptr; c->dPlan = nullptr; c->dWalkBlk = nullptr; c->dWalkPre = nullptr;
-    c->hOrder = nullptr; c->hSlotOf = nullptr; c->hMeta = nullptr; c->hOffsets = nullptr;
+    c->hOrder = nullptr; c->hSlotOf = nullptr; c->hMeta = nullptr; c->hOffsets = nullptr; c->dEnds = nullptr; c->hEnds = nullptr;
     c->dSlotOf = nullptr; c->dTotals = nullptr; c->hTotals = nullptr; c->dBwtCounts = nullptr;
     c->capacity = 0;
 }
@@ -343,11 +350,13 @@ ensureScratch( mi355x_bz2_ctx* c, uint32_t nBlocks )
     const size_t oSlotOf = reserve( deviceBytes, (size_t)cap * sizeof( uint32_t ) );
     const size_t oTotals = reserve( deviceBytes, 2 * sizeof( uint64_t ) );
     const size_t oBwtCounts = reserve( deviceBytes, (size_t)std::min( cap, BWT_SPLIT_BLOCKS ) * BWT_COUNTS_PER_BLOCK * sizeof( uint32_t ) );
+    const size_t oEnds = reserve( deviceBytes, (size_t)cap * sizeof( uint64_t ) );
     const size_t hOrderAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
     const size_t hSlotOfAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
     const size_t hMetaAt = reserve( hostBytes, (size_t)cap * sizeof( BlockMeta ) );
     const size_t hOffsetsAt = reserve( hostBytes, (size_t)cap * sizeof( uint64_t ) );
     const size_t hTotalsAt = reserve( hostBytes, 2 * sizeof( uint64_t ) );
+    const size_t hEndsAt = reserve( hostBytes, (size_t)cap * sizeof( uint64_t ) );
 
     const auto tAlloc = std::chrono::steady_clock::now();
     HIP_TRY( c, hipMalloc( &c->dScratch, deviceBytes ) );
@@ -385,11 +394,13 @@ ensureScratch( mi355x_bz2_ctx* c, uint32_t nBlocks )
     c->dSlotOf = reinterpret_cast<uint32_t*>( d + oSlotOf );
     c->dTotals = reinterpret_cast<uint64_t*>( d + oTotals );
     c->dBwtCounts = reinterpret_cast<uint32_t*>( d + oBwtCounts );
+    c->dEnds = reinterpret_cast<uint64_t*>( d + oEnds );
     c->hOrder = reinterpret_cast<uint32_t*>( h + hOrderAt );
     c->hSlotOf = reinterpret_cast<uint32_t*>( h + hSlotOfAt );
     c->hMeta = reinterpret_cast<BlockMeta*>( h + hMetaAt );
     c->hOffsets = reinterpret_cast<uint64_t*>( h + hOffsetsAt );
     c->hTotals = reinterpret_cast<uint64_t*>( h + hTotalsAt );
+    c->hEnds = reinterpret_cast<uint64_t*>( h + hEndsAt );
     c->capacity = cap;
     c->scratchBytes = deviceBytes;
     c->scratchHostBytes = hostBytes;
@@ -742,6 +753,7 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     (void)hipHostFree( c->hGatherTiles );
     (void)hipFree( c->dGatherStage );
     (void)hipHostFree( c->hGatherStage );
+    (void)hipFree( c->dResult );
     if ( c->copyStream ) (void)hipStreamSynchronize( c->copyStream );
     for ( auto& buffer : c->out ) {
         (void)hipFree( buffer.bytes );
@@ -1038,6 +1050,14 @@ mi355x_bz2_decode_batch( mi355x_bz2_ctx* c, const uint64_t* offsets, uint32_t n,
 int
 mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint32_t n )
 {
+    return mi355x::decodeBatchBegin( c, offsets, nullptr, n );
+}
+
+}  // extern "C"
+
+int
+mi355x::decodeBatchBegin( mi355x_bz2_ctx* c, const uint64_t* offsets, const uint64_t* endBytes, uint32_t n )
+{
     if ( c == nullptr || ( n > 0 && offsets == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     if ( c->pendingBlocks != 0 ) {
@@ -1092,6 +1112,9 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     std::copy( plan.slotOf.begin(), plan.slotOf.end(), c->hSlotOf );
     std::copy( plan.offsets.begin(), plan.offsets.end(), c->hOffsets );
     std::copy( plan.order.begin(), plan.order.end(), c->hOrder );
+    if ( endBytes != nullptr ) {
+        for ( uint32_t i = 0; i < n; ++i ) c->hEnds[plan.slotOf[i]] = endBytes[i];
+    }
 
     for ( auto& bits : c->launched ) bits = 0;
     if ( c->inPending ) {
@@ -1103,6 +1126,9 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     HIP_TRY( c, hipMemcpyAsync( c->dOffsets, c->hOffsets, (size_t)n * sizeof( uint64_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemcpyAsync( c->dOrder, c->hOrder, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemcpyAsync( c->dSlotOf, c->hSlotOf, (size_t)n * sizeof( uint32_t ), hipMemcpyHostToDevice, c->stream ) );
+    if ( endBytes != nullptr ) {
+        HIP_TRY( c, hipMemcpyAsync( c->dEnds, c->hEnds, (size_t)n * sizeof( uint64_t ), hipMemcpyHostToDevice, c->stream ) );
+    }
     HIP_TRY( c, hipEventRecord( c->evStep[1], c->stream ) );
     /* the expensive group's lane is the high-priority stream */
     auto streamOfLane = [&] ( int l ) { return l == layout.highLane ? c->highStream : c->lane[l]; };
@@ -1147,15 +1173,16 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
             HuffTables* const htab = c->dHtab + first;
             uint32_t* const gpos = c->dGpos + (size_t)first * GPOS_STRIDE;
             const auto* const inWords = reinterpret_cast<const uint32_t*>( inBase );
+            const uint64_t* const ends = endBytes != nullptr ? c->dEnds + first : nullptr;
             if ( plan.scanWaves[g] == 8 ) {
                 TIMED_LAUNCH( c, g, q, 12, k_hscan_spec<8>, dim3( m ), dim3( 512 ), 0, q, inWords, inSize, c->dOffsets + first,
-                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
+                              ends, meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
             } else if ( plan.scanWaves[g] == 4 ) {
                 TIMED_LAUNCH( c, g, q, 12, k_hscan_spec<4>, dim3( m ), dim3( 256 ), 0, q, inWords, inSize, c->dOffsets + first,
-                              meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
+                              ends, meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
             } else {
                 TIMED_LAUNCH( c, g, q, 12, ( k_hscan<1, REGS_SCAN> ), dim3( m ), dim3( 64 ), sizeof( ScanShared<1> ), q, inWords,
-                              inSize, c->dOffsets + first, meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
+                              inSize, c->dOffsets + first, ends, meta, hmeta, smeta, sel, stb, htab, gpos, m, order );
             }
 #define HSYM( T ) TIMED_LAUNCH( c, g, q, 13, k_hsym<T>, dim3( ( MAX_SCAN_GROUPS + ( T ) * SYM_CHUNKS - 1 ) / ( ( T ) * SYM_CHUNKS ), m ), dim3( T ), \
                                 sizeof( SymShared<T> ), q, inWords, meta, hmeta, smeta, sel, htab, gpos, sym )
@@ -1247,6 +1274,63 @@ mi355x_bz2_decode_batch_begin( mi355x_bz2_ctx* c, const uint64_t* offsets, uint3
     }
     return MI355X_BZ2_OK;
 }
+
+int
+mi355x::resultBuffer( mi355x_bz2_ctx* c, uint64_t size, uint64_t keep, uint8_t** device )
+{
+    if ( c == nullptr || device == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const std::scoped_lock lock( c->mutex );
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    if ( size > c->resultCap || c->dResult == nullptr ) {
+        /* the output functions may still address the old buffer: nothing reads it once the stream is idle */
+        HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+        const uint64_t cap = std::max<uint64_t>( { size, c->resultCap + c->resultCap / 2, uint64_t( 1 ) << 20 } );
+        if ( c->dOut == c->dResult ) c->dOut = c->out[c->outCurrent].bytes;
+        uint8_t* grown = nullptr;
+        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &grown ), cap ) );
+        if ( keep != 0 && c->dResult != nullptr ) {
+            HIP_TRY( c, hipMemcpyAsync( grown, c->dResult, std::min( keep, c->resultCap ), hipMemcpyDeviceToDevice, c->stream ) );
+            HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+        }
+        retire( c, c->dResult, c->resultCap, false, cap );
+        c->dResult = grown;
+        c->resultCap = cap;
+    }
+    *device = c->dResult;
+    return MI355X_BZ2_OK;
+}
+
+int
+mi355x::deviceOf( const mi355x_bz2_ctx* c )
+{
+    return c->device;
+}
+
+uint64_t
+mi355x::inputCapacity( const mi355x_bz2_ctx* c )
+{
+    const std::scoped_lock lock( c->mutex );
+    return std::max( c->in[0].capacity, c->in[1].capacity );
+}
+
+void
+mi355x::setLastError( mi355x_bz2_ctx* c, const std::string& message )
+{
+    const std::scoped_lock lock( c->mutex );
+    c->lastError = message;
+}
+
+int
+mi355x::publishResult( mi355x_bz2_ctx* c, uint64_t size )
+{
+    if ( c == nullptr || size > c->resultCap ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const std::scoped_lock lock( c->mutex );
+    c->dOut = c->dResult;   /* until the next decode_batch_begin chooses its output buffer again */
+    c->outSize = size;
+    return MI355X_BZ2_OK;
+}
+
+extern "C" {
 
 int
 mi355x_bz2_decode_batch_end( mi355x_bz2_ctx* c, mi355x_bz2_block_result* results, uint64_t* totalDecoded )
@@ -1368,6 +1452,11 @@ mi355x_bz2_copy_output_begin( mi355x_bz2_ctx* c, uint64_t offset, uint64_t size,
     if ( c == nullptr || ( hostDst == nullptr && size > 0 ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     if ( offset + size > c->outSize || c->pendingBlocks != 0 ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    if ( c->dResult != nullptr && c->dOut == c->dResult ) {
+        /* the background copy belongs to the double-buffered batch output; a decompress_buffers result is not in it */
+        c->lastError = "copy_output_begin: the output is a decompress_buffers result: use mi355x_bz2_copy_output";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
     HIP_TRY( c, hipSetDevice( c->device ) );
     auto& buffer = c->out[c->outCurrent];
     if ( c->copyStream == nullptr ) HIP_TRY( c, hipStreamCreateWithFlags( &c->copyStream, hipStreamNonBlocking ) );
@@ -1440,7 +1529,7 @@ mi355x_bz2_device_memory( const mi355x_bz2_ctx* c, uint64_t* scratchBytes, uint6
     if ( c == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     if ( scratchBytes != nullptr ) *scratchBytes = c->scratchBytes;
-    if ( outputBytes != nullptr ) *outputBytes = c->out[0].capacity + c->out[1].capacity;
+    if ( outputBytes != nullptr ) *outputBytes = c->out[0].capacity + c->out[1].capacity + c->resultCap;
     return MI355X_BZ2_OK;
 }
 

@@ -680,6 +680,18 @@ scan_build_rows( uint32_t rw, bool nearEnd, ScanSlot& slot, const uint8_t* lenlu
 #undef SCAN_CASE
 }
 
+/** End of the input for block b: the whole input, or the block's own end (end_bytes, indexed like offsets; a batch of
+ * unrelated buffers packed back to back, mi355x_bz2_decompress_buffers).  Everything behind scan_parse works on the
+ * block-relative size_bits it derives from this, so a block never reads a neighbour's bits as its own (DESIGN.md,
+ * "Many independent buffers"). */
+__device__ __forceinline__ uint64_t
+block_end( uint64_t in_size_bytes, const uint64_t* __restrict__ end_bytes, uint32_t b )
+{
+    if ( end_bytes == nullptr ) return in_size_bytes;
+    const uint64_t end = end_bytes[b];
+    return end < in_size_bytes ? end : in_size_bytes;
+}
+
 /* W = wavefronts per SIMD that the kernel's registers must leave room for.  Its LDS alone allows 2.5 per SIMD, and the
  * compiler, seeing that, spends 172 registers per lane: fine for this kernel by itself, but two such waves on a SIMD leave
  * no room for ONE wave of k_mtf or k_link2 (169 to 171 registers) of the batches beside it, and only 2 048 of a big batch's
@@ -690,6 +702,7 @@ __global__ __launch_bounds__( 64 * K ) __attribute__( ( amdgpu_waves_per_eu( W, 
 k_hscan( const uint32_t* __restrict__ in_words,
          uint64_t                     in_size_bytes,
          const uint64_t* __restrict__ offsets,
+         const uint64_t* __restrict__ end_bytes,
          BlockMeta* __restrict__      meta,
          HuffMeta* __restrict__       hmeta,
          ScanMeta* __restrict__       smeta,
@@ -713,7 +726,7 @@ k_hscan( const uint32_t* __restrict__ in_words,
     const uint64_t start = offsets[b];
 
     if ( wave == 0 ) {
-        scan_parse<K>( sh, in_words, in_size_bytes, start, sel, stb_buf, tab_buf + b, b, lane );
+        scan_parse<K>( sh, in_words, block_end( in_size_bytes, end_bytes, b ), start, sel, stb_buf, tab_buf + b, b, lane );
         __threadfence_block();   /* the selectors are read back below */
     }
     scan_sync<K>();
@@ -930,6 +943,7 @@ __global__ __launch_bounds__( 64 * K ) void
 k_hscan_spec( const uint32_t* __restrict__ in_words,
               uint64_t                     in_size_bytes,
               const uint64_t* __restrict__ offsets,
+              const uint64_t* __restrict__ end_bytes,
               BlockMeta* __restrict__      meta,
               HuffMeta* __restrict__       hmeta,
               ScanMeta* __restrict__       smeta,
@@ -952,7 +966,7 @@ k_hscan_spec( const uint32_t* __restrict__ in_words,
     const uint64_t start = offsets[b];
 
     if ( wave == 0 ) {
-        scan_parse<1>( sh, in_words, in_size_bytes, start, sel, stb_buf, tab_buf + b, b, lane );
+        scan_parse<1>( sh, in_words, block_end( in_size_bytes, end_bytes, b ), start, sel, stb_buf, tab_buf + b, b, lane );
         __threadfence_block();   /* the selectors are read back below */
     }
     __syncthreads();
