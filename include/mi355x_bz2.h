@@ -277,6 +277,52 @@ int mi355x_bz2_decompress_buffers( mi355x_bz2_ctx* ctx, const uint8_t* const* bu
                                    uint32_t n, uint32_t max_launch_blocks /* 0 = 512 */,
                                    mi355x_bz2_buffer_result* results, uint64_t* total_decoded );
 
+/* bzip2 compression of many buffers (ZIP members, Avro / Hadoop blocks, one blob per sample) in shared GPU launches.
+ * Buffer i becomes one complete single-stream .bz2 ("BZh<level>", its blocks, the end-of-stream block) that libbz2 and
+ * this library decode back to exactly buffers[i]; an empty buffer becomes the 14-byte empty stream.  `level` 1..9 has
+ * bzip2's meaning (blocks of 100k x level RLE1 bytes) and the blocks are cut exactly where libbz2 cuts them
+ * (mi355x_bz2_plan_compress_blocks), so the block index matches that of libbz2's file of the same bytes; the encoded
+ * bits may differ from libbz2's (Huffman tables are chosen independently; no randomised blocks).
+ * Blocks of all buffers are encoded together in launches of at most max_launch_blocks (0 = 512) blocks and a device
+ * memory budget (12 GiB; bz2_compress.hpp); a buffer whose blocks span several launches comes out byte-identical to one
+ * compressed in a single launch.  Everything from RLE1 to bit packing runs in HIP kernels; the host only plans the
+ * block cuts and places the blocks.  The outputs go back to back, in input order, into the context's result buffer:
+ * buffer i is [output_offset, output_offset + compressed_size) of mi355x_bz2_output_device, read with
+ * mi355x_bz2_copy_output or mi355x_bz2_gather_output (mi355x_bz2_copy_output_begin refuses it); valid until the next
+ * batch or call on the context.  *total_compressed = the sum of compressed_size.  The encoder's device scratch is
+ * allocated by the first call and kept (mi355x_bz2_encoder_memory); the decoder's scratch does not change.  Returns
+ * MI355X_BZ2_ERR_INVALID_ARGUMENT for a level outside 1..9.  No reference counterpart (the reference only decodes). */
+typedef struct mi355x_bz2_compress_result {
+    uint64_t output_offset;      /* of this buffer's stream in the context's output */
+    uint64_t compressed_size;    /* bytes */
+    uint64_t map_first;          /* where this buffer's entries start in the block map of the call */
+    uint32_t n_blocks;           /* data blocks */
+    uint32_t map_entries;        /* entries of its block map (mi355x_bz2_compress_block_map) */
+    int32_t  status;             /* mi355x_bz2_status */
+    int32_t  reserved;
+} mi355x_bz2_compress_result;
+
+int mi355x_bz2_compress_buffers( mi355x_bz2_ctx* ctx, const uint8_t* const* buffers, const uint64_t* sizes, uint32_t n,
+                                 int level, uint32_t max_launch_blocks /* 0 = 512 */,
+                                 mi355x_bz2_compress_result* results, uint64_t* total_compressed );
+
+/* The block map of buffer `buffer` of the last compress call: what mi355x_bz2_reader_block_offsets returns for its
+ * output (bit offsets in the buffer's stream, decoded byte offsets): every data block, the end-of-stream block and the
+ * end of the file -- {0: 0} for an empty buffer.  *count = the number of entries; at most `capacity` are written.
+ * Ready for mi355x_bz2_reader_set_block_offsets. */
+int mi355x_bz2_compress_block_map( mi355x_bz2_ctx* ctx, uint32_t buffer, uint64_t* bit_offsets, uint64_t* byte_offsets,
+                                   uint64_t capacity, uint64_t* count );
+
+/* Device bytes of the encoder's scratch (0 until the context's first compress call). */
+int mi355x_bz2_encoder_memory( mi355x_bz2_ctx* ctx, uint64_t* bytes );
+
+/* Host only, no GPU: the input sizes of the blocks libbz2 cuts `size` bytes into at `level` (RLE1 pieces -- runs of one
+ * byte cut every 255 bytes, L < 4 bytes taking L RLE1 bytes, L >= 4 taking 5 -- and a block ending with the first piece
+ * that brings its RLE1 size to 100000 x level - 19 or more).  *count = the number of blocks; at most `capacity` sizes
+ * are written. */
+int mi355x_bz2_plan_compress_blocks( const uint8_t* data, uint64_t size, int level, uint64_t* block_sizes,
+                                     uint64_t capacity, uint64_t* count );
+
 /* ------------------------------------------------------------------------------------------------ 2. magic scan */
 
 #define MI355X_BZ2_MAGIC_BLOCK 0x314159265359ULL   /* bzip2.hpp:103 */

@@ -1,4 +1,5 @@
-"""indexed_bzip2_amd -- MI355X-native parallel bzip2 block decoder behind the indexed_bzip2 API.
+"""indexed_bzip2_amd -- MI355X-native parallel bzip2 block decoder behind the indexed_bzip2 API, and a GPU encoder
+(compress, compress_many).
 
 Host-side mirror of python/indexed_bzip2/indexed_bzip2.pyx (open, IndexedBzip2File, ...) over the C ABI of
 include/mi355x_bz2.h.  All decoding happens in hand-written HIP kernels on gfx950; there is no CPU fallback.
@@ -14,8 +15,10 @@ import os as _os
 # existing setting wins
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from ._native import Bz2Error, Decoder, find_magic, lib, status_string, warmup  # noqa: F401
-from .buffers import decompress, decompress_many, decompress_many_to_tensor  # noqa: F401
+from ._native import (Bz2Error, Decoder, find_magic, lib, plan_compress_blocks, status_string,  # noqa: F401
+                      warmup)
+from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
+                      decompress_many_to_tensor)
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401
                      write_block_offsets)
 

@@ -96,6 +96,15 @@ class BufferResult(ctypes.Structure):
         return {name: getattr(self, name) for name, _ in self._fields_}
 
 
+class CompressResult(ctypes.Structure):
+    _fields_ = [("output_offset", ctypes.c_uint64), ("compressed_size", ctypes.c_uint64),
+                ("map_first", ctypes.c_uint64), ("n_blocks", ctypes.c_uint32), ("map_entries", ctypes.c_uint32),
+                ("status", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+    def as_dict(self):
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
 # every symbol include/mi355x_bz2.h declares: (name, restype, argtypes)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
 _vp = ctypes.c_void_p
@@ -156,6 +165,12 @@ SYMBOLS = [
     ("mi355x_bz2_reader_statistics", ctypes.c_int, [_vp, ctypes.POINTER(ReaderStats)]),
     ("mi355x_bz2_decompress_buffers", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_uint32,
                                                       ctypes.c_uint32, ctypes.POINTER(BufferResult), _u64p]),
+    ("mi355x_bz2_compress_buffers", ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_void_p), _u64p, ctypes.c_uint32,
+                                                    ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(CompressResult), _u64p]),
+    ("mi355x_bz2_compress_block_map", ctypes.c_int, [_vp, ctypes.c_uint32, _u64p, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_encoder_memory", ctypes.c_int, [_vp, _u64p]),
+    ("mi355x_bz2_plan_compress_blocks", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, _u64p,
+                                                        ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_decode_chunk", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                ctypes.c_uint64, ctypes.POINTER(ChunkResult), ctypes.POINTER(BlockResult),
                                                ctypes.c_uint32, ctypes.POINTER(ChunkBoundary), ctypes.c_uint32]),
@@ -215,6 +230,18 @@ def find_magic(data: bytes, magic: int = MAGIC_BLOCK, threads: int = 0):
     arr = (ctypes.c_uint64 * max(1, n))()
     L.mi355x_bz2_find_magic(data, len(data), magic, arr, n, threads)
     return list(arr[:n])
+
+
+def plan_compress_blocks(data, level: int = 9):
+    """Input sizes of the blocks libbz2 cuts `data` into at `level` (host only, no GPU)."""
+    data = bytes(_byte_view(data))
+    n = ctypes.c_uint64()
+    rc = lib().mi355x_bz2_plan_compress_blocks(data, len(data), level, None, 0, ctypes.byref(n))
+    if rc != OK:
+        raise Bz2Error(rc)
+    arr = (ctypes.c_uint64 * max(1, n.value))()
+    lib().mi355x_bz2_plan_compress_blocks(data, len(data), level, arr, n.value, ctypes.byref(n))
+    return list(arr[:n.value])
 
 
 def _byte_view(obj) -> memoryview:
@@ -344,6 +371,36 @@ class Decoder:
         self._check(lib().mi355x_bz2_decompress_buffers(self._h, ptrs, sizes, n, max_launch_blocks, res,
                                                         ctypes.byref(total)))
         return [res[i].as_dict() for i in range(n)], total.value
+
+    def compress_buffers(self, buffers, level: int = 9, max_launch_blocks: int = 0):
+        """mi355x_bz2_compress_buffers over C-contiguous byte buffers: returns (list of CompressResult dicts, total).
+        Buffer i's stream is [output_offset, output_offset + compressed_size) of the output (copy_output,
+        gather_output, output_device_ptr)."""
+        import numpy as np
+        arrays = [np.frombuffer(_byte_view(b), dtype=np.uint8) for b in buffers]
+        n = len(arrays)
+        ptrs = (ctypes.c_void_p * max(1, n))(*[a.ctypes.data if a.size else None for a in arrays])
+        sizes = (ctypes.c_uint64 * max(1, n))(*[a.size for a in arrays])
+        res = (CompressResult * max(1, n))()
+        total = ctypes.c_uint64()
+        self._check(lib().mi355x_bz2_compress_buffers(self._h, ptrs, sizes, n, level, max_launch_blocks, res,
+                                                      ctypes.byref(total)))
+        return [res[i].as_dict() for i in range(n)], total.value
+
+    def compress_block_map(self, buffer: int) -> dict:
+        """Block map {bit offset: decoded offset} of buffer `buffer` of the last compress_buffers call."""
+        n = ctypes.c_uint64()
+        self._check(lib().mi355x_bz2_compress_block_map(self._h, buffer, None, None, 0, ctypes.byref(n)))
+        bits = (ctypes.c_uint64 * max(1, n.value))()
+        byts = (ctypes.c_uint64 * max(1, n.value))()
+        self._check(lib().mi355x_bz2_compress_block_map(self._h, buffer, bits, byts, n.value, ctypes.byref(n)))
+        return {bits[i]: byts[i] for i in range(n.value)}
+
+    def encoder_memory(self) -> int:
+        """bytes of HBM the encoder's scratch holds (0 before the first compress call)"""
+        b = ctypes.c_uint64(0)
+        self._check(lib().mi355x_bz2_encoder_memory(self._h, ctypes.byref(b)))
+        return b.value
 
     def find_magic(self, magic: int = MAGIC_BLOCK):
         """Magic-bit scan of the resident input on the GPU (k_find_magic)."""

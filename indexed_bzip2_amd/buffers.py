@@ -1,4 +1,5 @@
-"""Many independent bzip2 buffers in one GPU batch: decompress, decompress_many, decompress_many_to_tensor.
+"""Many independent bzip2 buffers in one GPU batch: decompress, decompress_many, decompress_many_to_tensor, and the
+other way round: compress, compress_many.
 
 Each buffer is a complete .bz2 byte string (a ZIP member stored with method 12, a block of an Avro or Hadoop file, one
 blob per sample) and decodes to what ``open(io.BytesIO(buffer), parallelization=1).read()`` returns, stream-CRC check
@@ -124,3 +125,35 @@ def decompress_many_to_tensor(buffers, device: int = -1, max_launch_blocks: int 
         bounds.append(bounds[-1] + r["decoded_size"])
     offsets = torch.tensor(bounds, dtype=torch.int64)
     return (data, offsets, _statuses(results)) if return_status else (data, offsets)
+
+
+def compress_many(buffers, compresslevel: int = 9, device: int = -1, max_launch_blocks: int = 0,
+                  return_index: bool = False):
+    """Compress every buffer (bytes, bytearray, memoryview, numpy uint8: any C-contiguous buffer; empty ones too) into
+    one complete single-stream .bz2 each -> list of bytes.  ``bz2.decompress`` and ``decompress_many`` give the buffer
+    back.  `compresslevel` 1..9 means what it means to bzip2 (blocks of 100k x level), and the blocks are cut exactly
+    where libbz2 cuts them; the encoded bits may differ from libbz2's.  Blocks of all buffers are encoded together on
+    the GPU, in launches of at most `max_launch_blocks` (0 = 512); the output does not depend on it.
+    With ``return_index=True`` the result is a list of ``(bytes, offsets)``: `offsets` is the block map
+    ``open(io.BytesIO(out), 0).block_offsets()`` would build, ready for ``set_block_offsets`` / ``write_block_offsets``.
+    Uses the device's kept context (created by the first call for the device, never by later ones)."""
+    if isinstance(compresslevel, bool) or not isinstance(compresslevel, int) or not 1 <= compresslevel <= 9:
+        raise ValueError("compresslevel must be an integer from 1 to 9")
+    if max_launch_blocks < 0:
+        raise ValueError("max_launch_blocks must not be negative")
+    buffers = list(buffers)
+    if not buffers:
+        return []
+    dec, lock = _decoder(device)
+    with lock:
+        results, total = dec.compress_buffers(buffers, compresslevel, max_launch_blocks)
+        blob = dec.copy_output(0, total) if total else b""
+        maps = [dec.compress_block_map(i) for i in range(len(buffers))] if return_index else None
+    out = [blob[r["output_offset"]:r["output_offset"] + r["compressed_size"]] for r in results]
+    return list(zip(out, maps)) if return_index else out
+
+
+def compress(data, compresslevel: int = 9, device: int = -1) -> bytes:
+    """One buffer: a .bz2 stream that bz2.decompress turns back into `data` (see compress_many).  Uses the device's
+    kept context."""
+    return compress_many([data], compresslevel=compresslevel, device=device)[0]

@@ -23,6 +23,10 @@ int resultBuffer( mi355x_bz2_ctx* ctx, uint64_t size, uint64_t keep, uint8_t** d
  * `size` bytes of the result buffer. */
 int publishResult( mi355x_bz2_ctx* ctx, uint64_t size );
 
+/** The encoder state slot of the context (nullptr until the first mi355x_bz2_compress_buffers); `release` frees what
+ * it holds when the context is destroyed. */
+void*& encoderOf( mi355x_bz2_ctx* ctx, void ( *release )( void* ) );
+
 /** The device ordinal the context was created on. */
 int deviceOf( const mi355x_bz2_ctx* ctx );
 

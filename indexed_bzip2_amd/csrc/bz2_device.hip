@@ -200,6 +200,10 @@ struct mi355x_bz2_ctx
     uint8_t* dResult{ nullptr };
     uint64_t resultCap{ 0 };
 
+    /* mi355x_bz2_compress_buffers: the encoder's state (bz2_compress.hip), created by the first compress call */
+    void* encoder{ nullptr };
+    void ( *encoderFree )( void* ){ nullptr };
+
     CrcConsts crc{};
     hipEvent_t ev[MAX_GROUPS][2 * MI355X_BZ2_MAX_KERNELS]{};   /* [group][2 * kernel + {start, end}] */
     hipEvent_t evStep[3]{};                                     /* step start, inputs uploaded, step end */
@@ -736,6 +740,7 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
         if ( c->lane[l] ) (void)hipStreamSynchronize( c->lane[l] );
     }
     if ( c->highStream ) (void)hipStreamSynchronize( c->highStream );
+    if ( c->encoder != nullptr ) c->encoderFree( c->encoder );
     freeScratch( c );
     freeRetired( c );
     c->upload.reset();   /* joins the copy thread (of the owner; sharers only drop their reference) before the memory goes */
@@ -1298,6 +1303,13 @@ mi355x::resultBuffer( mi355x_bz2_ctx* c, uint64_t size, uint64_t keep, uint8_t**
     }
     *device = c->dResult;
     return MI355X_BZ2_OK;
+}
+
+void*&
+mi355x::encoderOf( mi355x_bz2_ctx* c, void ( *release )( void* ) )
+{
+    c->encoderFree = release;
+    return c->encoder;
 }
 
 int
