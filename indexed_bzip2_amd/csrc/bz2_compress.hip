@@ -719,11 +719,16 @@ struct DeviceBuffer
     uint64_t cap{ 0 };
 };
 
+enum EncBuffer   /* the encoder's device buffers, each grown on its own (ensure) */
+{
+    B_IN, B_RLE, B_L, B_SA, B_RANK, B_KA, B_KB, B_VA, B_VB, B_ACT0, B_ACT1, B_HEADS, B_FLAGS, B_SYMS, B_SEL, B_SELMTF, B_GOFF,
+    B_BLOCKS, B_META, B_FREQS, B_TABLES, B_BITPOS, B_JOBS, B_COUNT, B_TEMP, ENC_BUFFERS
+};
+
 struct Encoder
 {
     int device{ 0 };
-    DeviceBuffer in, rle, L, sa, rank, kA, kB, vA, vB, act0, act1, heads, flags, syms, sel, selMtf, goff, blocks, meta,
-        freqs, tables, bitPos, jobs, count, temp;
+    DeviceBuffer buffer[ENC_BUFFERS];
     std::vector<uint64_t> mapBits, mapBytes, mapFirst, mapCount;
     std::vector<uint8_t> staging;
 
@@ -731,21 +736,14 @@ struct Encoder
     bytes() const
     {
         uint64_t total = 0;
-        for ( const DeviceBuffer* b : { &in, &rle, &L, &sa, &rank, &kA, &kB, &vA, &vB, &act0, &act1, &heads, &flags, &syms,
-                                        &sel, &selMtf, &goff, &blocks, &meta, &freqs, &tables, &bitPos, &jobs, &count,
-                                        &temp } ) {
-            total += b->cap;
-        }
+        for ( const DeviceBuffer& b : buffer ) total += b.cap;
         return total;
     }
 
     ~Encoder()
     {
         (void)hipSetDevice( device );
-        for ( DeviceBuffer* b : { &in, &rle, &L, &sa, &rank, &kA, &kB, &vA, &vB, &act0, &act1, &heads, &flags, &syms, &sel,
-                                  &selMtf, &goff, &blocks, &meta, &freqs, &tables, &bitPos, &jobs, &count, &temp } ) {
-            (void)hipFree( b->p );
-        }
+        for ( DeviceBuffer& b : buffer ) (void)hipFree( b.p );
     }
 };
 
@@ -925,7 +923,7 @@ runCall( mi355x_bz2_ctx* ctx, Encoder& e, const uint8_t* const* buffers, const u
             selector += selectorSlots( b.rle );
         }
         const uint32_t N = pos, nb = launch.count;
-        uint8_t* dIn = ensure<uint8_t>( e.in, launch.inputBytes + 64 );
+        uint8_t* dIn = ensure<uint8_t>( e.buffer[B_IN], launch.inputBytes + 64 );
         ENC_TRY( hipMemcpyAsync( dIn, e.staging.data(), launch.inputBytes, hipMemcpyHostToDevice, stream ) );
         ENC_TRY( hipStreamSynchronize( stream ) );
         crcs.resize( nb );
@@ -933,34 +931,34 @@ runCall( mi355x_bz2_ctx* ctx, Encoder& e, const uint8_t* const* buffers, const u
         if ( rc != MI355X_BZ2_OK ) throw Failure{ rc, "block CRCs failed" };
         for ( uint32_t k = 0; k < nb; ++k ) hb[k].crc = crcs[k];
 
-        EncBlock* dBlocks = ensure<EncBlock>( e.blocks, nb );
-        EncMeta* dMeta = ensure<EncMeta>( e.meta, nb );
-        uint8_t* dRle = ensure<uint8_t>( e.rle, N );
-        uint8_t* dL = ensure<uint8_t>( e.L, N );
-        uint32_t* dSa = ensure<uint32_t>( e.sa, N );
-        uint32_t* dRank = ensure<uint32_t>( e.rank, N );
-        uint64_t* dKA = ensure<uint64_t>( e.kA, N );
-        uint64_t* dKB = ensure<uint64_t>( e.kB, N );
-        uint32_t* dVA = ensure<uint32_t>( e.vA, N );
-        uint32_t* dVB = ensure<uint32_t>( e.vB, N );
-        uint32_t* dAct[2] = { ensure<uint32_t>( e.act0, N ), ensure<uint32_t>( e.act1, N ) };
-        uint32_t* dHeads = ensure<uint32_t>( e.heads, N );
-        uint8_t* dFlags = ensure<uint8_t>( e.flags, N );
-        uint16_t* dSyms = ensure<uint16_t>( e.syms, sym );
-        uint8_t* dSel = ensure<uint8_t>( e.sel, selector );
-        uint8_t* dSelMtf = ensure<uint8_t>( e.selMtf, selector );
-        uint32_t* dGoff = ensure<uint32_t>( e.goff, selector );
-        uint32_t* dFreqs = ensure<uint32_t>( e.freqs, (uint64_t)nb * MAX_ALPHA );
-        EncTables* dTables = ensure<EncTables>( e.tables, nb );
-        uint64_t* dBitPos = ensure<uint64_t>( e.bitPos, nb );
-        uint32_t* dCount = ensure<uint32_t>( e.count, 1 );
+        EncBlock* dBlocks = ensure<EncBlock>( e.buffer[B_BLOCKS], nb );
+        EncMeta* dMeta = ensure<EncMeta>( e.buffer[B_META], nb );
+        uint8_t* dRle = ensure<uint8_t>( e.buffer[B_RLE], N );
+        uint8_t* dL = ensure<uint8_t>( e.buffer[B_L], N );
+        uint32_t* dSa = ensure<uint32_t>( e.buffer[B_SA], N );
+        uint32_t* dRank = ensure<uint32_t>( e.buffer[B_RANK], N );
+        uint64_t* dKA = ensure<uint64_t>( e.buffer[B_KA], N );
+        uint64_t* dKB = ensure<uint64_t>( e.buffer[B_KB], N );
+        uint32_t* dVA = ensure<uint32_t>( e.buffer[B_VA], N );
+        uint32_t* dVB = ensure<uint32_t>( e.buffer[B_VB], N );
+        uint32_t* dAct[2] = { ensure<uint32_t>( e.buffer[B_ACT0], N ), ensure<uint32_t>( e.buffer[B_ACT1], N ) };
+        uint32_t* dHeads = ensure<uint32_t>( e.buffer[B_HEADS], N );
+        uint8_t* dFlags = ensure<uint8_t>( e.buffer[B_FLAGS], N );
+        uint16_t* dSyms = ensure<uint16_t>( e.buffer[B_SYMS], sym );
+        uint8_t* dSel = ensure<uint8_t>( e.buffer[B_SEL], selector );
+        uint8_t* dSelMtf = ensure<uint8_t>( e.buffer[B_SELMTF], selector );
+        uint32_t* dGoff = ensure<uint32_t>( e.buffer[B_GOFF], selector );
+        uint32_t* dFreqs = ensure<uint32_t>( e.buffer[B_FREQS], (uint64_t)nb * MAX_ALPHA );
+        EncTables* dTables = ensure<EncTables>( e.buffer[B_TABLES], nb );
+        uint64_t* dBitPos = ensure<uint64_t>( e.buffer[B_BITPOS], nb );
+        uint32_t* dCount = ensure<uint32_t>( e.buffer[B_COUNT], 1 );
         size_t sortBytes = 0, scanBytes = 0, selectBytes = 0;
         ENC_TRY( rocprim::radix_sort_pairs( nullptr, sortBytes, dKA, dKB, dVA, dVB, N, 0, 64, stream ) );
         ENC_TRY( rocprim::inclusive_scan( nullptr, scanBytes, dHeads, dHeads, N, rocprim::maximum<uint32_t>(), stream ) );
         ENC_TRY( rocprim::select( nullptr, selectBytes, dAct[0], dFlags, dAct[1], dCount, N, stream ) );
         size_t tempBytes = std::max( { sortBytes, scanBytes, selectBytes } );
-        void* dTemp = ensure<uint8_t>( e.temp, tempBytes );
-        tempBytes = e.temp.cap;
+        void* dTemp = ensure<uint8_t>( e.buffer[B_TEMP], tempBytes );
+        tempBytes = e.buffer[B_TEMP].cap;
 
         ENC_TRY( hipMemcpyAsync( dBlocks, hb.data(), nb * sizeof( EncBlock ), hipMemcpyHostToDevice, stream ) );
         ENC_TRY( hipMemsetAsync( dMeta, 0, nb * sizeof( EncMeta ), stream ) );
@@ -1059,7 +1057,7 @@ runCall( mi355x_bz2_ctx* ctx, Encoder& e, const uint8_t* const* buffers, const u
     advance( n );
     zeroTo( outEnd );
     if ( !frames.empty() ) {
-        FrameJob* dJobs = ensure<FrameJob>( e.jobs, frames.size() );
+        FrameJob* dJobs = ensure<FrameJob>( e.buffer[B_JOBS], frames.size() );
         ENC_TRY( hipMemcpyAsync( dJobs, frames.data(), frames.size() * sizeof( FrameJob ), hipMemcpyHostToDevice, stream ) );
         hipLaunchKernelGGL( k_enc_frame, gridFor( frames.size(), 64 ), dim3( 64 ), 0, stream, dJobs,
                             (uint32_t)frames.size(), reinterpret_cast<uint32_t*>( dResult ) );

@@ -28,6 +28,7 @@
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
 #include "bz2_plan.hpp"
+#include "bz2_scratch.hpp"
 #include "bz2_lanes.hpp"
 #include "bz2_ctx.hpp"
 
@@ -79,7 +80,64 @@ struct InputUpload
     }
 };
 
-struct mi355x_bz2_ctx
+namespace
+{
+/* the records whose sizes the scratch layout is given: tests/native/scratch_cases.cpp pins the totals with these values */
+constexpr ScratchSizes SCRATCH_SIZES{ sizeof( BlockMeta ), sizeof( HuffMeta ), sizeof( ScanMeta ), sizeof( HuffTables ), sizeof( WalkPlan ) };
+static_assert( sizeof( BlockMeta ) == 88 && sizeof( HuffMeta ) == 16 && sizeof( ScanMeta ) == 32 && sizeof( HuffTables ) == 17216 && sizeof( WalkPlan ) == 160 );
+
+/** Per-block scratch: one device and one page-locked host allocation and every region of bz2_scratch.hpp's list in them. */
+struct Scratch
+{
+    uint32_t capacity{ 0 };   /* in blocks */
+    ScratchLayout layout;
+    uint8_t* dScratch{ nullptr };
+    uint8_t* hScratch{ nullptr };
+#define BZ2_POINTER( memory, name, type, ... ) type* name{ nullptr };
+    BZ2_SCRATCH_REGIONS( BZ2_POINTER )
+#undef BZ2_POINTER
+};
+
+void retire( mi355x_bz2_ctx* c, void* pointer, uint64_t bytes, bool host, uint64_t inUseNow );
+
+/** A buffer that only grows.  hipFree / hipHostFree wait for the whole device, i.e. for the batches of every other
+ * context: the allocation it outgrows is put aside (retire) and freed when the context goes. */
+struct GrowBuffer
+{
+    uint8_t* bytes{ nullptr };
+    uint64_t capacity{ 0 };
+    bool host{ false };       /* page-locked host memory */
+
+    /** Nothing on the device may still be reading the allocation: the caller has synchronised the streams that did. */
+    void
+    putAside( mi355x_bz2_ctx* c, uint64_t inUseNow )
+    {
+        retire( c, bytes, capacity, host, inUseNow );
+        bytes = nullptr;
+        capacity = 0;
+    }
+    /** Room for `need` bytes: if there is less, an allocation of `newCapacity` bytes replaces the present one (putAside). */
+    hipError_t
+    grow( mi355x_bz2_ctx* c, uint64_t need, uint64_t newCapacity, uint64_t inUseNow )
+    {
+        if ( need <= capacity ) return hipSuccess;
+        putAside( c, inUseNow );
+        const hipError_t err = host ? hipHostMalloc( reinterpret_cast<void**>( &bytes ), newCapacity, hipHostMallocDefault )
+                                    : hipMalloc( reinterpret_cast<void**>( &bytes ), newCapacity );
+        if ( err == hipSuccess ) capacity = newCapacity;
+        return err;
+    }
+    void
+    release()
+    {
+        if ( host ) (void)hipHostFree( bytes ); else (void)hipFree( bytes );
+        bytes = nullptr;
+        capacity = 0;
+    }
+};
+}  // namespace
+
+struct mi355x_bz2_ctx : Scratch
 {
     int device{ 0 };
     uint32_t flags{ 0 };
@@ -96,12 +154,7 @@ struct mi355x_bz2_ctx
     /* input */
     /* ctx-owned copies of the input.  A copy queued while a batch is in flight (set_input_host_async: the bytes of the
      * NEXT batch, beside the kernels of this one) goes into the second buffer, on a stream of its own */
-    struct InBuffer
-    {
-        uint8_t* bytes{ nullptr };
-        uint64_t capacity{ 0 };
-    };
-    InBuffer in[2];
+    GrowBuffer in[2];
     int inCurrent{ 0 };                 /* the buffer c->dIn points into, if it is ctx-owned */
     int inFlight{ -1 };                 /* the buffer the batch in flight reads, -1 if none of the two */
     hipStream_t inStream{ nullptr };
@@ -111,8 +164,7 @@ struct mi355x_bz2_ctx
     uint64_t inSize{ 0 };
     std::shared_ptr<InputUpload> upload;   /* set while / after a streamed copy of the input */
 
-    /* Buffers that have been replaced by larger ones.  hipFree / hipHostFree wait for the whole device, i.e. for the
-     * batches of every other context: a growing buffer is put aside instead and freed when the context goes, or when
+    /* Allocations that have been replaced by larger ones (GrowBuffer, the scratch): freed when the context goes, or when
      * what has been put aside outweighs what is in use (then the wait is paid once, see retire). */
     struct Retired
     {
@@ -123,50 +175,11 @@ struct mi355x_bz2_ctx
     std::vector<Retired> retired;
     uint64_t retiredBytes{ 0 };
 
-    /* per-block scratch, capacity in blocks: one device and one page-locked host allocation, carved up by ensureScratch */
-    uint32_t capacity{ 0 };
-    uint64_t scratchBytes{ 0 }, scratchHostBytes{ 0 };
-    uint8_t* dScratch{ nullptr };
-    uint8_t* hScratch{ nullptr };
-    uint64_t* dOffsets{ nullptr };
-    uint32_t* dOrder{ nullptr };
-    uint32_t* hOrder{ nullptr };       /* pinned */
-    BlockMeta* dMeta{ nullptr };
-    uint8_t* dSel{ nullptr };
-    uint16_t* dSym{ nullptr };
-    uint8_t* dStb{ nullptr };
-    HuffMeta* dHmeta{ nullptr };
-    ScanMeta* dSmeta{ nullptr };      /* k_hscan -> k_hsym */
-    HuffTables* dHtab{ nullptr };     /* decode tables per block */
-    uint32_t* dGpos{ nullptr };       /* [cap][GPOS_STRIDE]: bit position of every 50-symbol group */
-    uint8_t* dL{ nullptr };
-    uint32_t* dTab{ nullptr };
-    uint8_t* dR{ nullptr };
-    uint32_t* dSegLen{ nullptr };
-    uint32_t* dSegSucc{ nullptr };
-    uint32_t* dSegCont{ nullptr };    /* [cap][SEG_STRIDE]: where a segment longer than STASH_BYTES goes on */
-    uint2*    dChain{ nullptr };      /* [cap][SEG_STRIDE]: segments in cycle order {offset, length, segment} */
-    uint32_t* dStash{ nullptr };      /* [cap][SEG_STRIDE][STASH_BYTES / 4]: first bytes of every segment */
-    WalkPlan* dPlan{ nullptr };       /* [MAX_GROUPS]: one per group */
-    uint32_t* dWalkBlk{ nullptr };    /* [MAX_GROUPS][cap + 16] */
-    uint32_t* dWalkPre{ nullptr };
-    uint32_t* hSlotOf{ nullptr };     /* pinned: original index -> slot */
-    uint32_t* dSlotOf{ nullptr };
-    uint64_t* dTotals{ nullptr };     /* k_offsets: {total decoded bytes, does not fit} */
-    uint32_t* dBwtCounts{ nullptr };  /* [min( cap, BWT_SPLIT_BLOCKS )][BWT_COUNTS_PER_BLOCK]: byte counts per chunk, small batches */
-    uint64_t* hTotals{ nullptr };     /* pinned */
-    BlockMeta* hMeta{ nullptr };       /* pinned */
-    uint64_t* hOffsets{ nullptr };     /* pinned */
-    uint64_t* dEnds{ nullptr };       /* per-block end of the input in bytes, by slot (decodeBatchBegin with ends only) */
-    uint64_t* hEnds{ nullptr };       /* pinned */
-
     /* output: dOut holds the last finished batch.  A caller that copies it out in the background
      * (mi355x_bz2_copy_output_begin) gets the next batch written into a second buffer, so that the copy and the next
      * decode overlap; callers that never do keep a single buffer. */
-    struct OutBuffer
+    struct OutBuffer : GrowBuffer
     {
-        uint8_t* bytes{ nullptr };
-        uint64_t capacity{ 0 };
         hipEvent_t copied{ nullptr };     /* behind the last background copy out of this buffer */
         bool copyIssued{ false };
     };
@@ -189,16 +202,10 @@ struct mi355x_bz2_ctx
 
     /* mi355x_bz2_gather_output: grow-only, so that a call allocates nothing once the sizes have been seen.  The tile
      * list (page-locked and on the device) and, for a host destination, the packed pieces (device and page-locked) */
-    GatherTile* hGatherTiles{ nullptr };
-    GatherTile* dGatherTiles{ nullptr };
-    uint64_t gatherTileCap{ 0 };
-    uint8_t* dGatherStage{ nullptr };
-    uint8_t* hGatherStage{ nullptr };
-    uint64_t gatherStageCap{ 0 };
+    GrowBuffer hGatherTiles{ nullptr, 0, true }, dGatherTiles, hGatherStage{ nullptr, 0, true }, dGatherStage;
 
-    /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back, grow-only (mi355x::resultBuffer) */
-    uint8_t* dResult{ nullptr };
-    uint64_t resultCap{ 0 };
+    /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
+    GrowBuffer result;
 
     /* mi355x_bz2_compress_buffers: the encoder's state (bz2_compress.hip), created by the first compress call */
     void* encoder{ nullptr };
@@ -215,7 +222,6 @@ struct mi355x_bz2_ctx
     bool trace{ false };              /* MI355X_BZ2_TRACE=1 when it was begun */
     int timingGroups{ 0 };            /* groups of the last batch */
     bool timingsResolved{ true };     /* timings.ms_kernel[] filled in for the last batch */
-    uint32_t nKernels{ 0 };
     mi355x_bz2_timings timings{};
 };
 
@@ -294,120 +300,35 @@ freeScratch( mi355x_bz2_ctx* c, bool now = true )
         (void)hipFree( c->dScratch );
         (void)hipHostFree( c->hScratch );
     } else {
-        retire( c, c->dScratch, c->scratchBytes, false, c->scratchBytes );
-        retire( c, c->hScratch, c->scratchHostBytes, true, c->scratchBytes );
+        retire( c, c->dScratch, c->layout.deviceBytes, false, c->layout.deviceBytes );
+        retire( c, c->hScratch, c->layout.hostBytes, true, c->layout.deviceBytes );
     }
-    c->dScratch = nullptr;
-    c->hScratch = nullptr;
-    c->scratchBytes = c->scratchHostBytes = 0;
-    c->dOffsets = nullptr; c->dOrder = nullptr; c->dMeta = nullptr; c->dSel = nullptr; c->dSym = nullptr; c->dStb = nullptr;
-    c->dHmeta = nullptr; c->dSmeta = nullptr; c->dHtab = nullptr; c->dGpos = nullptr; c->dL = nullptr; c->dTab = nullptr;
-    c->dR = nullptr; c->dSegLen = nullptr; c->dSegSucc = nullptr; c->dSegCont = nullptr;
-    c->dChain = nullptr; c->dStash = nullptr; c->dPlan = nullptr; c->dWalkBlk = nullptr; c->dWalkPre = nullptr;
-    c->hOrder = nullptr; c->hSlotOf = nullptr; c->hMeta = nullptr; c->hOffsets = nullptr; c->dEnds = nullptr; c->hEnds = nullptr;
-    c->dSlotOf = nullptr; c->dTotals = nullptr; c->hTotals = nullptr; c->dBwtCounts = nullptr;
-    c->capacity = 0;
+    static_cast<Scratch&>( *c ) = Scratch{};
 }
 
 /** Per-block scratch for `nBlocks` blocks: ONE device allocation and ONE page-locked host allocation, carved into the
- * buffers (two dozen separate allocations cost 80 ms per context, which a reader pays before its first byte). */
+ * regions of bz2_scratch.hpp (two dozen separate allocations cost 80 ms per context, which a reader pays before its first byte). */
 int
 ensureScratch( mi355x_bz2_ctx* c, uint32_t nBlocks )
 {
     if ( nBlocks <= c->capacity ) return MI355X_BZ2_OK;
     HIP_TRY( c, hipStreamSynchronize( c->stream ) );
     freeScratch( c, /* now */ false );
-    /* about 10 MB of scratch per block: powers of two while that is cheap, multiples of 256 blocks beyond */
-    uint32_t cap = 8;
-    while ( cap < nBlocks && cap < 512 ) cap *= 2;
-    if ( cap < nBlocks ) cap = ( nBlocks + 255u ) & ~255u;
-
-    size_t deviceBytes = 0, hostBytes = 0;
-    const auto reserve = [] ( size_t& total, size_t bytes ) {
-        const size_t at = total;
-        total += ( bytes + 255 ) & ~size_t( 255 );
-        return at;
-    };
-    const size_t oOffsets = reserve( deviceBytes, (size_t)cap * sizeof( uint64_t ) );
-    const size_t oOrder = reserve( deviceBytes, (size_t)cap * sizeof( uint32_t ) );
-    const size_t oMeta = reserve( deviceBytes, (size_t)cap * sizeof( BlockMeta ) );
-    const size_t oSel = reserve( deviceBytes, (size_t)cap * SEL_STRIDE + 256 );
-    const size_t oStb = reserve( deviceBytes, (size_t)cap * 256 );
-    const size_t oHmeta = reserve( deviceBytes, (size_t)cap * sizeof( HuffMeta ) );
-    const size_t oSmeta = reserve( deviceBytes, (size_t)cap * sizeof( ScanMeta ) );
-    const size_t oHtab = reserve( deviceBytes, (size_t)cap * sizeof( HuffTables ) );
-    const size_t oGpos = reserve( deviceBytes, (size_t)cap * GPOS_STRIDE * sizeof( uint32_t ) );
-    const size_t oL = reserve( deviceBytes, (size_t)cap * L_STRIDE + 256 );
-    const size_t oTab = reserve( deviceBytes, (size_t)cap * TAB_STRIDE * sizeof( uint32_t ) );
-    /* the bytes of the inverse BWT (k_emit -> k_rle) go where the block's last column was (k_mtf -> table build): same
-     * slot, same stream, never alive together; 0.9 MB per block less.  Not when the caller wants to look at the stages. */
-    const bool keepStages = ( c->flags & MI355X_BZ2_FLAG_KEEP_STAGES ) != 0;
-    const size_t oR = keepStages ? reserve( deviceBytes, (size_t)cap * L_STRIDE + 256 ) : oL;
-    const size_t oSegLen = reserve( deviceBytes, (size_t)cap * SEG_STRIDE * sizeof( uint32_t ) );
-    const size_t oSegSucc = reserve( deviceBytes, (size_t)cap * SEG_STRIDE * sizeof( uint32_t ) );
-    const size_t oSegCont = reserve( deviceBytes, (size_t)cap * SEG_STRIDE * sizeof( uint32_t ) );
-    const size_t oChain = reserve( deviceBytes, (size_t)cap * SEG_STRIDE * sizeof( uint2 ) );
-    const size_t oStash = reserve( deviceBytes, (size_t)cap * SEG_STRIDE * STASH_BYTES );
-    const size_t oPlan = reserve( deviceBytes, MAX_GROUPS * sizeof( WalkPlan ) );
-    const size_t oWalkBlk = reserve( deviceBytes, MAX_GROUPS * ( (size_t)cap + 16 ) * sizeof( uint32_t ) );
-    const size_t oWalkPre = reserve( deviceBytes, MAX_GROUPS * ( (size_t)cap + 16 ) * sizeof( uint32_t ) );
-    const size_t oSlotOf = reserve( deviceBytes, (size_t)cap * sizeof( uint32_t ) );
-    const size_t oTotals = reserve( deviceBytes, 2 * sizeof( uint64_t ) );
-    const size_t oBwtCounts = reserve( deviceBytes, (size_t)std::min( cap, BWT_SPLIT_BLOCKS ) * BWT_COUNTS_PER_BLOCK * sizeof( uint32_t ) );
-    const size_t oEnds = reserve( deviceBytes, (size_t)cap * sizeof( uint64_t ) );
-    const size_t hOrderAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
-    const size_t hSlotOfAt = reserve( hostBytes, (size_t)cap * sizeof( uint32_t ) );
-    const size_t hMetaAt = reserve( hostBytes, (size_t)cap * sizeof( BlockMeta ) );
-    const size_t hOffsetsAt = reserve( hostBytes, (size_t)cap * sizeof( uint64_t ) );
-    const size_t hTotalsAt = reserve( hostBytes, 2 * sizeof( uint64_t ) );
-    const size_t hEndsAt = reserve( hostBytes, (size_t)cap * sizeof( uint64_t ) );
+    const ScratchLayout layout = layScratch( capacityFor( nBlocks ), ( c->flags & MI355X_BZ2_FLAG_KEEP_STAGES ) != 0, SCRATCH_SIZES );
 
     const auto tAlloc = std::chrono::steady_clock::now();
-    HIP_TRY( c, hipMalloc( &c->dScratch, deviceBytes ) );
-    HIP_TRY( c, hipHostMalloc( &c->hScratch, hostBytes, hipHostMallocDefault ) );
+    HIP_TRY( c, hipMalloc( &c->dScratch, layout.deviceBytes ) );
+    HIP_TRY( c, hipHostMalloc( &c->hScratch, layout.hostBytes, hipHostMallocDefault ) );
     if ( std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr ) {
-        std::fprintf( stderr, "[device] scratch for %u blocks (%.0f MB): %.1f ms\n", cap, deviceBytes / 1e6,
+        std::fprintf( stderr, "[device] scratch for %u blocks (%.0f MB): %.1f ms\n", layout.capacity, layout.deviceBytes / 1e6,
                       std::chrono::duration<double, std::milli>( std::chrono::steady_clock::now() - tAlloc ).count() );
     }
-    uint8_t* const d = c->dScratch;
-    uint8_t* const h = c->hScratch;
-    c->dOffsets = reinterpret_cast<uint64_t*>( d + oOffsets );
-    c->dOrder = reinterpret_cast<uint32_t*>( d + oOrder );
-    c->dMeta = reinterpret_cast<BlockMeta*>( d + oMeta );
-    c->dSel = d + oSel;
-    c->dStb = d + oStb;
-    c->dHmeta = reinterpret_cast<HuffMeta*>( d + oHmeta );
-    c->dSmeta = reinterpret_cast<ScanMeta*>( d + oSmeta );
-    c->dHtab = reinterpret_cast<HuffTables*>( d + oHtab );
-    c->dGpos = reinterpret_cast<uint32_t*>( d + oGpos );
-    c->dL = d + oL;
-    c->dTab = reinterpret_cast<uint32_t*>( d + oTab );
-    c->dR = d + oR;
-    c->dSegLen = reinterpret_cast<uint32_t*>( d + oSegLen );
-    c->dSegSucc = reinterpret_cast<uint32_t*>( d + oSegSucc );
-    c->dSegCont = reinterpret_cast<uint32_t*>( d + oSegCont );
-    c->dChain = reinterpret_cast<uint2*>( d + oChain );
-    c->dStash = reinterpret_cast<uint32_t*>( d + oStash );
-    /* the Huffman symbols of a block (k_hsym -> k_mtf) live where the block's stash will be (k_walk -> k_emit): same slot
-     * size, never alive together, producers and consumers of a block slot on one stream in that order; 1.8 MB per block less */
-    static_assert( (size_t)SYM_STRIDE * sizeof( uint16_t ) == (size_t)SEG_STRIDE * STASH_BYTES );
-    c->dSym = reinterpret_cast<uint16_t*>( d + oStash );
-    c->dPlan = reinterpret_cast<WalkPlan*>( d + oPlan );
-    c->dWalkBlk = reinterpret_cast<uint32_t*>( d + oWalkBlk );
-    c->dWalkPre = reinterpret_cast<uint32_t*>( d + oWalkPre );
-    c->dSlotOf = reinterpret_cast<uint32_t*>( d + oSlotOf );
-    c->dTotals = reinterpret_cast<uint64_t*>( d + oTotals );
-    c->dBwtCounts = reinterpret_cast<uint32_t*>( d + oBwtCounts );
-    c->dEnds = reinterpret_cast<uint64_t*>( d + oEnds );
-    c->hOrder = reinterpret_cast<uint32_t*>( h + hOrderAt );
-    c->hSlotOf = reinterpret_cast<uint32_t*>( h + hSlotOfAt );
-    c->hMeta = reinterpret_cast<BlockMeta*>( h + hMetaAt );
-    c->hOffsets = reinterpret_cast<uint64_t*>( h + hOffsetsAt );
-    c->hTotals = reinterpret_cast<uint64_t*>( h + hTotalsAt );
-    c->hEnds = reinterpret_cast<uint64_t*>( h + hEndsAt );
-    c->capacity = cap;
-    c->scratchBytes = deviceBytes;
-    c->scratchHostBytes = hostBytes;
+#define BZ2_POINT( memory, name, type, ... ) \
+    c->name = reinterpret_cast<type*>( ( memory == PINNED ? c->hScratch : c->dScratch ) + layout.offset[R_##name] );
+    BZ2_SCRATCH_REGIONS( BZ2_POINT )
+#undef BZ2_POINT
+    c->layout = layout;
+    c->capacity = layout.capacity;
     return MI355X_BZ2_OK;
 }
 
@@ -425,22 +346,14 @@ ensureOutput( mi355x_bz2_ctx* c, uint64_t size )
     if ( size + 256 > buffer.capacity ) {
         HIP_TRY( c, hipStreamSynchronize( c->stream ) );
         if ( buffer.copyIssued ) HIP_TRY( c, hipEventSynchronize( buffer.copied ) );
-        retire( c, buffer.bytes, buffer.capacity, false, size );
-        buffer.bytes = nullptr;
-        buffer.capacity = 0;
-        const uint64_t cap = size + size / 8 + ( 1u << 20 );
-        HIP_TRY( c, hipMalloc( &buffer.bytes, cap ) );
-        buffer.capacity = cap;
+        HIP_TRY( c, buffer.grow( c, size + 256, size + size / 8 + ( 1u << 20 ), size ) );
     }
     buffer.copyIssued = false;
     c->outCurrent = target;
     c->dOut = buffer.bytes;
     return MI355X_BZ2_OK;
 }
-}  // namespace
 
-namespace
-{
 const char* const KERNEL_NAMES[] = {
     "(k_huff: gone)", "k_mtf<272>", "k_bwt_build", "k_walk", "k_link2", "k_emit", "k_replicate", "k_rle<false>",
     "k_rle<true>", "k_crc", "k_walk_plan", "k_mtf<144>", "k_hscan", "k_hsym"
@@ -579,6 +492,30 @@ ensureLanes( mi355x_bz2_ctx* c, const LaneLayout& layout )
     }
     return MI355X_BZ2_OK;
 }
+
+/** The streams, events and scratch of a context just made (mi355x_bz2_create, which destroys it if this fails). */
+int
+initContext( mi355x_bz2_ctx* c, uint32_t initialBlocks )
+{
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    HIP_TRY( c, hipStreamCreateWithFlags( &c->stream, hipStreamNonBlocking ) );
+    c->lane[0] = c->stream;
+    /* the other lanes come with the first batch that uses them (ensureLanes), or now: see lanesAtCreation */
+    BatchPlan widest;
+    widest.groups = MAX_GROUPS;
+    widest.expensive = MAX_GROUPS - 1;
+    const uint32_t lanes = lanesAtCreation( queueBudget(), (uint32_t)walkChainOf( c->device ).liveContexts.load() );
+    if ( ensureLanes( c, layLanes( lanes, widest ) ) != MI355X_BZ2_OK ) return MI355X_BZ2_ERR_DEVICE;
+    for ( auto& e : c->evGroupDone ) HIP_TRY( c, hipEventCreate( &e ) );
+    for ( auto& group : c->ev ) {
+        for ( auto& e : group ) HIP_TRY( c, hipEventCreate( &e ) );
+    }
+    for ( auto& e : c->evStep ) HIP_TRY( c, hipEventCreate( &e ) );
+    initCrcConsts( c->crc );
+    const int rc = ensureScratch( c, initialBlocks );
+    if ( rc != MI355X_BZ2_OK ) std::fprintf( stderr, "mi355x_bz2_create: %s\n", c->lastError.c_str() );
+    return rc;
+}
 }  // namespace
 
 extern "C" {
@@ -680,49 +617,9 @@ mi355x_bz2_create( const mi355x_bz2_config* config, mi355x_bz2_ctx** out )
     c->device = device;
     walkChainOf( device ).liveContexts.fetch_add( 1 );
     c->flags = config != nullptr ? config->flags : 0;
-    if ( hipSetDevice( device ) != hipSuccess
-         || hipStreamCreateWithFlags( &c->stream, hipStreamNonBlocking ) != hipSuccess ) {
-        mi355x_bz2_destroy( c );   /* releases whatever exists so far */
-        return MI355X_BZ2_ERR_DEVICE;
-    }
-    c->lane[0] = c->stream;
-    {
-        /* the other lanes come with the first batch that uses them (ensureLanes), or now: see lanesAtCreation */
-        BatchPlan widest;
-        widest.groups = MAX_GROUPS;
-        widest.expensive = MAX_GROUPS - 1;
-        const uint32_t lanes = lanesAtCreation( queueBudget(), (uint32_t)walkChainOf( device ).liveContexts.load() );
-        if ( ensureLanes( c, layLanes( lanes, widest ) ) != MI355X_BZ2_OK ) {
-            mi355x_bz2_destroy( c );
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-    }
-    for ( auto& e : c->evGroupDone ) {
-        if ( hipEventCreate( &e ) != hipSuccess ) {
-            mi355x_bz2_destroy( c );
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-    }
-    for ( auto& group : c->ev ) {
-        for ( auto& e : group ) {
-            if ( hipEventCreate( &e ) != hipSuccess ) {
-                mi355x_bz2_destroy( c );
-                return MI355X_BZ2_ERR_DEVICE;
-            }
-        }
-    }
-    for ( auto& e : c->evStep ) {
-        if ( hipEventCreate( &e ) != hipSuccess ) {
-            mi355x_bz2_destroy( c );
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-    }
-    initCrcConsts( c->crc );
-    const uint32_t initial = ( config != nullptr && config->max_batch_blocks > 0 ) ? config->max_batch_blocks : 64;
-    const int rc = ensureScratch( c, initial );
+    const int rc = initContext( c, ( config != nullptr && config->max_batch_blocks > 0 ) ? config->max_batch_blocks : 64 );
     if ( rc != MI355X_BZ2_OK ) {
-        std::fprintf( stderr, "mi355x_bz2_create: %s\n", c->lastError.c_str() );
-        mi355x_bz2_destroy( c );
+        mi355x_bz2_destroy( c );   /* releases whatever exists so far */
         return rc;
     }
     *out = c;
@@ -745,7 +642,7 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     freeRetired( c );
     c->upload.reset();   /* joins the copy thread (of the owner; sharers only drop their reference) before the memory goes */
     if ( c->inStream ) (void)hipStreamSynchronize( c->inStream );
-    for ( auto& buffer : c->in ) (void)hipFree( buffer.bytes );
+    for ( auto& buffer : c->in ) buffer.release();
     if ( c->inReady ) (void)hipEventDestroy( c->inReady );
     if ( c->inStream ) (void)hipStreamDestroy( c->inStream );
     if ( c->scanStream ) {
@@ -754,14 +651,10 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     }
     (void)hipFree( c->dScanFound );
     (void)hipFree( c->dScanCounter );
-    (void)hipFree( c->dGatherTiles );
-    (void)hipHostFree( c->hGatherTiles );
-    (void)hipFree( c->dGatherStage );
-    (void)hipHostFree( c->hGatherStage );
-    (void)hipFree( c->dResult );
+    for ( GrowBuffer* buffer : { &c->dGatherTiles, &c->hGatherTiles, &c->dGatherStage, &c->hGatherStage, &c->result } ) buffer->release();
     if ( c->copyStream ) (void)hipStreamSynchronize( c->copyStream );
     for ( auto& buffer : c->out ) {
-        (void)hipFree( buffer.bytes );
+        buffer.release();
         if ( buffer.copied ) (void)hipEventDestroy( buffer.copied );
     }
     if ( c->copyStream ) (void)hipStreamDestroy( c->copyStream );
@@ -805,11 +698,7 @@ reserveInput( mi355x_bz2_ctx* c, int which, uint64_t size )
     if ( padded > buffer.capacity ) {
         /* nothing reads this buffer: the batch in flight, if any, reads the other one */
         if ( c->inStream ) HIP_TRY( c, hipStreamSynchronize( c->inStream ) );
-        retire( c, buffer.bytes, buffer.capacity, false, padded );
-        buffer.bytes = nullptr;
-        buffer.capacity = 0;
-        HIP_TRY( c, hipMalloc( &buffer.bytes, padded ) );
-        buffer.capacity = padded;
+        HIP_TRY( c, buffer.grow( c, padded, padded, padded ) );
     }
     return MI355X_BZ2_OK;
 }
@@ -916,10 +805,7 @@ mi355x_bz2_set_input_host_streamed( mi355x_bz2_ctx* c, const uint8_t* bytes, uin
     HIP_TRY( c, hipSetDevice( c->device ) );
     c->upload.reset();
     if ( c->inStream ) HIP_TRY( c, hipStreamSynchronize( c->inStream ) );
-    for ( auto& buffer : c->in ) {      /* the streamed copy owns its buffers */
-        (void)hipFree( buffer.bytes );
-        buffer = {};
-    }
+    for ( auto& buffer : c->in ) buffer.release();      /* the streamed copy owns its buffers */
     c->inPending = false;
     {
         /* the whole file becomes resident (bounded residency is not implemented): say so if it cannot */
@@ -1286,22 +1172,23 @@ mi355x::resultBuffer( mi355x_bz2_ctx* c, uint64_t size, uint64_t keep, uint8_t**
     if ( c == nullptr || device == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     HIP_TRY( c, hipSetDevice( c->device ) );
-    if ( size > c->resultCap || c->dResult == nullptr ) {
+    GrowBuffer& result = c->result;
+    if ( size > result.capacity || result.bytes == nullptr ) {
         /* the output functions may still address the old buffer: nothing reads it once the stream is idle */
         HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-        const uint64_t cap = std::max<uint64_t>( { size, c->resultCap + c->resultCap / 2, uint64_t( 1 ) << 20 } );
-        if ( c->dOut == c->dResult ) c->dOut = c->out[c->outCurrent].bytes;
-        uint8_t* grown = nullptr;
-        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &grown ), cap ) );
-        if ( keep != 0 && c->dResult != nullptr ) {
-            HIP_TRY( c, hipMemcpyAsync( grown, c->dResult, std::min( keep, c->resultCap ), hipMemcpyDeviceToDevice, c->stream ) );
+        const uint64_t cap = std::max<uint64_t>( { size, result.capacity + result.capacity / 2, uint64_t( 1 ) << 20 } );
+        if ( c->dOut == result.bytes ) c->dOut = c->out[c->outCurrent].bytes;
+        /* the new allocation first: the old one is put aside only when its first `keep` bytes have been copied */
+        GrowBuffer grown;
+        HIP_TRY( c, grown.grow( c, cap, cap, cap ) );
+        if ( keep != 0 && result.bytes != nullptr ) {
+            HIP_TRY( c, hipMemcpyAsync( grown.bytes, result.bytes, std::min( keep, result.capacity ), hipMemcpyDeviceToDevice, c->stream ) );
             HIP_TRY( c, hipStreamSynchronize( c->stream ) );
         }
-        retire( c, c->dResult, c->resultCap, false, cap );
-        c->dResult = grown;
-        c->resultCap = cap;
+        std::swap( result, grown );
+        grown.putAside( c, cap );
     }
-    *device = c->dResult;
+    *device = result.bytes;
     return MI355X_BZ2_OK;
 }
 
@@ -1335,9 +1222,9 @@ mi355x::setLastError( mi355x_bz2_ctx* c, const std::string& message )
 int
 mi355x::publishResult( mi355x_bz2_ctx* c, uint64_t size )
 {
-    if ( c == nullptr || size > c->resultCap ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    if ( c == nullptr || size > c->result.capacity ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
-    c->dOut = c->dResult;   /* until the next decode_batch_begin chooses its output buffer again */
+    c->dOut = c->result.bytes;   /* until the next decode_batch_begin chooses its output buffer again */
     c->outSize = size;
     return MI355X_BZ2_OK;
 }
@@ -1464,7 +1351,7 @@ mi355x_bz2_copy_output_begin( mi355x_bz2_ctx* c, uint64_t offset, uint64_t size,
     if ( c == nullptr || ( hostDst == nullptr && size > 0 ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     if ( offset + size > c->outSize || c->pendingBlocks != 0 ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    if ( c->dResult != nullptr && c->dOut == c->dResult ) {
+    if ( c->result.bytes != nullptr && c->dOut == c->result.bytes ) {
         /* the background copy belongs to the double-buffered batch output; a decompress_buffers result is not in it */
         c->lastError = "copy_output_begin: the output is a decompress_buffers result: use mi355x_bz2_copy_output";
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
@@ -1540,8 +1427,8 @@ mi355x_bz2_device_memory( const mi355x_bz2_ctx* c, uint64_t* scratchBytes, uint6
 {
     if ( c == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
-    if ( scratchBytes != nullptr ) *scratchBytes = c->scratchBytes;
-    if ( outputBytes != nullptr ) *outputBytes = c->out[0].capacity + c->out[1].capacity + c->resultCap;
+    if ( scratchBytes != nullptr ) *scratchBytes = c->layout.deviceBytes;
+    if ( outputBytes != nullptr ) *outputBytes = c->out[0].capacity + c->out[1].capacity + c->result.capacity;
     return MI355X_BZ2_OK;
 }
 
@@ -1694,29 +1581,17 @@ mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* piec
     }
     HIP_TRY( c, hipSetDevice( c->device ) );
     /* the previous call's tile list has been consumed (every call waits for its kernel) */
-    if ( nTiles > c->gatherTileCap ) {
-        const uint64_t cap = std::max<uint64_t>( 2 * c->gatherTileCap, nTiles );
-        retire( c, c->hGatherTiles, c->gatherTileCap * sizeof( GatherTile ), true, cap * sizeof( GatherTile ) );
-        retire( c, c->dGatherTiles, c->gatherTileCap * sizeof( GatherTile ), false, cap * sizeof( GatherTile ) );
-        c->hGatherTiles = nullptr;
-        c->dGatherTiles = nullptr;
-        c->gatherTileCap = 0;
-        HIP_TRY( c, hipHostMalloc( reinterpret_cast<void**>( &c->hGatherTiles ), cap * sizeof( GatherTile ), hipHostMallocDefault ) );
-        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &c->dGatherTiles ), cap * sizeof( GatherTile ) ) );
-        c->gatherTileCap = cap;
-    }
+    const uint64_t tileBytes = nTiles * sizeof( GatherTile ), tileCap = std::max( 2 * c->dGatherTiles.capacity, tileBytes );
+    HIP_TRY( c, c->hGatherTiles.grow( c, tileBytes, tileCap, tileCap ) );
+    HIP_TRY( c, c->dGatherTiles.grow( c, tileBytes, tileCap, tileCap ) );
     const bool toHost = dstIsDevice == 0;
-    if ( toHost && total > c->gatherStageCap ) {
-        const uint64_t cap = std::max<uint64_t>( c->gatherStageCap + c->gatherStageCap / 2, total );
-        retire( c, c->hGatherStage, c->gatherStageCap, true, cap );
-        retire( c, c->dGatherStage, c->gatherStageCap, false, cap );
-        c->hGatherStage = nullptr;
-        c->dGatherStage = nullptr;
-        c->gatherStageCap = 0;
-        HIP_TRY( c, hipHostMalloc( reinterpret_cast<void**>( &c->hGatherStage ), cap, hipHostMallocDefault ) );
-        HIP_TRY( c, hipMalloc( reinterpret_cast<void**>( &c->dGatherStage ), cap ) );
-        c->gatherStageCap = cap;
+    if ( toHost ) {
+        const uint64_t cap = std::max( c->dGatherStage.capacity + c->dGatherStage.capacity / 2, total );
+        HIP_TRY( c, c->hGatherStage.grow( c, total, cap, cap ) );
+        HIP_TRY( c, c->dGatherStage.grow( c, total, cap, cap ) );
     }
+    GatherTile* const hTiles = reinterpret_cast<GatherTile*>( c->hGatherTiles.bytes );
+    GatherTile* const dTiles = reinterpret_cast<GatherTile*>( c->dGatherTiles.bytes );
     /* a host destination gets the pieces packed back to back in the staging buffer, one D2H copy of exactly the requested
      * bytes, and then each piece copied to its place: bytes of `dst` between the pieces are never written */
     uint64_t tile = 0, staged = 0;
@@ -1724,22 +1599,22 @@ mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* piec
         const auto& p = pieces[i];
         const uint64_t at = toHost ? staged : p.dst_offset;
         for ( uint64_t k = 0; k < p.size; k += GATHER_TILE ) {
-            c->hGatherTiles[tile++] = { p.src_offset + k, at + k, std::min<uint64_t>( GATHER_TILE, p.size - k ) };
+            hTiles[tile++] = { p.src_offset + k, at + k, std::min<uint64_t>( GATHER_TILE, p.size - k ) };
         }
         staged += p.size;
     }
-    HIP_TRY( c, hipMemcpyAsync( c->dGatherTiles, c->hGatherTiles, nTiles * sizeof( GatherTile ), hipMemcpyHostToDevice, c->stream ) );
-    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, c->dGatherTiles, c->dOut,
-                        toHost ? c->dGatherStage : static_cast<uint8_t*>( dst ) );
+    HIP_TRY( c, hipMemcpyAsync( dTiles, hTiles, tileBytes, hipMemcpyHostToDevice, c->stream ) );
+    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, dTiles, c->dOut,
+                        toHost ? c->dGatherStage.bytes : static_cast<uint8_t*>( dst ) );
     HIP_TRY( c, hipGetLastError() );
     if ( toHost ) {
-        HIP_TRY( c, hipMemcpyAsync( c->hGatherStage, c->dGatherStage, total, hipMemcpyDeviceToHost, c->stream ) );
+        HIP_TRY( c, hipMemcpyAsync( c->hGatherStage.bytes, c->dGatherStage.bytes, total, hipMemcpyDeviceToHost, c->stream ) );
     }
     HIP_TRY( c, hipStreamSynchronize( c->stream ) );
     if ( toHost ) {
         staged = 0;
         for ( uint32_t i = 0; i < nPieces; ++i ) {
-            std::memcpy( static_cast<uint8_t*>( dst ) + pieces[i].dst_offset, c->hGatherStage + staged, pieces[i].size );
+            std::memcpy( static_cast<uint8_t*>( dst ) + pieces[i].dst_offset, c->hGatherStage.bytes + staged, pieces[i].size );
             staged += pieces[i].size;
         }
     }
@@ -1752,8 +1627,8 @@ mi355x_bz2_debug_copy_stage( mi355x_bz2_ctx* c, uint32_t index, int stage, void*
     if ( c == nullptr || hostDst == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     const std::scoped_lock lock( c->mutex );
     if ( index >= c->lastBlocks ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    if ( ( c->flags & MI355X_BZ2_FLAG_KEEP_STAGES ) == 0 && ( stage == 0 || stage == 2 ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;      /* the two share their memory in a context made without the flag */
+    if ( c->layout.aliasOf[R_dR] == R_dL && ( stage == 0 || stage == 2 ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;      /* the two share their memory in a context made without KEEP_STAGES */
     }
     index = c->hSlotOf[index];   /* per-block buffers are in slot order */
     const uint64_t N = c->hMeta[index].n;

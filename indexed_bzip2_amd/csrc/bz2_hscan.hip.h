@@ -39,7 +39,6 @@ constexpr uint32_t SCAN_MAX_SPAN = 1024;        /* bit positions per build; 50 c
 constexpr uint32_t SCAN_ROWS = SCAN_MAX_SPAN / 64;
 constexpr uint32_t GROUP_SYMS = 50;
 constexpr uint32_t MAX_SCAN_GROUPS = 18002;     /* 900 100 symbols: more than any block that k_mtf accepts */
-constexpr uint32_t GPOS_STRIDE = 18048;         /* u32 per block */
 constexpr uint32_t LEN_STOP = 0x80u;            /* length-table flag: the code is the end-of-block symbol */
 constexpr uint32_t SYM_THREADS = 128;           /* groups per chunk of a k_hsym workgroup (default: 256, bz2_device.hip) */
 constexpr uint32_t SYM_CHUNKS = 4;              /* chunks per workgroup */

@@ -19,16 +19,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "bz2_plan.hpp"   /* BWT_SPLIT_MAX */
+#include "bz2_scratch.hpp"   /* the strides of the per-block buffers */
 
 namespace bz2gpu
 {
 constexpr uint32_t MAX_N = 900000;            /* bzip2.hpp:416 dbuf size */
-constexpr uint32_t L_STRIDE = 900096;         /* bytes per block in the L and R buffers (multiple of 256) */
-constexpr uint32_t SEL_STRIDE = 32768;        /* bzip2.hpp:451 */
-constexpr uint32_t TAB_STRIDE = 1u << 20;     /* u32 entries per block: every 20-bit index stays in bounds */
-constexpr uint32_t KMAX = 32768;              /* max regular walk segments per block (+1 for origPtr) */
-constexpr uint32_t SEG_STRIDE = KMAX + 64;
 constexpr uint32_t MIN_SEG_STRIDE = 16;
 constexpr uint32_t MARK = 0x80000000u;
 constexpr uint32_t LF_MASK = 0xFFFFFu;
@@ -251,8 +246,6 @@ popc_below( uint64_t mask, uint32_t lane )
  * LF = T^-1 needs no scatter and is walked backwards from origPtr: out[N-1-k] = L[LF^k(origPtr)].
  * One workgroup of 1024 threads (16 waves) per block; wave w owns a contiguous 1/16 of the block.
  * ============================================================================================================= */
-constexpr int BWT_WAVES = 16;
-
 __global__ __launch_bounds__( 1024 ) void
 k_bwt_build( const BlockMeta* __restrict__ meta,
              const uint8_t* __restrict__   l_buf,
@@ -356,8 +349,6 @@ k_bwt_build( const BlockMeta* __restrict__ meta,
  * (s, b) turns the counts of all chunks in front of its own into the first rank of every byte value in each of its
  * chunks, then ranks its slice exactly as k_bwt_build's second pass does.
  * ------------------------------------------------------------------------------------------------------------- */
-constexpr uint32_t BWT_COUNTS_PER_BLOCK = BWT_SPLIT_MAX * BWT_WAVES * 256;   /* u32 */
-
 __device__ __forceinline__ void
 bwt_chunk_range( uint32_t N, uint32_t slices, uint32_t slice, uint32_t wave, uint32_t& begin, uint32_t& end )
 {

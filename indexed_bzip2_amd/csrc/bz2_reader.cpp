@@ -322,7 +322,7 @@ public:
     {
         mi355x_bz2_config config{};
         config.device = device;
-        /* scratch (13 MB per block) grows with the batches that are really launched: a reader that seeks and reads a
+        /* scratch (10.1 MB per block) grows with the batches that are really launched: a reader that seeks and reads a
          * little never pays for a full batch, a sequential one pays once per context, on that context's own thread */
         config.max_batch_blocks = 1;
         mi355x_bz2_ctx* ctx = nullptr;
@@ -635,7 +635,7 @@ private:
         }
         /* as many as fit: a batch, the room in flight, the window of blocks decoded ahead (finished ones that are still
          * wanted must not be pushed out by newer ones, BlockFetcher.hpp:527-535) */
-        /* the first launches are small and grow (64, 256, 1 024 blocks): a context's scratch for a full batch (13 MB per block)
+        /* the first launches are small and grow (64, 256, 1 024 blocks): a context's scratch for a full batch (10.1 MB per block)
          * takes longer to allocate than the batch to decode, and the reader should not wait for that before its first bytes */
         size_t room = std::min( { m_batch, limit - m_inFlightBlocks, end - from, m_ramp } );
         const size_t ahead = m_ready.blocksWithin( wanted.first, end ) + m_inFlightBlocks;

@@ -26,10 +26,9 @@ namespace bz2gpu
 {
 constexpr uint32_t WALK_THREADS = 256;
 constexpr uint32_t WALK_QUEUES = 8;
-constexpr uint32_t STASH_BYTES = 128;        /* bytes of a segment the first walk keeps (two 64-B lines per segment: 1 % of the
-                                                bytes lie beyond, 10 % with one line).  Round 3 measured a quarter of the
-                                                segments with 512 stashed bytes each: k_link2 4.7 -> 1.8 ms, but k_walk 21 -> 32
-                                                and k_emit 5.3 -> 10.8 ms for the bench's batch; gone again */
+/* STASH_BYTES (bz2_scratch.hpp) = 128: two 64-B lines per segment, 1 % of the bytes lie beyond, 10 % with one line.  Round 3
+ * measured a quarter of the segments with 512 stashed bytes each: k_link2 4.7 -> 1.8 ms, but k_walk 21 -> 32 and k_emit
+ * 5.3 -> 10.8 ms for the bench's batch; gone again */
 constexpr uint32_t EMIT_THREADS = 256;       /* segments (consecutive along the cycle) per k_emit workgroup */
 constexpr uint32_t EMIT_TILES = 4;           /* such pieces per workgroup, one after the other */
 constexpr uint32_t EMIT_STAGE = 16384;       /* LDS bytes that collect their output before it is written in whole lines */

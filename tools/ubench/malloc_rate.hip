@@ -1,4 +1,4 @@
-// Micro-benchmark: what does device memory cost to allocate?  (the reader's scratch is 13 MB per block)
+// Micro-benchmark: what does device memory cost to allocate?  (the reader's scratch is 10.1 MB per block)
 // Finding (two boxes): it depends on the state of the VRAM, not on the call.  The first allocation of a process that
 // reaches pages another process has used pays for clearing them (0.6-1.8 s for 16 GB, whether through hipMalloc or
 // hipMallocAsync); the same size again, or on a fresh box, is free (0.3 ms).  So the only lever is to allocate less.
