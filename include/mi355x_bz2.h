@@ -239,6 +239,27 @@ typedef struct mi355x_bz2_gather_piece {
 int mi355x_bz2_gather_output( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, uint32_t n_pieces,
                               void* dst, int dst_is_device );
 
+/* One byte value in spans of the last batch's output (mi355x_bz2_output_device), on the GPU: the kernels under the
+ * reader's newline index and line ranges.  The same rules as mi355x_bz2_gather_output: the spans lie inside the last
+ * batch's output (else MI355X_BZ2_ERR_INVALID_ARGUMENT) at any alignment, the work runs on the context's stream, the
+ * calls return when it is done, and no batch may be in flight.  Spans are cut into 64-KiB tiles, one workgroup each, so a
+ * span of any length is counted in parallel and searched without walking it; a span given several times is counted
+ * once.  No reference counterpart for bzip2 (rapidgzip counts newlines per chunk on the host,
+ * src/rapidgzip/ParallelGzipReader.hpp:1056-1145).
+ *   _count_byte  counts[i] = the number of bytes equal to `value` in [offset, offset + size) of span i  (k_count_byte).
+ *   _find_byte   positions[i] = the offset in the output of the rank-th (1-based; 0 is refused) byte equal to `value`
+ *                in span i, or UINT64_MAX if the span holds fewer than rank of them  (k_count_byte, then k_find_byte). */
+typedef struct mi355x_bz2_byte_span {
+    uint64_t offset, size;
+} mi355x_bz2_byte_span;
+typedef struct mi355x_bz2_byte_query {
+    uint64_t offset, size, rank;
+} mi355x_bz2_byte_query;
+int mi355x_bz2_count_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t value,
+                           uint64_t* counts );
+int mi355x_bz2_find_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_query* queries, uint32_t n, uint8_t value,
+                          uint64_t* positions );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -378,6 +399,49 @@ int      mi355x_bz2_reader_block_offsets_complete( const mi355x_bz2_reader* r );
  * unspecified).  No reference counterpart (ParallelBZ2Reader reads one range at a time). */
 int mi355x_bz2_reader_read_ranges( mi355x_bz2_reader* r, const uint64_t* offsets, const uint64_t* sizes, uint32_t n,
                                    void* dst, int dst_is_device, uint64_t* n_read );
+
+/* ---- line access.  D = the decoded file, `nl` = one delimiter byte (any value: '\n', '\r', 0).  N = the number of nl
+ * bytes in D.  Line k (0-based) starts at s(k): s(0) = 0, s(k) = 1 + the position of the k-th nl (1 <= k <= N); line N
+ * is the unterminated tail D[s(N):], possibly empty.  The line range (first, count) is D[s(first) : s(first + count)]
+ * (closing nl included) if first + count <= N, D[s(first):] if first <= N < first + count, and nothing if first > N or
+ * count == 0: the readLines loop of rapidgzip (src/tools/rapidgzip.cpp:624-748) -- the reference has line access for
+ * gzip only, not for bzip2.
+ * The line index has one entry per data block plus the end: {decoded offset of the block's first byte -> nl bytes in
+ * front of it}, ..., {size of D -> N}; {0 -> 0} for an empty file (rapidgzip's m_newlineOffsets: one NewlineOffset per
+ * chunk and the final one, ParallelGzipReader.hpp:90, 1056-1145).  The reader keeps one index, together with its nl; a
+ * line function called with another nl, or before any index exists, builds it first.
+ * All of these are positionless like read_ranges: tell(), eof() and the sequential reader's decoded runs stay as they
+ * are, the launches go to the front of the queue and decode at most `parallelization` blocks each. */
+
+/* The line index for `nl`, built if the reader does not hold it: the block map is completed first if it is not (as
+ * block_offsets does), then every data block is decoded once and k_count_byte counts nl in it; nothing but the counts
+ * leaves the GPU.  Two-call protocol as block_offsets: capacity 0 gives the count in *n. */
+int mi355x_bz2_reader_line_offsets( mi355x_bz2_reader* r, uint8_t nl, uint64_t* bytes, uint64_t* lines,
+                                    uint64_t capacity, uint64_t* n );
+/* Import of a line index for `nl`.  Needs a complete block map (MI355X_BZ2_ERR_INVALID_ARGUMENT otherwise, and when the
+ * keys are not exactly the data blocks' decoded offsets plus the size, the values do not start at 0 or decrease, or a
+ * block is given more delimiters than it has bytes).  An index that fits the map but not the data is found out when a
+ * line is looked for: that call fails with MI355X_BZ2_ERR_LOGIC. */
+int mi355x_bz2_reader_set_line_offsets( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* bytes, const uint64_t* lines,
+                                        uint64_t n );
+/* byte_offsets[i] = s( lines[i] ), or the size of D for lines[i] > N.  Decodes only the blocks that hold one of the
+ * delimiters asked for (k_find_byte finds them); no data byte is copied out. */
+int mi355x_bz2_reader_line_starts( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* lines, uint32_t n,
+                                   uint64_t* byte_offsets );
+/* Many line ranges at once, in two steps, because nobody knows a range's size before its blocks are decoded (compare
+ * mi355x_bz2_decompress_buffers followed by mi355x_bz2_copy_output / _gather_output).
+ * Step 1, _read_line_ranges: every block some range needs -- from the block that holds the first-th delimiter through
+ * the one that holds the (first + count)-th, or the last block -- is decoded once, k_find_byte resolves the ranges' ends
+ * in the decoded blocks, and k_gather packs each launch's pieces into a buffer of the context that ran it, where they
+ * are held.  byte_sizes[i] = the bytes of range i, *total their sum.  keep_on_device tells where step 2 will write
+ * (1: device memory); it is recorded for the check in step 2 and moves no data.
+ * Step 2, _take_line_ranges: writes range i at dst + byte_sizes[0] + ... + byte_sizes[i - 1] (dst_is_device must equal
+ * keep_on_device; for a host destination exactly the requested bytes cross to the host, for a device destination none)
+ * and releases what step 1 held.  The next line call, or close, releases it as well.
+ * A block that fails to decode fails step 1 with its status and bit offset. */
+int mi355x_bz2_reader_read_line_ranges( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* first, const uint64_t* count,
+                                        uint32_t n, int keep_on_device, uint64_t* byte_sizes, uint64_t* total );
+int mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dst_is_device );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

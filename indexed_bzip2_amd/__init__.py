@@ -20,7 +20,7 @@ from ._native import (Bz2Error, Decoder, find_magic, lib, plan_compress_blocks, 
 from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
                       decompress_many_to_tensor)
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401
-                     write_block_offsets)
+                     read_line_offsets, write_block_offsets, write_line_offsets)
 
 if _os.environ.get("MI355X_BZ2_WARMUP") == "1":     # opt-in: see warmup()
     warmup()

@@ -87,6 +87,14 @@ class GatherPiece(ctypes.Structure):
     _fields_ = [("src_offset", ctypes.c_uint64), ("dst_offset", ctypes.c_uint64), ("size", ctypes.c_uint64)]
 
 
+class ByteSpan(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_uint64), ("size", ctypes.c_uint64)]
+
+
+class ByteQuery(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_uint64), ("size", ctypes.c_uint64), ("rank", ctypes.c_uint64)]
+
+
 class BufferResult(ctypes.Structure):
     _fields_ = [("output_offset", ctypes.c_uint64), ("decoded_size", ctypes.c_uint64),
                 ("error_offset_bits", ctypes.c_uint64), ("n_blocks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
@@ -140,6 +148,8 @@ SYMBOLS = [
     ("mi355x_bz2_find_magic_device", ctypes.c_int, [_vp, ctypes.c_uint64, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_crc32_device", ctypes.c_int, [_vp, _vp, _u64p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
     ("mi355x_bz2_gather_output", ctypes.c_int, [_vp, ctypes.POINTER(GatherPiece), ctypes.c_uint32, _vp, ctypes.c_int]),
+    ("mi355x_bz2_count_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
+    ("mi355x_bz2_find_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteQuery), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -159,6 +169,12 @@ SYMBOLS = [
     ("mi355x_bz2_reader_available_block_offsets", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_set_block_offsets", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64]),
     ("mi355x_bz2_reader_read_ranges", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint32, _vp, ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_line_offsets", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_reader_set_line_offsets", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, _u64p, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_line_starts", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, ctypes.c_uint32, _u64p]),
+    ("mi355x_bz2_reader_read_line_ranges", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, _u64p, ctypes.c_uint32, ctypes.c_int,
+                                                           _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_line_ranges", ctypes.c_int, [_vp, _vp, ctypes.c_int]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -437,6 +453,23 @@ class Decoder:
         """The same into device memory at `device_ptr` (on the decoder's device): each piece written in place."""
         pieces, arr = self._pieces(pieces)
         self._check(lib().mi355x_bz2_gather_output(self._h, arr, len(pieces), ctypes.c_void_p(device_ptr), 1))
+
+    def count_byte(self, value: int, spans):
+        """k_count_byte: how often the byte `value` occurs in each span [(offset, size)] of the last batch's output."""
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        out = (ctypes.c_uint64 * max(1, len(spans)))()
+        self._check(lib().mi355x_bz2_count_byte(self._h, arr, len(spans), value, out))
+        return list(out[:len(spans)])
+
+    def find_byte(self, value: int, queries):
+        """k_find_byte: for each query (offset, size, rank) the offset in the last batch's output of the rank-th
+        (1-based) byte `value` in the span, or None if the span holds fewer."""
+        queries = [(int(o), int(n), int(r)) for o, n, r in queries]
+        arr = (ByteQuery * max(1, len(queries)))(*[ByteQuery(o, n, r) for o, n, r in queries])
+        out = (ctypes.c_uint64 * max(1, len(queries)))()
+        self._check(lib().mi355x_bz2_find_byte(self._h, arr, len(queries), value, out))
+        return [None if p == 2**64 - 1 else p for p in out[:len(queries)]]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -19,6 +19,11 @@ int decodeBatchBegin( mi355x_bz2_ctx* ctx, const uint64_t* offsets, const uint64
  * calls. */
 int resultBuffer( mi355x_bz2_ctx* ctx, uint64_t size, uint64_t keep, uint8_t** device );
 
+/** mi355x_bz2_gather_output with the result buffer as the source: pieces [src_offset, src_offset + size) of it go to
+ * `dst`.  Unlike the public call it may run while a batch is in flight on the context (the result buffer is not a batch
+ * output); the kernel then queues behind what that batch has put on the context's stream. */
+int gatherResult( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice );
+
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */
 int publishResult( mi355x_bz2_ctx* ctx, uint64_t size );

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstring>
 #include <condition_variable>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -24,6 +25,7 @@
 
 #include "../../include/mi355x_bz2.h"
 #include "bz2_kernels.hip.h"
+#include "bz2_lines.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -203,6 +205,10 @@ struct mi355x_bz2_ctx : Scratch
     /* mi355x_bz2_gather_output: grow-only, so that a call allocates nothing once the sizes have been seen.  The tile
      * list (page-locked and on the device) and, for a host destination, the packed pieces (device and page-locked) */
     GrowBuffer hGatherTiles{ nullptr, 0, true }, dGatherTiles, hGatherStage{ nullptr, 0, true }, dGatherStage;
+
+    /* mi355x_bz2_count_byte / _find_byte: tiles, queries, tile counts and results of one call, page-locked and on the
+     * device (selectBytes lays them out) */
+    GrowBuffer hSelect{ nullptr, 0, true }, dSelect;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
     GrowBuffer result;
@@ -651,7 +657,8 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     }
     (void)hipFree( c->dScanFound );
     (void)hipFree( c->dScanCounter );
-    for ( GrowBuffer* buffer : { &c->dGatherTiles, &c->hGatherTiles, &c->dGatherStage, &c->hGatherStage, &c->result } ) buffer->release();
+    for ( GrowBuffer* buffer : { &c->dGatherTiles, &c->hGatherTiles, &c->dGatherStage, &c->hGatherStage, &c->hSelect, &c->dSelect,
+                                &c->result } ) buffer->release();
     if ( c->copyStream ) (void)hipStreamSynchronize( c->copyStream );
     for ( auto& buffer : c->out ) {
         buffer.release();
@@ -1173,10 +1180,12 @@ mi355x::resultBuffer( mi355x_bz2_ctx* c, uint64_t size, uint64_t keep, uint8_t**
     const std::scoped_lock lock( c->mutex );
     HIP_TRY( c, hipSetDevice( c->device ) );
     GrowBuffer& result = c->result;
-    if ( size > result.capacity || result.bytes == nullptr ) {
+    /* 256 bytes of slack behind the bytes, as the batch output buffers have: the aligned loads of k_gather and
+     * k_count_byte reach a few bytes behind the last one */
+    if ( size + 256 > result.capacity || result.bytes == nullptr ) {
         /* the output functions may still address the old buffer: nothing reads it once the stream is idle */
         HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-        const uint64_t cap = std::max<uint64_t>( { size, result.capacity + result.capacity / 2, uint64_t( 1 ) << 20 } );
+        const uint64_t cap = std::max<uint64_t>( { size + 256, result.capacity + result.capacity / 2, uint64_t( 1 ) << 20 } );
         if ( c->dOut == result.bytes ) c->dOut = c->out[c->outCurrent].bytes;
         /* the new allocation first: the old one is put aside only when its first `keep` bytes have been copied */
         GrowBuffer grown;
@@ -1553,21 +1562,21 @@ mi355x_bz2_crc32_device( mi355x_bz2_ctx* c, const void* deviceBytes, const uint6
     return MI355X_BZ2_OK;
 }
 
-int
-mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst,
-                          int dstIsDevice )
+}  // extern "C"
+
+namespace
 {
-    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = "gather_output: a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    /* every piece inside the last batch's output; tiles of at most GATHER_TILE bytes */
+/** k_gather over pieces of the `srcSize` bytes at `src` (device memory of the context), see mi355x_bz2_gather_output.
+ * The caller holds the context's lock. */
+int
+gatherPieces( mi355x_bz2_ctx* c, const uint8_t* src, uint64_t srcSize, const mi355x_bz2_gather_piece* pieces,
+              uint32_t nPieces, void* dst, int dstIsDevice )
+{
+    /* every piece inside the source; tiles of at most GATHER_TILE bytes */
     uint64_t nTiles = 0, total = 0;
     for ( uint32_t i = 0; i < nPieces; ++i ) {
         const auto& p = pieces[i];
-        if ( p.size > c->outSize || p.src_offset > c->outSize - p.size || p.dst_offset > ~uint64_t( 0 ) - p.size ) {
+        if ( p.size > srcSize || p.src_offset > srcSize - p.size || p.dst_offset > ~uint64_t( 0 ) - p.size ) {
             c->lastError = "gather_output: piece " + std::to_string( i ) + " lies outside the last batch's output";
             return MI355X_BZ2_ERR_INVALID_ARGUMENT;
         }
@@ -1604,7 +1613,7 @@ mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* piec
         staged += p.size;
     }
     HIP_TRY( c, hipMemcpyAsync( dTiles, hTiles, tileBytes, hipMemcpyHostToDevice, c->stream ) );
-    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, dTiles, c->dOut,
+    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, dTiles, src,
                         toHost ? c->dGatherStage.bytes : static_cast<uint8_t*>( dst ) );
     HIP_TRY( c, hipGetLastError() );
     if ( toHost ) {
@@ -1619,6 +1628,143 @@ mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* piec
         }
     }
     return MI355X_BZ2_OK;
+}
+
+/**
+ * Both byte calls: the distinct spans are cut into tiles, k_count_byte counts every tile, and either the spans' sums or
+ * (ranks given) the positions k_find_byte finds come back.  One page-locked and one device allocation hold the tiles,
+ * the queries, the tile counts and the results of the call.
+ */
+int
+selectBytes( mi355x_bz2_ctx* c, const char* what, uint8_t value, uint32_t n, const uint64_t* offsets, const uint64_t* sizes,
+             const uint64_t* ranks, uint64_t* results )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    /* every span inside the last batch's output; a span named several times is counted once */
+    std::map<std::pair<uint64_t, uint64_t>, uint32_t> known;
+    std::vector<uint32_t> spanOf( n );
+    std::vector<std::pair<uint64_t, uint64_t> > spans;
+    std::vector<uint64_t> firstTile;
+    uint64_t nTiles = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( sizes[i] > c->outSize || offsets[i] > c->outSize - sizes[i] || ( ranks != nullptr && ranks[i] == 0 ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i )
+                           + " lies outside the last batch's output, or its rank is 0";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        const auto [entry, isNew] = known.emplace( std::make_pair( offsets[i], sizes[i] ), (uint32_t)spans.size() );
+        spanOf[i] = entry->second;
+        if ( isNew ) {
+            spans.push_back( entry->first );
+            firstTile.push_back( nTiles );
+            nTiles += ( sizes[i] + COUNT_TILE - 1 ) / COUNT_TILE;
+        }
+    }
+    firstTile.push_back( nTiles );
+    const bool find = ranks != nullptr;
+    for ( uint32_t i = 0; i < n; ++i ) results[i] = find ? FIND_NONE : 0;
+    if ( nTiles == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][queries][results]; device only: [tile counts] behind them */
+    const uint64_t nResults = find ? n : spans.size();
+    const uint64_t tilesAt = 0, queriesAt = tilesAt + nTiles * sizeof( CountTile );
+    const uint64_t resultsAt = queriesAt + ( find ? n * sizeof( FindQuery ) : 0 );
+    const uint64_t countsAt = resultsAt + nResults * sizeof( uint64_t ), bytes = countsAt + nTiles * sizeof( uint32_t );
+    const uint64_t cap = std::max( 2 * c->dSelect.capacity, bytes );
+    /* the previous call's lists have been consumed (every call waits for its kernels) */
+    HIP_TRY( c, c->hSelect.grow( c, countsAt, cap, cap ) );
+    HIP_TRY( c, c->dSelect.grow( c, bytes, cap, cap ) );
+    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSelect.bytes + tilesAt );
+    auto* const hQueries = reinterpret_cast<FindQuery*>( c->hSelect.bytes + queriesAt );
+    auto* const hResults = reinterpret_cast<uint64_t*>( c->hSelect.bytes + resultsAt );
+    uint64_t tile = 0;
+    for ( size_t s = 0; s < spans.size(); ++s ) {
+        for ( uint64_t k = 0; k < spans[s].second; k += COUNT_TILE ) {
+            hTiles[tile++] = { spans[s].first + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].second - k ), (uint32_t)s };
+        }
+    }
+    for ( uint32_t i = 0; find && i < n; ++i ) {
+        hQueries[i] = { ranks[i], (uint32_t)firstTile[spanOf[i]], (uint32_t)( firstTile[spanOf[i] + 1] - firstTile[spanOf[i]] ) };
+    }
+    uint8_t* const d = c->dSelect.bytes;
+    HIP_TRY( c, hipMemcpyAsync( d, c->hSelect.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( !find ) HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, nResults * sizeof( uint64_t ), c->stream ) );
+    const uint32_t pattern = 0x01010101u * value;
+    hipLaunchKernelGGL( k_count_byte, dim3( (uint32_t)nTiles ), dim3( COUNT_THREADS ), 0, c->stream,
+                        reinterpret_cast<const CountTile*>( d + tilesAt ), c->dOut, pattern,
+                        reinterpret_cast<uint32_t*>( d + countsAt ),
+                        find ? nullptr : reinterpret_cast<unsigned long long*>( d + resultsAt ) );
+    HIP_TRY( c, hipGetLastError() );
+    if ( find ) {
+        hipLaunchKernelGGL( k_find_byte, dim3( n ), dim3( FIND_THREADS ), 0, c->stream,
+                            reinterpret_cast<const FindQuery*>( d + queriesAt ), reinterpret_cast<const CountTile*>( d + tilesAt ),
+                            reinterpret_cast<const uint32_t*>( d + countsAt ), c->dOut, pattern,
+                            reinterpret_cast<uint64_t*>( d + resultsAt ) );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    HIP_TRY( c, hipMemcpyAsync( hResults, d + resultsAt, nResults * sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( uint32_t i = 0; i < n; ++i ) results[i] = find ? hResults[i] : hResults[spanOf[i]];
+    return MI355X_BZ2_OK;
+}
+}  // namespace
+
+int
+mi355x::gatherResult( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice )
+{
+    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const std::scoped_lock lock( c->mutex );
+    return gatherPieces( c, c->result.bytes, c->result.capacity, pieces, nPieces, dst, dstIsDevice );
+}
+
+extern "C" {
+
+int
+mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst,
+                          int dstIsDevice )
+{
+    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = "gather_output: a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return gatherPieces( c, c->dOut, c->outSize, pieces, nPieces, dst, dstIsDevice );
+}
+
+int
+mi355x_bz2_count_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t value, uint64_t* counts )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    std::vector<uint64_t> offsets( n ), sizes( n );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        offsets[i] = spans[i].offset;
+        sizes[i] = spans[i].size;
+    }
+    return selectBytes( c, "count_byte", value, n, offsets.data(), sizes.data(), nullptr, counts );
+}
+
+int
+mi355x_bz2_find_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_query* queries, uint32_t n, uint8_t value,
+                      uint64_t* positions )
+{
+    if ( c == nullptr || ( n > 0 && ( queries == nullptr || positions == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    std::vector<uint64_t> offsets( n ), sizes( n ), ranks( n );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        offsets[i] = queries[i].offset;
+        sizes[i] = queries[i].size;
+        ranks[i] = queries[i].rank;
+    }
+    return selectBytes( c, "find_byte", value, n, offsets.data(), sizes.data(), ranks.data(), positions );
 }
 
 int

@@ -38,6 +38,8 @@
 
 #include "../../include/mi355x_bz2.h"
 #include "bz2_host.hpp"
+#include "bz2_ctx.hpp"
+#include "bz2_lines.hpp"
 #include "bz2_ranges.hpp"
 
 namespace mi355x
@@ -481,14 +483,48 @@ public:
     /** One launch of read_ranges: blocks that need not be consecutive, decoded once and gathered straight into the
      * caller's destination.  It goes ahead of everything queued (somebody waits for it), publishes no run and is not a
      * flight: the runs, flights and look-ahead of the sequential reader are not disturbed. */
+    struct LineWork;
     struct RangesWork
     {
         const bz2gpu::RangeLaunch* launch{ nullptr };
         std::vector<mi355x_bz2_gather_piece> pieces;
         void* dst{ nullptr };
         bool dstIsDevice{ false };
+        LineWork* lines{ nullptr };  /* set: a launch of the line functions, `pieces` and `dst` are not used */
         std::promise<void> done;     /* a Bz2Exception if a block or the device failed */
     };
+
+    /** A piece of a line range, packed into the result buffer of the context that decoded it (step 1 of
+     * read_line_ranges), where it stays until step 2 puts it in place. */
+    struct HeldPiece
+    {
+        mi355x_bz2_ctx* ctx{ nullptr };
+        uint32_t range{ 0 };
+        uint64_t offset{ 0 }, size{ 0 };
+    };
+
+    /** What a launch of the line functions does with its decoded blocks instead of gathering into a destination; owned
+     * by the caller, who waits for the launch.  In this order: count `nl` in every block (the line index), find the
+     * plan's boundary queries of this launch (positions[query], an array all launches of the call share), resolve the
+     * launch's segments with them and pack the pieces behind what the context already holds. */
+    struct LineWork
+    {
+        uint8_t nl{ 0 };
+        bool countBlocks{ false };
+        std::vector<uint64_t> blockCounts;          /* out: per block of the launch */
+        const bz2gpu::LinePlan* plan{ nullptr };
+        std::vector<uint32_t> queries, segments;    /* of this launch: indexes into the plan's lists */
+        uint64_t* positions{ nullptr };
+        std::vector<HeldPiece> held;                /* out: one per segment that has bytes */
+    };
+
+    /** Forget what the contexts hold for read_line_ranges (the buffers stay: they only grow). */
+    void
+    dropHeld()
+    {
+        const std::scoped_lock lock( m_queueMutex );
+        m_heldBytes.clear();
+    }
 
     [[nodiscard]] std::future<void>
     launchRanges( std::unique_ptr<RangesWork> ranges )
@@ -707,6 +743,74 @@ private:
         return result;
     }
 
+    /** The line functions' part of a launch whose blocks have just been decoded into the context's output (see
+     * LineWork).  Returns the failure, if any. */
+    [[nodiscard]] std::exception_ptr
+    runLineWork( mi355x_bz2_ctx* const ctx, const bz2gpu::RangeLaunch& launch, LineWork& work )
+    {
+        const auto deviceFailure = [ctx] ( int rc ) {
+            return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+        };
+        if ( work.countBlocks ) {
+            std::vector<mi355x_bz2_byte_span> spans( launch.bits.size() );
+            for ( size_t k = 0; k < spans.size(); ++k ) spans[k] = { launch.outOffsets[k], launch.sizes[k] };
+            work.blockCounts.assign( spans.size(), 0 );
+            const int rc = mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, work.blockCounts.data() );
+            if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
+        }
+        if ( !work.queries.empty() ) {
+            std::vector<mi355x_bz2_byte_query> queries( work.queries.size() );
+            std::vector<uint64_t> found( queries.size() );
+            for ( size_t k = 0; k < queries.size(); ++k ) {
+                const auto& q = work.plan->queries[work.queries[k]];
+                queries[k] = { q.spanOffset, q.spanSize, q.rank };
+            }
+            /* an index that gives a queried block another count than the block has would cut lines in the wrong places */
+            std::vector<mi355x_bz2_byte_span> spans( queries.size() );
+            std::vector<uint64_t> counted( queries.size() );
+            for ( size_t k = 0; k < queries.size(); ++k ) spans[k] = { queries[k].offset, queries[k].size };
+            int rc = mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, counted.data() );
+            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_find_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, found.data() );
+            if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
+            for ( size_t k = 0; k < queries.size(); ++k ) {
+                const auto& q = work.plan->queries[work.queries[k]];
+                work.positions[work.queries[k]] = found[k];
+                if ( found[k] == bz2gpu::NOT_FOUND || counted[k] != q.blockCount ) {
+                    return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC,
+                        "the line index gives the block at decoded offset " + std::to_string( q.blockStart ) + " "
+                        + std::to_string( q.blockCount ) + " delimiters, it holds " + std::to_string( counted[k] ) ) );
+                }
+            }
+        }
+        if ( work.segments.empty() ) return nullptr;
+        std::vector<mi355x_bz2_gather_piece> pieces;
+        uint64_t base = 0;
+        {
+            const std::scoped_lock lock( m_queueMutex );
+            base = m_heldBytes[ctx];
+        }
+        uint64_t at = base;
+        for ( const auto index : work.segments ) {
+            const auto& segment = work.plan->segments[index];
+            uint64_t src = 0, size = 0;
+            if ( !bz2gpu::resolveSegment( *work.plan, segment, work.positions, &src, &size ) ) {
+                return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC, "the line index contradicts the decoded data" ) );
+            }
+            if ( size == 0 ) continue;
+            pieces.push_back( { src, at, size } );
+            work.held.push_back( { ctx, segment.range, at, size } );
+            at += size;
+        }
+        if ( at == base ) return nullptr;
+        uint8_t* held = nullptr;
+        int rc = resultBuffer( ctx, at, base, &held );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_gather_output( ctx, pieces.data(), (uint32_t)pieces.size(), held, 1 );
+        if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
+        const std::scoped_lock lock( m_queueMutex );
+        m_heldBytes[ctx] = at;
+        return nullptr;
+    }
+
     /** One submission thread per decoder context: takes a launch, decodes the batch, copies it to a page-locked buffer,
      * publishes the run.  Replaces the thread pool of per-block tasks (BlockFetcher.hpp:620-642).
      * The copy of a batch runs in the background while the context's next batch is launched (the context writes to a
@@ -820,7 +924,9 @@ private:
                         error( MI355X_BZ2_ERR_LOGIC, "the block index promises more bytes than the block decodes to" ) );
                 }
             }
-            if ( !failure ) {
+            if ( !failure && work.lines != nullptr ) {
+                failure = runLineWork( ctx, launch, *work.lines );
+            } else if ( !failure ) {
                 rc = mi355x_bz2_gather_output( ctx, work.pieces.data(), (uint32_t)work.pieces.size(), work.dst,
                                                work.dstIsDevice ? 1 : 0 );
                 if ( rc != MI355X_BZ2_OK ) failure = std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
@@ -950,6 +1056,7 @@ private:
     const bool m_trace{ std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr };
     const std::chrono::steady_clock::time_point m_created{ std::chrono::steady_clock::now() };
     std::string m_workerError;
+    std::map<mi355x_bz2_ctx*, uint64_t> m_heldBytes;   /* of each context's result buffer: held for read_line_ranges */
     uint64_t m_batches{ 0 };
     uint64_t m_blocksDecoded{ 0 };
     double m_decodeSeconds{ 0 };
@@ -981,6 +1088,7 @@ public:
     void
     close()
     {
+        m_held.reset();
         m_scheduler.reset();
         m_finder.reset();
         m_source.reset();
@@ -1171,22 +1279,118 @@ public:
         for ( const auto& piece : plan.pieces ) {
             works[piece.launch]->pieces.push_back( { piece.src, piece.dst, piece.size } );
         }
-        /* each to the front of the queue: the last one first, so that the first launch is taken first */
-        std::vector<std::future<void> > pending( works.size() );
-        for ( size_t l = works.size(); l-- > 0; ) {
-            pending[l] = scheduler().launchRanges( std::move( works[l] ) );
+        runLaunches( works );
+        std::copy( plan.nRead.begin(), plan.nRead.end(), nRead );
+    }
+
+    /* ---------------------------------------------------------------------------------------- line access */
+    using LinePairs = std::vector<std::pair<uint64_t, uint64_t> >;
+
+    /** The line index for `nl` as {decoded offset, delimiters in front of it} pairs (mi355x_bz2_reader_line_offsets). */
+    [[nodiscard]] LinePairs
+    lineOffsets( uint8_t nl )
+    {
+        const auto& index = lineIndex( nl );
+        LinePairs pairs( index.bytes.size() );
+        for ( size_t i = 0; i < pairs.size(); ++i ) pairs[i] = { index.bytes[i], index.lines[i] };
+        return pairs;
+    }
+
+    void
+    setLineOffsets( uint8_t nl, const uint64_t* bytes, const uint64_t* lines, size_t n )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "set_line_offsets on a closed reader" );
+        if ( !m_index.sealed() ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "a line index needs the complete block map: set_block_offsets or block_offsets first" );
         }
-        /* all of them are waited for (they write into dst) before the first failure in file order is reported */
-        std::exception_ptr failure;
-        for ( auto& launch : pending ) {
-            try {
-                launch.get();
-            } catch ( ... ) {
-                if ( !failure ) failure = std::current_exception();
+        if ( n == 0 ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "an empty line index cannot be loaded" );
+        bz2gpu::checkLineIndex( m_index.snapshot(), bytes, lines, n );   /* std::invalid_argument */
+        dropHeldLines();
+        m_lines = LineIndex{ nl, { bytes, bytes + n }, { lines, lines + n } };
+    }
+
+    /** s(k) for every line number given (mi355x_bz2_reader_line_starts): only blocks that hold a boundary are decoded. */
+    void
+    lineStarts( uint8_t nl, const uint64_t* lines, size_t n, uint64_t* byteOffsets )
+    {
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        const auto plan = bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
+                                             lines, nullptr, n, /* startsOnly */ true, m_batch, packedLaunches(),
+                                             m_source->size() );
+        std::vector<uint64_t> positions( plan.queries.size(), bz2gpu::NOT_FOUND );
+        std::vector<BatchScheduler::LineWork> lineWorks;
+        runLineLaunches( plan, nl, positions, lineWorks );
+        for ( size_t i = 0; i < n; ++i ) {
+            const auto& start = plan.starts[i];
+            byteOffsets[i] = start.query == bz2gpu::NO_QUERY
+                             ? start.fixed : bz2gpu::lineStartOf( plan.queries[start.query], positions[start.query] );
+        }
+    }
+
+    /** Step 1 of the line ranges (mi355x_bz2_reader_read_line_ranges): decode, resolve, gather into the contexts' result
+     * buffers; the pieces are held for takeLineRanges. */
+    void
+    readLineRanges( uint8_t nl, const uint64_t* first, const uint64_t* count, size_t n, bool keepOnDevice,
+                    uint64_t* byteSizes, uint64_t* total )
+    {
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        const auto plan = bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
+                                             first, count, n, /* startsOnly */ false, m_batch, packedLaunches(),
+                                             m_source->size() );
+        std::vector<uint64_t> positions( plan.queries.size(), bz2gpu::NOT_FOUND );
+        std::vector<BatchScheduler::LineWork> lineWorks;
+        try {
+            runLineLaunches( plan, nl, positions, lineWorks );
+        } catch ( ... ) {
+            dropHeldLines();
+            throw;
+        }
+        HeldLines held;
+        held.onDevice = keepOnDevice;
+        held.sizes.assign( n, 0 );
+        /* launch by launch: a range's segments come front to back, in launch order */
+        for ( const auto& work : lineWorks ) {
+            for ( const auto& piece : work.held ) {
+                held.sizes[piece.range] += piece.size;
+                held.pieces.push_back( piece );
             }
         }
-        if ( failure ) std::rethrow_exception( failure );
-        std::copy( plan.nRead.begin(), plan.nRead.end(), nRead );
+        uint64_t sum = 0;
+        for ( size_t i = 0; i < n; ++i ) {
+            byteSizes[i] = held.sizes[i];
+            sum += held.sizes[i];
+        }
+        if ( total != nullptr ) *total = sum;
+        m_held = std::move( held );
+    }
+
+    /** Step 2 (mi355x_bz2_reader_take_line_ranges): the held pieces to their places in `dst`, range i behind the ranges
+     * in front of it; then nothing is held any more. */
+    void
+    takeLineRanges( void* dst, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_line_ranges on a closed reader" );
+        if ( !m_held ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_line_ranges: no line ranges are held (read_line_ranges first)" );
+        const auto held = std::move( *m_held );
+        dropHeldLines();
+        if ( held.onDevice != dstIsDevice ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_line_ranges: the destination is not where read_line_ranges was told it would be" );
+        }
+        if ( held.pieces.empty() ) return;
+        if ( dst == nullptr ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_line_ranges: no destination" );
+        std::vector<uint64_t> at( held.sizes.size(), 0 );
+        for ( size_t i = 1; i < at.size(); ++i ) at[i] = at[i - 1] + held.sizes[i - 1];
+        std::map<mi355x_bz2_ctx*, std::vector<mi355x_bz2_gather_piece> > perContext;
+        for ( const auto& piece : held.pieces ) {
+            perContext[piece.ctx].push_back( { piece.offset, at[piece.range], piece.size } );
+            at[piece.range] += piece.size;
+        }
+        for ( const auto& [ctx, pieces] : perContext ) {
+            const int rc = gatherResult( ctx, pieces.data(), (uint32_t)pieces.size(), dst, dstIsDevice ? 1 : 0 );
+            if ( rc != MI355X_BZ2_OK ) fail( rc, mi355x_bz2_last_error( ctx ) );
+        }
     }
 
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
@@ -1223,6 +1427,7 @@ public:
             fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "an index needs at least one block and the end-of-file entry" );
         }
         m_index.assign( BlockIndex::Pairs( offsets.begin(), offsets.end() ) );
+        m_lines.reset();   /* a line index belongs to the block map it was built or checked against */
     }
 
     [[nodiscard]] size_t
@@ -1236,6 +1441,7 @@ public:
     void
     joinThreads()
     {
+        m_held.reset();   /* it lives in the contexts' buffers */
         m_scheduler.reset();
         m_finder.reset();
     }
@@ -1247,6 +1453,124 @@ public:
     }
 
 private:
+    struct LineIndex
+    {
+        uint8_t nl{ 0 };
+        std::vector<uint64_t> bytes, lines;   /* one entry per data block and the end */
+    };
+
+    struct HeldLines
+    {
+        bool onDevice{ false };
+        std::vector<uint64_t> sizes;                       /* per range */
+        std::vector<BatchScheduler::HeldPiece> pieces;     /* front to back within every range */
+    };
+
+    void
+    dropHeldLines()
+    {
+        m_held.reset();
+        if ( m_scheduler ) m_scheduler->dropHeld();
+    }
+
+    /** Each launch to the front of the queue -- the last one first, so that the first launch is taken first --, and all
+     * of them waited for (they write into memory of the caller) before the first failure in file order is reported. */
+    void
+    runLaunches( std::vector<std::unique_ptr<BatchScheduler::RangesWork> >& works )
+    {
+        std::vector<std::future<void> > pending( works.size() );
+        for ( size_t l = works.size(); l-- > 0; ) {
+            pending[l] = scheduler().launchRanges( std::move( works[l] ) );
+        }
+        std::exception_ptr failure;
+        for ( auto& launch : pending ) {
+            try {
+                launch.get();
+            } catch ( ... ) {
+                if ( !failure ) failure = std::current_exception();
+            }
+        }
+        if ( failure ) std::rethrow_exception( failure );
+    }
+
+    /** Bounded residency: launches bring the packed windows of their own blocks (bz2_ranges.hpp). */
+    [[nodiscard]] bool packedLaunches() { return !scheduler().inputResident(); }
+
+    /** The launches of a line plan, each with its own queries and segments. */
+    void
+    runLineLaunches( const bz2gpu::LinePlan& plan, uint8_t nl, std::vector<uint64_t>& positions,
+                     std::vector<BatchScheduler::LineWork>& lineWorks )
+    {
+        lineWorks.assign( plan.launches.size(), {} );
+        for ( auto& work : lineWorks ) {
+            work.nl = nl;
+            work.plan = &plan;
+            work.positions = positions.data();
+        }
+        for ( size_t q = 0; q < plan.queries.size(); ++q ) lineWorks[plan.queries[q].launch].queries.push_back( (uint32_t)q );
+        for ( size_t k = 0; k < plan.segments.size(); ++k ) lineWorks[plan.segments[k].launch].segments.push_back( (uint32_t)k );
+        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
+        for ( size_t l = 0; l < works.size(); ++l ) {
+            works[l] = std::make_unique<BatchScheduler::RangesWork>();
+            works[l]->launch = &plan.launches[l];
+            works[l]->lines = &lineWorks[l];
+        }
+        runLaunches( works );
+    }
+
+    /** The line index for `nl`: the one the reader holds, or a new one.  The block map is completed first if it has to
+     * be (the position and eof() stay); then every data block is decoded once more, in launches of the read_ranges kind
+     * that count `nl` per block and copy nothing out. */
+    [[nodiscard]] const LineIndex&
+    lineIndex( uint8_t nl )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "line access on a closed reader" );
+        if ( m_lines && m_lines->nl == nl ) return *m_lines;
+        dropHeldLines();
+        if ( !m_index.sealed() ) {
+            const size_t position = m_position;
+            const bool atEnd = m_atEnd;
+            try {
+                m_position = (size_t)m_index.frontier();
+                m_atEnd = false;
+                read( Sink() );
+            } catch ( ... ) {
+                m_position = position;
+                m_atEnd = atEnd;
+                throw;
+            }
+            m_position = position;
+            m_atEnd = atEnd;
+            if ( !m_index.sealed() ) fail( MI355X_BZ2_ERR_LOGIC, "the whole file was read but its block index is not complete" );
+        }
+        const auto map = m_index.snapshot();
+        const uint64_t total = map.empty() ? 0 : map.back().second;
+        const uint64_t offset = 0;
+        const auto plan = bz2gpu::planRanges( map, &offset, &total, 1, m_batch, total > 0 && packedLaunches(), m_source->size() );
+        std::vector<BatchScheduler::LineWork> lineWorks( plan.launches.size() );
+        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
+        for ( size_t l = 0; l < works.size(); ++l ) {
+            lineWorks[l].nl = nl;
+            lineWorks[l].countBlocks = true;
+            works[l] = std::make_unique<BatchScheduler::RangesWork>();
+            works[l]->launch = &plan.launches[l];
+            works[l]->lines = &lineWorks[l];
+        }
+        runLaunches( works );
+        LineIndex index;
+        index.nl = nl;
+        std::vector<uint64_t> lengths;
+        bz2gpu::dataBlocksOf( map, index.bytes, lengths );
+        index.bytes.push_back( total );
+        index.lines.push_back( 0 );
+        for ( const auto& work : lineWorks ) {
+            for ( const auto count : work.blockCounts ) index.lines.push_back( index.lines.back() + count );
+        }
+        if ( index.lines.size() != index.bytes.size() ) fail( MI355X_BZ2_ERR_LOGIC, "the line index does not match the block map" );
+        m_lines = std::move( index );
+        return *m_lines;
+    }
+
     [[nodiscard]] static const BlockRecord&
     recordIn( const DecodedRun& run, uint64_t bits )
     {
@@ -1365,6 +1689,9 @@ private:
     std::shared_ptr<BlockFinder> m_finder;
     BlockIndex m_index;
     std::unique_ptr<BatchScheduler> m_scheduler;
+
+    std::optional<LineIndex> m_lines;     /* the one line index the reader keeps, with its delimiter */
+    std::optional<HeldLines> m_held;      /* between read_line_ranges and take_line_ranges */
 };
 }  // namespace mi355x
 
@@ -1587,6 +1914,52 @@ mi355x_bz2_reader_read_ranges( mi355x_bz2_reader* r, const uint64_t* offsets, co
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
         reader.readRanges( offsets, sizes, n, dst, dstIsDevice != 0, nRead );
     } );
+}
+
+int
+mi355x_bz2_reader_line_offsets( mi355x_bz2_reader* r, uint8_t nl, uint64_t* bytes, uint64_t* lines, uint64_t capacity,
+                                uint64_t* n )
+{
+    if ( capacity > 0 && ( bytes == nullptr || lines == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        const auto pairs = reader.lineOffsets( nl );
+        if ( n != nullptr ) *n = pairs.size();
+        for ( uint64_t i = 0; i < pairs.size() && i < capacity; ++i ) {
+            bytes[i] = pairs[i].first;
+            lines[i] = pairs[i].second;
+        }
+    } );
+}
+
+int
+mi355x_bz2_reader_set_line_offsets( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* bytes, const uint64_t* lines, uint64_t n )
+{
+    if ( n > 0 && ( bytes == nullptr || lines == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.setLineOffsets( nl, bytes, lines, (size_t)n ); } );
+}
+
+int
+mi355x_bz2_reader_line_starts( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* lines, uint32_t n, uint64_t* byteOffsets )
+{
+    if ( n > 0 && ( lines == nullptr || byteOffsets == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.lineStarts( nl, lines, n, byteOffsets ); } );
+}
+
+int
+mi355x_bz2_reader_read_line_ranges( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* first, const uint64_t* count,
+                                    uint32_t n, int keepOnDevice, uint64_t* byteSizes, uint64_t* total )
+{
+    if ( total != nullptr ) *total = 0;
+    if ( n > 0 && ( first == nullptr || count == nullptr || byteSizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.readLineRanges( nl, first, count, n, keepOnDevice != 0, byteSizes, total );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dstIsDevice )
+{
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeLineRanges( dst, dstIsDevice != 0 ); } );
 }
 
 int

@@ -39,7 +39,7 @@ struct Options
     bool toStdout{ false }, decompress{ false }, force{ false }, keep{ false }, test{ false }, help{ false };
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
-    bool listCompressed{ false }, listOffsets{ false };
+    bool listCompressed{ false }, listOffsets{ false }, countLines{ false };
     std::string input, output, listCompressedPath, listOffsetsPath;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -78,7 +78,9 @@ printHelp()
         "                                decoded data is already written to stdout.\n"
         "  -L, --list-offsets [arg]      List bzip2 block offsets in bits and also the corresponding offsets in the\n"
         "                                decoded data at the beginning of each block in bytes as comma separated pairs\n"
-        "                                per line '<encoded bits>,<decoded bytes>'.\n\n"
+        "                                per line '<encoded bits>,<decoded bytes>'.\n"
+        "      --count-lines             Count the newline characters of the decoded data on the GPU (nothing is\n"
+        "                                decompressed to the host), print the number and exit.\n\n"
         " Advanced options:\n"
         "      --buffer-size arg         Controls the output buffer size. By default, the decoded data is written in\n"
         "                                one pass per block. (default: 0)\n\n"
@@ -88,7 +90,9 @@ printHelp()
         "Find and list the bzip2 block offsets to be used for another tool:\n"
         "  ibzip2-mi355x -l blockoffsets.dat -- file.bz2\n\n"
         "List block offsets in both the compressed as well as the decompressed data:\n"
-        "  ibzip2-mi355x -L blockoffsets.dat file.bz2 > /dev/null\n";
+        "  ibzip2-mi355x -L blockoffsets.dat file.bz2 > /dev/null\n\n"
+        "Count the lines of a compressed file:\n"
+        "  ibzip2-mi355x --count-lines file.bz2\n";
 }
 
 bool
@@ -173,6 +177,7 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "version" ) o.version = true;
             else if ( name == "input" ) { if ( !need( o.input ) ) return 1; }
             else if ( name == "output" ) { if ( !need( o.output ) ) return 1; o.hasOutput = true; }
+            else if ( name == "count-lines" ) o.countLines = true;
             else if ( name == "list-compressed-offsets" ) {
                 o.listCompressed = true;
                 if ( hasInline ) o.listCompressedPath = inlineValue; else optionalValue( i, o.listCompressedPath );
@@ -369,6 +374,41 @@ main( int argc, char** argv )
     if ( !stdinHasInput() && o.input.empty() ) {
         std::cerr << "Either stdin must have input, e.g., by piping to it, or an input file must be specified!\n";
         return 1;
+    }
+
+    /* an action of its own (rapidgzip --count-lines, src/tools/rapidgzip.cpp; ibzip2 has none): the number of newline
+     * characters in the decoded data, from the reader's line index */
+    if ( o.countLines ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t count = 0;
+        rc = mi355x_bz2_reader_line_offsets( reader, '\n', nullptr, nullptr, 0, &count );
+        std::vector<uint64_t> bytes( count ), lines( count );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_line_offsets( reader, '\n', bytes.data(), lines.data(), count, &count );
+        if ( rc != MI355X_BZ2_OK || lines.empty() ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        std::cout << lines.back() << "\n";
+        return 0;
     }
 
     /* output file name rules, ibzip2.cpp:316-331 */

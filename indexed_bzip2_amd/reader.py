@@ -40,6 +40,7 @@ class _IndexedBzip2FileParallel:
             raise TypeError(f"Parallelization argument must be an integer not '{parallelization}'!")
         self._h = ctypes.c_void_p()
         self._keepalive = None
+        self._device = device
         L = N.lib()
         if isinstance(file, int):
             rc = L.mi355x_bz2_reader_open_fd(file, parallelization, device, ctypes.byref(self._h))
@@ -214,6 +215,117 @@ class _IndexedBzip2FileParallel:
             at += size
         return result
 
+    # -- line access: `newline` is one delimiter byte; line k (0-based) starts behind the k-th delimiter, the last line
+    # is the unterminated tail (possibly empty), and a range (first, count) holds its lines with their delimiters
+    @staticmethod
+    def _newline(newline):
+        if not isinstance(newline, (bytes, bytearray)) or len(newline) != 1:
+            raise ValueError("newline must be exactly one byte, e.g. b'\\n'")
+        return newline[0]
+
+    @staticmethod
+    def _u64(values, what):
+        values = [int(v) for v in values]
+        if any(v < 0 for v in values):
+            raise ValueError(f"{what} must not be negative")
+        if any(v >= 2**64 for v in values):
+            raise ValueError(f"{what} must fit 64 bits")
+        return values, (ctypes.c_uint64 * max(1, len(values)))(*values)
+
+    def line_offsets(self, newline=b"\n"):
+        """The line index {decoded byte offset of a block's first byte: delimiters in front of it}, one entry per data
+        block and {size: number of delimiters} at the end; {0: 0} for an empty file.  Built on the GPU when the reader
+        does not hold it for this `newline` (the block map is completed first): every block is decoded once, counted
+        where it lies, and only the counts come back.  Positionless."""
+        self._require()
+        nl = self._newline(newline)
+        fn = N.lib().mi355x_bz2_reader_line_offsets
+        n = ctypes.c_uint64()
+        self._check(fn(self._h, nl, None, None, 0, ctypes.byref(n)))
+        byts = (ctypes.c_uint64 * max(1, n.value))()
+        lines = (ctypes.c_uint64 * max(1, n.value))()
+        self._check(fn(self._h, nl, byts, lines, n.value, ctypes.byref(n)))
+        return {byts[i]: lines[i] for i in range(n.value)}
+
+    def set_line_offsets(self, offsets, newline=b"\n"):
+        """Import a line index (line_offsets() of an earlier session, read_line_offsets); the block map must be complete
+        (set_block_offsets).  ValueError if it does not fit the block map."""
+        self._require()
+        nl = self._newline(newline)
+        items = sorted(dict(offsets).items())
+        _, byts = self._u64([k for k, _ in items], "offsets")
+        _, lines = self._u64([v for _, v in items], "line numbers")
+        self._check(N.lib().mi355x_bz2_reader_set_line_offsets(self._h, nl, byts, lines, len(items)))
+
+    def count_lines(self, newline=b"\n"):
+        """The number of `newline` bytes in the decoded file (the last value of line_offsets)."""
+        offsets = self.line_offsets(newline)
+        return max(offsets.values())
+
+    def line_starts(self, lines, newline=b"\n"):
+        """Decoded byte offset at which each of the given lines starts (numpy uint64); the size of the file for line
+        numbers beyond the last line.  Only the blocks that hold one of these line starts are decoded."""
+        import numpy as np
+        self._require()
+        nl = self._newline(newline)
+        lines, arr = self._u64(lines, "line numbers")
+        out = (ctypes.c_uint64 * max(1, len(lines)))()
+        self._check(N.lib().mi355x_bz2_reader_line_starts(self._h, nl, arr, len(lines), out))
+        return np.frombuffer(out, dtype=np.uint64, count=len(lines)).copy()
+
+    def _read_line_ranges(self, ranges, newline, on_device):
+        """Step 1 (mi355x_bz2_reader_read_line_ranges): returns the byte size of every range."""
+        self._require()
+        nl = self._newline(newline)
+        ranges = [(int(f), int(c)) for f, c in ranges]
+        if any(f < 0 or c < 0 for f, c in ranges):
+            raise ValueError("line numbers and counts must not be negative")
+        _, first = self._u64([f for f, _ in ranges], "line numbers")
+        _, count = self._u64([min(c, 2**64 - 1) for _, c in ranges], "counts")
+        sizes = (ctypes.c_uint64 * max(1, len(ranges)))()
+        total = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_read_line_ranges(self._h, nl, first, count, len(ranges),
+                                                                1 if on_device else 0, sizes, ctypes.byref(total)))
+        return [sizes[i] for i in range(len(ranges))], total.value
+
+    def read_line_ranges(self, ranges, newline=b"\n"):
+        """[(first line, number of lines), ...] -> one bytes object per range: the lines with their delimiters; what the
+        file holds of them if the range reaches beyond the last line; b"" if it starts beyond it.  Every block the
+        ranges need is decoded once, the lines are found on the GPU, and only their bytes are copied out.  Builds the
+        line index first if the reader does not hold one for `newline`.  Positionless."""
+        sizes, total = self._read_line_ranges(ranges, newline, False)
+        out = bytearray(total)
+        dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
+        self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
+        del dst
+        result, at = [], 0
+        for size in sizes:
+            result.append(bytes(out[at:at + size]))
+            at += size
+        return result
+
+    def read_lines(self, first, count=1, newline=b"\n"):
+        """`count` lines from line `first` (0-based) as one bytes object, delimiters included."""
+        return self.read_line_ranges([(first, count)], newline)[0]
+
+    def read_line_ranges_to_tensor(self, ranges, newline=b"\n"):
+        """read_line_ranges into ONE contiguous torch.uint8 tensor on the reader's device -> (data, offsets): range i is
+        ``data[offsets[i]:offsets[i + 1]]``; `offsets` is an int64 CPU tensor of n + 1 boundaries.  The bytes never pass
+        through the host."""
+        import torch
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        sizes, total = self._read_line_ranges(ranges, newline, True)
+        data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+        if total:
+            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(data.device).synchronize()
+        self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, ctypes.c_void_p(data.data_ptr()) if total else None, 1))
+        bounds = [0]
+        for size in sizes:
+            bounds.append(bounds[-1] + size)
+        return data, torch.tensor(bounds, dtype=torch.int64)
+
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
         like the reference, whose serial reader checks and whose parallel reader does not)."""
@@ -288,6 +400,39 @@ class IndexedBzip2File(io.BufferedReader):
             raise ValueError("I/O operation on closed file.")
         return self.bz2reader.read_ranges_into(offsets, sizes, out)
 
+    def _open_reader(self):
+        if self.closed:
+            raise ValueError("I/O operation on closed file.")
+        return self.bz2reader
+
+    def line_offsets(self, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.line_offsets."""
+        return self._open_reader().line_offsets(newline)
+
+    def set_line_offsets(self, offsets, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.set_line_offsets."""
+        return self._open_reader().set_line_offsets(offsets, newline)
+
+    def count_lines(self, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.count_lines."""
+        return self._open_reader().count_lines(newline)
+
+    def line_starts(self, lines, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.line_starts."""
+        return self._open_reader().line_starts(lines, newline)
+
+    def read_line_ranges(self, ranges, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_line_ranges."""
+        return self._open_reader().read_line_ranges(ranges, newline)
+
+    def read_lines(self, first, count=1, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_lines."""
+        return self._open_reader().read_lines(first, count, newline)
+
+    def read_line_ranges_to_tensor(self, ranges, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_line_ranges_to_tensor."""
+        return self._open_reader().read_line_ranges_to_tensor(ranges, newline)
+
 
 builtins_open = builtins.open
 
@@ -330,5 +475,37 @@ def read_block_offsets(file):
         parts = line.split(",")
         if len(parts) != 2:
             raise ValueError(f"line {number}: expected '<compressed bits>,<decoded bytes>', got {line!r}")
+        offsets[int(parts[0])] = int(parts[1])
+    return offsets
+
+
+def write_line_offsets(offsets, file):
+    """Line index (line_offsets()) as text, one "<decoded byte offset>,<line offset>" per line.  `file` is a path or a
+    text file object."""
+    text = "".join(f"{int(byts)},{int(lines)}\n" for byts, lines in sorted(offsets.items()))
+    if hasattr(file, "write"):
+        file.write(text)
+    else:
+        with builtins_open(file, "w") as f:
+            f.write(text)
+
+
+def read_line_offsets(file):
+    """Inverse of write_line_offsets: returns the dict that set_line_offsets() takes."""
+    if hasattr(file, "read"):
+        text = file.read()
+    else:
+        with builtins_open(file, "r") as f:
+            text = f.read()
+    if isinstance(text, bytes):
+        text = text.decode("ascii")
+    offsets = {}
+    for number, line in enumerate(text.splitlines(), 1):
+        line = line.strip()
+        if not line:
+            continue
+        parts = line.split(",")
+        if len(parts) != 2:
+            raise ValueError(f"line {number}: expected '<decoded bytes>,<line offset>', got {line!r}")
         offsets[int(parts[0])] = int(parts[1])
     return offsets
