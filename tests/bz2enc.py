@@ -1,30 +1,37 @@
 """A small bzip2 ENCODER for tests: produces valid single-block streams that libbz2 never would -- Huffman codes up to
 20 bits, any number of tables (2..6), arbitrary selector patterns, unused symbols in the map -- so that the decoder
 paths for them can be checked against the oracle, CPython's bz2 and the reference ("gaps the build must cover
-itself").  Plain Python, small inputs only (the BWT sorts rotations)."""
+itself"), and blocks that carry any last column at all (encode_block_from_bwt; tests/crafted.py).  Plain Python:
+encode_block is for small inputs only (bwt() sorts rotations), bwt_numpy and encode_block_from_bwt take full-size blocks."""
 
 
 class BitWriter:
+    """Most significant bit first.  The pending bits sit in one int and leave as whole bytes, so a block of several
+    hundred thousand symbols is written in about a second."""
+
     def __init__(self):
-        self.bits = []
+        self.out = bytearray()
+        self.acc = 0
+        self.n = 0
 
     def put(self, value, n):
-        for i in range(n - 1, -1, -1):
-            self.bits.append((value >> i) & 1)
+        self.acc = (self.acc << n) | (value & ((1 << n) - 1))
+        self.n += n
+        if self.n >= 256:
+            keep = self.n & 7
+            self.out += (self.acc >> keep).to_bytes(self.n >> 3, "big")
+            self.acc &= (1 << keep) - 1
+            self.n = keep
 
     def align(self):
-        while len(self.bits) % 8:
-            self.bits.append(0)
+        if self.n % 8:
+            self.put(0, 8 - self.n % 8)
 
     def bytes(self):
         self.align()
-        out = bytearray()
-        for i in range(0, len(self.bits), 8):
-            b = 0
-            for bit in self.bits[i:i + 8]:
-                b = (b << 1) | bit
-            out.append(b)
-        return bytes(out)
+        self.out += self.acc.to_bytes(self.n >> 3, "big")
+        self.acc = self.n = 0
+        return bytes(self.out)
 
 
 def crc32_bzip2(data, crc=0xFFFFFFFF):
@@ -59,8 +66,32 @@ def bwt(s):
     return last, order.index(0)
 
 
-def mtf_rle2(last):
-    used = sorted(set(last))
+def bwt_numpy(s):
+    """The same cyclic BWT for long inputs: ranks of the rotations by prefix doubling (stable argsort of (rank[i],
+    rank[i + k]) pairs, k = 1, 2, 4, ... until the ranks are distinct or k >= n).  Identical rotations keep their index
+    order, as in bwt(); any of their rows is a valid origPtr."""
+    import numpy as np
+    a = np.frombuffer(bytes(s), dtype=np.uint8)
+    n = len(a)
+    rank = a.astype(np.int64)
+    k = 1
+    while True:
+        key = rank * (int(rank.max()) + 1) + np.roll(rank, -k)
+        order = np.argsort(key, kind="stable")
+        sorted_key = key[order]
+        rank = np.empty(n, dtype=np.int64)
+        rank[order] = np.concatenate(([0], np.cumsum(sorted_key[1:] != sorted_key[:-1])))
+        k *= 2
+        if int(rank.max()) == n - 1 or k >= n:
+            break
+    order = np.argsort(rank, kind="stable")
+    last = a[(order - 1) % n].tobytes()
+    return last, int(np.flatnonzero(order == 0)[0])
+
+
+def mtf_rle2(last, declared=None):
+    """Move-to-front over `declared` (default: the byte values that occur) with zero runs as RUNA/RUNB digits."""
+    used = sorted(set(last)) if declared is None else list(declared)
     lst = used[:]
     symbols = []
     run = 0
@@ -75,10 +106,10 @@ def mtf_rle2(last):
                 symbols.append(1)
                 run = (run - 2) >> 1
     for b in last:
-        p = lst.index(b)
-        if p == 0:
+        if b == lst[0]:
             run += 1
             continue
+        p = lst.index(b)
         flush()
         symbols.append(p + 1)
         del lst[p]
@@ -128,45 +159,27 @@ def skewed_lengths(alphabet, ranking, max_len=20):
     return lengths
 
 
-def encode_block(data, level=9, n_groups=2, length_fn=None, selector_fn=None, extra_selectors=0, declare_unused=(),
-                 faults=None):
-    """Single-stream, single-block .bz2 of `data` (non-empty, short).
+def encode_block(data, level=9, **options):
+    """Single-stream, single-block .bz2 of `data` (non-empty, short: bwt() sorts rotations in Python).  Options as for
+    encode_block_from_bwt."""
+    assert data
+    last, orig_ptr = bwt(rle1(data))
+    return encode_block_from_bwt(last, orig_ptr, crc32_bzip2(data) ^ 0xFFFFFFFF, level, **options)
+
+
+def encode_block_from_bwt(last, orig_ptr, block_crc, level=9, n_groups=2, length_fn=None, selector_fn=None,
+                          extra_selectors=0, declare_unused=(), faults=None):
+    """Single-stream, single-block .bz2 whose block carries the last column `last` and `orig_ptr` as they are -- the format
+    lets a block carry any column, a BWT of something or not -- with `block_crc` as the CRC of what it decodes to.
     length_fn(table_index, alphabet, frequencies) -> code lengths; selector_fn(group_index) -> table index.
     faults: dict of deliberate violations for error-path tests -- randomized (bit), orig_ptr (value written),
     n_groups_field (3-bit field written), n_selectors_field (15-bit field written), drop_selectors (selectors left
     out), symbols (replaces the symbol list; must use the block's alphabet and end with end-of-block)."""
-    assert data
+    assert last
     faults = faults or {}
-    block_crc = crc32_bzip2(data) ^ 0xFFFFFFFF
-    last, orig_ptr = bwt(rle1(data))
-    used, symbols = mtf_rle2(last)
-    declared = sorted(set(used) | set(declare_unused))
-    if declared != used:
-        # symbols of the map that never occur: positions shift, re-run MTF over the declared list
-        lst = declared[:]
-        symbols = []
-        run = 0
-
-        def flush():
-            nonlocal run
-            while run > 0:
-                if run & 1:
-                    symbols.append(0)
-                    run = (run - 1) >> 1
-                else:
-                    symbols.append(1)
-                    run = (run - 2) >> 1
-        for b in last:
-            p = lst.index(b)
-            if p == 0:
-                run += 1
-                continue
-            flush()
-            symbols.append(p + 1)
-            del lst[p]
-            lst.insert(0, b)
-        flush()
-        symbols.append(len(declared) + 1)
+    used = sorted(set(last))
+    declared = sorted(set(used) | set(declare_unused))     # may hold symbols of the map that never occur
+    _, symbols = mtf_rle2(last, declared)
     alphabet = len(declared) + 2
     if "symbols" in faults:
         symbols = list(faults["symbols"])
