@@ -260,6 +260,23 @@ int mi355x_bz2_count_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* span
 int mi355x_bz2_find_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_query* queries, uint32_t n, uint8_t value,
                           uint64_t* positions );
 
+/* A byte string in spans of the last batch's output, on the GPU: the kernels under the reader's search.  The same rules
+ * as mi355x_bz2_count_byte.  pattern_size is 1 to 256 (else MI355X_BZ2_ERR_INVALID_ARGUMENT).  A match of span i is every
+ * offset p of the output with output[p : p + pattern_size] == pattern, offset <= p and p + pattern_size <= offset + size:
+ * no byte outside the span decides anything, a span shorter than the pattern has none, and matches that overlap
+ * themselves all count.  The start positions of a span are cut into 16-KiB tiles, one wave each; a span given twice is
+ * searched twice.
+ *   _count_bytes  counts[i] = the matches of span i  (k_count_bytes).
+ *   _find_bytes   the same counts, and positions[] = the matches' offsets in the output, span by span in caller order and
+ *                 ascending within a span, the first `capacity` of them (k_count_bytes, k_scan_tiles, k_emit_bytes: the
+ *                 order comes from prefix sums, the same call gives the same array).  counts[i] is the true count of
+ *                 span i whatever the capacity.  If the positions do not fit on the device the call fails with
+ *                 MI355X_BZ2_ERR_DEVICE; nothing is truncated silently. */
+int mi355x_bz2_count_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                            uint32_t pattern_size, uint64_t* counts );
+int mi355x_bz2_find_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                           uint32_t pattern_size, uint64_t* positions, uint64_t capacity, uint64_t* counts );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -442,6 +459,29 @@ int mi355x_bz2_reader_line_starts( mi355x_bz2_reader* r, uint8_t nl, const uint6
 int mi355x_bz2_reader_read_line_ranges( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* first, const uint64_t* count,
                                         uint32_t n, int keep_on_device, uint64_t* byte_sizes, uint64_t* total );
 int mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dst_is_device );
+
+/* ---- search.  D = the decoded file, P = `pattern`, m = pattern_size with 1 <= m <= 256 (the slack behind the output
+ * buffers, and what keeps the bytes a launch hands the host for its seams under 512); m == 0 or m > 256 is
+ * MI355X_BZ2_ERR_INVALID_ARGUMENT.  A match is every offset p with D[p : p + m] == P, start <= p and p + m <= end, where
+ * start and end are clipped to [0, size of D]; an empty range, or one shorter than m, has none.  Matches that overlap
+ * themselves all count: "abab" in "abababab" matches at 0, 2 and 4 (bytes.count of Python says 2).
+ * Positionless like read_ranges and the line functions: tell(), eof(), the sequential reader's decoded runs and the held
+ * line ranges stay as they are, the launches go to the front of the queue and decode at most `parallelization` blocks
+ * each (0 = 512), and a part of the file in front of `end` that is not indexed yet is indexed first.  Every data block
+ * that intersects [start, end) is decoded once per call; k_count_bytes / k_emit_bytes find the matches inside a launch's
+ * part of the range, and the matches that straddle two or more launches are found on the host from the first and last
+ * m - 1 bytes of each part (bz2_search.hpp).  Nothing but counts, positions and those seam bytes leaves the GPU.  A
+ * block that fails to decode fails the call with its status and bit offset.  No reference counterpart.
+ * Two steps, as for line ranges, because nobody knows the number of matches in advance.
+ * Step 1, _search.  limit == 0: count only -- *n_matches is the number of matches in the range, nothing is held and no
+ * emitting pass runs.  limit > 0 (UINT64_MAX: all): the first min( limit, total ) positions, ascending, are held on the
+ * host and *n_matches is their number; no launch is started after the one in which the limit was reached (launches
+ * already taken by a context finish).
+ * Step 2, _take_matches: copies the held positions (at most `capacity`) and releases them; the next search, or close,
+ * releases them as well.  Held matches and held line ranges are independent. */
+int mi355x_bz2_reader_search( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint64_t start,
+                              uint64_t end, uint64_t limit, uint64_t* n_matches );
+int mi355x_bz2_reader_take_matches( mi355x_bz2_reader* r, uint64_t* positions, uint64_t capacity );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

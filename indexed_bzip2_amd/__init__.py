@@ -3,6 +3,10 @@
 
 Host-side mirror of python/indexed_bzip2/indexed_bzip2.pyx (open, IndexedBzip2File, ...) over the C ABI of
 include/mi355x_bz2.h.  All decoding happens in hand-written HIP kernels on gfx950; there is no CPU fallback.
+
+Beyond the reference's API the reader answers questions about the decoded file while its bytes stay in HBM: byte ranges
+(read_ranges), lines (count_lines, line_starts, read_line_ranges) and where a byte string occurs (count_matches,
+find_all, find: every offset p with data[p:p + len(pattern)] == pattern, overlapping occurrences included).
 """
 __version__ = "0.1.0"
 

@@ -150,6 +150,10 @@ SYMBOLS = [
     ("mi355x_bz2_gather_output", ctypes.c_int, [_vp, ctypes.POINTER(GatherPiece), ctypes.c_uint32, _vp, ctypes.c_int]),
     ("mi355x_bz2_count_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
     ("mi355x_bz2_find_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteQuery), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
+    ("mi355x_bz2_count_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
+                                               ctypes.c_uint32, _u64p]),
+    ("mi355x_bz2_find_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
+                                              ctypes.c_uint32, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -175,6 +179,9 @@ SYMBOLS = [
     ("mi355x_bz2_reader_read_line_ranges", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, _u64p, ctypes.c_uint32, ctypes.c_int,
                                                            _u64p, _u64p]),
     ("mi355x_bz2_reader_take_line_ranges", ctypes.c_int, [_vp, _vp, ctypes.c_int]),
+    ("mi355x_bz2_reader_search", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
+                                                 ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_reader_take_matches", ctypes.c_int, [_vp, _u64p, ctypes.c_uint64]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -470,6 +477,32 @@ class Decoder:
         out = (ctypes.c_uint64 * max(1, len(queries)))()
         self._check(lib().mi355x_bz2_find_byte(self._h, arr, len(queries), value, out))
         return [None if p == 2**64 - 1 else p for p in out[:len(queries)]]
+
+    def count_bytes(self, pattern, spans):
+        """k_count_bytes: how often the byte string `pattern` (1 to 256 bytes) occurs in each span [(offset, size)] of the
+        last batch's output.  A match lies inside its span; matches that overlap themselves all count."""
+        pattern = bytes(pattern)
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        out = (ctypes.c_uint64 * max(1, len(spans)))()
+        self._check(lib().mi355x_bz2_count_bytes(self._h, arr, len(spans), pattern, len(pattern), out))
+        return list(out[:len(spans)])
+
+    def find_bytes(self, pattern, spans, capacity=None):
+        """k_count_bytes, k_scan_tiles, k_emit_bytes: (positions, counts) -- the offsets in the last batch's output at
+        which `pattern` occurs, span by span and ascending within a span, the first `capacity` of them (None: all), and
+        the true count of every span."""
+        pattern = bytes(pattern)
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        counts = (ctypes.c_uint64 * max(1, len(spans)))()
+        if capacity is None:
+            self._check(lib().mi355x_bz2_count_bytes(self._h, arr, len(spans), pattern, len(pattern), counts))
+            capacity = sum(counts[:len(spans)])
+        positions = (ctypes.c_uint64 * max(1, capacity))()
+        self._check(lib().mi355x_bz2_find_bytes(self._h, arr, len(spans), pattern, len(pattern), positions, capacity, counts))
+        found = min(capacity, sum(counts[:len(spans)]))
+        return list(positions[:found]), list(counts[:len(spans)])
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

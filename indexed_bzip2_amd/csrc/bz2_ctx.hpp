@@ -6,6 +6,7 @@
 
 #include <cstdint>
 #include <string>
+#include <vector>
 
 #include "../../include/mi355x_bz2.h"
 
@@ -23,6 +24,14 @@ int resultBuffer( mi355x_bz2_ctx* ctx, uint64_t size, uint64_t keep, uint8_t** d
  * `dst`.  Unlike the public call it may run while a batch is in flight on the context (the result buffer is not a batch
  * output); the kernel then queues behind what that batch has put on the context's stream. */
 int gatherResult( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice );
+
+/** The reader's search in one launch: the matches of `pattern` (m bytes) inside `extent` of the last batch's output,
+ * as mi355x_bz2_find_bytes with that one span.  *count is the true count; with `positions` given it is resized to the
+ * first min( *count, limit ) offsets in the output (nullptr: count only, no emitting pass).  The first and the last
+ * min( m - 1, extent.size ) bytes of the extent come back in the same D2H as the count: seamBytes[0, ...) and
+ * seamBytes[256, ...) of a 512-byte array. */
+int searchOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m, uint64_t limit,
+                  std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

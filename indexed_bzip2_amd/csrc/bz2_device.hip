@@ -26,6 +26,7 @@
 #include "../../include/mi355x_bz2.h"
 #include "bz2_kernels.hip.h"
 #include "bz2_lines.hip.h"
+#include "bz2_search.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -209,6 +210,10 @@ struct mi355x_bz2_ctx : Scratch
     /* mi355x_bz2_count_byte / _find_byte: tiles, queries, tile counts and results of one call, page-locked and on the
      * device (selectBytes lays them out) */
     GrowBuffer hSelect{ nullptr, 0, true }, dSelect;
+
+    /* mi355x_bz2_count_bytes / _find_bytes: tiles, pattern, counts and seam bytes of one call, page-locked and on the
+     * device, and the positions of the emitting pass on the device (searchBytes lays them out) */
+    GrowBuffer hSearch{ nullptr, 0, true }, dSearch, dSearchPositions;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
     GrowBuffer result;
@@ -658,7 +663,7 @@ mi355x_bz2_destroy( mi355x_bz2_ctx* c )
     (void)hipFree( c->dScanFound );
     (void)hipFree( c->dScanCounter );
     for ( GrowBuffer* buffer : { &c->dGatherTiles, &c->hGatherTiles, &c->dGatherStage, &c->hGatherStage, &c->hSelect, &c->dSelect,
-                                &c->result } ) buffer->release();
+                                &c->hSearch, &c->dSearch, &c->dSearchPositions, &c->result } ) buffer->release();
     if ( c->copyStream ) (void)hipStreamSynchronize( c->copyStream );
     for ( auto& buffer : c->out ) {
         buffer.release();
@@ -1716,7 +1721,136 @@ selectBytes( mi355x_bz2_ctx* c, const char* what, uint8_t value, uint32_t n, con
     for ( uint32_t i = 0; i < n; ++i ) results[i] = find ? hResults[i] : hResults[spanOf[i]];
     return MI355X_BZ2_OK;
 }
+
+/**
+ * Both string calls.  The start positions every span allows are cut into tiles (spans in caller order, a span given twice
+ * is searched twice: its positions are wanted twice), k_count_bytes counts every tile and adds to its span's counter, and
+ * the counts -- with the seam bytes of `seam`, if given -- come back in one D2H.  With positions wanted, min( total,
+ * capacity ) of them are then made room for on the device (a failure to allocate fails the call), k_scan_tiles turns the
+ * tile counts into places, k_emit_bytes writes the positions and a second D2H brings them to `positions`, or to `grown`
+ * resized to their number.
+ */
+int
+searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+             uint32_t m, bool wantPositions, uint64_t capacity, uint64_t* positions, std::vector<uint64_t>* grown,
+             uint64_t* counts, const mi355x_bz2_byte_span* seam, uint8_t* seamBytes )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    if ( m == 0 || m > SEARCH_MAX_PATTERN ) {
+        c->lastError = std::string( what ) + ": the pattern must have 1 to " + std::to_string( SEARCH_MAX_PATTERN ) + " bytes";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    const auto inside = [c] ( const mi355x_bz2_byte_span& span ) {
+        return span.size <= c->outSize && span.offset <= c->outSize - span.size;
+    };
+    uint64_t nTiles = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( !inside( spans[i] ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        counts[i] = 0;
+        if ( spans[i].size >= m ) nTiles += ( spans[i].size - m + 1 + SEARCH_TILE - 1 ) / SEARCH_TILE;
+    }
+    if ( seam != nullptr && !inside( *seam ) ) {
+        c->lastError = std::string( what ) + ": the seam span lies outside the last batch's output";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    const uint32_t seamN = seam != nullptr ? (uint32_t)std::min<uint64_t>( m - 1, seam->size ) : 0u;
+    if ( grown != nullptr ) grown->clear();
+    if ( nTiles == 0 && seamN == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][pattern][span counts][seam bytes]; device only: [tile counts][tile places] behind them */
+    const uint64_t patternAt = nTiles * sizeof( CountTile ), resultsAt = patternAt + SEARCH_MAX_PATTERN;
+    const uint64_t seamAt = resultsAt + n * sizeof( uint64_t ), countsAt = seamAt + 2 * SEARCH_MAX_PATTERN;
+    const uint64_t placesAt = countsAt + ( ( nTiles * sizeof( uint32_t ) + 7 ) & ~uint64_t( 7 ) );
+    const uint64_t bytes = placesAt + nTiles * sizeof( uint64_t );
+    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
+    /* the previous call's lists have been consumed (every call waits for its kernels) */
+    HIP_TRY( c, c->hSearch.grow( c, countsAt, cap, cap ) );
+    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
+    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSearch.bytes );
+    uint64_t tile = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        if ( spans[s].size < m ) continue;
+        const uint64_t starts = spans[s].size - m + 1;
+        for ( uint64_t k = 0; k < starts; k += SEARCH_TILE ) {
+            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( SEARCH_TILE, starts - k ), s };
+        }
+    }
+    std::memset( c->hSearch.bytes + patternAt, 0, SEARCH_MAX_PATTERN );
+    std::memcpy( c->hSearch.bytes + patternAt, pattern, m );
+    uint8_t* const d = c->dSearch.bytes;
+    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
+    auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_count_bytes, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            d + patternAt, m, dTileCounts, reinterpret_cast<unsigned long long*>( d + resultsAt ) );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    if ( seamN > 0 ) {
+        hipLaunchKernelGGL( k_seam_bytes, dim3( 1 ), dim3( 2 * SEARCH_MAX_PATTERN ), 0, c->stream, c->dOut, seam->offset,
+                            seam->size, seamN, d + seamAt );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    HIP_TRY( c, hipMemcpyAsync( c->hSearch.bytes + resultsAt, d + resultsAt, countsAt - resultsAt, hipMemcpyDeviceToHost,
+                                c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    uint64_t total = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        counts[i] = reinterpret_cast<const uint64_t*>( c->hSearch.bytes + resultsAt )[i];
+        total += counts[i];
+    }
+    if ( seamN > 0 ) {
+        std::memcpy( seamBytes, c->hSearch.bytes + seamAt, seamN );
+        std::memcpy( seamBytes + SEARCH_MAX_PATTERN, c->hSearch.bytes + seamAt + SEARCH_MAX_PATTERN, seamN );
+    }
+    const uint64_t wanted = wantPositions ? std::min( total, capacity ) : 0;
+    if ( wanted == 0 ) return MI355X_BZ2_OK;
+
+    if ( grown != nullptr ) {
+        try {
+            grown->resize( wanted );
+        } catch ( const std::exception& ) {
+            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " positions";
+            return MI355X_BZ2_ERR_DEVICE;
+        }
+        positions = grown->data();
+    }
+    const uint64_t need = wanted * sizeof( uint64_t );
+    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
+    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
+    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
+    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_emit_bytes, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0, c->stream, dTiles, c->dOut,
+                        d + patternAt, m, dPlaces, wanted, dPositions );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, need, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
 }  // namespace
+
+int
+mi355x::searchOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m,
+                      uint64_t limit, std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes )
+{
+    if ( c == nullptr || pattern == nullptr || count == nullptr || seamBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return searchBytes( c, "search", &extent, 1, pattern, m, positions != nullptr, limit, nullptr, positions, count, &extent,
+                        seamBytes );
+}
 
 int
 mi355x::gatherResult( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice )
@@ -1765,6 +1899,28 @@ mi355x_bz2_find_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_query* queries, u
         ranks[i] = queries[i].rank;
     }
     return selectBytes( c, "find_byte", value, n, offsets.data(), sizes.data(), ranks.data(), positions );
+}
+
+int
+mi355x_bz2_count_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                        uint32_t patternSize, uint64_t* counts )
+{
+    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return searchBytes( c, "count_bytes", spans, n, pattern, patternSize, false, 0, nullptr, nullptr, counts, nullptr, nullptr );
+}
+
+int
+mi355x_bz2_find_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                       uint32_t patternSize, uint64_t* positions, uint64_t capacity, uint64_t* counts )
+{
+    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
+         || ( capacity > 0 && positions == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return searchBytes( c, "find_bytes", spans, n, pattern, patternSize, true, capacity, positions, nullptr, counts, nullptr,
+                        nullptr );
 }
 
 int

@@ -40,6 +40,7 @@
 #include "bz2_host.hpp"
 #include "bz2_ctx.hpp"
 #include "bz2_lines.hpp"
+#include "bz2_search.hpp"
 #include "bz2_ranges.hpp"
 
 namespace mi355x
@@ -484,6 +485,7 @@ public:
      * caller's destination.  It goes ahead of everything queued (somebody waits for it), publishes no run and is not a
      * flight: the runs, flights and look-ahead of the sequential reader are not disturbed. */
     struct LineWork;
+    struct SearchWork;
     struct RangesWork
     {
         const bz2gpu::RangeLaunch* launch{ nullptr };
@@ -491,6 +493,7 @@ public:
         void* dst{ nullptr };
         bool dstIsDevice{ false };
         LineWork* lines{ nullptr };  /* set: a launch of the line functions, `pieces` and `dst` are not used */
+        SearchWork* search{ nullptr };   /* set: a launch of a search, likewise */
         std::promise<void> done;     /* a Bz2Exception if a block or the device failed */
     };
 
@@ -516,6 +519,34 @@ public:
         std::vector<uint32_t> queries, segments;    /* of this launch: indexes into the plan's lists */
         uint64_t* positions{ nullptr };
         std::vector<HeldPiece> held;                /* out: one per segment that has bytes */
+    };
+
+    /** What the launches of one search share: the pattern, and -- with a limit -- how many matches the launches at the
+     * front of the range that are through have found.  Once these reach the limit, no further launch is started. */
+    struct SearchCall
+    {
+        const uint8_t* pattern{ nullptr };
+        uint32_t m{ 0 };
+        uint64_t limit{ 0 };                        /* 0: count only */
+        std::mutex mutex;
+        std::vector<uint8_t> finished;              /* per launch */
+        std::vector<uint64_t> counts;
+        size_t through{ 0 };                        /* launches [0, through) are finished ... */
+        uint64_t found{ 0 };                        /* ... and have found this many */
+        std::atomic<bool> stop{ false };
+    };
+
+    /** What a launch of a search does with its decoded blocks: mi355x::searchOutput over its extent.  Owned by the
+     * caller, who waits for the launch. */
+    struct SearchWork
+    {
+        SearchCall* call{ nullptr };
+        uint32_t index{ 0 };
+        bz2gpu::SearchExtent extent;
+        bool skipped{ false };                      /* out: not started, the limit had been reached */
+        uint64_t count{ 0 };                        /* out: matches inside the extent */
+        std::vector<uint64_t> positions;            /* out (limit > 0): the first min( count, limit ), in the launch's output */
+        uint8_t seam[2 * bz2gpu::SEARCH_PATTERN_MAX]{};   /* out: head at 0, tail at SEARCH_PATTERN_MAX */
     };
 
     /** Forget what the contexts hold for read_line_ranges (the buffers stay: they only grow). */
@@ -811,6 +842,26 @@ private:
         return nullptr;
     }
 
+    /** The search's part of a launch whose blocks have just been decoded into the context's output. */
+    [[nodiscard]] std::exception_ptr
+    runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
+    {
+        auto& call = *work.call;
+        const int rc = searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern, call.m, call.limit,
+                                     call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam );
+        if ( rc != MI355X_BZ2_OK ) return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+        if ( call.limit > 0 ) {
+            const std::scoped_lock lock( call.mutex );
+            call.finished[work.index] = 1;
+            call.counts[work.index] = work.count;
+            while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
+                call.found += call.counts[call.through++];
+            }
+            if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
+        }
+        return nullptr;
+    }
+
     /** One submission thread per decoder context: takes a launch, decodes the batch, copies it to a page-locked buffer,
      * publishes the run.  Replaces the thread pool of per-block tasks (BlockFetcher.hpp:620-642).
      * The copy of a batch runs in the background while the context's next batch is launched (the context writes to a
@@ -880,6 +931,11 @@ private:
          * the bytes are in the caller's destination.  Nothing reads this buffer afterwards, so the context's next batch
          * may write into it at once. */
         const auto runRanges = [&] ( RangesWork& work ) {
+            if ( work.search != nullptr && work.search->call->stop.load( std::memory_order_acquire ) ) {
+                work.search->skipped = true;     /* the launches in front of it have found what was asked for */
+                work.done.set_value();
+                return;
+            }
             const auto t0 = std::chrono::steady_clock::now();
             const auto& launch = *work.launch;
             const auto n = (uint32_t)launch.bits.size();
@@ -924,7 +980,9 @@ private:
                         error( MI355X_BZ2_ERR_LOGIC, "the block index promises more bytes than the block decodes to" ) );
                 }
             }
-            if ( !failure && work.lines != nullptr ) {
+            if ( !failure && work.search != nullptr ) {
+                failure = runSearchWork( ctx, *work.search );
+            } else if ( !failure && work.lines != nullptr ) {
                 failure = runLineWork( ctx, launch, *work.lines );
             } else if ( !failure ) {
                 rc = mi355x_bz2_gather_output( ctx, work.pieces.data(), (uint32_t)work.pieces.size(), work.dst,
@@ -1089,6 +1147,7 @@ public:
     close()
     {
         m_held.reset();
+        m_matches.reset();
         m_scheduler.reset();
         m_finder.reset();
         m_source.reset();
@@ -1239,28 +1298,8 @@ public:
         for ( size_t i = 0; i < n; ++i ) {
             if ( sizes[i] > 0 ) furthest = std::max( furthest, offsets[i] + std::min( sizes[i], ~uint64_t( 0 ) - offsets[i] ) );
         }
-        if ( !m_index.sealed() && ( furthest > m_index.frontier() ) ) {
-            const size_t position = m_position;
-            const bool atEnd = m_atEnd;
-            try {
-                m_position = (size_t)m_index.frontier();
-                m_atEnd = false;
-                read( Sink(), (size_t)( furthest - m_position ) );
-            } catch ( ... ) {
-                m_position = position;
-                m_atEnd = atEnd;
-                throw;
-            }
-            m_position = position;
-            m_atEnd = atEnd;
-        }
-
-        /* the map as far as it is known; while it is not complete, its last entry is followed by the end of the open block */
-        auto map = m_index.snapshot();
-        if ( !m_index.sealed() && !map.empty() ) {
-            const auto open = m_index.locate( map.back().second );
-            if ( open.bitLength > 0 ) map.emplace_back( map.back().first + open.bitLength, map.back().second + open.byteLength );
-        }
+        indexUpTo( furthest );
+        const auto map = knownMap();
         auto plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, false, m_source->size() );
         if ( plan.distinctBlocks > 0 && !scheduler().inputResident() ) {
             plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, true, m_source->size() );
@@ -1281,6 +1320,89 @@ public:
         }
         runLaunches( works );
         std::copy( plan.nRead.begin(), plan.nRead.end(), nRead );
+    }
+
+    /* ---------------------------------------------------------------------------------------- search */
+    /** Step 1 (mi355x_bz2_reader_search): the launches of bz2_search.hpp's plan, each searching its extent on the context
+     * that decoded it; then the matches no launch can see (seamMatches), and both merged in file order. */
+    void
+    search( const uint8_t* pattern, uint32_t m, uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "search on a closed reader" );
+        if ( m == 0 || m > bz2gpu::SEARCH_PATTERN_MAX ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "search: the pattern must have 1 to 256 bytes, not " + std::to_string( m ) );
+        }
+        m_matches.reset();
+        *nMatches = 0;
+        if ( start >= end ) {
+            if ( limit > 0 ) m_matches.emplace();
+            return;
+        }
+        indexUpTo( end );
+        const auto map = knownMap();
+        auto plan = bz2gpu::planSearch( map, start, end, m, m_batch, false, m_source->size() );
+        if ( !plan.launches.empty() && !scheduler().inputResident() ) {
+            plan = bz2gpu::planSearch( map, start, end, m, m_batch, true, m_source->size() );
+        }
+        const size_t n = plan.launches.size();
+        BatchScheduler::SearchCall call;
+        call.pattern = pattern;
+        call.m = m;
+        call.limit = limit;
+        call.finished.assign( n, 0 );
+        call.counts.assign( n, 0 );
+        std::vector<BatchScheduler::SearchWork> searches( n );
+        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( n );
+        for ( size_t l = 0; l < n; ++l ) {
+            searches[l].call = &call;
+            searches[l].index = (uint32_t)l;
+            searches[l].extent = plan.extents[l];
+            works[l] = std::make_unique<BatchScheduler::RangesWork>();
+            works[l]->launch = &plan.launches[l];
+            works[l]->search = &searches[l];
+        }
+        runLaunches( works );
+
+        /* the launches in front of the first one that was not started: with a limit they hold at least `limit` matches,
+         * and every match that needs a byte behind them starts behind all of those (bz2_search.hpp) */
+        size_t usable = 0;
+        while ( usable < n && !searches[usable].skipped ) ++usable;
+        std::vector<bz2gpu::ExtentSeam> seams( usable );
+        for ( size_t l = 0; l < usable; ++l ) {
+            const auto& extent = searches[l].extent;
+            const auto k = bz2gpu::seamLength( m, extent.size );
+            seams[l] = { extent.fileOffset, extent.size, { searches[l].seam, searches[l].seam + k },
+                         { searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX, searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX + k } };
+        }
+        const auto between = bz2gpu::seamMatches( pattern, m, seams );
+        if ( limit == 0 ) {
+            uint64_t total = between.size();
+            for ( const auto& work : searches ) total += work.count;
+            *nMatches = total;
+            return;
+        }
+        /* extent by extent: its own matches, then those that start in it and end behind it */
+        std::vector<uint64_t> merged;
+        size_t seam = 0;
+        for ( size_t l = 0; l < usable && merged.size() < limit; ++l ) {
+            const auto& extent = searches[l].extent;
+            for ( const auto position : searches[l].positions ) merged.push_back( extent.fileOffset + ( position - extent.src ) );
+            for ( ; seam < between.size() && between[seam] < extent.fileOffset + extent.size; ++seam ) merged.push_back( between[seam] );
+        }
+        if ( merged.size() > limit ) merged.resize( (size_t)limit );
+        *nMatches = merged.size();
+        m_matches = std::move( merged );
+    }
+
+    /** Step 2 (mi355x_bz2_reader_take_matches): the held positions, then nothing is held any more. */
+    void
+    takeMatches( uint64_t* positions, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_matches on a closed reader" );
+        if ( !m_matches ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_matches: no matches are held (search with a limit first)" );
+        const auto held = std::move( *m_matches );
+        m_matches.reset();
+        std::copy_n( held.begin(), (size_t)std::min<uint64_t>( capacity, held.size() ), positions );
     }
 
     /* ---------------------------------------------------------------------------------------- line access */
@@ -1471,6 +1593,38 @@ private:
     {
         m_held.reset();
         if ( m_scheduler ) m_scheduler->dropHeld();
+    }
+
+    /** Index the file up to the decoded offset `furthest`, as a forward seek would; the position and eof() stay. */
+    void
+    indexUpTo( uint64_t furthest )
+    {
+        if ( m_index.sealed() || ( furthest <= m_index.frontier() ) ) return;
+        const size_t position = m_position;
+        const bool atEnd = m_atEnd;
+        try {
+            m_position = (size_t)m_index.frontier();
+            m_atEnd = false;
+            read( Sink(), (size_t)( furthest - m_position ) );
+        } catch ( ... ) {
+            m_position = position;
+            m_atEnd = atEnd;
+            throw;
+        }
+        m_position = position;
+        m_atEnd = atEnd;
+    }
+
+    /** The map as far as it is known; while it is not complete, its last entry is followed by the end of the open block. */
+    [[nodiscard]] std::vector<std::pair<uint64_t, uint64_t> >
+    knownMap() const
+    {
+        auto map = m_index.snapshot();
+        if ( !m_index.sealed() && !map.empty() ) {
+            const auto open = m_index.locate( map.back().second );
+            if ( open.bitLength > 0 ) map.emplace_back( map.back().first + open.bitLength, map.back().second + open.byteLength );
+        }
+        return map;
     }
 
     /** Each launch to the front of the queue -- the last one first, so that the first launch is taken first --, and all
@@ -1692,6 +1846,7 @@ private:
 
     std::optional<LineIndex> m_lines;     /* the one line index the reader keeps, with its delimiter */
     std::optional<HeldLines> m_held;      /* between read_line_ranges and take_line_ranges */
+    std::optional<std::vector<uint64_t> > m_matches;   /* between search (with a limit) and take_matches */
 };
 }  // namespace mi355x
 
@@ -1960,6 +2115,21 @@ int
 mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dstIsDevice )
 {
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeLineRanges( dst, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_search( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint64_t start, uint64_t end,
+                          uint64_t limit, uint64_t* nMatches )
+{
+    if ( pattern == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.search( pattern, patternSize, start, end, limit, nMatches ); } );
+}
+
+int
+mi355x_bz2_reader_take_matches( mi355x_bz2_reader* r, uint64_t* positions, uint64_t capacity )
+{
+    if ( capacity > 0 && positions == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeMatches( positions, capacity ); } );
 }
 
 int

@@ -39,8 +39,8 @@ struct Options
     bool toStdout{ false }, decompress{ false }, force{ false }, keep{ false }, test{ false }, help{ false };
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
-    bool listCompressed{ false }, listOffsets{ false }, countLines{ false };
-    std::string input, output, listCompressedPath, listOffsetsPath;
+    bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false };
+    std::string input, output, listCompressedPath, listOffsetsPath, pattern;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
     int device{ -1 };
@@ -80,7 +80,10 @@ printHelp()
         "                                decoded data at the beginning of each block in bytes as comma separated pairs\n"
         "                                per line '<encoded bits>,<decoded bytes>'.\n"
         "      --count-lines             Count the newline characters of the decoded data on the GPU (nothing is\n"
-        "                                decompressed to the host), print the number and exit.\n\n"
+        "                                decompressed to the host), print the number and exit.\n"
+        "      --count-matches arg       Count the occurrences of the given string (1 to 256 bytes; occurrences that\n"
+        "                                overlap each other all count) in the decoded data on the GPU, print the\n"
+        "                                number and exit.\n\n"
         " Advanced options:\n"
         "      --buffer-size arg         Controls the output buffer size. By default, the decoded data is written in\n"
         "                                one pass per block. (default: 0)\n\n"
@@ -92,7 +95,9 @@ printHelp()
         "List block offsets in both the compressed as well as the decompressed data:\n"
         "  ibzip2-mi355x -L blockoffsets.dat file.bz2 > /dev/null\n\n"
         "Count the lines of a compressed file:\n"
-        "  ibzip2-mi355x --count-lines file.bz2\n";
+        "  ibzip2-mi355x --count-lines file.bz2\n\n"
+        "Count the occurrences of a string in a compressed file:\n"
+        "  ibzip2-mi355x --count-matches ERROR file.bz2\n";
 }
 
 bool
@@ -178,6 +183,7 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "input" ) { if ( !need( o.input ) ) return 1; }
             else if ( name == "output" ) { if ( !need( o.output ) ) return 1; o.hasOutput = true; }
             else if ( name == "count-lines" ) o.countLines = true;
+            else if ( name == "count-matches" ) { if ( !need( o.pattern ) ) return 1; o.countMatches = true; }
             else if ( name == "list-compressed-offsets" ) {
                 o.listCompressed = true;
                 if ( hasInline ) o.listCompressedPath = inlineValue; else optionalValue( i, o.listCompressedPath );
@@ -408,6 +414,39 @@ main( int argc, char** argv )
         }
         mi355x_bz2_reader_close( reader );
         std::cout << lines.back() << "\n";
+        return 0;
+    }
+
+    /* likewise an action of its own: the number of matches of a string in the decoded data, from the reader's search */
+    if ( o.countMatches ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t count = 0;
+        rc = mi355x_bz2_reader_search( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(), 0,
+                                       ~uint64_t( 0 ), 0, &count );
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Search failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        std::cout << count << "\n";
         return 0;
     }
 

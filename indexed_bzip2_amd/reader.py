@@ -326,6 +326,54 @@ class _IndexedBzip2FileParallel:
             bounds.append(bounds[-1] + size)
         return data, torch.tensor(bounds, dtype=torch.int64)
 
+    # -- search: a match of `pattern` (1 to 256 bytes) is every offset p with data[p:p + len(pattern)] == pattern,
+    # start <= p and p + len(pattern) <= end; start and end are clipped to the decoded size
+    @staticmethod
+    def _pattern(pattern):
+        pattern = bytes(memoryview(pattern))     # TypeError for what is not bytes-like
+        if not 1 <= len(pattern) <= 256:
+            raise ValueError(f"the pattern must have 1 to 256 bytes, not {len(pattern)}")
+        return pattern
+
+    def _search(self, pattern, start, end, limit):
+        """Step 1 (mi355x_bz2_reader_search): the number of matches (limit 0), or of the positions now held."""
+        self._require()
+        pattern = self._pattern(pattern)
+        start, end = int(start), 2**64 - 1 if end is None else int(end)
+        if start < 0 or end < 0:
+            raise ValueError("start and end must not be negative")
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_search(self._h, pattern, len(pattern), min(start, 2**64 - 1),
+                                                     min(end, 2**64 - 1), limit, ctypes.byref(n)))
+        return n.value
+
+    def count_matches(self, pattern, start=0, end=None):
+        """How often the byte string `pattern` occurs in data[start:end] of the decoded file.  Occurrences that overlap
+        each other all count -- b"abab" occurs 3 times in b"abababab" -- unlike bytes.count, which says 2.  Every block
+        that intersects the range is decoded once, the matches are found on the GPU and only their number leaves it.
+        Positionless."""
+        return self._search(pattern, start, end, 0)
+
+    def find_all(self, pattern, start=0, end=None, limit=None):
+        """The offsets in the decoded file of the occurrences of `pattern` in data[start:end] (numpy uint64, ascending),
+        at most `limit` of them (None: all).  With a limit, no launch is started once it has been reached.  Overlapping
+        occurrences as in count_matches.  Positionless."""
+        import numpy as np
+        if limit is not None and int(limit) < 0:
+            raise ValueError("limit must not be negative")
+        if limit is not None and int(limit) == 0:
+            self._pattern(pattern)
+            return np.empty(0, dtype=np.uint64)
+        n = self._search(pattern, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1))
+        out = (ctypes.c_uint64 * max(1, n))()
+        self._check(N.lib().mi355x_bz2_reader_take_matches(self._h, out, n))
+        return np.frombuffer(out, dtype=np.uint64, count=n).copy()
+
+    def find(self, pattern, start=0, end=None):
+        """The offset of the first occurrence of `pattern` in data[start:end], or -1: find_all with limit=1."""
+        first = self.find_all(pattern, start, end, 1)
+        return int(first[0]) if len(first) else -1
+
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
         like the reference, whose serial reader checks and whose parallel reader does not)."""
@@ -432,6 +480,18 @@ class IndexedBzip2File(io.BufferedReader):
     def read_line_ranges_to_tensor(self, ranges, newline=b"\n"):
         """See _IndexedBzip2FileParallel.read_line_ranges_to_tensor."""
         return self._open_reader().read_line_ranges_to_tensor(ranges, newline)
+
+    def count_matches(self, pattern, start=0, end=None):
+        """See _IndexedBzip2FileParallel.count_matches."""
+        return self._open_reader().count_matches(pattern, start, end)
+
+    def find_all(self, pattern, start=0, end=None, limit=None):
+        """See _IndexedBzip2FileParallel.find_all."""
+        return self._open_reader().find_all(pattern, start, end, limit)
+
+    def find(self, pattern, start=0, end=None):
+        """See _IndexedBzip2FileParallel.find."""
+        return self._open_reader().find(pattern, start, end)
 
 
 builtins_open = builtins.open
