@@ -248,17 +248,32 @@ int mi355x_bz2_gather_output( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece
  * src/rapidgzip/ParallelGzipReader.hpp:1056-1145).
  *   _count_byte  counts[i] = the number of bytes equal to `value` in [offset, offset + size) of span i  (k_count_byte).
  *   _find_byte   positions[i] = the offset in the output of the rank-th (1-based; 0 is refused) byte equal to `value`
- *                in span i, or UINT64_MAX if the span holds fewer than rank of them  (k_count_byte, then k_find_byte). */
+ *                in span i, or UINT64_MAX if the span holds fewer than rank of them  (k_count_byte, then k_find_byte).
+ *   _rank_byte   the inverse: ranks[i] = the number of bytes equal to `value` in [offset, position) of the output, for
+ *                offset <= position <= offset + size (anything else is MI355X_BZ2_ERR_INVALID_ARGUMENT); a position at
+ *                the span's end gives the span's count.  Queries come in any order.  k_count_byte, then k_rank_byte with
+ *                one wave per 64-KiB tile that holds a position: a tile is read once however many positions fall into
+ *                it.  The call's lists take 12 bytes per position beside the tiles, in page-locked and in device memory
+ *                that the context keeps until it is destroyed, like the lists of the other byte calls (grow-only; a call
+ *                whose lists need more than 64 MiB and do not fit gets new buffers of that need and an eighth, a smaller
+ *                one of twice the present size, or its need if that is more): ten million positions in
+ *                one call leave the context with about 135 MB of each.  ranks[] is written only once every query has
+ *                passed its check. */
 typedef struct mi355x_bz2_byte_span {
     uint64_t offset, size;
 } mi355x_bz2_byte_span;
 typedef struct mi355x_bz2_byte_query {
     uint64_t offset, size, rank;
 } mi355x_bz2_byte_query;
+typedef struct mi355x_bz2_rank_query {
+    uint64_t offset, size, position;
+} mi355x_bz2_rank_query;
 int mi355x_bz2_count_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t value,
                            uint64_t* counts );
 int mi355x_bz2_find_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_query* queries, uint32_t n, uint8_t value,
                           uint64_t* positions );
+int mi355x_bz2_rank_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_rank_query* queries, uint32_t n, uint8_t value,
+                          uint64_t* ranks );
 
 /* A byte string in spans of the last batch's output, on the GPU: the kernels under the reader's search.  The same rules
  * as mi355x_bz2_count_byte.  pattern_size is 1 to 256 (else MI355X_BZ2_ERR_INVALID_ARGUMENT).  A match of span i is every
@@ -482,6 +497,37 @@ int mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dst
 int mi355x_bz2_reader_search( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint64_t start,
                               uint64_t end, uint64_t limit, uint64_t* n_matches );
 int mi355x_bz2_reader_take_matches( mi355x_bz2_reader* r, uint64_t* positions, uint64_t capacity );
+
+/* ---- grep and line numbers: the line functions and the search joined.  D, nl, N and s(k) as under line access.
+ * L(p) = the number of nl bytes in D[0 : min( p, size )]: the 0-based line that holds byte p, s( L(p) ) <= p <
+ * s( L(p) + 1 ) for p < size (with s(N + 1) read as the size); L(p) = N for every p at or beyond the size, and 0 for every
+ * p of an empty file.  Positionless like the line functions, and built on the same line index (built first if the reader
+ * does not hold one for nl). */
+
+/* lines[i] = L( offsets[i] ), the inverse of _line_starts; the offsets come in any order, repeats included.  Decodes only
+ * the blocks that hold an offset which is not their first byte (the index answers that one, and everything at or beyond
+ * the size); k_rank_byte counts the delimiters in front of the offsets, one pass over a 64-KiB tile however many offsets
+ * fall into it, and only the counts leave the GPU.  An imported index that does not fit the data of a decoded block
+ * fails the call with MI355X_BZ2_ERR_LOGIC.  Releases held line ranges, as every line call does. */
+int mi355x_bz2_reader_line_numbers( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* offsets, uint64_t n, uint64_t* lines );
+/* The lines that hold a match (bzgrep -F, grep -n).  The matches are exactly those of _search for (pattern, start, end):
+ * 1 <= pattern_size <= 256 (else, or with a null pattern, MI355X_BZ2_ERR_INVALID_ARGUMENT before anything is launched),
+ * overlapping matches included, start and end bound the matches and not the lines.  A match belongs to the line of its
+ * FIRST byte (the pattern may contain nl).  A matching line is a line with at least one match: each is reported once, in
+ * ascending order, whole and with its delimiter -- also where it reaches outside [start, end) --, the unterminated tail
+ * as it is.
+ * Step 1, _grep.  max_lines == 0: count only -- *n_lines is the number of distinct matching lines, nothing is held.
+ * Otherwise the first min( max_lines, all ) matching lines are held as by _read_line_ranges with one range (line, 1)
+ * each, *n_lines is their number and *total_bytes the sum of their sizes; keep_on_device as there.  Three passes: the
+ * search over the whole of [start, end) whatever max_lines is, the rank pass of _line_numbers over the blocks that hold
+ * a match's first byte (decoded a second time: the passes share nothing), and the line ranges.  Matches and line ranges
+ * held by earlier calls are released.
+ * Step 2, _take_grep: the numbers and byte sizes of the held lines (at most `capacity`); the bytes stay held.  With
+ * nothing held: MI355X_BZ2_ERR_INVALID_ARGUMENT.
+ * Step 3, the bytes: _take_line_ranges, which releases everything. */
+int mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint8_t nl, uint64_t start,
+                            uint64_t end, uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+int mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* line_numbers, uint64_t* byte_sizes, uint64_t capacity );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

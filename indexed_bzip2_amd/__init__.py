@@ -5,8 +5,10 @@ Host-side mirror of python/indexed_bzip2/indexed_bzip2.pyx (open, IndexedBzip2Fi
 include/mi355x_bz2.h.  All decoding happens in hand-written HIP kernels on gfx950; there is no CPU fallback.
 
 Beyond the reference's API the reader answers questions about the decoded file while its bytes stay in HBM: byte ranges
-(read_ranges), lines (count_lines, line_starts, read_line_ranges) and where a byte string occurs (count_matches,
-find_all, find: every offset p with data[p:p + len(pattern)] == pattern, overlapping occurrences included).
+(read_ranges), lines (count_lines, line_starts, line_numbers, read_line_ranges), where a byte string occurs
+(count_matches, find_all, find: every offset p with data[p:p + len(pattern)] == pattern, overlapping occurrences included)
+and which lines hold it (grep, count_matching_lines, grep_to_tensor: the lines of the matches' first bytes, each once,
+whole, with their 0-based numbers).
 """
 __version__ = "0.1.0"
 

@@ -95,6 +95,10 @@ class ByteQuery(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint64), ("size", ctypes.c_uint64), ("rank", ctypes.c_uint64)]
 
 
+class RankQuery(ctypes.Structure):
+    _fields_ = [("offset", ctypes.c_uint64), ("size", ctypes.c_uint64), ("position", ctypes.c_uint64)]
+
+
 class BufferResult(ctypes.Structure):
     _fields_ = [("output_offset", ctypes.c_uint64), ("decoded_size", ctypes.c_uint64),
                 ("error_offset_bits", ctypes.c_uint64), ("n_blocks", ctypes.c_uint32), ("n_streams", ctypes.c_uint32),
@@ -150,6 +154,7 @@ SYMBOLS = [
     ("mi355x_bz2_gather_output", ctypes.c_int, [_vp, ctypes.POINTER(GatherPiece), ctypes.c_uint32, _vp, ctypes.c_int]),
     ("mi355x_bz2_count_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
     ("mi355x_bz2_find_byte", ctypes.c_int, [_vp, ctypes.POINTER(ByteQuery), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
+    ("mi355x_bz2_rank_byte", ctypes.c_int, [_vp, ctypes.POINTER(RankQuery), ctypes.c_uint32, ctypes.c_uint8, _u64p]),
     ("mi355x_bz2_count_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
                                                ctypes.c_uint32, _u64p]),
     ("mi355x_bz2_find_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
@@ -182,6 +187,10 @@ SYMBOLS = [
     ("mi355x_bz2_reader_search", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64,
                                                  ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_take_matches", ctypes.c_int, [_vp, _u64p, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_line_numbers", ctypes.c_int, [_vp, ctypes.c_uint8, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_reader_grep", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint64,
+                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_grep", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -477,6 +486,14 @@ class Decoder:
         out = (ctypes.c_uint64 * max(1, len(queries)))()
         self._check(lib().mi355x_bz2_find_byte(self._h, arr, len(queries), value, out))
         return [None if p == 2**64 - 1 else p for p in out[:len(queries)]]
+
+    def rank_byte(self, queries, value: int):
+        """k_rank_byte: for each query (offset, size, position) the number of bytes equal to `value` in
+        [offset, position) of the last batch's output; offset <= position <= offset + size."""
+        arr = (RankQuery * max(1, len(queries)))(*[RankQuery(o, n, p) for o, n, p in queries])
+        out = (ctypes.c_uint64 * max(1, len(queries)))()
+        self._check(lib().mi355x_bz2_rank_byte(self._h, arr, len(queries), value, out))
+        return [out[i] for i in range(len(queries))]
 
     def count_bytes(self, pattern, spans):
         """k_count_bytes: how often the byte string `pattern` (1 to 256 bytes) occurs in each span [(offset, size)] of the

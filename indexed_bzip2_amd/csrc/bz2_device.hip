@@ -1723,6 +1723,115 @@ selectBytes( mi355x_bz2_ctx* c, const char* what, uint8_t value, uint32_t n, con
 }
 
 /**
+ * mi355x_bz2_rank_byte: the distinct spans are cut into tiles and counted as in selectBytes; the positions are sorted
+ * span by span and grouped by tile, and k_rank_byte runs one wave per tile that holds a position.  A position at a
+ * span's first byte is answered here (0); a position at a tile's first byte is the end of the tile in front of it, so
+ * that a position at the span's end needs no tile behind the span.
+ */
+constexpr uint64_t RANK_LIST_DOUBLING = 64ull << 20;
+
+int
+rankBytes( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, uint32_t n, uint8_t value, uint64_t* ranks )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = "rank_byte: a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    std::map<std::pair<uint64_t, uint64_t>, uint32_t> known;
+    std::vector<std::pair<uint64_t, uint64_t> > spans;
+    std::vector<uint64_t> firstTile;
+    struct Asked { uint64_t tile; uint32_t end, input; };   /* tile in the list, bytes of it in front of the position */
+    std::vector<Asked> asked;
+    asked.reserve( n );
+    uint64_t nTiles = 0;
+    /* nothing is written before every query has passed */
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& q = queries[i];
+        if ( q.size > c->outSize || q.offset > c->outSize - q.size || q.position < q.offset || q.position - q.offset > q.size ) {
+            c->lastError = "rank_byte: query " + std::to_string( i )
+                           + " names a span outside the last batch's output, or a position outside its span";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+    }
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& q = queries[i];
+        const auto [entry, isNew] = known.emplace( std::make_pair( q.offset, q.size ), (uint32_t)spans.size() );
+        if ( isNew ) {
+            spans.push_back( entry->first );
+            firstTile.push_back( nTiles );
+            nTiles += ( q.size + COUNT_TILE - 1 ) / COUNT_TILE;
+        }
+        ranks[i] = 0;
+        const uint64_t in = q.position - q.offset;
+        if ( in == 0 ) continue;
+        asked.push_back( { firstTile[entry->second] + ( in - 1 ) / COUNT_TILE, (uint32_t)( ( in - 1 ) % COUNT_TILE ) + 1, i } );
+    }
+    if ( asked.empty() ) return MI355X_BZ2_OK;
+    if ( nTiles > 0x7FFFFFFFu ) {
+        c->lastError = "rank_byte: too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    std::sort( asked.begin(), asked.end(), [] ( const Asked& a, const Asked& b ) {
+        return a.tile != b.tile ? a.tile < b.tile : a.end < b.end;
+    } );
+    uint64_t nWork = 0;
+    for ( size_t k = 0; k < asked.size(); ++k ) nWork += k == 0 || asked[k].tile != asked[k - 1].tile ? 1 : 0;
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][tiles with queries][ends, padded to 8 bytes][ranks]; device only: [tile counts] behind */
+    const uint64_t nAsked = asked.size();
+    const uint64_t tilesAt = 0, workAt = tilesAt + nTiles * sizeof( CountTile ), endsAt = workAt + nWork * sizeof( RankTile );
+    const uint64_t resultsAt = endsAt + ( ( nAsked + 1 ) & ~uint64_t( 1 ) ) * sizeof( uint32_t );
+    const uint64_t countsAt = resultsAt + nAsked * sizeof( uint64_t ), bytes = countsAt + nTiles * sizeof( uint32_t );
+    /* the lists of this call can be orders of magnitude larger than the other byte calls' (12 bytes per position, and a
+     * search hands over millions): a need of up to RANK_LIST_DOUBLING doubles the device buffer as the other calls do, a
+     * larger one gets the need and an eighth.  One capacity for both buffers, derived from the device's, which holds
+     * all the host's holds and the tile counts: it is at least `bytes`, and the host needs `countsAt` < `bytes` */
+    const uint64_t cap = bytes <= RANK_LIST_DOUBLING ? std::max( 2 * c->dSelect.capacity, bytes ) : bytes + bytes / 8;
+    /* the previous call's lists have been consumed (every call waits for its kernels) */
+    HIP_TRY( c, c->hSelect.grow( c, countsAt, cap, cap ) );
+    HIP_TRY( c, c->dSelect.grow( c, bytes, cap, cap ) );
+    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSelect.bytes + tilesAt );
+    auto* const hWork = reinterpret_cast<RankTile*>( c->hSelect.bytes + workAt );
+    auto* const hEnds = reinterpret_cast<uint32_t*>( c->hSelect.bytes + endsAt );
+    auto* const hResults = reinterpret_cast<uint64_t*>( c->hSelect.bytes + resultsAt );
+    uint64_t tile = 0;
+    std::vector<uint32_t> spanOfTile( nTiles );
+    for ( size_t s = 0; s < spans.size(); ++s ) {
+        for ( uint64_t k = 0; k < spans[s].second; k += COUNT_TILE ) {
+            spanOfTile[tile] = (uint32_t)s;
+            hTiles[tile++] = { spans[s].first + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].second - k ), (uint32_t)s };
+        }
+    }
+    uint64_t work = 0;
+    for ( size_t k = 0; k < asked.size(); ++k ) {
+        if ( k == 0 || asked[k].tile != asked[k - 1].tile ) {
+            hWork[work++] = { (uint32_t)asked[k].tile, (uint32_t)firstTile[spanOfTile[asked[k].tile]], (uint32_t)k, 0 };
+        }
+        ++hWork[work - 1].nQueries;
+        hEnds[k] = asked[k].end;
+    }
+    if ( ( nAsked & 1 ) != 0 ) hEnds[nAsked] = 0;
+    uint8_t* const d = c->dSelect.bytes;
+    HIP_TRY( c, hipMemcpyAsync( d, c->hSelect.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    const uint32_t pattern = 0x01010101u * value;
+    hipLaunchKernelGGL( k_count_byte, dim3( (uint32_t)nTiles ), dim3( COUNT_THREADS ), 0, c->stream,
+                        reinterpret_cast<const CountTile*>( d + tilesAt ), c->dOut, pattern,
+                        reinterpret_cast<uint32_t*>( d + countsAt ), nullptr );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_rank_byte, dim3( (uint32_t)nWork ), dim3( FIND_THREADS ), 0, c->stream,
+                        reinterpret_cast<const RankTile*>( d + workAt ), reinterpret_cast<const CountTile*>( d + tilesAt ),
+                        reinterpret_cast<const uint32_t*>( d + countsAt ), reinterpret_cast<const uint32_t*>( d + endsAt ),
+                        c->dOut, pattern, reinterpret_cast<uint64_t*>( d + resultsAt ) );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( hResults, d + resultsAt, nAsked * sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( size_t k = 0; k < asked.size(); ++k ) ranks[asked[k].input] = hResults[k];
+    return MI355X_BZ2_OK;
+}
+
+/**
  * Both string calls.  The start positions every span allows are cut into tiles (spans in caller order, a span given twice
  * is searched twice: its positions are wanted twice), k_count_bytes counts every tile and adds to its span's counter, and
  * the counts -- with the seam bytes of `seam`, if given -- come back in one D2H.  With positions wanted, min( total,
@@ -1899,6 +2008,13 @@ mi355x_bz2_find_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_query* queries, u
         ranks[i] = queries[i].rank;
     }
     return selectBytes( c, "find_byte", value, n, offsets.data(), sizes.data(), ranks.data(), positions );
+}
+
+int
+mi355x_bz2_rank_byte( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, uint32_t n, uint8_t value, uint64_t* ranks )
+{
+    if ( c == nullptr || ( n > 0 && ( queries == nullptr || ranks == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return rankBytes( c, queries, n, value, ranks );
 }
 
 int

@@ -18,6 +18,15 @@
  *                 vectors, a wave prefix picks the one that holds the occurrence; (3) the vector -- the lanes take that
  *                 lane's vectors one each, a wave prefix picks the vector and the lane that has it picks the bit.
  *                 "Fewer than rank occurrences" (also: counts that do not add up) gives UINT64_MAX.
+ *   k_rank_byte   the inverse: how many occurrences lie in front of a position.  One wave per TILE that holds queries,
+ *                 however many: the host sorts a span's positions and groups them by tile, so that a tile is read at most
+ *                 once per call (the matches of a frequent string fall into one tile by the thousand).  The wave (1) sums
+ *                 the counts of the span's tiles in front of its own, 64 per step; (2) walks its tile 64 vectors (1 KiB)
+ *                 per step: a wave-inclusive scan of the lanes' popcounts gives the count in front of every vector of the
+ *                 step; (3) answers the step's queries 64 at a time -- the lane of a query fetches the exclusive prefix
+ *                 and the hit mask of the query's vector with __shfl and adds the hits below the position --; and stops
+ *                 behind the tile's last query.  No atomics, no LDS, and every loop is bounded by the tile and the
+ *                 query count.
  */
 #pragma once
 
@@ -43,6 +52,16 @@ struct FindQuery
 {
     uint64_t rank;     /* 1-based */
     uint32_t firstTile, nTiles;
+};
+
+/** The queries of one tile for k_rank_byte: ends[firstQuery .. firstQuery + nQueries) ascending, each the number of the
+ * tile's bytes in front of the position, 1 .. the tile's size (a position at a tile's first byte belongs to the tile in
+ * front, as its end; the host answers a position at the span's first byte itself). */
+struct RankTile
+{
+    uint32_t tile;         /* in the tile list */
+    uint32_t firstTile;    /* of the tile's span */
+    uint32_t firstQuery, nQueries;
 };
 
 /** Bit 7 of every byte of x that is zero (exact: the sums stay inside their bytes). */
@@ -194,5 +213,55 @@ k_find_byte( const FindQuery* __restrict__ queries, const CountTile* __restrict_
         rank -= __shfl( upTo, 63 );
     }
     if ( lane == 0 ) positions[blockIdx.x] = FIND_NONE;
+}
+__global__ __launch_bounds__( FIND_THREADS ) void
+k_rank_byte( const RankTile* __restrict__ work, const CountTile* __restrict__ tiles, const uint32_t* __restrict__ tileCounts,
+             const uint32_t* __restrict__ ends, const uint8_t* __restrict__ out, uint32_t pattern,
+             uint64_t* __restrict__ ranks )
+{
+    const RankTile w = work[blockIdx.x];
+    const uint32_t lane = threadIdx.x;
+
+    /* (1) the occurrences in the span's tiles in front of this one; the same in every lane */
+    uint64_t running = 0;
+    for ( uint32_t t0 = w.firstTile; t0 < w.tile; t0 += 64 ) {
+        const uint32_t c = t0 + lane < w.tile ? tileCounts[t0 + lane] : 0u;
+        running += __shfl( waveInclusiveScan( c, lane ), 63 );
+    }
+
+    /* (2) the tile, 64 vectors per step, as far as its last query */
+    const CountTile t = tiles[w.tile];
+    const uint64_t begin = t.src, end = t.src + t.size;
+    const uint64_t base = begin & ~uint64_t( 15 );
+    const uint32_t lead = (uint32_t)( begin - base );
+    const uint32_t vectors = (uint32_t)( ( end - base + 15 ) >> 4 );
+    const uint4* const v = reinterpret_cast<const uint4*>( out + base );
+    const uint32_t* const e = ends + w.firstQuery;
+    uint64_t* const r = ranks + w.firstQuery;
+    uint32_t q = 0;   /* queries answered; the same in every lane */
+    for ( uint32_t k0 = 0; k0 < vectors && q < w.nQueries; k0 += 64 ) {
+        const uint32_t k = k0 + lane;
+        /* the mask matters on the tile's first vector only (bytes in front of the tile): what lies behind a position is
+         * masked per query below, and no query lies behind the tile's end */
+        const uint32_t hits = k < vectors ? matches16( v[k], pattern ) & validBytes16( base + 16ull * k, begin, end ) : 0u;
+        const uint32_t c = __popc( hits );
+        const uint32_t upTo = waveInclusiveScan( c, lane );
+        const uint32_t before = upTo - c;
+
+        /* (3) the queries whose last byte in front of the position lies in this step, 64 at a time */
+        while ( q < w.nQueries ) {
+            const bool have = q + lane < w.nQueries;
+            const uint32_t last = have ? lead + e[q + lane] - 1 : 0u;   /* that byte, from `base` */
+            const bool mine = have && ( last >> 4 ) < k0 + 64;
+            const uint32_t from = mine ? ( last >> 4 ) - k0 : 0u;
+            const uint32_t prefix = __shfl( before, (int)from );
+            const uint32_t mask = __shfl( hits, (int)from );
+            if ( mine ) r[q + lane] = running + prefix + __popc( mask & ( 0xFFFFu >> ( 15u - ( last & 15u ) ) ) );
+            const uint32_t answered = (uint32_t)__popcll( __ballot( mine ) );
+            q += answered;
+            if ( answered < 64 ) break;
+        }
+        running += __shfl( upTo, 63 );
+    }
 }
 }  // namespace bz2gpu

@@ -1,7 +1,9 @@
 /**
  * bz2_lines.hpp -- how a batch of line ranges of the decoded file (mi355x_bz2_reader_read_line_ranges, _line_starts) is
  * turned into GPU launches, boundary queries and gather pieces.  Host arithmetic only, no HIP: the reader calls it, and
- * tests/native/lines_cases.cpp pins every decision on the CPU.
+ * tests/native/lines_cases.cpp pins every decision on the CPU.  The inverse direction -- byte offsets to line numbers,
+ * planLineNumbers, under mi355x_bz2_reader_line_numbers and _grep -- is at the end of the file, pinned by
+ * tests/native/linenum_cases.cpp.
  *
  * Semantics (D = the decoded file, nl = the delimiter, N = the number of nl bytes in D): line k starts at s(k), s(0) = 0
  * and s(k) = 1 + the position of the k-th nl for 1 <= k <= N; line N is the unterminated tail.  The range (first, count)
@@ -236,5 +238,116 @@ resolveSegment( const LinePlan& plan, const LineSegment& segment, const uint64_t
     *src = from;
     *size = to - from;
     return true;
+}
+
+/* ------------------------------------------------------------------------------------------------ line numbers
+ * The inverse of line_starts (mi355x_bz2_reader_line_numbers): L(p) = the number of nl bytes in D[0 : min( p, size )],
+ * i.e. the 0-based line that holds byte p, and N for every p at or behind the size.  The index gives lines[b] for the
+ * block b that holds p; what is missing is the number of nl bytes in [the block's first byte, p): a rank query, answered
+ * by k_rank_byte in the decoded block.
+ *
+ *   launches  planRanges' launches for the blocks that hold a queried offset, each block once, in file order: planRanges
+ *             is called with the 1-byte ranges (p, 1), and the one piece of such a range is the launch and the position
+ *             of p in that launch's output.
+ *   queries   one per distinct {block, offset in block}, sorted by block and position; and behind the queries of every
+ *             block one at the end of its span, whose rank must be the count the index gives the block (`expected`): an
+ *             imported index that does not fit the data is found out without another kernel.
+ *   answers   per input, in caller order: L(p) = fixed, plus the rank of `query` if there is one.  No query for the
+ *             first byte of a block (lines[b]), an offset at or behind the size (N), or an empty file (0).
+ */
+struct RankQuery
+{
+    uint32_t launch{ 0 };
+    uint64_t spanOffset{ 0 }, spanSize{ 0 };   /* the block in the launch's output */
+    uint64_t position{ 0 };                    /* in the launch's output: spanOffset <= position <= spanOffset + spanSize */
+    uint64_t blockStart{ 0 };                  /* decoded offset of the block's first byte */
+    uint64_t expected{ NOT_FOUND };            /* set (end of the span): the delimiters the index gives the block */
+};
+
+struct LineNumber
+{
+    uint64_t fixed{ 0 };
+    uint32_t query{ NO_QUERY };
+};
+
+struct LineNumberPlan
+{
+    std::vector<RangeLaunch> launches;
+    std::vector<RankQuery> queries;
+    std::vector<LineNumber> answers;
+    size_t distinctBlocks{ 0 };
+};
+
+/** map, lineBytes / lineLines / nIndex, cap, packed, fileBytes: as planLines.  offsets: in caller order, any order. */
+inline LineNumberPlan
+planLineNumbers( const std::vector<std::pair<uint64_t, uint64_t> >& map, const uint64_t* lineBytes, const uint64_t* lineLines,
+                 size_t nIndex, const uint64_t* offsets, size_t n, size_t cap, bool packed, uint64_t fileBytes )
+{
+    checkLineIndex( map, lineBytes, lineLines, nIndex );
+    std::vector<uint64_t> starts, lengths;
+    dataBlocksOf( map, starts, lengths );
+    const size_t B = starts.size();
+    const uint64_t total = map.empty() ? 0 : map.back().second;
+    const uint64_t N = lineLines[B];
+
+    LineNumberPlan plan;
+    plan.answers.assign( n, {} );
+    std::vector<uint64_t> sizes( n, 0 );       /* 1: the offset needs a query */
+    std::vector<size_t> asking;
+    for ( size_t i = 0; i < n; ++i ) {
+        if ( offsets[i] >= total ) {
+            plan.answers[i].fixed = N;
+            continue;
+        }
+        const size_t b = static_cast<size_t>( std::upper_bound( starts.begin(), starts.end(), offsets[i] ) - starts.begin() ) - 1;
+        plan.answers[i].fixed = lineLines[b];
+        if ( offsets[i] == starts[b] ) continue;
+        sizes[i] = 1;
+        asking.push_back( i );
+    }
+    if ( asking.size() >= NO_QUERY / 2 ) throw std::invalid_argument( "planLineNumbers: too many offsets for one call" );
+    auto cover = planRanges( map, offsets, sizes.data(), n, cap, packed, fileBytes );
+    plan.launches = std::move( cover.launches );
+    plan.distinctBlocks = cover.distinctBlocks;
+    if ( cover.pieces.size() != asking.size() ) throw std::logic_error( "planLineNumbers: an offset without its piece" );
+
+    /* piece k belongs to asking[k] (both in caller order); the queries in file order, one per distinct offset */
+    std::vector<size_t> order( asking.size() );
+    for ( size_t k = 0; k < order.size(); ++k ) order[k] = k;
+    /* (grep hands over the search's positions, which are ascending already: then there is nothing to sort) */
+    const auto before = [&] ( size_t a, size_t b ) { return offsets[asking[a]] < offsets[asking[b]]; };
+    if ( !std::is_sorted( order.begin(), order.end(), before ) ) std::sort( order.begin(), order.end(), before );
+    size_t block = B;   /* of the queries being added */
+    const auto closeBlock = [&] () {
+        if ( block == B ) return;
+        auto end = plan.queries.back();
+        end.position = end.spanOffset + end.spanSize;
+        end.expected = lineLines[block + 1] - lineLines[block];
+        plan.queries.push_back( end );
+    };
+    for ( size_t j = 0; j < order.size(); ++j ) {
+        const size_t i = asking[order[j]];
+        if ( j > 0 && offsets[i] == offsets[asking[order[j - 1]]] ) {
+            plan.answers[i].query = plan.answers[asking[order[j - 1]]].query;
+            continue;
+        }
+        const auto& piece = cover.pieces[order[j]];
+        const size_t b = static_cast<size_t>( std::upper_bound( starts.begin(), starts.end(), offsets[i] ) - starts.begin() ) - 1;
+        if ( b != block ) {
+            closeBlock();
+            block = b;
+        }
+        plan.answers[i].query = (uint32_t)plan.queries.size();
+        plan.queries.push_back( { piece.launch, piece.src - ( offsets[i] - starts[b] ), lengths[b], piece.src, starts[b], NOT_FOUND } );
+    }
+    closeBlock();
+    return plan;
+}
+
+/** L(p) of an answer, once the ranks of the plan's queries are known. */
+inline uint64_t
+lineNumberOf( const LineNumber& answer, const uint64_t* ranks )
+{
+    return answer.fixed + ( answer.query == NO_QUERY ? 0 : ranks[answer.query] );
 }
 }  // namespace bz2gpu

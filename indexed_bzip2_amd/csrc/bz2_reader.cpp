@@ -486,6 +486,7 @@ public:
      * flight: the runs, flights and look-ahead of the sequential reader are not disturbed. */
     struct LineWork;
     struct SearchWork;
+    struct RankWork;
     struct RangesWork
     {
         const bz2gpu::RangeLaunch* launch{ nullptr };
@@ -494,6 +495,7 @@ public:
         bool dstIsDevice{ false };
         LineWork* lines{ nullptr };  /* set: a launch of the line functions, `pieces` and `dst` are not used */
         SearchWork* search{ nullptr };   /* set: a launch of a search, likewise */
+        RankWork* rank{ nullptr };       /* set: a launch of line_numbers, likewise */
         std::promise<void> done;     /* a Bz2Exception if a block or the device failed */
     };
 
@@ -547,6 +549,17 @@ public:
         uint64_t count{ 0 };                        /* out: matches inside the extent */
         std::vector<uint64_t> positions;            /* out (limit > 0): the first min( count, limit ), in the launch's output */
         uint8_t seam[2 * bz2gpu::SEARCH_PATTERN_MAX]{};   /* out: head at 0, tail at SEARCH_PATTERN_MAX */
+    };
+
+    /** What a launch of line_numbers does with its decoded blocks: mi355x_bz2_rank_byte for the plan's queries of this
+     * launch, queries [first, first + count) -- the planner lists them launch by launch --, into ranks[query], an array
+     * all launches of the call share.  Owned by the caller, who waits for the launch. */
+    struct RankWork
+    {
+        uint8_t nl{ 0 };
+        const bz2gpu::LineNumberPlan* plan{ nullptr };
+        size_t first{ 0 }, count{ 0 };
+        uint64_t* ranks{ nullptr };
     };
 
     /** Forget what the contexts hold for read_line_ranges (the buffers stay: they only grow). */
@@ -842,6 +855,34 @@ private:
         return nullptr;
     }
 
+    /** The part of line_numbers of a launch whose blocks have just been decoded into the context's output (see RankWork).
+     * The rank at the end of a block's span is the block's count: an index that says otherwise does not fit the data. */
+    [[nodiscard]] std::exception_ptr
+    runRankWork( mi355x_bz2_ctx* const ctx, RankWork& work )
+    {
+        if ( work.count == 0 ) return nullptr;
+        if ( work.count > std::numeric_limits<uint32_t>::max() ) {
+            return std::make_exception_ptr( error( MI355X_BZ2_ERR_INVALID_ARGUMENT, "line_numbers: too many offsets in one launch" ) );
+        }
+        std::vector<mi355x_bz2_rank_query> queries( work.count );
+        for ( size_t k = 0; k < work.count; ++k ) {
+            const auto& q = work.plan->queries[work.first + k];
+            queries[k] = { q.spanOffset, q.spanSize, q.position };
+        }
+        uint64_t* const ranks = work.ranks + work.first;
+        const int rc = mi355x_bz2_rank_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, ranks );
+        if ( rc != MI355X_BZ2_OK ) return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+        for ( size_t k = 0; k < work.count; ++k ) {
+            const auto& q = work.plan->queries[work.first + k];
+            if ( q.expected != bz2gpu::NOT_FOUND && ranks[k] != q.expected ) {
+                return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC,
+                    "the line index gives the block at decoded offset " + std::to_string( q.blockStart ) + " "
+                    + std::to_string( q.expected ) + " delimiters, it holds " + std::to_string( ranks[k] ) ) );
+            }
+        }
+        return nullptr;
+    }
+
     /** The search's part of a launch whose blocks have just been decoded into the context's output. */
     [[nodiscard]] std::exception_ptr
     runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
@@ -984,6 +1025,8 @@ private:
                 failure = runSearchWork( ctx, *work.search );
             } else if ( !failure && work.lines != nullptr ) {
                 failure = runLineWork( ctx, launch, *work.lines );
+            } else if ( !failure && work.rank != nullptr ) {
+                failure = runRankWork( ctx, *work.rank );
             } else if ( !failure ) {
                 rc = mi355x_bz2_gather_output( ctx, work.pieces.data(), (uint32_t)work.pieces.size(), work.dst,
                                                work.dstIsDevice ? 1 : 0 );
@@ -1450,6 +1493,89 @@ public:
         }
     }
 
+    /** L(p) for every offset given (mi355x_bz2_reader_line_numbers), the inverse of lineStarts: only blocks that hold an
+     * offset which is not their first byte are decoded, and k_rank_byte counts the delimiters in front of the offsets. */
+    void
+    lineNumbers( uint8_t nl, const uint64_t* offsets, size_t n, uint64_t* lines )
+    {
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        const auto plan = bz2gpu::planLineNumbers( m_index.snapshot(), index.bytes.data(), index.lines.data(),
+                                                   index.bytes.size(), offsets, n, m_batch, packedLaunches(),
+                                                   m_source->size() );
+        std::vector<uint64_t> ranks( plan.queries.size(), 0 );
+        std::vector<BatchScheduler::RankWork> rankWorks( plan.launches.size() );
+        for ( auto& work : rankWorks ) {
+            work.nl = nl;
+            work.plan = &plan;
+            work.ranks = ranks.data();
+        }
+        /* the queries come launch by launch */
+        for ( size_t q = 0; q < plan.queries.size(); ++q ) {
+            auto& work = rankWorks[plan.queries[q].launch];
+            if ( work.count++ == 0 ) work.first = q;
+        }
+        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
+        for ( size_t l = 0; l < works.size(); ++l ) {
+            works[l] = std::make_unique<BatchScheduler::RangesWork>();
+            works[l]->launch = &plan.launches[l];
+            works[l]->rank = &rankWorks[l];
+        }
+        runLaunches( works );
+        for ( size_t i = 0; i < n; ++i ) lines[i] = bz2gpu::lineNumberOf( plan.answers[i], ranks.data() );
+    }
+
+    /** Step 1 of grep (mi355x_bz2_reader_grep): the search for all matches, the lines of their first bytes, repeats
+     * dropped, the first maxLines of them; then -- unless only their number is wanted -- readLineRanges with one range
+     * (line, 1) per matching line, whose pieces stay held for takeLineRanges.  Matches and line ranges held by earlier
+     * calls are released.  The rank pass decodes the blocks with matches a second time, the line pass a third. */
+    void
+    grep( const uint8_t* pattern, uint32_t m, uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, bool keepOnDevice,
+          uint64_t* nLines, uint64_t* totalBytes )
+    {
+        uint64_t nMatches = 0;
+        search( pattern, m, start, end, std::numeric_limits<uint64_t>::max(), &nMatches );
+        const auto positions = std::move( *m_matches );
+        m_matches.reset();
+        dropHeldLines();
+        *nLines = 0;
+        *totalBytes = 0;
+        if ( positions.empty() ) {
+            /* no match: no line index is built or asked, nothing is decoded again; empty results are held */
+            if ( maxLines > 0 ) {
+                HeldLines held;
+                held.onDevice = keepOnDevice;
+                m_held = std::move( held );
+                m_grep = HeldGrep{};
+            }
+            return;
+        }
+        std::vector<uint64_t> numbers( positions.size() );
+        lineNumbers( nl, positions.data(), positions.size(), numbers.data() );
+        numbers.erase( std::unique( numbers.begin(), numbers.end() ), numbers.end() );
+        *totalBytes = 0;
+        if ( maxLines > 0 && numbers.size() > maxLines ) numbers.resize( (size_t)maxLines );
+        *nLines = numbers.size();
+        if ( maxLines == 0 ) return;
+        HeldGrep held;
+        held.sizes.assign( numbers.size(), 0 );
+        const std::vector<uint64_t> ones( numbers.size(), 1 );
+        readLineRanges( nl, numbers.data(), ones.data(), numbers.size(), keepOnDevice, held.sizes.data(), totalBytes );
+        held.numbers = std::move( numbers );
+        m_grep = std::move( held );
+    }
+
+    /** mi355x_bz2_reader_take_grep: the held line numbers and sizes; the bytes stay held for takeLineRanges. */
+    void
+    takeGrep( uint64_t* lineNumbers, uint64_t* byteSizes, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_grep on a closed reader" );
+        if ( !m_grep || !m_held ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_grep: no lines are held (grep with max_lines > 0 first)" );
+        const size_t n = (size_t)std::min<uint64_t>( capacity, m_grep->numbers.size() );
+        std::copy_n( m_grep->numbers.begin(), n, lineNumbers );
+        std::copy_n( m_grep->sizes.begin(), n, byteSizes );
+    }
+
     /** Step 1 of the line ranges (mi355x_bz2_reader_read_line_ranges): decode, resolve, gather into the contexts' result
      * buffers; the pieces are held for takeLineRanges. */
     void
@@ -1564,6 +1690,7 @@ public:
     joinThreads()
     {
         m_held.reset();   /* it lives in the contexts' buffers */
+        m_grep.reset();
         m_scheduler.reset();
         m_finder.reset();
     }
@@ -1588,10 +1715,16 @@ private:
         std::vector<BatchScheduler::HeldPiece> pieces;     /* front to back within every range */
     };
 
+    struct HeldGrep
+    {
+        std::vector<uint64_t> numbers, sizes;              /* per matching line; the bytes are m_held's */
+    };
+
     void
     dropHeldLines()
     {
         m_held.reset();
+        m_grep.reset();
         if ( m_scheduler ) m_scheduler->dropHeld();
     }
 
@@ -1847,6 +1980,7 @@ private:
     std::optional<LineIndex> m_lines;     /* the one line index the reader keeps, with its delimiter */
     std::optional<HeldLines> m_held;      /* between read_line_ranges and take_line_ranges */
     std::optional<std::vector<uint64_t> > m_matches;   /* between search (with a limit) and take_matches */
+    std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
 };
 }  // namespace mi355x
 
@@ -2130,6 +2264,32 @@ mi355x_bz2_reader_take_matches( mi355x_bz2_reader* r, uint64_t* positions, uint6
 {
     if ( capacity > 0 && positions == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeMatches( positions, capacity ); } );
+}
+
+int
+mi355x_bz2_reader_line_numbers( mi355x_bz2_reader* r, uint8_t nl, const uint64_t* offsets, uint64_t n, uint64_t* lines )
+{
+    if ( n > 0 && ( offsets == nullptr || lines == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.lineNumbers( nl, offsets, (size_t)n, lines ); } );
+}
+
+int
+mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint8_t nl, uint64_t start,
+                        uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+{
+    if ( pattern == nullptr || nLines == nullptr || totalBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    *totalBytes = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.grep( pattern, patternSize, nl, start, end, maxLines, keepOnDevice != 0, nLines, totalBytes );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* lineNumbers, uint64_t* byteSizes, uint64_t capacity )
+{
+    if ( capacity > 0 && ( lineNumbers == nullptr || byteSizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeGrep( lineNumbers, byteSizes, capacity ); } );
 }
 
 int

@@ -39,7 +39,7 @@ struct Options
     bool toStdout{ false }, decompress{ false }, force{ false }, keep{ false }, test{ false }, help{ false };
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
-    bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false };
+    bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false }, grep{ false }, lineNumber{ false };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -83,7 +83,13 @@ printHelp()
         "                                decompressed to the host), print the number and exit.\n"
         "      --count-matches arg       Count the occurrences of the given string (1 to 256 bytes; occurrences that\n"
         "                                overlap each other all count) in the decoded data on the GPU, print the\n"
-        "                                number and exit.\n\n"
+        "                                number and exit.\n"
+        "      --grep arg                Print the lines of the decoded data that contain the given string (1 to 256\n"
+        "                                bytes, taken literally as by grep -F) in file order, each once, and exit.\n"
+        "                                Matches and lines are found on the GPU; only the matching lines are copied\n"
+        "                                to the host. The exit status is 0 whether or not a line matched: 1 means\n"
+        "                                error here.\n"
+        "      --line-number             With --grep: prefix each line with its 1-based line number and ':'.\n\n"
         " Advanced options:\n"
         "      --buffer-size arg         Controls the output buffer size. By default, the decoded data is written in\n"
         "                                one pass per block. (default: 0)\n\n"
@@ -97,7 +103,9 @@ printHelp()
         "Count the lines of a compressed file:\n"
         "  ibzip2-mi355x --count-lines file.bz2\n\n"
         "Count the occurrences of a string in a compressed file:\n"
-        "  ibzip2-mi355x --count-matches ERROR file.bz2\n";
+        "  ibzip2-mi355x --count-matches ERROR file.bz2\n\n"
+        "Print the lines of a compressed file that contain a string, with their numbers:\n"
+        "  ibzip2-mi355x --grep ERROR --line-number file.bz2\n";
 }
 
 bool
@@ -184,6 +192,8 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "output" ) { if ( !need( o.output ) ) return 1; o.hasOutput = true; }
             else if ( name == "count-lines" ) o.countLines = true;
             else if ( name == "count-matches" ) { if ( !need( o.pattern ) ) return 1; o.countMatches = true; }
+            else if ( name == "grep" ) { if ( !need( o.pattern ) ) return 1; o.grep = true; }
+            else if ( name == "line-number" ) o.lineNumber = true;
             else if ( name == "list-compressed-offsets" ) {
                 o.listCompressed = true;
                 if ( hasInline ) o.listCompressedPath = inlineValue; else optionalValue( i, o.listCompressedPath );
@@ -372,6 +382,14 @@ main( int argc, char** argv )
         printHelp();
         return 0;
     }
+    if ( o.grep && o.countMatches ) {
+        std::cerr << "Options '--grep' and '--count-matches' cannot be combined\n";
+        return 1;
+    }
+    if ( o.lineNumber && !o.grep ) {
+        std::cerr << "Option '--line-number' needs '--grep'\n";
+        return 1;
+    }
     if ( o.version ) {
         std::cout << "ibzip2-mi355x, CLI to the MI355X bzip2 block decoder (C ABI version " << mi355x_bz2_abi_version()
                   << "), option-compatible with ibzip2 of indexed-bzip2 1.7.0.\n";
@@ -448,6 +466,52 @@ main( int argc, char** argv )
         mi355x_bz2_reader_close( reader );
         std::cout << count << "\n";
         return 0;
+    }
+
+    /* likewise: the lines that hold a match (bzgrep -F), from the reader's grep; 0 also when no line matched */
+    if ( o.grep ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t nLines = 0, total = 0;
+        rc = mi355x_bz2_reader_grep( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(), '\n',
+                                     0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0, &nLines, &total );
+        std::vector<uint64_t> numbers( nLines ), sizes( nLines );
+        std::vector<char> bytes( total );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_line_ranges( reader, bytes.data(), 0 );
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Search failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        if ( !o.lineNumber ) {
+            std::cout.write( bytes.data(), (std::streamsize)bytes.size() );
+        } else {
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < nLines; at += sizes[i], ++i ) {
+                std::cout << numbers[i] + 1 << ':';
+                std::cout.write( bytes.data() + at, (std::streamsize)sizes[i] );
+            }
+        }
+        std::cout.flush();
+        return std::cout.good() ? 0 : 1;
     }
 
     /* output file name rules, ibzip2.cpp:316-331 */

@@ -374,6 +374,113 @@ class _IndexedBzip2FileParallel:
         first = self.find_all(pattern, start, end, 1)
         return int(first[0]) if len(first) else -1
 
+    # -- grep: the lines that hold a match.  A match belongs to the line of its first byte (the pattern may contain the
+    # delimiter); start and end bound the matches, not the lines, which always come whole
+    def line_numbers(self, offsets, newline=b"\n"):
+        """The 0-based number of the line that holds each decoded byte offset (numpy uint64): the number of `newline`
+        bytes in front of it, the inverse of line_starts.  Offsets at or beyond the size give the number of delimiters
+        in the file.  Only the blocks that hold one of the offsets are decoded, the delimiters are counted on the GPU
+        and only the numbers come back.  Builds the line index first if the reader does not hold one for `newline`.
+        Positionless."""
+        import numpy as np
+        self._require()
+        nl = self._newline(newline)
+        if isinstance(offsets, np.ndarray) and offsets.dtype == np.uint64:
+            values = np.ascontiguousarray(offsets).ravel()
+        else:
+            values, _ = self._u64(offsets, "offsets")
+            values = np.array(values, dtype=np.uint64)
+        out = np.empty(len(values), dtype=np.uint64)
+        as_u64p = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if len(a) else None
+        self._check(N.lib().mi355x_bz2_reader_line_numbers(self._h, nl, as_u64p(values), len(values), as_u64p(out)))
+        return out
+
+    def _grep_arguments(self, pattern, start, end, newline):
+        pattern = self._pattern(pattern)
+        nl = self._newline(newline)
+        start, end = int(start), 2**64 - 1 if end is None else int(end)
+        if start < 0 or end < 0:
+            raise ValueError("start and end must not be negative")
+        return pattern, nl, start, end
+
+    def _grep(self, pattern, start, end, limit, newline, on_device):
+        """Step 1 (mi355x_bz2_reader_grep) and the numbers and sizes of the held lines (_take_grep): (numbers, sizes,
+        total bytes); with limit 0 nothing is held and the number of matching lines comes back instead."""
+        import numpy as np
+        self._require()
+        pattern, nl, start, end = self._grep_arguments(pattern, start, end, newline)
+        n, total = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_grep(self._h, pattern, len(pattern), nl, min(start, 2**64 - 1),
+                                                   min(end, 2**64 - 1), limit, 1 if on_device else 0, ctypes.byref(n),
+                                                   ctypes.byref(total)))
+        if limit == 0:
+            return n.value
+        numbers = (ctypes.c_uint64 * max(1, n.value))()
+        sizes = (ctypes.c_uint64 * max(1, n.value))()
+        self._check(N.lib().mi355x_bz2_reader_take_grep(self._h, numbers, sizes, n.value))
+        return (np.frombuffer(numbers, dtype=np.uint64, count=n.value).copy(), [sizes[i] for i in range(n.value)],
+                total.value)
+
+    @staticmethod
+    def _line_limit(limit):
+        if limit is not None and int(limit) < 0:
+            raise ValueError("limit must not be negative")
+        return 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1)
+
+    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n"):
+        """The number of distinct lines that hold an occurrence of `pattern` in data[start:end] (`grep -c -F`)."""
+        return self._grep(pattern, start, end, 0, newline, False)
+
+    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+        """The lines that hold an occurrence of `pattern` in data[start:end] (`grep -n -F`) -> (numbers, lines): the
+        0-based line numbers (numpy uint64, strictly ascending) and one bytes object per line, whole and with its
+        delimiter (the unterminated tail as it is), at most `limit` lines (None: all).  An occurrence belongs to the
+        line of its first byte; start and end bound the occurrences, not the lines.  Three passes on the GPU: the
+        search, the line numbers of the matches (k_rank_byte), and the lines themselves; only numbers, sizes and the
+        lines' bytes leave it.  Releases matches and line ranges held by earlier calls.  Positionless."""
+        import numpy as np
+        limit = self._line_limit(limit)
+        if limit == 0:                                 # nothing is asked for: the arguments are checked, nothing runs
+            self._require()
+            self._grep_arguments(pattern, start, end, newline)
+            return np.empty(0, dtype=np.uint64), []
+        numbers, sizes, total = self._grep(pattern, start, end, limit, newline, False)
+        out = bytearray(total)
+        dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
+        self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
+        del dst
+        lines, at = [], 0
+        for size in sizes:
+            lines.append(bytes(out[at:at + size]))
+            at += size
+        return numbers, lines
+
+    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+        """grep into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), data and
+        offsets laid out as read_line_ranges_to_tensor: line i is ``data[offsets[i]:offsets[i + 1]]``.  The lines' bytes
+        never pass through the host."""
+        import numpy as np
+        import torch
+        limit = self._line_limit(limit)
+        self._require()
+        self._grep_arguments(pattern, start, end, newline)
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        if limit == 0:
+            numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
+        else:
+            numbers, sizes, total = self._grep(pattern, start, end, limit, newline, True)
+        data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+        if total:
+            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(data.device).synchronize()
+        if limit != 0:
+            self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, ctypes.c_void_p(data.data_ptr()) if total else None, 1))
+        bounds = [0]
+        for size in sizes:
+            bounds.append(bounds[-1] + size)
+        return numbers, data, torch.tensor(bounds, dtype=torch.int64)
+
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
         like the reference, whose serial reader checks and whose parallel reader does not)."""
@@ -492,6 +599,22 @@ class IndexedBzip2File(io.BufferedReader):
     def find(self, pattern, start=0, end=None):
         """See _IndexedBzip2FileParallel.find."""
         return self._open_reader().find(pattern, start, end)
+
+    def line_numbers(self, offsets, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.line_numbers."""
+        return self._open_reader().line_numbers(offsets, newline)
+
+    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.grep."""
+        return self._open_reader().grep(pattern, start, end, limit, newline)
+
+    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.count_matching_lines."""
+        return self._open_reader().count_matching_lines(pattern, start, end, newline)
+
+    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.grep_to_tensor."""
+        return self._open_reader().grep_to_tensor(pattern, start, end, limit, newline)
 
 
 builtins_open = builtins.open
