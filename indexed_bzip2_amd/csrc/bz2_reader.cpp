@@ -25,6 +25,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <future>
 #include <iostream>
 #include <list>
@@ -33,6 +34,7 @@
 #include <queue>
 #include <sstream>
 #include <string>
+#include <variant>
 
 #include <hip/hip_runtime.h>
 
@@ -69,6 +71,13 @@ error( int status, const std::string& detail = {} )
 fail( int status, const std::string& detail = {} )
 {
     throw error( status, detail );
+}
+
+/** A failure of a call on a decoder context becomes an exception with the context's last error. */
+static void
+checkDevice( mi355x_bz2_ctx* ctx, int rc )
+{
+    if ( rc != MI355X_BZ2_OK ) fail( rc, mi355x_bz2_last_error( ctx ) );
 }
 
 /* ------------------------------------------------------------------------------------------------ compressed source */
@@ -318,7 +327,7 @@ public:
         }
     }
 
-    /** A decoder context over the file: the first one starts the copy to the GPU (in the background, in pieces: the first
+    /** A decoder context over the file: the first one starts the copy to the GPU (in the background, in parts: the first
      * blocks decode while the rest of a large file is still on its way), the others share it. */
     int
     createContext( int device, mi355x_bz2_ctx* shareFrom, mi355x_bz2_ctx*& out, std::string& detail ) const
@@ -481,103 +490,27 @@ public:
         return run;
     }
 
-    /** One launch of read_ranges: blocks that need not be consecutive, decoded once and gathered straight into the
-     * caller's destination.  It goes ahead of everything queued (somebody waits for it), publishes no run and is not a
-     * flight: the runs, flights and look-ahead of the sequential reader are not disturbed. */
-    struct LineWork;
-    struct SearchWork;
-    struct RankWork;
-    struct RangesWork
+    /** Blocks that need not be consecutive, decoded once by one launch and left in the context's output for the job's
+     * afterDecode, which runs on the worker's thread behind the decode and the per-block check and reports a failure by
+     * throwing.  What it does there is the submitter's business (see "decode jobs" below).  A job goes ahead of
+     * everything queued (somebody waits for it), publishes no run and is not a flight: the runs, flights and look-ahead
+     * of the sequential reader are not disturbed. */
+    struct Job
     {
+        using AfterDecode = std::function<void( mi355x_bz2_ctx*, const bz2gpu::RangeLaunch& )>;
+
         const bz2gpu::RangeLaunch* launch{ nullptr };
-        std::vector<mi355x_bz2_gather_piece> pieces;
-        void* dst{ nullptr };
-        bool dstIsDevice{ false };
-        LineWork* lines{ nullptr };  /* set: a launch of the line functions, `pieces` and `dst` are not used */
-        SearchWork* search{ nullptr };   /* set: a launch of a search, likewise */
-        RankWork* rank{ nullptr };       /* set: a launch of line_numbers, likewise */
-        std::promise<void> done;     /* a Bz2Exception if a block or the device failed */
+        const std::atomic<bool>* cancel{ nullptr };   /* set when the job is taken: it is neither decoded nor counted */
+        AfterDecode afterDecode;
+        std::promise<bool> done;     /* false: cancelled; an exception if a block, the device or afterDecode failed */
     };
 
-    /** A piece of a line range, packed into the result buffer of the context that decoded it (step 1 of
-     * read_line_ranges), where it stays until step 2 puts it in place. */
-    struct HeldPiece
+    [[nodiscard]] std::future<bool>
+    submit( std::unique_ptr<Job> job )
     {
-        mi355x_bz2_ctx* ctx{ nullptr };
-        uint32_t range{ 0 };
-        uint64_t offset{ 0 }, size{ 0 };
-    };
-
-    /** What a launch of the line functions does with its decoded blocks instead of gathering into a destination; owned
-     * by the caller, who waits for the launch.  In this order: count `nl` in every block (the line index), find the
-     * plan's boundary queries of this launch (positions[query], an array all launches of the call share), resolve the
-     * launch's segments with them and pack the pieces behind what the context already holds. */
-    struct LineWork
-    {
-        uint8_t nl{ 0 };
-        bool countBlocks{ false };
-        std::vector<uint64_t> blockCounts;          /* out: per block of the launch */
-        const bz2gpu::LinePlan* plan{ nullptr };
-        std::vector<uint32_t> queries, segments;    /* of this launch: indexes into the plan's lists */
-        uint64_t* positions{ nullptr };
-        std::vector<HeldPiece> held;                /* out: one per segment that has bytes */
-    };
-
-    /** What the launches of one search share: the pattern, and -- with a limit -- how many matches the launches at the
-     * front of the range that are through have found.  Once these reach the limit, no further launch is started. */
-    struct SearchCall
-    {
-        const uint8_t* pattern{ nullptr };
-        uint32_t m{ 0 };
-        uint64_t limit{ 0 };                        /* 0: count only */
-        std::mutex mutex;
-        std::vector<uint8_t> finished;              /* per launch */
-        std::vector<uint64_t> counts;
-        size_t through{ 0 };                        /* launches [0, through) are finished ... */
-        uint64_t found{ 0 };                        /* ... and have found this many */
-        std::atomic<bool> stop{ false };
-    };
-
-    /** What a launch of a search does with its decoded blocks: mi355x::searchOutput over its extent.  Owned by the
-     * caller, who waits for the launch. */
-    struct SearchWork
-    {
-        SearchCall* call{ nullptr };
-        uint32_t index{ 0 };
-        bz2gpu::SearchExtent extent;
-        bool skipped{ false };                      /* out: not started, the limit had been reached */
-        uint64_t count{ 0 };                        /* out: matches inside the extent */
-        std::vector<uint64_t> positions;            /* out (limit > 0): the first min( count, limit ), in the launch's output */
-        uint8_t seam[2 * bz2gpu::SEARCH_PATTERN_MAX]{};   /* out: head at 0, tail at SEARCH_PATTERN_MAX */
-    };
-
-    /** What a launch of line_numbers does with its decoded blocks: mi355x_bz2_rank_byte for the plan's queries of this
-     * launch, queries [first, first + count) -- the planner lists them launch by launch --, into ranks[query], an array
-     * all launches of the call share.  Owned by the caller, who waits for the launch. */
-    struct RankWork
-    {
-        uint8_t nl{ 0 };
-        const bz2gpu::LineNumberPlan* plan{ nullptr };
-        size_t first{ 0 }, count{ 0 };
-        uint64_t* ranks{ nullptr };
-    };
-
-    /** Forget what the contexts hold for read_line_ranges (the buffers stay: they only grow). */
-    void
-    dropHeld()
-    {
+        auto result = job->done.get_future();
         const std::scoped_lock lock( m_queueMutex );
-        m_heldBytes.clear();
-    }
-
-    [[nodiscard]] std::future<void>
-    launchRanges( std::unique_ptr<RangesWork> ranges )
-    {
-        auto work = std::make_unique<Launch>();
-        auto result = ranges->done.get_future();
-        work->ranges = std::move( ranges );
-        const std::scoped_lock lock( m_queueMutex );
-        m_queue.push_front( std::move( work ) );
+        m_queue.emplace_front( std::move( job ) );
         m_queueChanged.notify_all();
         return result;
     }
@@ -603,8 +536,9 @@ private:
         bool lookAhead{ false };
         std::promise<RunPtr> promise;
         std::shared_ptr<std::atomic<bool> > done;
-        std::unique_ptr<RangesWork> ranges;    /* set: a read_ranges launch, none of the fields above are used */
     };
+
+    using Queued = std::variant<std::unique_ptr<Launch>, std::unique_ptr<Job> >;
 
     struct Flight
     {
@@ -691,7 +625,7 @@ private:
          * blocked on a run when a context becomes free */
         const size_t limit = m_batch * ( m_contexts + ( m_batch >= 64 ? 1 : 0 ) );
         if ( m_inFlightBlocks >= limit ) return;
-        /* While a launch is held back for want of blocks (rule at the end) a sequential reader gains about one candidate
+        /* While a launch is kept back for want of blocks (rule at the end) a sequential reader gains about one candidate
          * per call: looking again on every call would cost O(batch^2) per batch. */
         if ( !somebodyWaits && ( m_holdOff > 0 ) && !m_flights.empty() ) {
             --m_holdOff;
@@ -787,122 +721,6 @@ private:
         return result;
     }
 
-    /** The line functions' part of a launch whose blocks have just been decoded into the context's output (see
-     * LineWork).  Returns the failure, if any. */
-    [[nodiscard]] std::exception_ptr
-    runLineWork( mi355x_bz2_ctx* const ctx, const bz2gpu::RangeLaunch& launch, LineWork& work )
-    {
-        const auto deviceFailure = [ctx] ( int rc ) {
-            return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
-        };
-        if ( work.countBlocks ) {
-            std::vector<mi355x_bz2_byte_span> spans( launch.bits.size() );
-            for ( size_t k = 0; k < spans.size(); ++k ) spans[k] = { launch.outOffsets[k], launch.sizes[k] };
-            work.blockCounts.assign( spans.size(), 0 );
-            const int rc = mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, work.blockCounts.data() );
-            if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
-        }
-        if ( !work.queries.empty() ) {
-            std::vector<mi355x_bz2_byte_query> queries( work.queries.size() );
-            std::vector<uint64_t> found( queries.size() );
-            for ( size_t k = 0; k < queries.size(); ++k ) {
-                const auto& q = work.plan->queries[work.queries[k]];
-                queries[k] = { q.spanOffset, q.spanSize, q.rank };
-            }
-            /* an index that gives a queried block another count than the block has would cut lines in the wrong places */
-            std::vector<mi355x_bz2_byte_span> spans( queries.size() );
-            std::vector<uint64_t> counted( queries.size() );
-            for ( size_t k = 0; k < queries.size(); ++k ) spans[k] = { queries[k].offset, queries[k].size };
-            int rc = mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, counted.data() );
-            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_find_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, found.data() );
-            if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
-            for ( size_t k = 0; k < queries.size(); ++k ) {
-                const auto& q = work.plan->queries[work.queries[k]];
-                work.positions[work.queries[k]] = found[k];
-                if ( found[k] == bz2gpu::NOT_FOUND || counted[k] != q.blockCount ) {
-                    return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC,
-                        "the line index gives the block at decoded offset " + std::to_string( q.blockStart ) + " "
-                        + std::to_string( q.blockCount ) + " delimiters, it holds " + std::to_string( counted[k] ) ) );
-                }
-            }
-        }
-        if ( work.segments.empty() ) return nullptr;
-        std::vector<mi355x_bz2_gather_piece> pieces;
-        uint64_t base = 0;
-        {
-            const std::scoped_lock lock( m_queueMutex );
-            base = m_heldBytes[ctx];
-        }
-        uint64_t at = base;
-        for ( const auto index : work.segments ) {
-            const auto& segment = work.plan->segments[index];
-            uint64_t src = 0, size = 0;
-            if ( !bz2gpu::resolveSegment( *work.plan, segment, work.positions, &src, &size ) ) {
-                return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC, "the line index contradicts the decoded data" ) );
-            }
-            if ( size == 0 ) continue;
-            pieces.push_back( { src, at, size } );
-            work.held.push_back( { ctx, segment.range, at, size } );
-            at += size;
-        }
-        if ( at == base ) return nullptr;
-        uint8_t* held = nullptr;
-        int rc = resultBuffer( ctx, at, base, &held );
-        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_gather_output( ctx, pieces.data(), (uint32_t)pieces.size(), held, 1 );
-        if ( rc != MI355X_BZ2_OK ) return deviceFailure( rc );
-        const std::scoped_lock lock( m_queueMutex );
-        m_heldBytes[ctx] = at;
-        return nullptr;
-    }
-
-    /** The part of line_numbers of a launch whose blocks have just been decoded into the context's output (see RankWork).
-     * The rank at the end of a block's span is the block's count: an index that says otherwise does not fit the data. */
-    [[nodiscard]] std::exception_ptr
-    runRankWork( mi355x_bz2_ctx* const ctx, RankWork& work )
-    {
-        if ( work.count == 0 ) return nullptr;
-        if ( work.count > std::numeric_limits<uint32_t>::max() ) {
-            return std::make_exception_ptr( error( MI355X_BZ2_ERR_INVALID_ARGUMENT, "line_numbers: too many offsets in one launch" ) );
-        }
-        std::vector<mi355x_bz2_rank_query> queries( work.count );
-        for ( size_t k = 0; k < work.count; ++k ) {
-            const auto& q = work.plan->queries[work.first + k];
-            queries[k] = { q.spanOffset, q.spanSize, q.position };
-        }
-        uint64_t* const ranks = work.ranks + work.first;
-        const int rc = mi355x_bz2_rank_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, ranks );
-        if ( rc != MI355X_BZ2_OK ) return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
-        for ( size_t k = 0; k < work.count; ++k ) {
-            const auto& q = work.plan->queries[work.first + k];
-            if ( q.expected != bz2gpu::NOT_FOUND && ranks[k] != q.expected ) {
-                return std::make_exception_ptr( error( MI355X_BZ2_ERR_LOGIC,
-                    "the line index gives the block at decoded offset " + std::to_string( q.blockStart ) + " "
-                    + std::to_string( q.expected ) + " delimiters, it holds " + std::to_string( ranks[k] ) ) );
-            }
-        }
-        return nullptr;
-    }
-
-    /** The search's part of a launch whose blocks have just been decoded into the context's output. */
-    [[nodiscard]] std::exception_ptr
-    runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
-    {
-        auto& call = *work.call;
-        const int rc = searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern, call.m, call.limit,
-                                     call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam );
-        if ( rc != MI355X_BZ2_OK ) return std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
-        if ( call.limit > 0 ) {
-            const std::scoped_lock lock( call.mutex );
-            call.finished[work.index] = 1;
-            call.counts[work.index] = work.count;
-            while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
-                call.found += call.counts[call.through++];
-            }
-            if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
-        }
-        return nullptr;
-    }
-
     /** One submission thread per decoder context: takes a launch, decodes the batch, copies it to a page-locked buffer,
      * publishes the run.  Replaces the thread pool of per-block tasks (BlockFetcher.hpp:620-642).
      * The copy of a batch runs in the background while the context's next batch is launched (the context writes to a
@@ -964,21 +782,19 @@ private:
 
         std::optional<Step> copying;    /* decoded, on its way to the host */
 
-        /* A read_ranges launch.  Ordering against the run of this context that may still be on its way to the host
-         * (`copying`): that copy reads the output buffer of the context's previous batch, on the context's copy stream.
+        /* A job.  Ordering against the run of this context that may still be on its way to the host (`copying`): that
+         * copy reads the output buffer of the context's previous batch, on the context's copy stream.
          * decode_batch_begin sees the copy and puts this batch into the context's other output buffer; while this batch
          * decodes, the copy is waited for and its run published; decode_batch_end then leaves this batch's buffer as the
-         * context's output, which k_gather reads on the context's stream, and mi355x_bz2_gather_output returns only when
-         * the bytes are in the caller's destination.  Nothing reads this buffer afterwards, so the context's next batch
-         * may write into it at once. */
-        const auto runRanges = [&] ( RangesWork& work ) {
-            if ( work.search != nullptr && work.search->call->stop.load( std::memory_order_acquire ) ) {
-                work.search->skipped = true;     /* the launches in front of it have found what was asked for */
-                work.done.set_value();
+         * context's output, which afterDecode reads with calls that return only when their results are where they
+         * belong.  Nothing reads this buffer afterwards, so the context's next batch may write into it at once. */
+        const auto runJob = [&] ( Job& job ) {
+            if ( job.cancel != nullptr && job.cancel->load( std::memory_order_acquire ) ) {
+                job.done.set_value( false );
                 return;
             }
             const auto t0 = std::chrono::steady_clock::now();
-            const auto& launch = *work.launch;
+            const auto& launch = *job.launch;
             const auto n = (uint32_t)launch.bits.size();
             std::vector<mi355x_bz2_block_result> results( n );
             std::shared_ptr<const uint8_t> staging;   /* bounded residency: the packed windows, page-locked */
@@ -1009,28 +825,19 @@ private:
             uint64_t total = 0;
             if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_decode_batch_end( ctx, results.data(), &total );
             std::exception_ptr failure;
-            if ( rc != MI355X_BZ2_OK ) {
-                failure = std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
-            }
-            for ( uint32_t k = 0; !failure && k < n; ++k ) {
-                const auto& r = results[k];
-                if ( r.status != MI355X_BZ2_OK ) {
-                    failure = std::make_exception_ptr( error( r.status, "block at bit offset " + std::to_string( launch.bits[k] ) ) );
-                } else if ( r.decoded_size != launch.sizes[k] || r.data_offset != launch.outOffsets[k] ) {
-                    failure = std::make_exception_ptr(
-                        error( MI355X_BZ2_ERR_LOGIC, "the block index promises more bytes than the block decodes to" ) );
+            try {
+                checkDevice( ctx, rc );
+                for ( uint32_t k = 0; k < n; ++k ) {
+                    const auto& r = results[k];
+                    if ( r.status != MI355X_BZ2_OK ) {
+                        fail( r.status, "block at bit offset " + std::to_string( launch.bits[k] ) );
+                    } else if ( r.decoded_size != launch.sizes[k] || r.data_offset != launch.outOffsets[k] ) {
+                        fail( MI355X_BZ2_ERR_LOGIC, "the block index promises more bytes than the block decodes to" );
+                    }
                 }
-            }
-            if ( !failure && work.search != nullptr ) {
-                failure = runSearchWork( ctx, *work.search );
-            } else if ( !failure && work.lines != nullptr ) {
-                failure = runLineWork( ctx, launch, *work.lines );
-            } else if ( !failure && work.rank != nullptr ) {
-                failure = runRankWork( ctx, *work.rank );
-            } else if ( !failure ) {
-                rc = mi355x_bz2_gather_output( ctx, work.pieces.data(), (uint32_t)work.pieces.size(), work.dst,
-                                               work.dstIsDevice ? 1 : 0 );
-                if ( rc != MI355X_BZ2_OK ) failure = std::make_exception_ptr( error( rc, mi355x_bz2_last_error( ctx ) ) );
+                job.afterDecode( ctx, launch );
+            } catch ( ... ) {
+                failure = std::current_exception();
             }
             staging.reset();
             {
@@ -1040,14 +847,14 @@ private:
                 m_decodeSeconds += std::chrono::duration<double>( std::chrono::steady_clock::now() - t0 ).count();
             }
             if ( failure ) {
-                work.done.set_exception( failure );
+                job.done.set_exception( failure );
             } else {
-                work.done.set_value();
+                job.done.set_value( true );
             }
         };
 
         while ( true ) {
-            Step step;
+            Queued next;
             {
                 std::unique_lock lock( m_queueMutex );
                 if ( copying && m_queue.empty() && !m_stop ) {
@@ -1061,13 +868,15 @@ private:
                 if ( m_queue.empty() ) {
                     break;   /* m_stop */
                 }
-                step.work = std::move( m_queue.front() );
+                next = std::move( m_queue.front() );
                 m_queue.pop_front();
             }
-            if ( step.work->ranges ) {
-                runRanges( *step.work->ranges );
+            if ( const auto* const job = std::get_if<std::unique_ptr<Job> >( &next ) ) {
+                runJob( **job );
                 continue;
             }
+            Step step;
+            step.work = std::move( std::get<std::unique_ptr<Launch> >( next ) );
             step.t0 = std::chrono::steady_clock::now();
             const auto n = (uint32_t)step.work->offsets.size();
             step.results.resize( n );
@@ -1152,18 +961,200 @@ private:
     std::thread m_scanner;       /* see scanOnDevice */
     mutable std::mutex m_queueMutex;
     std::condition_variable m_queueChanged;
-    std::deque<std::unique_ptr<Launch> > m_queue;
+    std::deque<Queued> m_queue;
     bool m_stop{ false };
     const bool m_trace{ std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr };
     const std::chrono::steady_clock::time_point m_created{ std::chrono::steady_clock::now() };
     std::string m_workerError;
-    std::map<mi355x_bz2_ctx*, uint64_t> m_heldBytes;   /* of each context's result buffer: held for read_line_ranges */
     uint64_t m_batches{ 0 };
     uint64_t m_blocksDecoded{ 0 };
     double m_decodeSeconds{ 0 };
 
     mi355x_bz2_reader_stats m_stats{};
 };
+
+/* ------------------------------------------------------------------------------------------------ decode jobs */
+/* What the reader's positionless calls do with a launch's blocks once they lie decoded in the context's output: the
+ * afterDecode of BatchScheduler::Job.  Each of these runs on the worker thread of the context it is given, reports a
+ * failure by throwing, and reads and writes memory of the call that submitted it (StreamReader::runJobs waits). */
+
+/** read_ranges: the launch's pieces, straight into the caller's destination. */
+static void
+gatherPieces( mi355x_bz2_ctx* const ctx, const std::vector<mi355x_bz2_gather_piece>& pieces, void* dst, bool dstIsDevice )
+{
+    checkDevice( ctx, mi355x_bz2_gather_output( ctx, pieces.data(), (uint32_t)pieces.size(), dst, dstIsDevice ? 1 : 0 ) );
+}
+
+/** A piece of a line range, packed into the result buffer of the context that decoded it (step 1 of
+ * read_line_ranges), where it stays until step 2 puts it in place. */
+struct HeldPiece
+{
+    mi355x_bz2_ctx* ctx{ nullptr };
+    uint32_t range{ 0 };
+    uint64_t offset{ 0 }, size{ 0 };
+};
+
+/** How many bytes of each context's result buffer are held for read_line_ranges.  The launches of a call run on
+ * several contexts at once, each on its context's thread: every access under the mutex. */
+struct HeldBytes
+{
+    std::mutex mutex;
+    std::map<mi355x_bz2_ctx*, uint64_t> of;
+};
+
+[[noreturn]] static void
+failLyingLineIndex( uint64_t blockStart, uint64_t promised, uint64_t counted )
+{
+    fail( MI355X_BZ2_ERR_LOGIC, "the line index gives the block at decoded offset " + std::to_string( blockStart ) + " "
+                                + std::to_string( promised ) + " delimiters, it holds " + std::to_string( counted ) );
+}
+
+/** What a launch of the line functions does with its decoded blocks, in this order: count `nl` in every block (the
+ * line index), find the plan's boundary queries of this launch (positions[query], an array all launches of the call
+ * share), resolve the launch's segments with them and pack the pieces behind what the context already holds. */
+struct LineWork
+{
+    uint8_t nl{ 0 };
+    bool countBlocks{ false };
+    std::vector<uint64_t> blockCounts;          /* out: per block of the launch */
+    const bz2gpu::LinePlan* plan{ nullptr };
+    std::vector<uint32_t> queries, segments;    /* of this launch: indexes into the plan's lists */
+    uint64_t* positions{ nullptr };
+    std::vector<HeldPiece> held;                /* out: one per segment that has bytes */
+};
+
+static void
+runLineWork( mi355x_bz2_ctx* const ctx, const bz2gpu::RangeLaunch& launch, LineWork& work, HeldBytes& heldBytes )
+{
+    if ( work.countBlocks ) {
+        std::vector<mi355x_bz2_byte_span> spans( launch.bits.size() );
+        for ( size_t k = 0; k < spans.size(); ++k ) spans[k] = { launch.outOffsets[k], launch.sizes[k] };
+        work.blockCounts.assign( spans.size(), 0 );
+        checkDevice( ctx, mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, work.blockCounts.data() ) );
+    }
+    if ( !work.queries.empty() ) {
+        std::vector<mi355x_bz2_byte_query> queries( work.queries.size() );
+        std::vector<uint64_t> found( queries.size() );
+        for ( size_t k = 0; k < queries.size(); ++k ) {
+            const auto& q = work.plan->queries[work.queries[k]];
+            queries[k] = { q.spanOffset, q.spanSize, q.rank };
+        }
+        /* an index that gives a queried block another count than the block has would cut lines in the wrong places */
+        std::vector<mi355x_bz2_byte_span> spans( queries.size() );
+        std::vector<uint64_t> counted( queries.size() );
+        for ( size_t k = 0; k < queries.size(); ++k ) spans[k] = { queries[k].offset, queries[k].size };
+        checkDevice( ctx, mi355x_bz2_count_byte( ctx, spans.data(), (uint32_t)spans.size(), work.nl, counted.data() ) );
+        checkDevice( ctx, mi355x_bz2_find_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, found.data() ) );
+        for ( size_t k = 0; k < queries.size(); ++k ) {
+            const auto& q = work.plan->queries[work.queries[k]];
+            work.positions[work.queries[k]] = found[k];
+            if ( found[k] == bz2gpu::NOT_FOUND || counted[k] != q.blockCount ) {
+                failLyingLineIndex( q.blockStart, q.blockCount, counted[k] );
+            }
+        }
+    }
+    if ( work.segments.empty() ) return;
+    std::vector<mi355x_bz2_gather_piece> pieces;
+    uint64_t base = 0;
+    {
+        const std::scoped_lock lock( heldBytes.mutex );
+        base = heldBytes.of[ctx];
+    }
+    uint64_t at = base;
+    for ( const auto index : work.segments ) {
+        const auto& segment = work.plan->segments[index];
+        uint64_t src = 0, size = 0;
+        if ( !bz2gpu::resolveSegment( *work.plan, segment, work.positions, &src, &size ) ) {
+            fail( MI355X_BZ2_ERR_LOGIC, "the line index contradicts the decoded data" );
+        }
+        if ( size == 0 ) continue;
+        pieces.push_back( { src, at, size } );
+        work.held.push_back( { ctx, segment.range, at, size } );
+        at += size;
+    }
+    if ( at == base ) return;
+    uint8_t* held = nullptr;
+    checkDevice( ctx, resultBuffer( ctx, at, base, &held ) );
+    checkDevice( ctx, mi355x_bz2_gather_output( ctx, pieces.data(), (uint32_t)pieces.size(), held, 1 ) );
+    const std::scoped_lock lock( heldBytes.mutex );
+    heldBytes.of[ctx] = at;
+}
+
+/** What a launch of line_numbers does with its decoded blocks: mi355x_bz2_rank_byte for the plan's queries of this
+ * launch, queries [first, first + count) -- the planner lists them launch by launch --, into ranks[query], an array
+ * all launches of the call share.  The rank at the end of a block's span is the block's count: an index that says
+ * otherwise does not fit the data. */
+struct RankWork
+{
+    uint8_t nl{ 0 };
+    const bz2gpu::LineNumberPlan* plan{ nullptr };
+    size_t first{ 0 }, count{ 0 };
+    uint64_t* ranks{ nullptr };
+};
+
+static void
+runRankWork( mi355x_bz2_ctx* const ctx, const RankWork& work )
+{
+    if ( work.count == 0 ) return;
+    if ( work.count > std::numeric_limits<uint32_t>::max() ) {
+        fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "line_numbers: too many offsets in one launch" );
+    }
+    std::vector<mi355x_bz2_rank_query> queries( work.count );
+    for ( size_t k = 0; k < work.count; ++k ) {
+        const auto& q = work.plan->queries[work.first + k];
+        queries[k] = { q.spanOffset, q.spanSize, q.position };
+    }
+    uint64_t* const ranks = work.ranks + work.first;
+    checkDevice( ctx, mi355x_bz2_rank_byte( ctx, queries.data(), (uint32_t)queries.size(), work.nl, ranks ) );
+    for ( size_t k = 0; k < work.count; ++k ) {
+        const auto& q = work.plan->queries[work.first + k];
+        if ( q.expected != bz2gpu::NOT_FOUND && ranks[k] != q.expected ) failLyingLineIndex( q.blockStart, q.expected, ranks[k] );
+    }
+}
+
+/** What the launches of one search share: the pattern, and -- with a limit -- how many matches the launches at the
+ * front of the range that are through have found.  Once these reach the limit, `stop` cancels the launches that have
+ * not been started. */
+struct SearchCall
+{
+    const uint8_t* pattern{ nullptr };
+    uint32_t m{ 0 };
+    uint64_t limit{ 0 };                        /* 0: count only */
+    std::mutex mutex;
+    std::vector<uint8_t> finished;              /* per launch */
+    std::vector<uint64_t> counts;
+    size_t through{ 0 };                        /* launches [0, through) are finished ... */
+    uint64_t found{ 0 };                        /* ... and have found this many */
+    std::atomic<bool> stop{ false };
+};
+
+/** What a launch of a search does with its decoded blocks: mi355x::searchOutput over its extent. */
+struct SearchWork
+{
+    SearchCall* call{ nullptr };
+    uint32_t index{ 0 };
+    bz2gpu::SearchExtent extent;
+    uint64_t count{ 0 };                        /* out: matches inside the extent */
+    std::vector<uint64_t> positions;            /* out (limit > 0): the first min( count, limit ), in the launch's output */
+    uint8_t seam[2 * bz2gpu::SEARCH_PATTERN_MAX]{};   /* out: head at 0, tail at SEARCH_PATTERN_MAX */
+};
+
+static void
+runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
+{
+    auto& call = *work.call;
+    checkDevice( ctx, searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern, call.m, call.limit,
+                                    call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam ) );
+    if ( call.limit > 0 ) {
+        const std::scoped_lock lock( call.mutex );
+        call.finished[work.index] = 1;
+        call.counts[work.index] = work.count;
+        while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
+            call.found += call.counts[call.through++];
+        }
+        if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
+    }
+}
 
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
@@ -1189,7 +1180,7 @@ public:
     void
     close()
     {
-        m_held.reset();
+        dropHeldLines();
         m_matches.reset();
         m_scheduler.reset();
         m_finder.reset();
@@ -1343,25 +1334,22 @@ public:
         }
         indexUpTo( furthest );
         const auto map = knownMap();
-        auto plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, false, m_source->size() );
-        if ( plan.distinctBlocks > 0 && !scheduler().inputResident() ) {
-            plan = bz2gpu::planRanges( map, offsets, sizes, n, m_batch, true, m_source->size() );
-        }
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planRanges( map, offsets, sizes, n, m_batch, packed, m_source->size() );
+        } );
         if ( !plan.pieces.empty() && dst == nullptr ) {
             fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "read_ranges: no destination" );
         }
 
-        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
-        for ( size_t l = 0; l < works.size(); ++l ) {
-            works[l] = std::make_unique<BatchScheduler::RangesWork>();
-            works[l]->launch = &plan.launches[l];
-            works[l]->dst = dst;
-            works[l]->dstIsDevice = dstIsDevice;
-        }
+        std::vector<std::vector<mi355x_bz2_gather_piece> > pieces( plan.launches.size() );
         for ( const auto& piece : plan.pieces ) {
-            works[piece.launch]->pieces.push_back( { piece.src, piece.dst, piece.size } );
+            pieces[piece.launch].push_back( { piece.src, piece.dst, piece.size } );
         }
-        runLaunches( works );
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [mine = &pieces[l], dst, dstIsDevice] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+                gatherPieces( ctx, *mine, dst, dstIsDevice );
+            };
+        } );
         std::copy( plan.nRead.begin(), plan.nRead.end(), nRead );
     }
 
@@ -1383,33 +1371,27 @@ public:
         }
         indexUpTo( end );
         const auto map = knownMap();
-        auto plan = bz2gpu::planSearch( map, start, end, m, m_batch, false, m_source->size() );
-        if ( !plan.launches.empty() && !scheduler().inputResident() ) {
-            plan = bz2gpu::planSearch( map, start, end, m, m_batch, true, m_source->size() );
-        }
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planSearch( map, start, end, m, m_batch, packed, m_source->size() );
+        } );
         const size_t n = plan.launches.size();
-        BatchScheduler::SearchCall call;
+        SearchCall call;
         call.pattern = pattern;
         call.m = m;
         call.limit = limit;
         call.finished.assign( n, 0 );
         call.counts.assign( n, 0 );
-        std::vector<BatchScheduler::SearchWork> searches( n );
-        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( n );
+        std::vector<SearchWork> searches( n );
         for ( size_t l = 0; l < n; ++l ) {
             searches[l].call = &call;
             searches[l].index = (uint32_t)l;
             searches[l].extent = plan.extents[l];
-            works[l] = std::make_unique<BatchScheduler::RangesWork>();
-            works[l]->launch = &plan.launches[l];
-            works[l]->search = &searches[l];
         }
-        runLaunches( works );
-
         /* the launches in front of the first one that was not started: with a limit they hold at least `limit` matches,
          * and every match that needs a byte behind them starts behind all of those (bz2_search.hpp) */
-        size_t usable = 0;
-        while ( usable < n && !searches[usable].skipped ) ++usable;
+        const size_t usable = runJobs( plan.launches, [&] ( size_t l ) {
+            return [work = &searches[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) { runSearchWork( ctx, *work ); };
+        }, &call.stop );
         std::vector<bz2gpu::ExtentSeam> seams( usable );
         for ( size_t l = 0; l < usable; ++l ) {
             const auto& extent = searches[l].extent;
@@ -1480,11 +1462,12 @@ public:
     {
         const auto& index = lineIndex( nl );
         dropHeldLines();
-        const auto plan = bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
-                                             lines, nullptr, n, /* startsOnly */ true, m_batch, packedLaunches(),
-                                             m_source->size() );
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
+                                      lines, nullptr, n, /* startsOnly */ true, m_batch, packed, m_source->size() );
+        } );
         std::vector<uint64_t> positions( plan.queries.size(), bz2gpu::NOT_FOUND );
-        std::vector<BatchScheduler::LineWork> lineWorks;
+        std::vector<LineWork> lineWorks;
         runLineLaunches( plan, nl, positions, lineWorks );
         for ( size_t i = 0; i < n; ++i ) {
             const auto& start = plan.starts[i];
@@ -1500,11 +1483,12 @@ public:
     {
         const auto& index = lineIndex( nl );
         dropHeldLines();
-        const auto plan = bz2gpu::planLineNumbers( m_index.snapshot(), index.bytes.data(), index.lines.data(),
-                                                   index.bytes.size(), offsets, n, m_batch, packedLaunches(),
-                                                   m_source->size() );
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLineNumbers( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
+                                            offsets, n, m_batch, packed, m_source->size() );
+        } );
         std::vector<uint64_t> ranks( plan.queries.size(), 0 );
-        std::vector<BatchScheduler::RankWork> rankWorks( plan.launches.size() );
+        std::vector<RankWork> rankWorks( plan.launches.size() );
         for ( auto& work : rankWorks ) {
             work.nl = nl;
             work.plan = &plan;
@@ -1515,13 +1499,9 @@ public:
             auto& work = rankWorks[plan.queries[q].launch];
             if ( work.count++ == 0 ) work.first = q;
         }
-        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
-        for ( size_t l = 0; l < works.size(); ++l ) {
-            works[l] = std::make_unique<BatchScheduler::RangesWork>();
-            works[l]->launch = &plan.launches[l];
-            works[l]->rank = &rankWorks[l];
-        }
-        runLaunches( works );
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [work = &rankWorks[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) { runRankWork( ctx, *work ); };
+        } );
         for ( size_t i = 0; i < n; ++i ) lines[i] = bz2gpu::lineNumberOf( plan.answers[i], ranks.data() );
     }
 
@@ -1584,11 +1564,12 @@ public:
     {
         const auto& index = lineIndex( nl );
         dropHeldLines();
-        const auto plan = bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
-                                             first, count, n, /* startsOnly */ false, m_batch, packedLaunches(),
-                                             m_source->size() );
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLines( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(),
+                                      first, count, n, /* startsOnly */ false, m_batch, packed, m_source->size() );
+        } );
         std::vector<uint64_t> positions( plan.queries.size(), bz2gpu::NOT_FOUND );
-        std::vector<BatchScheduler::LineWork> lineWorks;
+        std::vector<LineWork> lineWorks;
         try {
             runLineLaunches( plan, nl, positions, lineWorks );
         } catch ( ... ) {
@@ -1636,8 +1617,7 @@ public:
             at[piece.range] += piece.size;
         }
         for ( const auto& [ctx, pieces] : perContext ) {
-            const int rc = gatherResult( ctx, pieces.data(), (uint32_t)pieces.size(), dst, dstIsDevice ? 1 : 0 );
-            if ( rc != MI355X_BZ2_OK ) fail( rc, mi355x_bz2_last_error( ctx ) );
+            checkDevice( ctx, gatherResult( ctx, pieces.data(), (uint32_t)pieces.size(), dst, dstIsDevice ? 1 : 0 ) );
         }
     }
 
@@ -1689,8 +1669,7 @@ public:
     void
     joinThreads()
     {
-        m_held.reset();   /* it lives in the contexts' buffers */
-        m_grep.reset();
+        dropHeldLines();   /* they live in the contexts' buffers */
         m_scheduler.reset();
         m_finder.reset();
     }
@@ -1712,7 +1691,7 @@ private:
     {
         bool onDevice{ false };
         std::vector<uint64_t> sizes;                       /* per range */
-        std::vector<BatchScheduler::HeldPiece> pieces;     /* front to back within every range */
+        std::vector<HeldPiece> pieces;                     /* front to back within every range */
     };
 
     struct HeldGrep
@@ -1725,20 +1704,19 @@ private:
     {
         m_held.reset();
         m_grep.reset();
-        if ( m_scheduler ) m_scheduler->dropHeld();
+        const std::scoped_lock lock( m_heldBytes.mutex );
+        m_heldBytes.of.clear();   /* the buffers stay: they only grow */
     }
 
-    /** Index the file up to the decoded offset `furthest`, as a forward seek would; the position and eof() stay. */
+    /** read( nowhere, wanted ) from the end of the indexed part of the file, as a forward seek would; the position and
+     * eof() stay as they are, also when the read fails. */
     void
-    indexUpTo( uint64_t furthest )
+    indexForward( size_t wanted = std::numeric_limits<size_t>::max() )
     {
-        if ( m_index.sealed() || ( furthest <= m_index.frontier() ) ) return;
-        const size_t position = m_position;
-        const bool atEnd = m_atEnd;
+        const size_t position = std::exchange( m_position, (size_t)m_index.frontier() );
+        const bool atEnd = std::exchange( m_atEnd, false );
         try {
-            m_position = (size_t)m_index.frontier();
-            m_atEnd = false;
-            read( Sink(), (size_t)( furthest - m_position ) );
+            read( Sink(), wanted );
         } catch ( ... ) {
             m_position = position;
             m_atEnd = atEnd;
@@ -1746,6 +1724,14 @@ private:
         }
         m_position = position;
         m_atEnd = atEnd;
+    }
+
+    /** Index the file up to the decoded offset `furthest`. */
+    void
+    indexUpTo( uint64_t furthest )
+    {
+        if ( m_index.sealed() || ( furthest <= m_index.frontier() ) ) return;
+        indexForward( (size_t)( furthest - m_index.frontier() ) );
     }
 
     /** The map as far as it is known; while it is not complete, its last entry is followed by the end of the open block. */
@@ -1760,33 +1746,53 @@ private:
         return map;
     }
 
-    /** Each launch to the front of the queue -- the last one first, so that the first launch is taken first --, and all
-     * of them waited for (they write into memory of the caller) before the first failure in file order is reported. */
-    void
-    runLaunches( std::vector<std::unique_ptr<BatchScheduler::RangesWork> >& works )
+    /** make( packed ) plans a call's launches; packed: the compressed file is not resident on the GPU and every launch
+     * brings the packed windows of its own blocks (bz2_ranges.hpp).  Only the scheduler knows which it is, and a plan
+     * without launches must not create one (and with it a GPU context): while there is none yet, the plan is made as
+     * for a resident file and made again if it has launches and their scheduler says otherwise. */
+    template<typename MakePlan>
+    [[nodiscard]] auto
+    planLaunches( const MakePlan& make ) -> decltype( make( false ) )
     {
-        std::vector<std::future<void> > pending( works.size() );
-        for ( size_t l = works.size(); l-- > 0; ) {
-            pending[l] = scheduler().launchRanges( std::move( works[l] ) );
+        auto plan = make( m_scheduler && !m_scheduler->inputResident() );
+        if ( !m_scheduler && !plan.launches.empty() && !scheduler().inputResident() ) plan = make( true );
+        return plan;
+    }
+
+    /** One job per launch of a plan, with afterDecodeOf( l ) as the job of launch l and `cancel`, if given, as the flag
+     * that keeps jobs not yet taken from being started.  Each job goes to the front of the queue -- the last one first,
+     * so that the first launch is taken first.  ALL of them are waited for before this returns or throws: that is what
+     * allows a job to point into the caller's plan, results and destination.  Then the first failure in launch order
+     * is thrown; otherwise the number of launches in front of the first cancelled one comes back. */
+    size_t
+    runJobs( const std::vector<bz2gpu::RangeLaunch>& launches,
+             const std::function<BatchScheduler::Job::AfterDecode( size_t )>& afterDecodeOf,
+             const std::atomic<bool>* cancel = nullptr )
+    {
+        std::vector<std::future<bool> > pending( launches.size() );
+        for ( size_t l = launches.size(); l-- > 0; ) {
+            auto job = std::make_unique<BatchScheduler::Job>();
+            job->launch = &launches[l];
+            job->cancel = cancel;
+            job->afterDecode = afterDecodeOf( l );
+            pending[l] = scheduler().submit( std::move( job ) );
         }
         std::exception_ptr failure;
-        for ( auto& launch : pending ) {
+        size_t started = pending.size();
+        for ( size_t l = 0; l < pending.size(); ++l ) {
             try {
-                launch.get();
+                if ( !pending[l].get() ) started = std::min( started, l );
             } catch ( ... ) {
                 if ( !failure ) failure = std::current_exception();
             }
         }
         if ( failure ) std::rethrow_exception( failure );
+        return started;
     }
-
-    /** Bounded residency: launches bring the packed windows of their own blocks (bz2_ranges.hpp). */
-    [[nodiscard]] bool packedLaunches() { return !scheduler().inputResident(); }
 
     /** The launches of a line plan, each with its own queries and segments. */
     void
-    runLineLaunches( const bz2gpu::LinePlan& plan, uint8_t nl, std::vector<uint64_t>& positions,
-                     std::vector<BatchScheduler::LineWork>& lineWorks )
+    runLineLaunches( const bz2gpu::LinePlan& plan, uint8_t nl, std::vector<uint64_t>& positions, std::vector<LineWork>& lineWorks )
     {
         lineWorks.assign( plan.launches.size(), {} );
         for ( auto& work : lineWorks ) {
@@ -1796,13 +1802,18 @@ private:
         }
         for ( size_t q = 0; q < plan.queries.size(); ++q ) lineWorks[plan.queries[q].launch].queries.push_back( (uint32_t)q );
         for ( size_t k = 0; k < plan.segments.size(); ++k ) lineWorks[plan.segments[k].launch].segments.push_back( (uint32_t)k );
-        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
-        for ( size_t l = 0; l < works.size(); ++l ) {
-            works[l] = std::make_unique<BatchScheduler::RangesWork>();
-            works[l]->launch = &plan.launches[l];
-            works[l]->lines = &lineWorks[l];
-        }
-        runLaunches( works );
+        runLineJobs( plan.launches, lineWorks );
+    }
+
+    /** Launch l as a job that does lineWorks[l]. */
+    void
+    runLineJobs( const std::vector<bz2gpu::RangeLaunch>& launches, std::vector<LineWork>& lineWorks )
+    {
+        runJobs( launches, [&] ( size_t l ) {
+            return [this, work = &lineWorks[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& launch ) {
+                runLineWork( ctx, launch, *work, m_heldBytes );
+            };
+        } );
     }
 
     /** The line index for `nl`: the one the reader holds, or a new one.  The block map is completed first if it has to
@@ -1815,35 +1826,21 @@ private:
         if ( m_lines && m_lines->nl == nl ) return *m_lines;
         dropHeldLines();
         if ( !m_index.sealed() ) {
-            const size_t position = m_position;
-            const bool atEnd = m_atEnd;
-            try {
-                m_position = (size_t)m_index.frontier();
-                m_atEnd = false;
-                read( Sink() );
-            } catch ( ... ) {
-                m_position = position;
-                m_atEnd = atEnd;
-                throw;
-            }
-            m_position = position;
-            m_atEnd = atEnd;
+            indexForward();
             if ( !m_index.sealed() ) fail( MI355X_BZ2_ERR_LOGIC, "the whole file was read but its block index is not complete" );
         }
         const auto map = m_index.snapshot();
         const uint64_t total = map.empty() ? 0 : map.back().second;
         const uint64_t offset = 0;
-        const auto plan = bz2gpu::planRanges( map, &offset, &total, 1, m_batch, total > 0 && packedLaunches(), m_source->size() );
-        std::vector<BatchScheduler::LineWork> lineWorks( plan.launches.size() );
-        std::vector<std::unique_ptr<BatchScheduler::RangesWork> > works( plan.launches.size() );
-        for ( size_t l = 0; l < works.size(); ++l ) {
-            lineWorks[l].nl = nl;
-            lineWorks[l].countBlocks = true;
-            works[l] = std::make_unique<BatchScheduler::RangesWork>();
-            works[l]->launch = &plan.launches[l];
-            works[l]->lines = &lineWorks[l];
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planRanges( map, &offset, &total, 1, m_batch, packed, m_source->size() );
+        } );
+        std::vector<LineWork> lineWorks( plan.launches.size() );
+        for ( auto& work : lineWorks ) {
+            work.nl = nl;
+            work.countBlocks = true;
         }
-        runLaunches( works );
+        runLineJobs( plan.launches, lineWorks );
         LineIndex index;
         index.nl = nl;
         std::vector<uint64_t> lengths;
@@ -1981,6 +1978,7 @@ private:
     std::optional<HeldLines> m_held;      /* between read_line_ranges and take_line_ranges */
     std::optional<std::vector<uint64_t> > m_matches;   /* between search (with a limit) and take_matches */
     std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
+    HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
 };
 }  // namespace mi355x
 

@@ -263,6 +263,49 @@ def test_lying_line_index(native, corpus):
         assert f.read(1000) == raw[:1000]
 
 
+def test_damaged_block(native, corpus, tmp_path):
+    """One byte flipped inside block b, both true indexes imported: line_numbers of offsets that keep clear of the block
+    is served, an offset in its middle fails with the block's status and bit offset; grep over the block fails the same
+    way and holds nothing afterwards; a grep that keeps clear of the block is served before and after."""
+    c, v = corpus, corpus["level9"]
+    raw, starts, newlines = c["raw"], v["starts"], c["newlines"]
+    b = len(starts) - 3
+    items = sorted(v["blocks"].items())
+    bits, next_bits, start, stop = [(x, nx, s, e) for (x, s), (nx, e) in zip(items, items[1:]) if e > s][b]
+    assert (start, stop) == (starts[b], starts[b + 1])
+    damaged = bytearray(v["enc"])
+    damaged[(bits + next_bits) // 16] ^= 0xFF
+    bad = tmp_path / "damaged.bz2"
+    bad.write_bytes(bytes(damaged))
+    line_index = {s: int(np.searchsorted(newlines, s)) for s in starts}
+    line_index[len(raw)] = len(newlines)
+    lib = native.lib()
+    with native.open(str(bad), parallelization=4) as f:
+        f.set_block_offsets(v["blocks"])
+        f.set_line_offsets(line_index)
+        # the damaged block's first byte is answered by the index, its neighbours' bytes by their own blocks
+        avoiding = [5, starts[1] - 1, start, start - 1, stop, stop + 7, starts[2] + 10, len(raw) - 1, len(raw) + 3]
+        assert np.array_equal(f.line_numbers(avoiding), grepgen.line_numbers_of(raw, avoiding))
+        with pytest.raises(native.Bz2Error) as failure:
+            f.line_numbers([5, (start + stop) // 2])
+        assert failure.value.status != 0
+        assert f"bit offset {bits}" in str(failure.value)
+        assert np.array_equal(f.line_numbers(avoiding), grepgen.line_numbers_of(raw, avoiding))
+        # a grep that keeps clear of the block is served (and its lines are taken)
+        numbers, _ = assert_grep(f, raw, NEEDLE, 0, starts[1])
+        assert len(numbers) >= 1
+        reader = f.bz2reader
+        for window in ((0, None), (start + 10, stop - 10)):
+            with pytest.raises(native.Bz2Error) as failure:
+                f.grep(NEEDLE, *window)
+            assert failure.value.status != 0
+            assert f"bit offset {bits}" in str(failure.value)
+            with pytest.raises(ValueError, match="no line ranges are held"):
+                reader._check(lib.mi355x_bz2_reader_take_line_ranges(reader._h, None, 0))
+            assert lib.mi355x_bz2_reader_take_grep(reader._h, None, None, 0) == 103
+        assert_grep(f, raw, NEEDLE, 0, starts[1])
+
+
 # ------------------------------------------------------------------------------------------------ grep
 
 def assert_grep(f, raw, pattern, start=0, end=None, limit=None):

@@ -360,6 +360,31 @@ def test_lying_line_index(native, corpus):
             assert f.read(1000) == raw[:1000]
 
 
+def test_damaged_block(native, corpus, tmp_path):
+    """One byte flipped inside a block: building the line index (its counting launches decode every block) fails with
+    the block's status and bit offset and leaves no index behind -- a second call fails the same way instead of returning
+    a partial one --, and read_ranges of clean ranges works after each failure."""
+    c = corpus["level9"]
+    raw = c["raw"]
+    items = sorted(c["blocks"].items())
+    blocks = [(b, nb, s, e) for (b, s), (nb, e) in zip(items, items[1:]) if e > s]
+    bits, next_bits, start, stop = blocks[4]
+    damaged = bytearray(c["enc"])
+    damaged[(bits + next_bits) // 16] ^= 0xFF
+    bad = tmp_path / "damaged.bz2"
+    bad.write_bytes(bytes(damaged))
+    avoid = [(blocks[k][2] + 10, 5000) for k in (0, 3, 5, 8)] + [(start - 100, 100), (stop, 300)]
+    with native.open(str(bad), parallelization=4) as f:
+        f.set_block_offsets(c["blocks"])
+        for call in (f.line_offsets, f.line_offsets, f.count_lines):
+            with pytest.raises(native.Bz2Error) as failure:
+                call()
+            assert failure.value.status != 0
+            assert f"bit offset {bits}" in str(failure.value)
+            assert f.read_ranges(avoid) == [raw[o:o + s] for o, s in avoid]
+        assert f.read(1000) == raw[:1000]
+
+
 def test_argument_errors(native, corpus):
     c = corpus["level9"]
     with native.open(c["path"], parallelization=4) as f:

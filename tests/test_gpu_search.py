@@ -224,6 +224,42 @@ def test_bounded_residency(native, corpus_a, monkeypatch):
             assert f.statistics()["input_resident"] == 0 and f.statistics()["input_bytes_uploaded"] > 0
 
 
+def test_damaged_block(native, corpus_a, tmp_path):
+    """One byte flipped inside block 7: a search whose range keeps clear of that block is served, one that needs it fails
+    with the block's status and bit offset, and the reader works afterwards.  (The damaged block may share a launch with
+    clean ones: only what the calls return or raise is asserted.)"""
+    c = corpus_a[16]
+    raw, needle = c["raw"], c["needle"]
+    items = sorted(c["blocks"].items())
+    bits, next_bits, start, stop = [(b, nb, s, e) for (b, s), (nb, e) in zip(items, items[1:]) if e > s][7]
+    assert (start, stop) == (7 * BLOCK, 8 * BLOCK)
+    damaged = bytearray(open(c["path"], "rb").read())
+    damaged[(bits + next_bits) // 16] ^= 0xFF
+    bad = tmp_path / "damaged.bz2"
+    bad.write_bytes(bytes(damaged))
+    clean = [(17, start), (stop, SIZE), (2 * BLOCK + 5, 5 * BLOCK), (stop, ALL)]
+    needing = [(0, ALL), (start - 1000, start + 1000), (stop - 300, stop + 300), (start + 500, start + 600)]
+
+    def check_clean(f):
+        for a, b in clean:
+            want = matches_of(raw, needle, a, b)
+            assert len(want) >= 2
+            assert f.count_matches(needle, a, b) == len(want), (a, b)
+            assert f.find_all(needle, a, b).tolist() == want, (a, b)
+
+    with native.open(str(bad), parallelization=4) as f:
+        f.set_block_offsets(c["blocks"])
+        check_clean(f)
+        for a, b in needing:
+            for call in (f.count_matches, f.find_all):
+                with pytest.raises(native.Bz2Error) as failure:
+                    call(needle, a, b)
+                assert failure.value.status != 0
+                assert f"bit offset {bits}" in str(failure.value)
+        # the reader stays usable
+        check_clean(f)
+
+
 # ------------------------------------------------------------------------------------------------ corpus B
 
 def test_extents_shorter_than_the_pattern(native, tmp_path):
