@@ -292,6 +292,28 @@ int mi355x_bz2_count_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spa
 int mi355x_bz2_find_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
                            uint32_t pattern_size, uint64_t* positions, uint64_t capacity, uint64_t* counts );
 
+/* A SET of byte strings in spans of the last batch's output, in one pass over the bytes: the kernels under the reader's
+ * search_set.  `patterns` is the concatenation of the n_patterns patterns in set order, pattern_sizes[i] the size m_i of
+ * pattern i.  1 <= n_patterns <= 1024, 1 <= m_i <= 256 and the sum of the m_i <= 16384, else
+ * MI355X_BZ2_ERR_INVALID_ARGUMENT before anything is launched (mi355x_bz2_last_error names the limit that was broken).
+ * Equal patterns and patterns that are prefixes of one another are allowed; each reports its own matches.  A match of span
+ * s is a pair (p, i) with output[p : p + m_i] == pattern i, offset <= p and p + m_i <= offset + size -- the end rule per
+ * pattern: near the end of a span a short pattern still matches where a long one no longer fits.  The matches of pattern
+ * i are exactly those of mi355x_bz2_find_bytes for it.  Otherwise the rules of _count_bytes / _find_bytes: the spans lie
+ * inside the last batch's output, no batch may be in flight, a span given twice is searched twice.
+ *   _count_bytes_set  counts[s] = the pairs of span s; per_pattern[i] (may be NULL) = the pairs of pattern i over all
+ *                     spans  (k_count_set).
+ *   _find_bytes_set   the same, and positions[] / ids[] = the pairs, span by span in caller order and by ascending
+ *                     (position, id) within a span, the first `capacity` of them (k_count_set, k_scan_tiles, k_emit_set:
+ *                     the order comes from prefix sums, the same call gives the same arrays).  The counts are true
+ *                     whatever the capacity.  If the pairs do not fit on the device the call fails with
+ *                     MI355X_BZ2_ERR_DEVICE; nothing is truncated silently. */
+int mi355x_bz2_count_bytes_set( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                                const uint32_t* pattern_sizes, uint32_t n_patterns, uint64_t* counts, uint64_t* per_pattern );
+int mi355x_bz2_find_bytes_set( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                               const uint32_t* pattern_sizes, uint32_t n_patterns, uint64_t* positions, uint32_t* ids,
+                               uint64_t capacity, uint64_t* counts, uint64_t* per_pattern );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -528,6 +550,33 @@ int mi355x_bz2_reader_line_numbers( mi355x_bz2_reader* r, uint8_t nl, const uint
 int mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint8_t nl, uint64_t start,
                             uint64_t end, uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 int mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* line_numbers, uint64_t* byte_sizes, uint64_t capacity );
+
+/* ---- search and grep for a set of patterns: what `grep -F -f FILE` does, with ONE decode of every block of the range
+ * whatever the number of patterns.  The set as for mi355x_bz2_count_bytes_set (patterns concatenated in set order; 1 to
+ * 1024 patterns of 1 to 256 bytes, 16384 bytes in total, else MI355X_BZ2_ERR_INVALID_ARGUMENT before anything is launched,
+ * the limit named by _last_error).  A match is a pair (p, i) with D[p : p + m_i] == pattern i, start <= p and
+ * p + m_i <= end, start and end clipped as for _search and the end rule applied per pattern; the matches of pattern i are
+ * exactly those of _search for it, overlapping ones included.  A result is ordered by ascending p, then ascending i.
+ * Positionless, same launches, residency and failure rules as _search; the pairs that straddle launches are found on the
+ * host from the first and last m_max - 1 bytes of each launch's part (bz2_search.hpp).
+ * Step 1, _search_set.  limit == 0: count only -- *n_matches is the number of pairs and per_pattern[i] (may be NULL) the
+ * count of pattern i, nothing is held.  limit > 0 (UINT64_MAX: all): the first min( limit, total ) pairs are held on the
+ * host, *n_matches is their number and per_pattern is not written.  The result with a limit is the first `limit` pairs
+ * of the result without one; the launches behind the front are skipped only once the front holds `limit` pairs that end
+ * m_max bytes in front of its end (a long pattern that crosses the front's end may sort in front of a short one inside).
+ * Step 2, _take_set_matches: copies the held pairs (at most `capacity`) and releases them; the next set search, or
+ * close, releases them as well.  Held set matches are independent of held single-pattern matches and of held line
+ * ranges. */
+int mi355x_bz2_reader_search_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
+                                  uint32_t n_patterns, uint64_t start, uint64_t end, uint64_t limit, uint64_t* n_matches,
+                                  uint64_t* per_pattern );
+int mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* positions, uint32_t* ids, uint64_t capacity );
+/* _grep with the set search as its first pass: a matching line is a line that holds the first byte of at least one pair,
+ * each reported once (the positions are deduplicated before the rank pass).  _take_grep and _take_line_ranges serve it
+ * unchanged. */
+int mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
+                                uint32_t n_patterns, uint8_t nl, uint64_t start, uint64_t end, uint64_t max_lines,
+                                int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

@@ -8,7 +8,8 @@ Beyond the reference's API the reader answers questions about the decoded file w
 (read_ranges), lines (count_lines, line_starts, line_numbers, read_line_ranges), where a byte string occurs
 (count_matches, find_all, find: every offset p with data[p:p + len(pattern)] == pattern, overlapping occurrences included)
 and which lines hold it (grep, count_matching_lines, grep_to_tensor: the lines of the matches' first bytes, each once,
-whole, with their 0-based numbers).
+whole, with their 0-based numbers).  The same for a set of up to 1 024 byte strings with one decode of the file per call
+(count_matches_each, find_all_any, find_any, grep_any, count_matching_lines_any, grep_any_to_tensor).
 """
 __version__ = "0.1.0"
 

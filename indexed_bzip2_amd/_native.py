@@ -119,6 +119,7 @@ class CompressResult(ctypes.Structure):
 
 # every symbol include/mi355x_bz2.h declares: (name, restype, argtypes)
 _u64p = ctypes.POINTER(ctypes.c_uint64)
+_u32p = ctypes.POINTER(ctypes.c_uint32)
 _vp = ctypes.c_void_p
 SYMBOLS = [
     ("mi355x_bz2_status_string", ctypes.c_char_p, [ctypes.c_int]),
@@ -159,6 +160,10 @@ SYMBOLS = [
                                                ctypes.c_uint32, _u64p]),
     ("mi355x_bz2_find_bytes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
                                               ctypes.c_uint32, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_count_bytes_set", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
+                                                   ctypes.c_uint32, _u64p, _u64p]),
+    ("mi355x_bz2_find_bytes_set", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
+                                                  ctypes.c_uint32, _u64p, _u32p, ctypes.c_uint64, _u64p, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -191,6 +196,12 @@ SYMBOLS = [
     ("mi355x_bz2_reader_grep", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint64,
                                                ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
     ("mi355x_bz2_reader_take_grep", ctypes.c_int, [_vp, _u64p, _u64p, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_search_set", ctypes.c_int, [_vp, ctypes.c_char_p, _u32p, ctypes.c_uint32, ctypes.c_uint64,
+                                                     ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_set_matches", ctypes.c_int, [_vp, _u64p, _u32p, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_grep_set", ctypes.c_int, [_vp, ctypes.c_char_p, _u32p, ctypes.c_uint32, ctypes.c_uint8,
+                                                   ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p,
+                                                   _u64p]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -282,6 +293,33 @@ def _byte_view(obj) -> memoryview:
     if not view.c_contiguous:
         raise ValueError("buffers must be C-contiguous")
     return view.cast("B") if view.format != "B" or view.ndim != 1 else view
+
+
+SET_MAX_PATTERNS, SET_MAX_PATTERN_BYTES, SET_MAX_BYTES = 1024, 256, 16384
+
+
+def pattern_set(patterns, check=True):
+    """A set of patterns for the *_set calls: (the patterns concatenated, their sizes as a uint32 array, their number).
+    `patterns` is any sequence of bytes-like objects; a str element, or a bare bytes-like object in place of the sequence,
+    is a TypeError.  With `check`, a set outside the limits of the search -- 1 to 1 024 patterns of 1 to 256 bytes, at
+    most 16 384 bytes in total -- is a ValueError (without it, the native call refuses the set)."""
+    if isinstance(patterns, (str, bytes, bytearray, memoryview)):
+        raise TypeError("patterns must be a sequence of bytes-like objects, not one " + type(patterns).__name__)
+    items = []
+    for pattern in patterns:
+        if isinstance(pattern, str):
+            raise TypeError("a pattern must be bytes-like, not str")
+        items.append(bytes(memoryview(pattern)))      # TypeError for what is not bytes-like
+    if check:
+        if not 1 <= len(items) <= SET_MAX_PATTERNS:
+            raise ValueError(f"the set must have 1 to {SET_MAX_PATTERNS} patterns, not {len(items)}")
+        for i, pattern in enumerate(items):
+            if not 1 <= len(pattern) <= SET_MAX_PATTERN_BYTES:
+                raise ValueError(f"every pattern must have 1 to {SET_MAX_PATTERN_BYTES} bytes, pattern {i} has {len(pattern)}")
+        if sum(map(len, items)) > SET_MAX_BYTES:
+            raise ValueError(f"the patterns must have at most {SET_MAX_BYTES} bytes in total, not {sum(map(len, items))}")
+    sizes = (ctypes.c_uint32 * max(1, len(items)))(*[len(pattern) for pattern in items])
+    return b"".join(items), sizes, len(items)
 
 
 class _KeptInputs(tuple):
@@ -520,6 +558,35 @@ class Decoder:
         self._check(lib().mi355x_bz2_find_bytes(self._h, arr, len(spans), pattern, len(pattern), positions, capacity, counts))
         found = min(capacity, sum(counts[:len(spans)]))
         return list(positions[:found]), list(counts[:len(spans)])
+
+    def count_bytes_set(self, patterns, spans):
+        """k_count_set: (counts, per_pattern) -- the number of (position, pattern) pairs in each span [(offset, size)] of
+        the last batch's output, and how often each pattern of the set occurs over all spans."""
+        data, sizes, k = pattern_set(patterns, check=False)
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        counts = (ctypes.c_uint64 * max(1, len(spans)))()
+        each = (ctypes.c_uint64 * max(1, k))()
+        self._check(lib().mi355x_bz2_count_bytes_set(self._h, arr, len(spans), data, sizes, k, counts, each))
+        return list(counts[:len(spans)]), list(each[:k])
+
+    def find_bytes_set(self, patterns, spans, capacity=None):
+        """k_count_set, k_scan_tiles, k_emit_set: (positions, ids, counts) -- the pairs (offset in the last batch's output,
+        index of the pattern in the set), span by span and by ascending (position, id) within a span, the first `capacity`
+        of them (None: all), and the true number of pairs of every span."""
+        data, sizes, k = pattern_set(patterns, check=False)
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        counts = (ctypes.c_uint64 * max(1, len(spans)))()
+        if capacity is None:
+            self._check(lib().mi355x_bz2_count_bytes_set(self._h, arr, len(spans), data, sizes, k, counts, None))
+            capacity = sum(counts[:len(spans)])
+        positions = (ctypes.c_uint64 * max(1, capacity))()
+        ids = (ctypes.c_uint32 * max(1, capacity))()
+        self._check(lib().mi355x_bz2_find_bytes_set(self._h, arr, len(spans), data, sizes, k, positions, ids, capacity, counts,
+                                                    None))
+        found = min(capacity, sum(counts[:len(spans)]))
+        return list(positions[:found]), list(ids[:found]), list(counts[:len(spans)])
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mi355x_bz2.h"
+#include "bz2_search.hpp"
 
 namespace mi355x
 {
@@ -32,6 +33,14 @@ int gatherResult( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, ui
  * seamBytes[256, ...) of a 512-byte array. */
 int searchOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m, uint64_t limit,
                   std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes );
+
+/** searchOutput for a set of patterns (as mi355x_bz2_find_bytes_set with that one span): *count is the true number of
+ * pairs; with `positions` and `ids` given they are resized to the first min( *count, limit ) pairs in (position, id) order
+ * (both nullptr: count only).  perPattern (may be nullptr) receives the count of every pattern inside the extent.  The
+ * first and the last min( m_max - 1, extent.size ) bytes of the extent come back as searchOutput hands them over. */
+int searchOutputSet( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const bz2gpu::PatternSet& set, uint64_t limit,
+                     std::vector<uint64_t>* positions, std::vector<uint32_t>* ids, uint64_t* count, uint64_t* perPattern,
+                     uint8_t* seamBytes );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

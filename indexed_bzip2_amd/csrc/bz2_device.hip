@@ -27,6 +27,7 @@
 #include "bz2_kernels.hip.h"
 #include "bz2_lines.hip.h"
 #include "bz2_search.hip.h"
+#include "bz2_search_set.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -1950,7 +1951,165 @@ searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* sp
     HIP_TRY( c, hipStreamSynchronize( c->stream ) );
     return MI355X_BZ2_OK;
 }
+
+/**
+ * Both set calls: searchBytes for a set of patterns.  The start positions every span allows for the shortest pattern are
+ * cut into tiles that carry their span's end, k_count_set counts the pairs of every tile, of every span and of every
+ * pattern, and the counts -- with the seam bytes of `seam`, if given: min( m_max - 1, size ) each -- come back in one
+ * D2H.  With pairs wanted, k_scan_tiles and k_emit_set write min( total, capacity ) positions and ids, which a second D2H
+ * brings to `positions` and `ids`, or to `grownPositions` and `grownIds` resized to their number.  perPattern (may be
+ * null) receives the count of every pattern over all spans.
+ */
+int
+searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const PatternSet& set,
+                bool wantPairs, uint64_t capacity, uint64_t* positions, uint32_t* ids, std::vector<uint64_t>* grownPositions,
+                std::vector<uint32_t>* grownIds, uint64_t* counts, uint64_t* perPattern, const mi355x_bz2_byte_span* seam,
+                uint8_t* seamBytes )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    const auto inside = [c] ( const mi355x_bz2_byte_span& span ) {
+        return span.size <= c->outSize && span.offset <= c->outSize - span.size;
+    };
+    const uint32_t k = set.count(), mMin = set.mMin;
+    uint64_t nTiles = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( !inside( spans[i] ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        counts[i] = 0;
+        if ( spans[i].size >= mMin ) nTiles += ( spans[i].size - mMin + 1 + SEARCH_TILE - 1 ) / SEARCH_TILE;
+    }
+    if ( seam != nullptr && !inside( *seam ) ) {
+        c->lastError = std::string( what ) + ": the seam span lies outside the last batch's output";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    const uint32_t seamN = seam != nullptr ? seamLength( set.mMax, seam->size ) : 0u;
+    if ( perPattern != nullptr ) std::fill_n( perPattern, k, uint64_t( 0 ) );
+    if ( grownPositions != nullptr ) grownPositions->clear();
+    if ( grownIds != nullptr ) grownIds->clear();
+    if ( nTiles == 0 && seamN == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][set image, at a multiple of 16][span counts][pattern counts][seam bytes]; device only:
+     * [tile counts][tile places] behind them */
+    const uint64_t imageAt = ( nTiles * sizeof( SetTile ) + 15 ) & ~uint64_t( 15 ), resultsAt = imageAt + SET_IMAGE_BYTES;
+    const uint64_t eachAt = resultsAt + n * sizeof( uint64_t ), seamAt = eachAt + k * sizeof( uint64_t );
+    const uint64_t countsAt = seamAt + 2 * SEARCH_MAX_PATTERN;
+    const uint64_t placesAt = countsAt + ( ( nTiles * sizeof( uint32_t ) + 7 ) & ~uint64_t( 7 ) );
+    const uint64_t bytes = placesAt + nTiles * sizeof( uint64_t );
+    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
+    /* the previous call's lists have been consumed (every call waits for its kernels) */
+    HIP_TRY( c, c->hSearch.grow( c, countsAt, cap, cap ) );
+    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
+    auto* const hTiles = reinterpret_cast<SetTile*>( c->hSearch.bytes );
+    uint64_t tile = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        if ( spans[s].size < mMin ) continue;
+        const uint64_t starts = spans[s].size - mMin + 1;
+        for ( uint64_t at = 0; at < starts; at += SEARCH_TILE ) {
+            hTiles[tile++] = { spans[s].offset + at, spans[s].offset + spans[s].size,
+                               (uint32_t)std::min<uint64_t>( SEARCH_TILE, starts - at ), s };
+        }
+    }
+    writeSetImage( set, c->hSearch.bytes + imageAt );
+    uint8_t* const d = c->dSearch.bytes;
+    const auto* const dTiles = reinterpret_cast<const SetTile*>( d );
+    auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
+    const auto nBytes = (uint32_t)set.bytes.size();
+    const auto groups = (uint32_t)std::min<uint64_t>( ( nTiles + SET_WAVES - 1 ) / SET_WAVES, SET_MAX_GROUPS );
+    HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_count_set, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
+                            d + imageAt, nBytes, k, dTileCounts, reinterpret_cast<unsigned long long*>( d + resultsAt ),
+                            reinterpret_cast<unsigned long long*>( d + eachAt ) );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    if ( seamN > 0 ) {
+        hipLaunchKernelGGL( k_seam_bytes, dim3( 1 ), dim3( 2 * SEARCH_MAX_PATTERN ), 0, c->stream, c->dOut, seam->offset,
+                            seam->size, seamN, d + seamAt );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    HIP_TRY( c, hipMemcpyAsync( c->hSearch.bytes + resultsAt, d + resultsAt, countsAt - resultsAt, hipMemcpyDeviceToHost,
+                                c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    uint64_t total = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        counts[i] = reinterpret_cast<const uint64_t*>( c->hSearch.bytes + resultsAt )[i];
+        total += counts[i];
+    }
+    if ( perPattern != nullptr ) std::memcpy( perPattern, c->hSearch.bytes + eachAt, k * sizeof( uint64_t ) );
+    if ( seamN > 0 ) {
+        std::memcpy( seamBytes, c->hSearch.bytes + seamAt, seamN );
+        std::memcpy( seamBytes + SEARCH_MAX_PATTERN, c->hSearch.bytes + seamAt + SEARCH_MAX_PATTERN, seamN );
+    }
+    const uint64_t wanted = wantPairs ? std::min( total, capacity ) : 0;
+    if ( wanted == 0 ) return MI355X_BZ2_OK;
+
+    if ( grownPositions != nullptr ) {
+        try {
+            grownPositions->resize( wanted );
+            grownIds->resize( wanted );
+        } catch ( const std::exception& ) {
+            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " pairs";
+            return MI355X_BZ2_ERR_DEVICE;
+        }
+        positions = grownPositions->data();
+        ids = grownIds->data();
+    }
+    /* the positions, then the ids */
+    const uint64_t idsAt = wanted * sizeof( uint64_t ), need = idsAt + wanted * sizeof( uint32_t );
+    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
+    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
+    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
+    auto* const dIds = reinterpret_cast<uint32_t*>( c->dSearchPositions.bytes + idsAt );
+    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_emit_set, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
+                        d + imageAt, nBytes, k, dPlaces, wanted, dPositions, dIds );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, idsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipMemcpyAsync( ids, dIds, wanted * sizeof( uint32_t ), hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
+/** The set of a C ABI call, checked: false with lastError set if it breaks a limit. */
+bool
+takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, PatternSet* set )
+{
+    const auto why = patternSetError( sizes, n );
+    if ( !why.empty() ) {
+        const std::scoped_lock lock( c->mutex );
+        c->lastError = std::string( what ) + ": " + why;
+        return false;
+    }
+    *set = makePatternSet( patterns, sizes, n );
+    return true;
+}
 }  // namespace
+
+int
+mi355x::searchOutputSet( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const bz2gpu::PatternSet& set, uint64_t limit,
+                         std::vector<uint64_t>* positions, std::vector<uint32_t>* ids, uint64_t* count, uint64_t* perPattern,
+                         uint8_t* seamBytes )
+{
+    if ( c == nullptr || count == nullptr || seamBytes == nullptr || ( positions == nullptr ) != ( ids == nullptr )
+         || !patternSetError( set.sizes.data(), set.count() ).empty() ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return searchBytesSet( c, "search_set", &extent, 1, set, positions != nullptr, limit, nullptr, nullptr, positions, ids,
+                           count, perPattern, &extent, seamBytes );
+}
 
 int
 mi355x::searchOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m,
@@ -2037,6 +2196,34 @@ mi355x_bz2_find_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uin
     }
     return searchBytes( c, "find_bytes", spans, n, pattern, patternSize, true, capacity, positions, nullptr, counts, nullptr,
                         nullptr );
+}
+
+int
+mi355x_bz2_count_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                            const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* counts, uint64_t* perPattern )
+{
+    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    PatternSet set;
+    if ( !takeSet( c, "count_bytes_set", patterns, patternSizes, nPatterns, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return searchBytesSet( c, "count_bytes_set", spans, n, set, false, 0, nullptr, nullptr, nullptr, nullptr, counts, perPattern,
+                           nullptr, nullptr );
+}
+
+int
+mi355x_bz2_find_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                           const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* positions, uint32_t* ids,
+                           uint64_t capacity, uint64_t* counts, uint64_t* perPattern )
+{
+    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
+         || ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    PatternSet set;
+    if ( !takeSet( c, "find_bytes_set", patterns, patternSizes, nPatterns, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return searchBytesSet( c, "find_bytes_set", spans, n, set, true, capacity, positions, ids, nullptr, nullptr, counts,
+                           perPattern, nullptr, nullptr );
 }
 
 int

@@ -1156,6 +1156,54 @@ runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
     }
 }
 
+/** SearchCall for a set of patterns.  `found` counts, of the pairs of the launches at the front that are through, only
+ * those that end m_max bytes in front of their extent's end (bz2_search.hpp: the limit of a set). */
+struct SetSearchCall
+{
+    const bz2gpu::PatternSet* set{ nullptr };
+    uint64_t limit{ 0 };                        /* 0: count only */
+    std::mutex mutex;
+    std::vector<uint8_t> finished;              /* per launch */
+    std::vector<uint64_t> safe;
+    size_t through{ 0 };
+    uint64_t found{ 0 };
+    std::atomic<bool> stop{ false };
+};
+
+struct SetSearchWork
+{
+    SetSearchCall* call{ nullptr };
+    uint32_t index{ 0 };
+    bz2gpu::SearchExtent extent;
+    uint64_t count{ 0 };                        /* out: pairs inside the extent */
+    std::vector<uint64_t> perPattern;           /* out (limit == 0): per pattern */
+    std::vector<uint64_t> positions;            /* out (limit > 0): the first min( count, limit ) pairs, positions in D */
+    std::vector<uint32_t> ids;
+    uint8_t seam[2 * bz2gpu::SEARCH_PATTERN_MAX]{};   /* out: head at 0, tail at SEARCH_PATTERN_MAX */
+};
+
+static void
+runSetSearchWork( mi355x_bz2_ctx* const ctx, SetSearchWork& work )
+{
+    auto& call = *work.call;
+    const bool pairs = call.limit > 0;
+    if ( !pairs ) work.perPattern.assign( call.set->count(), 0 );
+    checkDevice( ctx, searchOutputSet( ctx, { work.extent.src, work.extent.size }, *call.set, call.limit,
+                                       pairs ? &work.positions : nullptr, pairs ? &work.ids : nullptr, &work.count,
+                                       pairs ? nullptr : work.perPattern.data(), work.seam ) );
+    if ( pairs ) {
+        for ( auto& position : work.positions ) position = work.extent.fileOffset + ( position - work.extent.src );
+        const std::scoped_lock lock( call.mutex );
+        call.finished[work.index] = 1;
+        call.safe[work.index] = bz2gpu::safePairs( work.positions.data(), work.positions.size(),
+                                                   work.extent.fileOffset + work.extent.size, call.set->mMax );
+        while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
+            call.found += call.safe[call.through++];
+        }
+        if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
+    }
+}
+
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
 {
@@ -1182,6 +1230,7 @@ public:
     {
         dropHeldLines();
         m_matches.reset();
+        m_setMatches.reset();
         m_scheduler.reset();
         m_finder.reset();
         m_source.reset();
@@ -1419,6 +1468,98 @@ public:
         m_matches = std::move( merged );
     }
 
+    /** Step 1 for a set (mi355x_bz2_reader_search_set): search with searchOutputSet per launch, seamMatchesSet for the
+     * pairs no launch can see, and a merge by (position, id) that is cut to the limit afterwards. */
+    void
+    searchSet( const bz2gpu::PatternSet& set, uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches, uint64_t* perPattern )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "search_set on a closed reader" );
+        m_setMatches.reset();
+        *nMatches = 0;
+        const uint32_t k = set.count();
+        if ( limit == 0 && perPattern != nullptr ) std::fill_n( perPattern, k, uint64_t( 0 ) );
+        if ( start >= end ) {
+            if ( limit > 0 ) m_setMatches.emplace();
+            return;
+        }
+        indexUpTo( end );
+        const auto map = knownMap();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planSearchSet( map, start, end, set, m_batch, packed, m_source->size() );
+        } );
+        const size_t n = plan.launches.size();
+        SetSearchCall call;
+        call.set = &set;
+        call.limit = limit;
+        call.finished.assign( n, 0 );
+        call.safe.assign( n, 0 );
+        std::vector<SetSearchWork> searches( n );
+        for ( size_t l = 0; l < n; ++l ) {
+            searches[l].call = &call;
+            searches[l].index = (uint32_t)l;
+            searches[l].extent = plan.extents[l];
+        }
+        /* the launches in front of the first one that was not started: with a limit they hold at least `limit` pairs that
+         * sort in front of every pair that needs a byte behind them (bz2_search.hpp) */
+        const size_t usable = runJobs( plan.launches, [&] ( size_t l ) {
+            return [work = &searches[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) { runSetSearchWork( ctx, *work ); };
+        }, &call.stop );
+        std::vector<bz2gpu::ExtentSeam> seams( usable );
+        for ( size_t l = 0; l < usable; ++l ) {
+            const auto& extent = searches[l].extent;
+            const auto length = bz2gpu::seamLength( set.mMax, extent.size );
+            seams[l] = { extent.fileOffset, extent.size, { searches[l].seam, searches[l].seam + length },
+                         { searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX, searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX + length } };
+        }
+        const auto between = bz2gpu::seamMatchesSet( set, seams );
+        if ( limit == 0 ) {
+            uint64_t total = between.size();
+            for ( const auto& work : searches ) total += work.count;
+            *nMatches = total;
+            if ( perPattern != nullptr ) {
+                for ( const auto& work : searches ) {
+                    for ( uint32_t i = 0; i < k; ++i ) perPattern[i] += work.perPattern[i];
+                }
+                for ( const auto& pair : between ) ++perPattern[pair.second];
+            }
+            return;
+        }
+        /* the extents' pairs lie in (position, id) order one extent behind the other; the seam pairs are merged into them */
+        HeldSetMatches merged;
+        size_t seam = 0;
+        const auto full = [&] { return merged.positions.size() >= limit; };
+        const auto push = [&] ( uint64_t position, uint32_t id ) {
+            merged.positions.push_back( position );
+            merged.ids.push_back( id );
+        };
+        for ( size_t l = 0; l < usable && !full(); ++l ) {
+            const auto& work = searches[l];
+            for ( size_t i = 0; i < work.positions.size() && !full(); ++i ) {
+                const bz2gpu::SetMatch own{ work.positions[i], work.ids[i] };
+                for ( ; seam < between.size() && between[seam] < own && !full(); ++seam ) push( between[seam].first, between[seam].second );
+                if ( !full() ) push( own.first, own.second );
+            }
+            /* a launch that held more pairs than the limit has emitted `limit` of them, and the result is full by now */
+            const uint64_t extentEnd = work.extent.fileOffset + work.extent.size;
+            for ( ; seam < between.size() && between[seam].first < extentEnd && !full(); ++seam ) push( between[seam].first, between[seam].second );
+        }
+        *nMatches = merged.positions.size();
+        m_setMatches = std::move( merged );
+    }
+
+    /** Step 2 (mi355x_bz2_reader_take_set_matches): the held pairs, then none are held any more. */
+    void
+    takeSetMatches( uint64_t* positions, uint32_t* ids, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_set_matches on a closed reader" );
+        if ( !m_setMatches ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_set_matches: no matches are held (search_set with a limit first)" );
+        const auto held = std::move( *m_setMatches );
+        m_setMatches.reset();
+        const auto n = (size_t)std::min<uint64_t>( capacity, held.positions.size() );
+        std::copy_n( held.positions.begin(), n, positions );
+        std::copy_n( held.ids.begin(), n, ids );
+    }
+
     /** Step 2 (mi355x_bz2_reader_take_matches): the held positions, then nothing is held any more. */
     void
     takeMatches( uint64_t* positions, uint64_t capacity )
@@ -1517,6 +1658,28 @@ public:
         search( pattern, m, start, end, std::numeric_limits<uint64_t>::max(), &nMatches );
         const auto positions = std::move( *m_matches );
         m_matches.reset();
+        grepPositions( positions, nl, maxLines, keepOnDevice, nLines, totalBytes );
+    }
+
+    /** mi355x_bz2_reader_grep_set: grep with the set search as its first pass.  The pairs of one position are one
+     * position for the rank pass. */
+    void
+    grepSet( const bz2gpu::PatternSet& set, uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, bool keepOnDevice,
+             uint64_t* nLines, uint64_t* totalBytes )
+    {
+        uint64_t nMatches = 0;
+        searchSet( set, start, end, std::numeric_limits<uint64_t>::max(), &nMatches, nullptr );
+        auto positions = std::move( m_setMatches->positions );
+        m_setMatches.reset();
+        positions.erase( std::unique( positions.begin(), positions.end() ), positions.end() );
+        grepPositions( positions, nl, maxLines, keepOnDevice, nLines, totalBytes );
+    }
+
+    /** The rank and line passes of grep, from the ascending positions of the matches' first bytes. */
+    void
+    grepPositions( const std::vector<uint64_t>& positions, uint8_t nl, uint64_t maxLines, bool keepOnDevice, uint64_t* nLines,
+                   uint64_t* totalBytes )
+    {
         dropHeldLines();
         *nLines = 0;
         *totalBytes = 0;
@@ -1977,6 +2140,12 @@ private:
     std::optional<LineIndex> m_lines;     /* the one line index the reader keeps, with its delimiter */
     std::optional<HeldLines> m_held;      /* between read_line_ranges and take_line_ranges */
     std::optional<std::vector<uint64_t> > m_matches;   /* between search (with a limit) and take_matches */
+    struct HeldSetMatches
+    {
+        std::vector<uint64_t> positions;
+        std::vector<uint32_t> ids;
+    };
+    std::optional<HeldSetMatches> m_setMatches;        /* between search_set (with a limit) and take_set_matches */
     std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
 };
@@ -2288,6 +2457,49 @@ mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* lineNumbers, uint64
 {
     if ( capacity > 0 && ( lineNumbers == nullptr || byteSizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeGrep( lineNumbers, byteSizes, capacity ); } );
+}
+
+/** The set of a reader call; a set that breaks a limit fails the call with the sentence that names it. */
+static bz2gpu::PatternSet
+setOf( const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n )
+{
+    const auto why = bz2gpu::patternSetError( sizes, n );
+    if ( !why.empty() ) mi355x::fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + why );
+    return bz2gpu::makePatternSet( patterns, sizes, n );
+}
+
+int
+mi355x_bz2_reader_search_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
+                              uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches, uint64_t* perPattern )
+{
+    if ( patterns == nullptr || patternSizes == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        const auto set = setOf( "search_set", patterns, patternSizes, nPatterns );
+        reader.searchSet( set, start, end, limit, nMatches, perPattern );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* positions, uint32_t* ids, uint64_t capacity )
+{
+    if ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeSetMatches( positions, ids, capacity ); } );
+}
+
+int
+mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
+                            uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines,
+                            uint64_t* totalBytes )
+{
+    if ( patterns == nullptr || patternSizes == nullptr || nLines == nullptr || totalBytes == nullptr ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    *nLines = 0;
+    *totalBytes = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        const auto set = setOf( "grep_set", patterns, patternSizes, nPatterns );
+        reader.grepSet( set, nl, start, end, maxLines, keepOnDevice != 0, nLines, totalBytes );
+    } );
 }
 
 int

@@ -29,6 +29,24 @@
  * i's end b, so p lies in [max( start of i, b - m + 1 ), b), and its bytes are the tail of i from p on followed by the
  * heads of i + 1, i + 2, ... -- a head that is shorter than m - 1 is its whole extent, so the heads in front of the
  * first full one lie back to back in D, and m - 1 bytes behind b are always enough.
+ *
+ * A SET of patterns S = (P_0 .. P_{k-1}) (mi355x_bz2_reader_search_set; 1 <= k <= SET_MAX_PATTERNS, 1 <= m_i <=
+ * SEARCH_PATTERN_MAX, sum of the m_i <= SET_MAX_BYTES, m_min and m_max their extremes; equal patterns and prefixes of one
+ * another allowed) is searched in one pass over the same launches: a match is a PAIR (p, i) with D[p : p + m_i] == P_i,
+ * start <= p and p + m_i <= end -- the end rule per pattern --, and a result is ordered by ascending p, then ascending i.
+ * planSearchSet is planSearch with m_min deciding whether the clipped range can hold any match.  Heads and tails have
+ * seamLength( m_max, size ) bytes, and pattern i uses the last m_i - 1 bytes of a tail and the first m_i - 1 bytes of a
+ * head: the argument above holds for every pattern on its own, with m = m_i, and m_i - 1 <= m_max - 1.
+ *
+ * The limit is the one place where a set differs.  With one pattern, every match that crosses the end b of the launches
+ * at the front starts behind every match inside them (p > b - m against p' <= b - m).  With a set this is false: a long
+ * pattern can cross b from p = b - 100 while a short one matches entirely inside the front at p' = b - 50, and (p, long)
+ * sorts in front of (p', short).  A pair that the front launches cannot see has p + m_i > b, hence p > b - m_max; a pair
+ * with p + m_max <= b therefore sorts in front of every unseen one.  So the launches behind the front may be skipped only
+ * once the finished front launches hold >= limit pairs with p + m_max <= b (safePairs counts them per extent, with the
+ * extent's own end for b, which is never behind the front's), and the merged result -- the extents' pairs and the seam
+ * pairs really merged by (p, i), since inside one extent seam pairs no longer all follow the extent's own pairs -- is
+ * cut to `limit` afterwards.  The invariant: the result with a limit is the first `limit` pairs of the result without.
  */
 #pragma once
 
@@ -36,6 +54,7 @@
 #include <cstdint>
 #include <cstring>
 #include <stdexcept>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -44,6 +63,18 @@
 namespace bz2gpu
 {
 constexpr uint32_t SEARCH_PATTERN_MAX = 256;
+constexpr uint32_t SET_MAX_PATTERNS = 1024;
+constexpr uint32_t SET_MAX_BYTES = 16384;
+
+/* The set as the kernels read it (bz2_search_set.hip.h), one image that a workgroup copies into LDS:
+ *   [0, SET_MAX_BYTES)      the pattern bytes, concatenated in set order;
+ *   SET_TABLE_AT            one uint32 per pattern, ordered by (first byte, id):
+ *                           offset of its bytes | (m_i - 1) << SET_ENTRY_SIZE_SHIFT | id << SET_ENTRY_ID_SHIFT;
+ *   SET_FIRST_AT            one uint32 per first byte: begin of its bucket in the table | length << 16; 0 = none. */
+constexpr uint32_t SET_TABLE_AT = SET_MAX_BYTES;
+constexpr uint32_t SET_FIRST_AT = SET_TABLE_AT + SET_MAX_PATTERNS * 4;
+constexpr uint32_t SET_IMAGE_BYTES = SET_FIRST_AT + 256 * 4;
+constexpr uint32_t SET_ENTRY_SIZE_SHIFT = 14, SET_ENTRY_ID_SHIFT = 22;
 
 struct SearchExtent
 {
@@ -141,5 +172,143 @@ seamMatches( const uint8_t* pattern, uint32_t m, const std::vector<ExtentSeam>& 
         }
     }
     return matches;
+}
+
+/* ------------------------------------------------------------------------------------------------ sets of patterns */
+
+struct PatternSet
+{
+    std::vector<uint8_t> bytes;             /* the patterns, concatenated in set order */
+    std::vector<uint32_t> offsets, sizes;   /* per pattern */
+    uint32_t mMin{ 0 }, mMax{ 0 };
+
+    [[nodiscard]] uint32_t count() const { return (uint32_t)sizes.size(); }
+    [[nodiscard]] const uint8_t* pattern( uint32_t i ) const { return bytes.data() + offsets[i]; }
+};
+
+/** A (position, pattern id) pair; ordered by position, then id. */
+using SetMatch = std::pair<uint64_t, uint32_t>;
+
+/** Empty if (sizes, n) is a set the search takes, else the sentence that names the limit that was broken. */
+[[nodiscard]] inline std::string
+patternSetError( const uint32_t* sizes, uint64_t n )
+{
+    if ( n == 0 || n > SET_MAX_PATTERNS ) {
+        return "the set must have 1 to " + std::to_string( SET_MAX_PATTERNS ) + " patterns, not " + std::to_string( n );
+    }
+    uint64_t sum = 0;
+    for ( uint64_t i = 0; i < n; ++i ) {
+        if ( sizes[i] == 0 || sizes[i] > SEARCH_PATTERN_MAX ) {
+            return "every pattern must have 1 to " + std::to_string( SEARCH_PATTERN_MAX ) + " bytes, pattern "
+                   + std::to_string( i ) + " has " + std::to_string( sizes[i] );
+        }
+        sum += sizes[i];
+    }
+    if ( sum > SET_MAX_BYTES ) {
+        return "the patterns must have at most " + std::to_string( SET_MAX_BYTES ) + " bytes in total, not " + std::to_string( sum );
+    }
+    return {};
+}
+
+/** `patterns`: the concatenation of the patterns in set order.  Throws std::invalid_argument with patternSetError. */
+inline PatternSet
+makePatternSet( const uint8_t* patterns, const uint32_t* sizes, uint64_t n )
+{
+    const auto why = patternSetError( sizes, n );
+    if ( !why.empty() ) throw std::invalid_argument( why );
+    PatternSet set;
+    set.sizes.assign( sizes, sizes + n );
+    set.offsets.resize( n );
+    uint32_t at = 0;
+    for ( uint64_t i = 0; i < n; ++i ) {
+        set.offsets[i] = at;
+        at += sizes[i];
+    }
+    set.bytes.assign( patterns, patterns + at );
+    set.mMin = *std::min_element( set.sizes.begin(), set.sizes.end() );
+    set.mMax = *std::max_element( set.sizes.begin(), set.sizes.end() );
+    return set;
+}
+
+/** The image of the set for the kernels: SET_IMAGE_BYTES bytes at `image` (4-byte aligned), laid out as described at
+ * SET_TABLE_AT. */
+inline void
+writeSetImage( const PatternSet& set, uint8_t* image )
+{
+    std::memset( image, 0, SET_IMAGE_BYTES );
+    std::memcpy( image, set.bytes.data(), set.bytes.size() );
+    std::vector<uint32_t> order( set.count() );
+    for ( uint32_t i = 0; i < set.count(); ++i ) order[i] = i;
+    std::stable_sort( order.begin(), order.end(), [&set] ( uint32_t a, uint32_t b ) { return set.pattern( a )[0] < set.pattern( b )[0]; } );
+    auto* const table = reinterpret_cast<uint32_t*>( image + SET_TABLE_AT );
+    auto* const first = reinterpret_cast<uint32_t*>( image + SET_FIRST_AT );
+    for ( uint32_t e = 0; e < set.count(); ++e ) {
+        const uint32_t id = order[e], byte = set.pattern( id )[0];
+        table[e] = set.offsets[id] | ( ( set.sizes[id] - 1 ) << SET_ENTRY_SIZE_SHIFT ) | ( id << SET_ENTRY_ID_SHIFT );
+        first[byte] = first[byte] == 0 ? ( e | ( 1u << 16 ) ) : first[byte] + ( 1u << 16 );
+    }
+}
+
+/** planSearch for a set: m_min decides whether the clipped range can hold any match. */
+inline SearchPlan
+planSearchSet( const std::vector<std::pair<uint64_t, uint64_t> >& map, uint64_t start, uint64_t end, const PatternSet& set,
+               size_t cap, bool packed, uint64_t fileBytes )
+{
+    if ( !patternSetError( set.sizes.data(), set.count() ).empty() ) throw std::invalid_argument( "search: not a set of patterns" );
+    return planSearch( map, start, end, set.mMin, cap, packed, fileBytes );
+}
+
+/**
+ * Every pair (p, i), in (p, i) order and once, with D[p : p + m_i] == P_i whose bytes lie inside the extents' union but not
+ * inside a single extent.  `seams` as for seamMatches, each with its head and tail of seamLength( m_max, size ) bytes.
+ */
+inline std::vector<SetMatch>
+seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams )
+{
+    if ( !patternSetError( set.sizes.data(), set.count() ).empty() ) throw std::invalid_argument( "seamMatchesSet: not a set of patterns" );
+    for ( size_t i = 0; i < seams.size(); ++i ) {
+        const auto n = seamLength( set.mMax, seams[i].size );
+        if ( seams[i].head.size() != n || seams[i].tail.size() != n
+             || ( i > 0 && seams[i].fileOffset != seams[i - 1].fileOffset + seams[i - 1].size ) ) {
+            throw std::invalid_argument( "seamMatchesSet: extent " + std::to_string( i ) + " does not follow the one in front of "
+                                         "it, or its head and tail have the wrong size" );
+        }
+    }
+    std::vector<SetMatch> matches;
+    if ( set.mMax == 1 || seams.empty() ) return matches;
+    const uint64_t unionEnd = seams.back().fileOffset + seams.back().size;
+    const uint32_t reach = set.mMax - 1;
+    std::vector<uint8_t> window;
+    for ( size_t i = 0; i + 1 < seams.size(); ++i ) {
+        const auto& extent = seams[i];
+        if ( extent.size == 0 ) continue;
+        const uint64_t b = extent.fileOffset + extent.size;
+        if ( b == unionEnd ) break;    /* nothing but empty extents follows */
+        /* the tail of i, then the heads behind b until m_max - 1 bytes are there or the extents end: the same window as
+         * seamMatches builds for m_max, of which pattern i looks at the m_i - 1 bytes on either side of b */
+        window.assign( extent.tail.begin(), extent.tail.end() );
+        const size_t inFront = window.size();
+        for ( size_t j = i + 1; j < seams.size() && window.size() - inFront < reach; ++j ) {
+            window.insert( window.end(), seams[j].head.begin(), seams[j].head.end() );
+        }
+        /* ascending p, then ascending id: a pair starts in the tail, reaches behind b and fits into the window */
+        for ( size_t at = 0; at < inFront; ++at ) {
+            for ( uint32_t id = 0; id < set.count(); ++id ) {
+                const uint32_t m = set.sizes[id];
+                if ( at + m <= inFront || at + m > window.size() ) continue;
+                if ( std::memcmp( window.data() + at, set.pattern( id ), m ) == 0 ) matches.push_back( { b - inFront + at, id } );
+            }
+        }
+    }
+    return matches;
+}
+
+/** Of the pairs of one extent (ascending positions in D), how many have p + m_max <= the extent's end: each sorts in
+ * front of every pair that needs a byte behind the extent, whatever its pattern (the file's header says why). */
+[[nodiscard]] inline uint64_t
+safePairs( const uint64_t* positions, uint64_t n, uint64_t extentEnd, uint32_t mMax )
+{
+    if ( extentEnd < mMax ) return 0;
+    return (uint64_t)( std::upper_bound( positions, positions + n, extentEnd - mMax ) - positions );
 }
 }  // namespace bz2gpu

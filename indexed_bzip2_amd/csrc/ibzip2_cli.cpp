@@ -22,6 +22,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <iterator>
 #include <string>
 #include <vector>
 
@@ -40,7 +41,8 @@ struct Options
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
     bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false }, grep{ false }, lineNumber{ false };
-    std::string input, output, listCompressedPath, listOffsetsPath, pattern;
+    bool grepFile{ false }, countMatchesFile{ false };
+    std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
     int device{ -1 };
@@ -89,7 +91,15 @@ printHelp()
         "                                Matches and lines are found on the GPU; only the matching lines are copied\n"
         "                                to the host. The exit status is 0 whether or not a line matched: 1 means\n"
         "                                error here.\n"
-        "      --line-number             With --grep: prefix each line with its 1-based line number and ':'.\n\n"
+        "      --grep-file arg           As --grep, for every string of a set at once (grep -F -f): the strings are the\n"
+        "                                lines of the given file (1 to 1024 of them, 1 to 256 bytes each, at most 16384\n"
+        "                                bytes in total; a final empty line is ignored, any other empty line refused).\n"
+        "                                A line that contains several of them is printed once. The data is decoded\n"
+        "                                once for the search whatever the number of strings.\n"
+        "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
+        "                                line, in the file's order.\n"
+        "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
+        "                                and ':'.\n\n"
         " Advanced options:\n"
         "      --buffer-size arg         Controls the output buffer size. By default, the decoded data is written in\n"
         "                                one pass per block. (default: 0)\n\n"
@@ -105,7 +115,34 @@ printHelp()
         "Count the occurrences of a string in a compressed file:\n"
         "  ibzip2-mi355x --count-matches ERROR file.bz2\n\n"
         "Print the lines of a compressed file that contain a string, with their numbers:\n"
-        "  ibzip2-mi355x --grep ERROR --line-number file.bz2\n";
+        "  ibzip2-mi355x --grep ERROR --line-number file.bz2\n\n"
+        "Print the lines that contain any of the strings listed in a file:\n"
+        "  ibzip2-mi355x --grep-file codes.txt file.bz2\n";
+}
+
+/** The patterns of --grep-file / --count-matches-file: the LF-separated lines of the file, concatenated, and their sizes.
+ * A final empty line from a trailing LF is ignored; any other empty line, or a file that cannot be read, is refused. */
+bool
+readPatternFile( const std::string& path, std::string& patterns, std::vector<uint32_t>& sizes )
+{
+    std::ifstream file( path, std::ios::binary );
+    if ( !file ) {
+        std::cerr << "Could not open the pattern file '" << path << "'\n";
+        return false;
+    }
+    const std::string text( ( std::istreambuf_iterator<char>( file ) ), std::istreambuf_iterator<char>() );
+    for ( size_t at = 0; at < text.size(); ) {
+        const auto lf = text.find( '\n', at );
+        const size_t stop = lf == std::string::npos ? text.size() : lf;
+        if ( stop == at ) {
+            std::cerr << "The pattern file '" << path << "' holds an empty line (line " << sizes.size() + 1 << ")\n";
+            return false;
+        }
+        patterns.append( text, at, stop - at );
+        sizes.push_back( (uint32_t)std::min<size_t>( stop - at, 0xFFFFFFFFu ) );
+        at = stop + 1;
+    }
+    return true;
 }
 
 bool
@@ -193,6 +230,8 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "count-lines" ) o.countLines = true;
             else if ( name == "count-matches" ) { if ( !need( o.pattern ) ) return 1; o.countMatches = true; }
             else if ( name == "grep" ) { if ( !need( o.pattern ) ) return 1; o.grep = true; }
+            else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
+            else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
             else if ( name == "line-number" ) o.lineNumber = true;
             else if ( name == "list-compressed-offsets" ) {
                 o.listCompressed = true;
@@ -386,8 +425,12 @@ main( int argc, char** argv )
         std::cerr << "Options '--grep' and '--count-matches' cannot be combined\n";
         return 1;
     }
-    if ( o.lineNumber && !o.grep ) {
-        std::cerr << "Option '--line-number' needs '--grep'\n";
+    if ( (int)o.grep + (int)o.countMatches + (int)o.grepFile + (int)o.countMatchesFile > 1 ) {
+        std::cerr << "Options '--grep', '--count-matches', '--grep-file' and '--count-matches-file' cannot be combined\n";
+        return 1;
+    }
+    if ( o.lineNumber && !o.grep && !o.grepFile ) {
+        std::cerr << "Option '--line-number' needs '--grep' or '--grep-file'\n";
         return 1;
     }
     if ( o.version ) {
@@ -502,6 +545,66 @@ main( int argc, char** argv )
         }
         mi355x_bz2_reader_close( reader );
         if ( !o.lineNumber ) {
+            std::cout.write( bytes.data(), (std::streamsize)bytes.size() );
+        } else {
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < nLines; at += sizes[i], ++i ) {
+                std::cout << numbers[i] + 1 << ':';
+                std::cout.write( bytes.data() + at, (std::streamsize)sizes[i] );
+            }
+        }
+        std::cout.flush();
+        return std::cout.good() ? 0 : 1;
+    }
+
+    /* the same two actions for a set of strings, from the reader's search_set and grep_set */
+    if ( o.grepFile || o.countMatchesFile ) {
+        std::string patterns;
+        std::vector<uint32_t> patternSizes;
+        if ( !readPatternFile( o.patternFile, patterns, patternSizes ) ) return 1;
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        const auto* const set = reinterpret_cast<const uint8_t*>( patterns.data() );
+        const auto nPatterns = (uint32_t)std::min<size_t>( patternSizes.size(), 0xFFFFFFFFu );
+        uint64_t nLines = 0, total = 0, nMatches = 0;
+        std::vector<uint64_t> numbers, sizes, each( patternSizes.size() );
+        std::vector<char> bytes;
+        if ( o.countMatchesFile ) {
+            rc = mi355x_bz2_reader_search_set( reader, set, patternSizes.data(), nPatterns, 0, ~uint64_t( 0 ), 0, &nMatches, each.data() );
+        } else {
+            rc = mi355x_bz2_reader_grep_set( reader, set, patternSizes.data(), nPatterns, '\n', 0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0,
+                                             &nLines, &total );
+            numbers.resize( nLines );
+            sizes.resize( nLines );
+            bytes.resize( total );
+            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );
+            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_line_ranges( reader, bytes.data(), 0 );
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Search failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        if ( o.countMatchesFile ) {
+            for ( const auto count : each ) std::cout << count << "\n";
+        } else if ( !o.lineNumber ) {
             std::cout.write( bytes.data(), (std::streamsize)bytes.size() );
         } else {
             uint64_t at = 0;

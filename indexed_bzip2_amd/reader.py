@@ -395,24 +395,31 @@ class _IndexedBzip2FileParallel:
         self._check(N.lib().mi355x_bz2_reader_line_numbers(self._h, nl, as_u64p(values), len(values), as_u64p(out)))
         return out
 
-    def _grep_arguments(self, pattern, start, end, newline):
-        pattern = self._pattern(pattern)
+    def _grep_arguments(self, pattern, start, end, newline, any_of=False):
+        pattern = N.pattern_set(pattern) if any_of else self._pattern(pattern)
         nl = self._newline(newline)
         start, end = int(start), 2**64 - 1 if end is None else int(end)
         if start < 0 or end < 0:
             raise ValueError("start and end must not be negative")
         return pattern, nl, start, end
 
-    def _grep(self, pattern, start, end, limit, newline, on_device):
-        """Step 1 (mi355x_bz2_reader_grep) and the numbers and sizes of the held lines (_take_grep): (numbers, sizes,
-        total bytes); with limit 0 nothing is held and the number of matching lines comes back instead."""
+    def _grep(self, pattern, start, end, limit, newline, on_device, any_of=False):
+        """Step 1 (mi355x_bz2_reader_grep, or _grep_set for a set of patterns) and the numbers and sizes of the held lines
+        (_take_grep): (numbers, sizes, total bytes); with limit 0 nothing is held and the number of matching lines comes
+        back instead."""
         import numpy as np
         self._require()
-        pattern, nl, start, end = self._grep_arguments(pattern, start, end, newline)
+        pattern, nl, start, end = self._grep_arguments(pattern, start, end, newline, any_of)
         n, total = ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_grep(self._h, pattern, len(pattern), nl, min(start, 2**64 - 1),
-                                                   min(end, 2**64 - 1), limit, 1 if on_device else 0, ctypes.byref(n),
-                                                   ctypes.byref(total)))
+        if any_of:
+            data, sizes, k = pattern
+            self._check(N.lib().mi355x_bz2_reader_grep_set(self._h, data, sizes, k, nl, min(start, 2**64 - 1),
+                                                           min(end, 2**64 - 1), limit, 1 if on_device else 0,
+                                                           ctypes.byref(n), ctypes.byref(total)))
+        else:
+            self._check(N.lib().mi355x_bz2_reader_grep(self._h, pattern, len(pattern), nl, min(start, 2**64 - 1),
+                                                       min(end, 2**64 - 1), limit, 1 if on_device else 0, ctypes.byref(n),
+                                                       ctypes.byref(total)))
         if limit == 0:
             return n.value
         numbers = (ctypes.c_uint64 * max(1, n.value))()
@@ -438,13 +445,16 @@ class _IndexedBzip2FileParallel:
         line of its first byte; start and end bound the occurrences, not the lines.  Three passes on the GPU: the
         search, the line numbers of the matches (k_rank_byte), and the lines themselves; only numbers, sizes and the
         lines' bytes leave it.  Releases matches and line ranges held by earlier calls.  Positionless."""
+        return self._grep_lines(pattern, start, end, limit, newline, False)
+
+    def _grep_lines(self, pattern, start, end, limit, newline, any_of):
         import numpy as np
         limit = self._line_limit(limit)
         if limit == 0:                                 # nothing is asked for: the arguments are checked, nothing runs
             self._require()
-            self._grep_arguments(pattern, start, end, newline)
+            self._grep_arguments(pattern, start, end, newline, any_of)
             return np.empty(0, dtype=np.uint64), []
-        numbers, sizes, total = self._grep(pattern, start, end, limit, newline, False)
+        numbers, sizes, total = self._grep(pattern, start, end, limit, newline, False, any_of)
         out = bytearray(total)
         dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
         self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
@@ -459,17 +469,20 @@ class _IndexedBzip2FileParallel:
         """grep into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), data and
         offsets laid out as read_line_ranges_to_tensor: line i is ``data[offsets[i]:offsets[i + 1]]``.  The lines' bytes
         never pass through the host."""
+        return self._grep_tensor(pattern, start, end, limit, newline, False)
+
+    def _grep_tensor(self, pattern, start, end, limit, newline, any_of):
         import numpy as np
         import torch
         limit = self._line_limit(limit)
         self._require()
-        self._grep_arguments(pattern, start, end, newline)
+        self._grep_arguments(pattern, start, end, newline, any_of)
         torch.cuda.init()
         dev = self._device if self._device >= 0 else torch.cuda.current_device()
         if limit == 0:
             numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
         else:
-            numbers, sizes, total = self._grep(pattern, start, end, limit, newline, True)
+            numbers, sizes, total = self._grep(pattern, start, end, limit, newline, True, any_of)
         data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
         if total:
             # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
@@ -480,6 +493,70 @@ class _IndexedBzip2FileParallel:
         for size in sizes:
             bounds.append(bounds[-1] + size)
         return numbers, data, torch.tensor(bounds, dtype=torch.int64)
+
+    # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
+    # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call
+    def _search_set(self, patterns, start, end, limit):
+        """Step 1 (mi355x_bz2_reader_search_set): (number of pairs, or of the pairs now held; per-pattern counts, which
+        the native call fills for limit 0 only)."""
+        import numpy as np
+        self._require()
+        data, sizes, k = N.pattern_set(patterns)
+        start, end = int(start), 2**64 - 1 if end is None else int(end)
+        if start < 0 or end < 0:
+            raise ValueError("start and end must not be negative")
+        n = ctypes.c_uint64()
+        each = np.zeros(k, dtype=np.uint64)
+        self._check(N.lib().mi355x_bz2_reader_search_set(self._h, data, sizes, k, min(start, 2**64 - 1), min(end, 2**64 - 1),
+                                                         limit, ctypes.byref(n),
+                                                         each.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return n.value, each
+
+    def count_matches_each(self, patterns, start=0, end=None):
+        """How often each byte string of the sequence `patterns` (1 to 1 024 of them, 1 to 256 bytes each, at most 16 384
+        bytes in total) occurs in data[start:end] -> numpy uint64, one count per pattern in the caller's order, each
+        equal to count_matches of that pattern.  Equal patterns and prefixes of one another are allowed.  ONE decode of
+        every block of the range whatever the number of patterns; only the counts leave the GPU.  Positionless."""
+        return self._search_set(patterns, start, end, 0)[1]
+
+    def find_all_any(self, patterns, start=0, end=None, limit=None):
+        """The occurrences of every pattern of `patterns` in data[start:end] -> (positions numpy uint64, ids numpy
+        uint32): pairs (offset, index of the pattern that occurs there) by ascending offset, then ascending index, at
+        most `limit` of them (None: all).  The pairs of pattern i are exactly find_all(patterns[i], start, end), and the
+        result with a limit is the first `limit` pairs of the result without one.  Positionless."""
+        import numpy as np
+        if limit is not None and int(limit) < 0:
+            raise ValueError("limit must not be negative")
+        if limit is not None and int(limit) == 0:
+            N.pattern_set(patterns)
+            return np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint32)
+        n, _ = self._search_set(patterns, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1))
+        positions, ids = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint32)
+        self._check(N.lib().mi355x_bz2_reader_take_set_matches(
+            self._h, positions.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if n else None,
+            ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if n else None, n))
+        return positions, ids
+
+    def find_any(self, patterns, start=0, end=None):
+        """(offset, index) of the first occurrence of any pattern of `patterns` in data[start:end] -- the lowest index
+        among those that occur at that offset --, or (-1, -1): find_all_any with limit=1."""
+        positions, ids = self.find_all_any(patterns, start, end, 1)
+        return (int(positions[0]), int(ids[0])) if len(positions) else (-1, -1)
+
+    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+        """grep for a set of patterns (`grep -n -F -f FILE`) -> (numbers, lines): the lines that hold the first byte of an
+        occurrence of at least one pattern, each once.  The set search is the first pass (one decode of the range
+        whatever the number of patterns); the rank and line passes are grep's."""
+        return self._grep_lines(patterns, start, end, limit, newline, True)
+
+    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n"):
+        """The number of distinct lines that hold an occurrence of at least one pattern (`grep -c -F -f FILE`)."""
+        return self._grep(patterns, start, end, 0, newline, False, True)
+
+    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+        """grep_any into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), as
+        grep_to_tensor."""
+        return self._grep_tensor(patterns, start, end, limit, newline, True)
 
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
@@ -615,6 +692,30 @@ class IndexedBzip2File(io.BufferedReader):
     def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
         """See _IndexedBzip2FileParallel.grep_to_tensor."""
         return self._open_reader().grep_to_tensor(pattern, start, end, limit, newline)
+
+    def count_matches_each(self, patterns, start=0, end=None):
+        """See _IndexedBzip2FileParallel.count_matches_each."""
+        return self._open_reader().count_matches_each(patterns, start, end)
+
+    def find_all_any(self, patterns, start=0, end=None, limit=None):
+        """See _IndexedBzip2FileParallel.find_all_any."""
+        return self._open_reader().find_all_any(patterns, start, end, limit)
+
+    def find_any(self, patterns, start=0, end=None):
+        """See _IndexedBzip2FileParallel.find_any."""
+        return self._open_reader().find_any(patterns, start, end)
+
+    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.grep_any."""
+        return self._open_reader().grep_any(patterns, start, end, limit, newline)
+
+    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.count_matching_lines_any."""
+        return self._open_reader().count_matching_lines_any(patterns, start, end, newline)
+
+    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+        """See _IndexedBzip2FileParallel.grep_any_to_tensor."""
+        return self._open_reader().grep_any_to_tensor(patterns, start, end, limit, newline)
 
 
 builtins_open = builtins.open
