@@ -23,6 +23,10 @@ class BitWriter:
             self.acc &= (1 << keep) - 1
             self.n = keep
 
+    def position(self):
+        """Bits written so far."""
+        return len(self.out) * 8 + self.n
+
     def align(self):
         if self.n % 8:
             self.put(0, 8 - self.n % 8)
@@ -200,6 +204,24 @@ def encode_block_from_bwt(last, orig_ptr, block_crc, level=9, n_groups=2, length
     selectors_written = selectors + [0] * extra_selectors
     if faults.get("drop_selectors"):
         selectors_written = selectors_written[:-faults["drop_selectors"]]
+    return encode_block_from_symbols(symbols, declared, orig_ptr, block_crc, [lengths for lengths, _ in tables], selectors,
+                                     selectors_written, level, faults)[0]
+
+
+def encode_block_from_symbols(symbols, declared, orig_ptr, block_crc, tables, selectors, selectors_written=None, level=9,
+                              faults=None):
+    """Single-stream, single-block .bz2 that carries `symbols` (RUNA = 0, RUNB = 1, MTF position + 1, the end of block
+    len(declared) + 1 last) as they are.  declared: the byte values of the map; tables: 2 to 6 lists of code lengths over
+    the alphabet len(declared) + 2; selectors: the table of every 50 symbols; selectors_written: what the header carries
+    (default: `selectors`; longer: surplus selectors of any pattern).  faults: the header fields of
+    encode_block_from_bwt.  Returns (stream, the absolute bit position of every group's first code)."""
+    faults = faults or {}
+    declared = sorted(declared)
+    assert len(selectors) == (len(symbols) + 49) // 50
+    if selectors_written is None:
+        selectors_written = selectors
+    n_groups = len(tables)
+    tables = [(lengths, canonical_codes(lengths)) for lengths in tables]
 
     w = BitWriter()
     w.put(0x425A68, 24)
@@ -232,9 +254,12 @@ def encode_block_from_bwt(last, orig_ptr, block_crc, level=9, n_groups=2, length
                 w.put(3, 2)
                 cur -= 1
             w.put(0, 1)
+    group_start_bits = []
     for i, s in enumerate(symbols):
+        if i % 50 == 0:
+            group_start_bits.append(w.position())
         lengths, codes = tables[selectors[i // 50]]
         w.put(codes[s], lengths[s])
     w.put(0x177245385090, 48)
     w.put(block_crc, 32)      # one block: stream CRC = rotl(0, 1) ^ blockCRC
-    return w.bytes()
+    return w.bytes(), group_start_bits
