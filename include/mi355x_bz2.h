@@ -286,11 +286,23 @@ int mi355x_bz2_rank_byte( mi355x_bz2_ctx* ctx, const mi355x_bz2_rank_query* quer
  *                 ascending within a span, the first `capacity` of them (k_count_bytes, k_scan_tiles, k_emit_bytes: the
  *                 order comes from prefix sums, the same call gives the same array).  counts[i] is the true count of
  *                 span i whatever the capacity.  If the positions do not fit on the device the call fails with
- *                 MI355X_BZ2_ERR_DEVICE; nothing is truncated silently. */
+ *                 MI355X_BZ2_ERR_DEVICE; nothing is truncated silently.
+ * The _ex forms take `flags`, a union of MI355X_BZ2_SEARCH_* bits; the plain forms are the _ex forms with flags 0.  Any
+ * other bit is MI355X_BZ2_ERR_INVALID_ARGUMENT before anything is launched, and mi355x_bz2_last_error names the bits.
+ *   MI355X_BZ2_SEARCH_IGNORE_CASE  two bytes are equal if they are equal after b -> b | 0x20 for 'A' <= b <= 'Z' (every
+ *                 other byte, 0x80 .. 0xFF included, stays as it is: bytes.lower() of Python, `LC_ALL=C grep -i`).  The
+ *                 pattern may be given in any case.  Nothing else changes: spans, overlaps, order and capacity as above
+ *                 (the folding instantiations of the same kernels, which read the same bytes). */
+#define MI355X_BZ2_SEARCH_IGNORE_CASE 1u
 int mi355x_bz2_count_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
                             uint32_t pattern_size, uint64_t* counts );
 int mi355x_bz2_find_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
                            uint32_t pattern_size, uint64_t* positions, uint64_t capacity, uint64_t* counts );
+int mi355x_bz2_count_bytes_ex( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                               uint32_t pattern_size, uint32_t flags, uint64_t* counts );
+int mi355x_bz2_find_bytes_ex( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                              uint32_t pattern_size, uint32_t flags, uint64_t* positions, uint64_t capacity,
+                              uint64_t* counts );
 
 /* A SET of byte strings in spans of the last batch's output, in one pass over the bytes: the kernels under the reader's
  * search_set.  `patterns` is the concatenation of the n_patterns patterns in set order, pattern_sizes[i] the size m_i of
@@ -307,12 +319,22 @@ int mi355x_bz2_find_bytes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* span
  *                     (position, id) within a span, the first `capacity` of them (k_count_set, k_scan_tiles, k_emit_set:
  *                     the order comes from prefix sums, the same call gives the same arrays).  The counts are true
  *                     whatever the capacity.  If the pairs do not fit on the device the call fails with
- *                     MI355X_BZ2_ERR_DEVICE; nothing is truncated silently. */
+ *                     MI355X_BZ2_ERR_DEVICE; nothing is truncated silently.
+ * The _ex forms take the flags of _count_bytes_ex.  With MI355X_BZ2_SEARCH_IGNORE_CASE a pair is (p, i) with output[p :
+ * p + m_i] equal to pattern i under the fold; patterns that are equal under the fold, or prefixes of one another under
+ * it, each report their own pairs, and the order stays (position, id). */
 int mi355x_bz2_count_bytes_set( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
                                 const uint32_t* pattern_sizes, uint32_t n_patterns, uint64_t* counts, uint64_t* per_pattern );
 int mi355x_bz2_find_bytes_set( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
                                const uint32_t* pattern_sizes, uint32_t n_patterns, uint64_t* positions, uint32_t* ids,
                                uint64_t capacity, uint64_t* counts, uint64_t* per_pattern );
+int mi355x_bz2_count_bytes_set_ex( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n,
+                                   const uint8_t* patterns, const uint32_t* pattern_sizes, uint32_t n_patterns,
+                                   uint32_t flags, uint64_t* counts, uint64_t* per_pattern );
+int mi355x_bz2_find_bytes_set_ex( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n,
+                                  const uint8_t* patterns, const uint32_t* pattern_sizes, uint32_t n_patterns,
+                                  uint32_t flags, uint64_t* positions, uint32_t* ids, uint64_t capacity, uint64_t* counts,
+                                  uint64_t* per_pattern );
 
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
@@ -515,9 +537,16 @@ int mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dst
  * host and *n_matches is their number; no launch is started after the one in which the limit was reached (launches
  * already taken by a context finish).
  * Step 2, _take_matches: copies the held positions (at most `capacity`) and releases them; the next search, or close,
- * releases them as well.  Held matches and held line ranges are independent. */
+ * releases them as well.  Held matches and held line ranges are independent.
+ * _search_ex is _search with `flags` (MI355X_BZ2_SEARCH_*; _search is flags 0).  An unknown bit is
+ * MI355X_BZ2_ERR_INVALID_ARGUMENT, named by _last_error, before anything is launched or held.  With
+ * MI355X_BZ2_SEARCH_IGNORE_CASE a match is every p with fold( D[p + j] ) == fold( P[j] ) for all j < m, fold( b ) =
+ * b | 0x20 for 'A' <= b <= 'Z' and b otherwise; the range rule, overlaps and the limit are unchanged, the same launches
+ * run, and the seam bytes are folded on the host. */
 int mi355x_bz2_reader_search( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint64_t start,
                               uint64_t end, uint64_t limit, uint64_t* n_matches );
+int mi355x_bz2_reader_search_ex( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint32_t flags,
+                                 uint64_t start, uint64_t end, uint64_t limit, uint64_t* n_matches );
 int mi355x_bz2_reader_take_matches( mi355x_bz2_reader* r, uint64_t* positions, uint64_t capacity );
 
 /* ---- grep and line numbers: the line functions and the search joined.  D, nl, N and s(k) as under line access.
@@ -546,9 +575,14 @@ int mi355x_bz2_reader_line_numbers( mi355x_bz2_reader* r, uint8_t nl, const uint
  * held by earlier calls are released.
  * Step 2, _take_grep: the numbers and byte sizes of the held lines (at most `capacity`); the bytes stay held.  With
  * nothing held: MI355X_BZ2_ERR_INVALID_ARGUMENT.
- * Step 3, the bytes: _take_line_ranges, which releases everything. */
+ * Step 3, the bytes: _take_line_ranges, which releases everything.
+ * _grep_ex passes `flags` to its search pass (the matches are those of _search_ex); the rank and line passes do not
+ * depend on them. */
 int mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint8_t nl, uint64_t start,
                             uint64_t end, uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+int mi355x_bz2_reader_grep_ex( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t pattern_size, uint32_t flags, uint8_t nl,
+                               uint64_t start, uint64_t end, uint64_t max_lines, int keep_on_device, uint64_t* n_lines,
+                               uint64_t* total_bytes );
 int mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* line_numbers, uint64_t* byte_sizes, uint64_t capacity );
 
 /* ---- search and grep for a set of patterns: what `grep -F -f FILE` does, with ONE decode of every block of the range
@@ -566,10 +600,14 @@ int mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* line_numbers, u
  * m_max bytes in front of its end (a long pattern that crosses the front's end may sort in front of a short one inside).
  * Step 2, _take_set_matches: copies the held pairs (at most `capacity`) and releases them; the next set search, or
  * close, releases them as well.  Held set matches are independent of held single-pattern matches and of held line
- * ranges. */
+ * ranges.
+ * _search_set_ex and _grep_set_ex take the flags of _search_ex, checked with the set before anything is launched. */
 int mi355x_bz2_reader_search_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
                                   uint32_t n_patterns, uint64_t start, uint64_t end, uint64_t limit, uint64_t* n_matches,
                                   uint64_t* per_pattern );
+int mi355x_bz2_reader_search_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
+                                     uint32_t n_patterns, uint32_t flags, uint64_t start, uint64_t end, uint64_t limit,
+                                     uint64_t* n_matches, uint64_t* per_pattern );
 int mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* positions, uint32_t* ids, uint64_t capacity );
 /* _grep with the set search as its first pass: a matching line is a line that holds the first byte of at least one pair,
  * each reported once (the positions are deduplicated before the rank pass).  _take_grep and _take_line_ranges serve it
@@ -577,6 +615,9 @@ int mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* position
 int mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
                                 uint32_t n_patterns, uint8_t nl, uint64_t start, uint64_t end, uint64_t max_lines,
                                 int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+int mi355x_bz2_reader_grep_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
+                                   uint32_t n_patterns, uint32_t flags, uint8_t nl, uint64_t start, uint64_t end,
+                                   uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

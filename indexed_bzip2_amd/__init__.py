@@ -9,7 +9,9 @@ Beyond the reference's API the reader answers questions about the decoded file w
 (count_matches, find_all, find: every offset p with data[p:p + len(pattern)] == pattern, overlapping occurrences included)
 and which lines hold it (grep, count_matching_lines, grep_to_tensor: the lines of the matches' first bytes, each once,
 whole, with their 0-based numbers).  The same for a set of up to 1 024 byte strings with one decode of the file per call
-(count_matches_each, find_all_any, find_any, grep_any, count_matching_lines_any, grep_any_to_tensor).
+(count_matches_each, find_all_any, find_any, grep_any, count_matching_lines_any, grep_any_to_tensor).  Every one of these
+search and grep methods takes the keyword-only ignore_case=True, which folds the ASCII letters of pattern and data on the
+GPU (bytes.lower() on both sides, `LC_ALL=C grep -i`; the bytes 0x80 to 0xFF are never folded).
 """
 __version__ = "0.1.0"
 

@@ -164,6 +164,15 @@ SYMBOLS = [
                                                    ctypes.c_uint32, _u64p, _u64p]),
     ("mi355x_bz2_find_bytes_set", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
                                                   ctypes.c_uint32, _u64p, _u32p, ctypes.c_uint64, _u64p, _u64p]),
+    ("mi355x_bz2_count_bytes_ex", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
+                                                  ctypes.c_uint32, ctypes.c_uint32, _u64p]),
+    ("mi355x_bz2_find_bytes_ex", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p,
+                                                 ctypes.c_uint32, ctypes.c_uint32, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_count_bytes_set_ex", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
+                                                      ctypes.c_uint32, ctypes.c_uint32, _u64p, _u64p]),
+    ("mi355x_bz2_find_bytes_set_ex", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
+                                                     ctypes.c_uint32, ctypes.c_uint32, _u64p, _u32p, ctypes.c_uint64, _u64p,
+                                                     _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -202,6 +211,16 @@ SYMBOLS = [
     ("mi355x_bz2_reader_grep_set", ctypes.c_int, [_vp, ctypes.c_char_p, _u32p, ctypes.c_uint32, ctypes.c_uint8,
                                                    ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p,
                                                    _u64p]),
+    ("mi355x_bz2_reader_search_ex", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64,
+                                                    ctypes.c_uint64, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_reader_grep_ex", ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint8,
+                                                  ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p,
+                                                  _u64p]),
+    ("mi355x_bz2_reader_search_set_ex", ctypes.c_int, [_vp, ctypes.c_char_p, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
+    ("mi355x_bz2_reader_grep_set_ex", ctypes.c_int, [_vp, ctypes.c_char_p, _u32p, ctypes.c_uint32, ctypes.c_uint32,
+                                                      ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                      ctypes.c_int, _u64p, _u64p]),
     ("mi355x_bz2_reader_join_threads", ctypes.c_int, [_vp]),
     ("mi355x_bz2_reader_set_verify_stream_crc", ctypes.c_int, [_vp, ctypes.c_int]),
     ("mi355x_bz2_reader_streams_verified", ctypes.c_uint64, [_vp]),
@@ -296,6 +315,9 @@ def _byte_view(obj) -> memoryview:
 
 
 SET_MAX_PATTERNS, SET_MAX_PATTERN_BYTES, SET_MAX_BYTES = 1024, 256, 16384
+
+
+SEARCH_IGNORE_CASE = 1          # MI355X_BZ2_SEARCH_IGNORE_CASE
 
 
 def pattern_set(patterns, check=True):
@@ -533,58 +555,64 @@ class Decoder:
         self._check(lib().mi355x_bz2_rank_byte(self._h, arr, len(queries), value, out))
         return [out[i] for i in range(len(queries))]
 
-    def count_bytes(self, pattern, spans):
+    def count_bytes(self, pattern, spans, *, ignore_case=False):
         """k_count_bytes: how often the byte string `pattern` (1 to 256 bytes) occurs in each span [(offset, size)] of the
-        last batch's output.  A match lies inside its span; matches that overlap themselves all count."""
+        last batch's output.  A match lies inside its span; matches that overlap themselves all count.  ignore_case=True:
+        the folding instantiation, which compares pattern and data under bytes.lower()."""
+        flags = SEARCH_IGNORE_CASE if ignore_case else 0
         pattern = bytes(pattern)
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
         out = (ctypes.c_uint64 * max(1, len(spans)))()
-        self._check(lib().mi355x_bz2_count_bytes(self._h, arr, len(spans), pattern, len(pattern), out))
+        self._check(lib().mi355x_bz2_count_bytes_ex(self._h, arr, len(spans), pattern, len(pattern), flags, out))
         return list(out[:len(spans)])
 
-    def find_bytes(self, pattern, spans, capacity=None):
+    def find_bytes(self, pattern, spans, capacity=None, *, ignore_case=False):
         """k_count_bytes, k_scan_tiles, k_emit_bytes: (positions, counts) -- the offsets in the last batch's output at
         which `pattern` occurs, span by span and ascending within a span, the first `capacity` of them (None: all), and
         the true count of every span."""
+        flags = SEARCH_IGNORE_CASE if ignore_case else 0
         pattern = bytes(pattern)
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
         counts = (ctypes.c_uint64 * max(1, len(spans)))()
         if capacity is None:
-            self._check(lib().mi355x_bz2_count_bytes(self._h, arr, len(spans), pattern, len(pattern), counts))
+            self._check(lib().mi355x_bz2_count_bytes_ex(self._h, arr, len(spans), pattern, len(pattern), flags, counts))
             capacity = sum(counts[:len(spans)])
         positions = (ctypes.c_uint64 * max(1, capacity))()
-        self._check(lib().mi355x_bz2_find_bytes(self._h, arr, len(spans), pattern, len(pattern), positions, capacity, counts))
+        self._check(lib().mi355x_bz2_find_bytes_ex(self._h, arr, len(spans), pattern, len(pattern), flags, positions, capacity,
+                                                   counts))
         found = min(capacity, sum(counts[:len(spans)]))
         return list(positions[:found]), list(counts[:len(spans)])
 
-    def count_bytes_set(self, patterns, spans):
+    def count_bytes_set(self, patterns, spans, *, ignore_case=False):
         """k_count_set: (counts, per_pattern) -- the number of (position, pattern) pairs in each span [(offset, size)] of
         the last batch's output, and how often each pattern of the set occurs over all spans."""
+        flags = SEARCH_IGNORE_CASE if ignore_case else 0
         data, sizes, k = pattern_set(patterns, check=False)
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
         counts = (ctypes.c_uint64 * max(1, len(spans)))()
         each = (ctypes.c_uint64 * max(1, k))()
-        self._check(lib().mi355x_bz2_count_bytes_set(self._h, arr, len(spans), data, sizes, k, counts, each))
+        self._check(lib().mi355x_bz2_count_bytes_set_ex(self._h, arr, len(spans), data, sizes, k, flags, counts, each))
         return list(counts[:len(spans)]), list(each[:k])
 
-    def find_bytes_set(self, patterns, spans, capacity=None):
+    def find_bytes_set(self, patterns, spans, capacity=None, *, ignore_case=False):
         """k_count_set, k_scan_tiles, k_emit_set: (positions, ids, counts) -- the pairs (offset in the last batch's output,
         index of the pattern in the set), span by span and by ascending (position, id) within a span, the first `capacity`
         of them (None: all), and the true number of pairs of every span."""
+        flags = SEARCH_IGNORE_CASE if ignore_case else 0
         data, sizes, k = pattern_set(patterns, check=False)
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
         counts = (ctypes.c_uint64 * max(1, len(spans)))()
         if capacity is None:
-            self._check(lib().mi355x_bz2_count_bytes_set(self._h, arr, len(spans), data, sizes, k, counts, None))
+            self._check(lib().mi355x_bz2_count_bytes_set_ex(self._h, arr, len(spans), data, sizes, k, flags, counts, None))
             capacity = sum(counts[:len(spans)])
         positions = (ctypes.c_uint64 * max(1, capacity))()
         ids = (ctypes.c_uint32 * max(1, capacity))()
-        self._check(lib().mi355x_bz2_find_bytes_set(self._h, arr, len(spans), data, sizes, k, positions, ids, capacity, counts,
-                                                    None))
+        self._check(lib().mi355x_bz2_find_bytes_set_ex(self._h, arr, len(spans), data, sizes, k, flags, positions, ids, capacity,
+                                                       counts, None))
         found = min(capacity, sum(counts[:len(spans)]))
         return list(positions[:found]), list(ids[:found]), list(counts[:len(spans)])
 

@@ -30,14 +30,15 @@ int gatherResult( mi355x_bz2_ctx* ctx, const mi355x_bz2_gather_piece* pieces, ui
  * as mi355x_bz2_find_bytes with that one span.  *count is the true count; with `positions` given it is resized to the
  * first min( *count, limit ) offsets in the output (nullptr: count only, no emitting pass).  The first and the last
  * min( m - 1, extent.size ) bytes of the extent come back in the same D2H as the count: seamBytes[0, ...) and
- * seamBytes[256, ...) of a 512-byte array. */
-int searchOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m, uint64_t limit,
-                  std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes );
+ * seamBytes[256, ...) of a 512-byte array, raw whatever the flags.  `flags`: MI355X_BZ2_SEARCH_*. */
+int searchOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m, uint32_t flags,
+                  uint64_t limit, std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes );
 
 /** searchOutput for a set of patterns (as mi355x_bz2_find_bytes_set with that one span): *count is the true number of
  * pairs; with `positions` and `ids` given they are resized to the first min( *count, limit ) pairs in (position, id) order
  * (both nullptr: count only).  perPattern (may be nullptr) receives the count of every pattern inside the extent.  The
- * first and the last min( m_max - 1, extent.size ) bytes of the extent come back as searchOutput hands them over. */
+ * first and the last min( m_max - 1, extent.size ) bytes of the extent come back as searchOutput hands them over.  The
+ * set carries the one flag there is: makePatternSet's fold. */
 int searchOutputSet( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const bz2gpu::PatternSet& set, uint64_t limit,
                      std::vector<uint64_t>* positions, std::vector<uint32_t>* ids, uint64_t* count, uint64_t* perPattern,
                      uint8_t* seamBytes );

@@ -1832,20 +1832,36 @@ rankBytes( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, uint32_t n, 
     return MI355X_BZ2_OK;
 }
 
+static_assert( SEARCH_IGNORE_CASE == MI355X_BZ2_SEARCH_IGNORE_CASE, "the planner's flag is the C ABI's" );
+
+/** True, with lastError set, if `flags` has a bit that no search knows.  The caller holds the context's mutex. */
+bool
+unknownSearchFlags( mi355x_bz2_ctx* c, const char* what, uint32_t flags )
+{
+    if ( ( flags & ~SEARCH_KNOWN_FLAGS ) == 0 ) return false;
+    char bits[16];
+    std::snprintf( bits, sizeof( bits ), "0x%X", flags & ~SEARCH_KNOWN_FLAGS );
+    c->lastError = std::string( what ) + ": unknown flag bits " + bits;
+    return true;
+}
+
 /**
  * Both string calls.  The start positions every span allows are cut into tiles (spans in caller order, a span given twice
  * is searched twice: its positions are wanted twice), k_count_bytes counts every tile and adds to its span's counter, and
  * the counts -- with the seam bytes of `seam`, if given -- come back in one D2H.  With positions wanted, min( total,
  * capacity ) of them are then made room for on the device (a failure to allocate fails the call), k_scan_tiles turns the
  * tile counts into places, k_emit_bytes writes the positions and a second D2H brings them to `positions`, or to `grown`
- * resized to their number.
+ * resized to their number.  With MI355X_BZ2_SEARCH_IGNORE_CASE in `flags` the pattern is uploaded under foldAscii and the
+ * folding instantiations of the two kernels run; the seam bytes come back raw.
  */
 int
 searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-             uint32_t m, bool wantPositions, uint64_t capacity, uint64_t* positions, std::vector<uint64_t>* grown,
-             uint64_t* counts, const mi355x_bz2_byte_span* seam, uint8_t* seamBytes )
+             uint32_t m, uint32_t flags, bool wantPositions, uint64_t capacity, uint64_t* positions,
+             std::vector<uint64_t>* grown, uint64_t* counts, const mi355x_bz2_byte_span* seam, uint8_t* seamBytes )
 {
     const std::scoped_lock lock( c->mutex );
+    if ( unknownSearchFlags( c, what, flags ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    const bool fold = ( flags & SEARCH_IGNORE_CASE ) != 0;
     if ( c->pendingBlocks != 0 ) {
         c->lastError = std::string( what ) + ": a batch is in flight";
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
@@ -1898,15 +1914,16 @@ searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* sp
         }
     }
     std::memset( c->hSearch.bytes + patternAt, 0, SEARCH_MAX_PATTERN );
-    std::memcpy( c->hSearch.bytes + patternAt, pattern, m );
+    for ( uint32_t j = 0; j < m; ++j ) c->hSearch.bytes[patternAt + j] = fold ? foldAscii( pattern[j] ) : pattern[j];
     uint8_t* const d = c->dSearch.bytes;
     const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
     auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
     HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
     if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_count_bytes, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0, c->stream, dTiles, c->dOut,
-                            d + patternAt, m, dTileCounts, reinterpret_cast<unsigned long long*>( d + resultsAt ) );
+        hipLaunchKernelGGL( fold ? k_count_bytes<true> : k_count_bytes<false>, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ),
+                            0, c->stream, dTiles, c->dOut, d + patternAt, m, dTileCounts,
+                            reinterpret_cast<unsigned long long*>( d + resultsAt ) );
         HIP_TRY( c, hipGetLastError() );
     }
     if ( seamN > 0 ) {
@@ -1944,8 +1961,8 @@ searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* sp
     auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
     hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
     HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( k_emit_bytes, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0, c->stream, dTiles, c->dOut,
-                        d + patternAt, m, dPlaces, wanted, dPositions );
+    hipLaunchKernelGGL( fold ? k_emit_bytes<true> : k_emit_bytes<false>, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0,
+                        c->stream, dTiles, c->dOut, d + patternAt, m, dPlaces, wanted, dPositions );
     HIP_TRY( c, hipGetLastError() );
     HIP_TRY( c, hipMemcpyAsync( positions, dPositions, need, hipMemcpyDeviceToHost, c->stream ) );
     HIP_TRY( c, hipStreamSynchronize( c->stream ) );
@@ -1958,7 +1975,8 @@ searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* sp
  * pattern, and the counts -- with the seam bytes of `seam`, if given: min( m_max - 1, size ) each -- come back in one
  * D2H.  With pairs wanted, k_scan_tiles and k_emit_set write min( total, capacity ) positions and ids, which a second D2H
  * brings to `positions` and `ids`, or to `grownPositions` and `grownIds` resized to their number.  perPattern (may be
- * null) receives the count of every pattern over all spans.
+ * null) receives the count of every pattern over all spans.  A set made with fold gets its image under foldAscii and the
+ * folding instantiations of the two kernels.
  */
 int
 searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const PatternSet& set,
@@ -1975,6 +1993,7 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
         return span.size <= c->outSize && span.offset <= c->outSize - span.size;
     };
     const uint32_t k = set.count(), mMin = set.mMin;
+    const bool fold = set.fold;
     uint64_t nTiles = 0;
     for ( uint32_t i = 0; i < n; ++i ) {
         if ( !inside( spans[i] ) ) {
@@ -2020,7 +2039,7 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
                                (uint32_t)std::min<uint64_t>( SEARCH_TILE, starts - at ), s };
         }
     }
-    writeSetImage( set, c->hSearch.bytes + imageAt );
+    writeSetImage( set, c->hSearch.bytes + imageAt, fold );
     uint8_t* const d = c->dSearch.bytes;
     const auto* const dTiles = reinterpret_cast<const SetTile*>( d );
     auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
@@ -2029,7 +2048,7 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
     HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
     HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
     if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_count_set, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
+        hipLaunchKernelGGL( fold ? k_count_set<true> : k_count_set<false>, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
                             d + imageAt, nBytes, k, dTileCounts, reinterpret_cast<unsigned long long*>( d + resultsAt ),
                             reinterpret_cast<unsigned long long*>( d + eachAt ) );
         HIP_TRY( c, hipGetLastError() );
@@ -2074,7 +2093,7 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
     auto* const dIds = reinterpret_cast<uint32_t*>( c->dSearchPositions.bytes + idsAt );
     hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
     HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( k_emit_set, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
+    hipLaunchKernelGGL( fold ? k_emit_set<true> : k_emit_set<false>, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
                         d + imageAt, nBytes, k, dPlaces, wanted, dPositions, dIds );
     HIP_TRY( c, hipGetLastError() );
     HIP_TRY( c, hipMemcpyAsync( positions, dPositions, idsAt, hipMemcpyDeviceToHost, c->stream ) );
@@ -2083,17 +2102,19 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
     return MI355X_BZ2_OK;
 }
 
-/** The set of a C ABI call, checked: false with lastError set if it breaks a limit. */
+/** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
-takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, PatternSet* set )
+takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
+         PatternSet* set )
 {
+    const std::scoped_lock lock( c->mutex );
+    if ( unknownSearchFlags( c, what, flags ) ) return false;
     const auto why = patternSetError( sizes, n );
     if ( !why.empty() ) {
-        const std::scoped_lock lock( c->mutex );
         c->lastError = std::string( what ) + ": " + why;
         return false;
     }
-    *set = makePatternSet( patterns, sizes, n );
+    *set = makePatternSet( patterns, sizes, n, ( flags & SEARCH_IGNORE_CASE ) != 0 );
     return true;
 }
 }  // namespace
@@ -2113,11 +2134,11 @@ mi355x::searchOutputSet( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, 
 
 int
 mi355x::searchOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m,
-                      uint64_t limit, std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes )
+                      uint32_t flags, uint64_t limit, std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes )
 {
     if ( c == nullptr || pattern == nullptr || count == nullptr || seamBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytes( c, "search", &extent, 1, pattern, m, positions != nullptr, limit, nullptr, positions, count, &extent,
-                        seamBytes );
+    return searchBytes( c, "search", &extent, 1, pattern, m, flags, positions != nullptr, limit, nullptr, positions, count,
+                        &extent, seamBytes );
 }
 
 int
@@ -2177,38 +2198,76 @@ mi355x_bz2_rank_byte( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, u
 }
 
 int
-mi355x_bz2_count_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-                        uint32_t patternSize, uint64_t* counts )
+mi355x_bz2_count_bytes_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                           uint32_t patternSize, uint32_t flags, uint64_t* counts )
 {
     if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     }
-    return searchBytes( c, "count_bytes", spans, n, pattern, patternSize, false, 0, nullptr, nullptr, counts, nullptr, nullptr );
+    return searchBytes( c, "count_bytes", spans, n, pattern, patternSize, flags, false, 0, nullptr, nullptr, counts, nullptr,
+                        nullptr );
+}
+
+int
+mi355x_bz2_count_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                        uint32_t patternSize, uint64_t* counts )
+{
+    return mi355x_bz2_count_bytes_ex( c, spans, n, pattern, patternSize, 0, counts );
+}
+
+int
+mi355x_bz2_find_bytes_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
+                          uint32_t patternSize, uint32_t flags, uint64_t* positions, uint64_t capacity, uint64_t* counts )
+{
+    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
+         || ( capacity > 0 && positions == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return searchBytes( c, "find_bytes", spans, n, pattern, patternSize, flags, true, capacity, positions, nullptr, counts,
+                        nullptr, nullptr );
 }
 
 int
 mi355x_bz2_find_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
                        uint32_t patternSize, uint64_t* positions, uint64_t capacity, uint64_t* counts )
 {
-    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
-         || ( capacity > 0 && positions == nullptr ) ) {
+    return mi355x_bz2_find_bytes_ex( c, spans, n, pattern, patternSize, 0, positions, capacity, counts );
+}
+
+int
+mi355x_bz2_count_bytes_set_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                               const uint32_t* patternSizes, uint32_t nPatterns, uint32_t flags, uint64_t* counts,
+                               uint64_t* perPattern )
+{
+    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     }
-    return searchBytes( c, "find_bytes", spans, n, pattern, patternSize, true, capacity, positions, nullptr, counts, nullptr,
-                        nullptr );
+    PatternSet set;
+    if ( !takeSet( c, "count_bytes_set", patterns, patternSizes, nPatterns, flags, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return searchBytesSet( c, "count_bytes_set", spans, n, set, false, 0, nullptr, nullptr, nullptr, nullptr, counts, perPattern,
+                           nullptr, nullptr );
 }
 
 int
 mi355x_bz2_count_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
                             const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* counts, uint64_t* perPattern )
 {
-    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
+    return mi355x_bz2_count_bytes_set_ex( c, spans, n, patterns, patternSizes, nPatterns, 0, counts, perPattern );
+}
+
+int
+mi355x_bz2_find_bytes_set_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
+                              const uint32_t* patternSizes, uint32_t nPatterns, uint32_t flags, uint64_t* positions,
+                              uint32_t* ids, uint64_t capacity, uint64_t* counts, uint64_t* perPattern )
+{
+    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
+         || ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) ) {
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     }
     PatternSet set;
-    if ( !takeSet( c, "count_bytes_set", patterns, patternSizes, nPatterns, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytesSet( c, "count_bytes_set", spans, n, set, false, 0, nullptr, nullptr, nullptr, nullptr, counts, perPattern,
-                           nullptr, nullptr );
+    if ( !takeSet( c, "find_bytes_set", patterns, patternSizes, nPatterns, flags, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return searchBytesSet( c, "find_bytes_set", spans, n, set, true, capacity, positions, ids, nullptr, nullptr, counts,
+                           perPattern, nullptr, nullptr );
 }
 
 int
@@ -2216,14 +2275,8 @@ mi355x_bz2_find_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans,
                            const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* positions, uint32_t* ids,
                            uint64_t capacity, uint64_t* counts, uint64_t* perPattern )
 {
-    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
-         || ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    PatternSet set;
-    if ( !takeSet( c, "find_bytes_set", patterns, patternSizes, nPatterns, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytesSet( c, "find_bytes_set", spans, n, set, true, capacity, positions, ids, nullptr, nullptr, counts,
-                           perPattern, nullptr, nullptr );
+    return mi355x_bz2_find_bytes_set_ex( c, spans, n, patterns, patternSizes, nPatterns, 0, positions, ids, capacity, counts,
+                                         perPattern );
 }
 
 int

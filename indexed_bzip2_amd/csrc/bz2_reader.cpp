@@ -1112,13 +1112,14 @@ runRankWork( mi355x_bz2_ctx* const ctx, const RankWork& work )
     }
 }
 
-/** What the launches of one search share: the pattern, and -- with a limit -- how many matches the launches at the
- * front of the range that are through have found.  Once these reach the limit, `stop` cancels the launches that have
+/** What the launches of one search share: the pattern (folded once here if the flags ask for it; the context folds what
+ * it uploads all the same), the flags, and -- with a limit -- how many matches the launches at the front of the range
+ * that are through have found.  Once these reach the limit, `stop` cancels the launches that have
  * not been started. */
 struct SearchCall
 {
-    const uint8_t* pattern{ nullptr };
-    uint32_t m{ 0 };
+    std::vector<uint8_t> pattern;
+    uint32_t flags{ 0 };                        /* MI355X_BZ2_SEARCH_* */
     uint64_t limit{ 0 };                        /* 0: count only */
     std::mutex mutex;
     std::vector<uint8_t> finished;              /* per launch */
@@ -1143,8 +1144,8 @@ static void
 runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
 {
     auto& call = *work.call;
-    checkDevice( ctx, searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern, call.m, call.limit,
-                                    call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam ) );
+    checkDevice( ctx, searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern.data(), (uint32_t)call.pattern.size(),
+                                    call.flags, call.limit, call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam ) );
     if ( call.limit > 0 ) {
         const std::scoped_lock lock( call.mutex );
         call.finished[work.index] = 1;
@@ -1156,7 +1157,7 @@ runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
     }
 }
 
-/** SearchCall for a set of patterns.  `found` counts, of the pairs of the launches at the front that are through, only
+/** SearchCall for a set of patterns; the set holds the flag and the patterns folded once.  `found` counts, of the pairs of the launches at the front that are through, only
  * those that end m_max bytes in front of their extent's end (bz2_search.hpp: the limit of a set). */
 struct SetSearchCall
 {
@@ -1406,9 +1407,10 @@ public:
     /** Step 1 (mi355x_bz2_reader_search): the launches of bz2_search.hpp's plan, each searching its extent on the context
      * that decoded it; then the matches no launch can see (seamMatches), and both merged in file order. */
     void
-    search( const uint8_t* pattern, uint32_t m, uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches )
+    search( const uint8_t* pattern, uint32_t m, uint32_t flags, uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches )
     {
         if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "search on a closed reader" );
+        const bool fold = ( flags & bz2gpu::SEARCH_IGNORE_CASE ) != 0;
         if ( m == 0 || m > bz2gpu::SEARCH_PATTERN_MAX ) {
             fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "search: the pattern must have 1 to 256 bytes, not " + std::to_string( m ) );
         }
@@ -1425,8 +1427,8 @@ public:
         } );
         const size_t n = plan.launches.size();
         SearchCall call;
-        call.pattern = pattern;
-        call.m = m;
+        call.pattern = bz2gpu::foldedBytes( pattern, m, fold );
+        call.flags = flags;
         call.limit = limit;
         call.finished.assign( n, 0 );
         call.counts.assign( n, 0 );
@@ -1448,7 +1450,7 @@ public:
             seams[l] = { extent.fileOffset, extent.size, { searches[l].seam, searches[l].seam + k },
                          { searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX, searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX + k } };
         }
-        const auto between = bz2gpu::seamMatches( pattern, m, seams );
+        const auto between = bz2gpu::seamMatches( call.pattern.data(), m, seams, fold );
         if ( limit == 0 ) {
             uint64_t total = between.size();
             for ( const auto& work : searches ) total += work.count;
@@ -1651,11 +1653,11 @@ public:
      * (line, 1) per matching line, whose pieces stay held for takeLineRanges.  Matches and line ranges held by earlier
      * calls are released.  The rank pass decodes the blocks with matches a second time, the line pass a third. */
     void
-    grep( const uint8_t* pattern, uint32_t m, uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, bool keepOnDevice,
-          uint64_t* nLines, uint64_t* totalBytes )
+    grep( const uint8_t* pattern, uint32_t m, uint32_t flags, uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines,
+          bool keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
     {
         uint64_t nMatches = 0;
-        search( pattern, m, start, end, std::numeric_limits<uint64_t>::max(), &nMatches );
+        search( pattern, m, flags, start, end, std::numeric_limits<uint64_t>::max(), &nMatches );
         const auto positions = std::move( *m_matches );
         m_matches.reset();
         grepPositions( positions, nl, maxLines, keepOnDevice, nLines, totalBytes );
@@ -2418,12 +2420,32 @@ mi355x_bz2_reader_take_line_ranges( mi355x_bz2_reader* r, void* dst, int dstIsDe
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeLineRanges( dst, dstIsDevice != 0 ); } );
 }
 
+/** A flag bit that no search knows fails the call before anything is launched or held. */
+static void
+checkSearchFlags( const char* what, uint32_t flags )
+{
+    if ( ( flags & ~bz2gpu::SEARCH_KNOWN_FLAGS ) == 0 ) return;
+    char bits[16];
+    std::snprintf( bits, sizeof( bits ), "0x%X", flags & ~bz2gpu::SEARCH_KNOWN_FLAGS );
+    mi355x::fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": unknown flag bits " + bits );
+}
+
+int
+mi355x_bz2_reader_search_ex( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint32_t flags, uint64_t start,
+                             uint64_t end, uint64_t limit, uint64_t* nMatches )
+{
+    if ( pattern == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        checkSearchFlags( "search", flags );
+        reader.search( pattern, patternSize, flags, start, end, limit, nMatches );
+    } );
+}
+
 int
 mi355x_bz2_reader_search( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint64_t start, uint64_t end,
                           uint64_t limit, uint64_t* nMatches )
 {
-    if ( pattern == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.search( pattern, patternSize, start, end, limit, nMatches ); } );
+    return mi355x_bz2_reader_search_ex( r, pattern, patternSize, 0, start, end, limit, nMatches );
 }
 
 int
@@ -2441,15 +2463,24 @@ mi355x_bz2_reader_line_numbers( mi355x_bz2_reader* r, uint8_t nl, const uint64_t
 }
 
 int
-mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint8_t nl, uint64_t start,
-                        uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+mi355x_bz2_reader_grep_ex( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint32_t flags, uint8_t nl,
+                           uint64_t start, uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines,
+                           uint64_t* totalBytes )
 {
     if ( pattern == nullptr || nLines == nullptr || totalBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     *nLines = 0;
     *totalBytes = 0;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
-        reader.grep( pattern, patternSize, nl, start, end, maxLines, keepOnDevice != 0, nLines, totalBytes );
+        checkSearchFlags( "grep", flags );
+        reader.grep( pattern, patternSize, flags, nl, start, end, maxLines, keepOnDevice != 0, nLines, totalBytes );
     } );
+}
+
+int
+mi355x_bz2_reader_grep( mi355x_bz2_reader* r, const uint8_t* pattern, uint32_t patternSize, uint8_t nl, uint64_t start,
+                        uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+{
+    return mi355x_bz2_reader_grep_ex( r, pattern, patternSize, 0, nl, start, end, maxLines, keepOnDevice, nLines, totalBytes );
 }
 
 int
@@ -2459,24 +2490,34 @@ mi355x_bz2_reader_take_grep( mi355x_bz2_reader* r, uint64_t* lineNumbers, uint64
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeGrep( lineNumbers, byteSizes, capacity ); } );
 }
 
-/** The set of a reader call; a set that breaks a limit fails the call with the sentence that names it. */
+/** The set of a reader call, its patterns folded once if the flags ask for it; a set that breaks a limit fails the call
+ * with the sentence that names it, and so does an unknown flag bit. */
 static bz2gpu::PatternSet
-setOf( const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n )
+setOf( const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags )
 {
+    checkSearchFlags( what, flags );
     const auto why = bz2gpu::patternSetError( sizes, n );
     if ( !why.empty() ) mi355x::fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + why );
-    return bz2gpu::makePatternSet( patterns, sizes, n );
+    return bz2gpu::makePatternSet( patterns, sizes, n, ( flags & bz2gpu::SEARCH_IGNORE_CASE ) != 0 );
+}
+
+int
+mi355x_bz2_reader_search_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes,
+                                 uint32_t nPatterns, uint32_t flags, uint64_t start, uint64_t end, uint64_t limit,
+                                 uint64_t* nMatches, uint64_t* perPattern )
+{
+    if ( patterns == nullptr || patternSizes == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        const auto set = setOf( "search_set", patterns, patternSizes, nPatterns, flags );
+        reader.searchSet( set, start, end, limit, nMatches, perPattern );
+    } );
 }
 
 int
 mi355x_bz2_reader_search_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
                               uint64_t start, uint64_t end, uint64_t limit, uint64_t* nMatches, uint64_t* perPattern )
 {
-    if ( patterns == nullptr || patternSizes == nullptr || nMatches == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
-        const auto set = setOf( "search_set", patterns, patternSizes, nPatterns );
-        reader.searchSet( set, start, end, limit, nMatches, perPattern );
-    } );
+    return mi355x_bz2_reader_search_set_ex( r, patterns, patternSizes, nPatterns, 0, start, end, limit, nMatches, perPattern );
 }
 
 int
@@ -2487,9 +2528,9 @@ mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* positions, u
 }
 
 int
-mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
-                            uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines,
-                            uint64_t* totalBytes )
+mi355x_bz2_reader_grep_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
+                               uint32_t flags, uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, int keepOnDevice,
+                               uint64_t* nLines, uint64_t* totalBytes )
 {
     if ( patterns == nullptr || patternSizes == nullptr || nLines == nullptr || totalBytes == nullptr ) {
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
@@ -2497,9 +2538,18 @@ mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const
     *nLines = 0;
     *totalBytes = 0;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
-        const auto set = setOf( "grep_set", patterns, patternSizes, nPatterns );
+        const auto set = setOf( "grep_set", patterns, patternSizes, nPatterns, flags );
         reader.grepSet( set, nl, start, end, maxLines, keepOnDevice != 0, nLines, totalBytes );
     } );
+}
+
+int
+mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* patternSizes, uint32_t nPatterns,
+                            uint8_t nl, uint64_t start, uint64_t end, uint64_t maxLines, int keepOnDevice, uint64_t* nLines,
+                            uint64_t* totalBytes )
+{
+    return mi355x_bz2_reader_grep_set_ex( r, patterns, patternSizes, nPatterns, 0, nl, start, end, maxLines, keepOnDevice,
+                                          nLines, totalBytes );
 }
 
 int

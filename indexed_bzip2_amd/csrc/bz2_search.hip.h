@@ -24,6 +24,11 @@
  *   k_seam_bytes   copies the first and the last `n` bytes of one extent behind the counts, so that they come back in
  *                  the same D2H (bz2_search.hpp: what the reader needs for matches that straddle two launches).
  *
+ * k_count_bytes and k_emit_bytes are templates over FOLD.  FOLD = false is the exact search.  FOLD = true ignores the
+ * case of ASCII letters (foldAscii of bz2_search.hpp: 'A' .. 'Z' | 0x20, every other byte unchanged): the pattern comes
+ * folded from the host, every 16-byte vector is folded once (fold16, four 32-bit SWAR steps) before matches16, and the
+ * verify folds the data byte it compares.  Folding changes no address: both instantiations read the same bytes.
+ *
  * Every loop is bounded by the tile's size (and m); no workgroup waits on another.
  */
 #pragma once
@@ -49,7 +54,35 @@ loadPattern( uint8_t* lds, const uint8_t* __restrict__ pattern, uint32_t lane )
     __syncthreads();
 }
 
-/** Bit i: a match starts at byte a + i, given the candidates (P[0] found there, inside the tile). */
+/** foldAscii on the four bytes of w: a byte gets 0x20 iff its top bit is clear and its low seven bits lie in 'A' .. 'Z'
+ * (0x41 + 0x3F and 0x5B + 0x25 carry into bit 7; no sum passes 0xBE, so nothing carries into the next byte). */
+__device__ __forceinline__ uint32_t
+fold4( uint32_t w )
+{
+    const uint32_t low = w & 0x7F7F7F7Fu;
+    const uint32_t up = ( low + 0x3F3F3F3Fu ) & ~( low + 0x25252525u ) & ~w & 0x80808080u;
+    return w | ( up >> 2 );
+}
+
+template<bool FOLD>
+__device__ __forceinline__ uint4
+fold16( uint4 d )
+{
+    if constexpr ( FOLD ) return uint4{ fold4( d.x ), fold4( d.y ), fold4( d.z ), fold4( d.w ) };
+    return d;
+}
+
+template<bool FOLD>
+__device__ __forceinline__ uint32_t
+foldByte( uint32_t b )
+{
+    if constexpr ( FOLD ) return b - 'A' < 26u ? b | 0x20u : b;
+    return b;
+}
+
+/** Bit i: a match starts at byte a + i, given the candidates (P[0] found there, inside the tile).  FOLD: the pattern in
+ * LDS is folded, and so is every data byte that is compared with it. */
+template<bool FOLD>
 __device__ __forceinline__ uint32_t
 verified16( const uint8_t* __restrict__ out, uint64_t a, uint32_t candidates, const uint8_t* lds, uint32_t m )
 {
@@ -59,12 +92,13 @@ verified16( const uint8_t* __restrict__ out, uint64_t a, uint32_t candidates, co
         candidates &= candidates - 1;
         const uint8_t* const at = out + a + bit;
         uint32_t j = 1;
-        while ( j < m && at[j] == lds[j] ) ++j;
+        while ( j < m && foldByte<FOLD>( at[j] ) == lds[j] ) ++j;
         hits |= ( j == m ? 1u : 0u ) << bit;
     }
     return hits;
 }
 
+template<bool FOLD>
 __global__ __launch_bounds__( SEARCH_THREADS ) void
 k_count_bytes( const CountTile* __restrict__ tiles, const uint8_t* __restrict__ out, const uint8_t* __restrict__ pattern,
                uint32_t m, uint32_t* __restrict__ tileCounts, unsigned long long* __restrict__ spanCounts )
@@ -82,8 +116,8 @@ k_count_bytes( const CountTile* __restrict__ tiles, const uint8_t* __restrict__ 
     uint32_t count = 0;
     for ( uint32_t k = lane; k < vectors; k += SEARCH_THREADS ) {
         const uint64_t a = base + 16ull * k;
-        const uint32_t candidates = matches16( v[k], first ) & validBytes16( a, begin, end );
-        count += __popc( verified16( out, a, candidates, lds, m ) );
+        const uint32_t candidates = matches16( fold16<FOLD>( v[k] ), first ) & validBytes16( a, begin, end );
+        count += __popc( verified16<FOLD>( out, a, candidates, lds, m ) );
     }
 #pragma unroll
     for ( uint32_t d = 32; d > 0; d >>= 1 ) count += __shfl_down( count, d );
@@ -116,6 +150,7 @@ k_scan_tiles( const uint32_t* __restrict__ tileCounts, uint32_t nTiles, uint64_t
     }
 }
 
+template<bool FOLD>
 __global__ __launch_bounds__( SEARCH_THREADS ) void
 k_emit_bytes( const CountTile* __restrict__ tiles, const uint8_t* __restrict__ out, const uint8_t* __restrict__ pattern,
               uint32_t m, const uint64_t* __restrict__ tileOffsets, uint64_t capacity, uint64_t* __restrict__ positions )
@@ -137,7 +172,7 @@ k_emit_bytes( const CountTile* __restrict__ tiles, const uint8_t* __restrict__ o
         const uint64_t a = base + 16ull * k;
         uint32_t hits = 0;
         if ( k < vectors ) {
-            hits = verified16( out, a, matches16( v[k], first ) & validBytes16( a, begin, end ), lds, m );
+            hits = verified16<FOLD>( out, a, matches16( fold16<FOLD>( v[k] ), first ) & validBytes16( a, begin, end ), lds, m );
         }
         const uint32_t c = __popc( hits );
         const uint32_t upTo = waveInclusiveScan( c, lane );

@@ -47,6 +47,12 @@
  * extent's own end for b, which is never behind the front's), and the merged result -- the extents' pairs and the seam
  * pairs really merged by (p, i), since inside one extent seam pairs no longer all follow the extent's own pairs -- is
  * cut to `limit` afterwards.  The invariant: the result with a limit is the first `limit` pairs of the result without.
+ *
+ * Ignoring case (SEARCH_IGNORE_CASE, `fold` below) changes one thing: two bytes are equal if foldAscii makes them equal.
+ * foldAscii( b ) = b | 0x20 for 'A' <= b <= 'Z' and b for every other byte -- bytes.lower() of Python, `LC_ALL=C grep -i`;
+ * the bytes 0x80 .. 0xFF are never changed.  A match of P at p is then foldAscii( D[p + j] ) == foldAscii( P[j] ) for all
+ * j < m.  No size, range, order or limit depends on it: the plans are the same plans, the seam bytes come back raw and
+ * are folded here, and patterns of a set that are equal under folding each report their own pairs.
  */
 #pragma once
 
@@ -66,11 +72,36 @@ constexpr uint32_t SEARCH_PATTERN_MAX = 256;
 constexpr uint32_t SET_MAX_PATTERNS = 1024;
 constexpr uint32_t SET_MAX_BYTES = 16384;
 
+/* The flags of a search (MI355X_BZ2_SEARCH_* of the C ABI).  Every later option of grep gets its bit here. */
+constexpr uint32_t SEARCH_IGNORE_CASE = 1u;
+constexpr uint32_t SEARCH_KNOWN_FLAGS = SEARCH_IGNORE_CASE;
+
+/** b | 0x20 for 'A' .. 'Z', every other byte as it is. */
+[[nodiscard]] constexpr uint8_t
+foldAscii( uint8_t b )
+{
+    return b >= 'A' && b <= 'Z' ? (uint8_t)( b | 0x20 ) : b;
+}
+
+/** bytes[0, n) under foldAscii if `fold`, else as they are. */
+[[nodiscard]] inline std::vector<uint8_t>
+foldedBytes( const uint8_t* bytes, size_t n, bool fold )
+{
+    std::vector<uint8_t> result( bytes, bytes + n );
+    if ( fold ) {
+        for ( auto& byte : result ) byte = foldAscii( byte );
+    }
+    return result;
+}
+
 /* The set as the kernels read it (bz2_search_set.hip.h), one image that a workgroup copies into LDS:
  *   [0, SET_MAX_BYTES)      the pattern bytes, concatenated in set order;
  *   SET_TABLE_AT            one uint32 per pattern, ordered by (first byte, id):
  *                           offset of its bytes | (m_i - 1) << SET_ENTRY_SIZE_SHIFT | id << SET_ENTRY_ID_SHIFT;
- *   SET_FIRST_AT            one uint32 per first byte: begin of its bucket in the table | length << 16; 0 = none. */
+ *   SET_FIRST_AT            one uint32 per first byte: begin of its bucket in the table | length << 16; 0 = none.
+ * For a search that ignores case (writeSetImage with fold) the pattern bytes are stored under foldAscii and "first byte"
+ * reads "folded first byte": a bucket holds every pattern whose first byte folds to its index, in id order, and the buckets
+ * of 'A' .. 'Z' are empty. */
 constexpr uint32_t SET_TABLE_AT = SET_MAX_BYTES;
 constexpr uint32_t SET_FIRST_AT = SET_TABLE_AT + SET_MAX_PATTERNS * 4;
 constexpr uint32_t SET_IMAGE_BYTES = SET_FIRST_AT + 256 * 4;
@@ -137,10 +168,10 @@ planSearch( const std::vector<std::pair<uint64_t, uint64_t> >& map, uint64_t sta
 /**
  * Every p, ascending and once, with D[p : p + m] == P whose bytes lie inside the extents' union but not inside a single
  * extent.  `seams`: the extents in file order, back to back (checked: std::invalid_argument), each with its head and
- * tail of seamLength( m, size ) bytes.
+ * tail of seamLength( m, size ) bytes, raw.  With `fold`, equal reads equal under foldAscii; the pattern in any case.
  */
 inline std::vector<uint64_t>
-seamMatches( const uint8_t* pattern, uint32_t m, const std::vector<ExtentSeam>& seams )
+seamMatches( const uint8_t* pattern, uint32_t m, const std::vector<ExtentSeam>& seams, bool fold = false )
 {
     if ( m == 0 || m > SEARCH_PATTERN_MAX ) throw std::invalid_argument( "seamMatches: the pattern must have 1 to 256 bytes" );
     for ( size_t i = 0; i < seams.size(); ++i ) {
@@ -154,6 +185,7 @@ seamMatches( const uint8_t* pattern, uint32_t m, const std::vector<ExtentSeam>& 
     std::vector<uint64_t> matches;
     if ( m == 1 || seams.empty() ) return matches;
     const uint64_t unionEnd = seams.back().fileOffset + seams.back().size;
+    const auto compared = foldedBytes( pattern, m, fold );
     std::vector<uint8_t> window;
     for ( size_t i = 0; i + 1 < seams.size(); ++i ) {
         const auto& extent = seams[i];
@@ -166,9 +198,12 @@ seamMatches( const uint8_t* pattern, uint32_t m, const std::vector<ExtentSeam>& 
         for ( size_t j = i + 1; j < seams.size() && window.size() - inFront < m - 1; ++j ) {
             window.insert( window.end(), seams[j].head.begin(), seams[j].head.end() );
         }
+        if ( fold ) {
+            for ( auto& byte : window ) byte = foldAscii( byte );
+        }
         /* starts in the tail; the match reaches behind b (inFront <= m - 1 < m) and must fit into the window */
         for ( size_t at = 0; at < inFront && at + m <= window.size(); ++at ) {
-            if ( std::memcmp( window.data() + at, pattern, m ) == 0 ) matches.push_back( b - inFront + at );
+            if ( std::memcmp( window.data() + at, compared.data(), m ) == 0 ) matches.push_back( b - inFront + at );
         }
     }
     return matches;
@@ -181,6 +216,8 @@ struct PatternSet
     std::vector<uint8_t> bytes;             /* the patterns, concatenated in set order */
     std::vector<uint32_t> offsets, sizes;   /* per pattern */
     uint32_t mMin{ 0 }, mMax{ 0 };
+    bool fold{ false };                     /* the search ignores case ... */
+    std::vector<uint8_t> folded;            /* ... and compares these: `bytes` under foldAscii (empty without fold) */
 
     [[nodiscard]] uint32_t count() const { return (uint32_t)sizes.size(); }
     [[nodiscard]] const uint8_t* pattern( uint32_t i ) const { return bytes.data() + offsets[i]; }
@@ -210,9 +247,10 @@ patternSetError( const uint32_t* sizes, uint64_t n )
     return {};
 }
 
-/** `patterns`: the concatenation of the patterns in set order.  Throws std::invalid_argument with patternSetError. */
+/** `patterns`: the concatenation of the patterns in set order.  Throws std::invalid_argument with patternSetError.  `fold`
+ * changes neither ids, sizes nor m_min and m_max. */
 inline PatternSet
-makePatternSet( const uint8_t* patterns, const uint32_t* sizes, uint64_t n )
+makePatternSet( const uint8_t* patterns, const uint32_t* sizes, uint64_t n, bool fold = false )
 {
     const auto why = patternSetError( sizes, n );
     if ( !why.empty() ) throw std::invalid_argument( why );
@@ -225,25 +263,31 @@ makePatternSet( const uint8_t* patterns, const uint32_t* sizes, uint64_t n )
         at += sizes[i];
     }
     set.bytes.assign( patterns, patterns + at );
+    set.fold = fold;
+    if ( fold ) set.folded = foldedBytes( patterns, at, true );
     set.mMin = *std::min_element( set.sizes.begin(), set.sizes.end() );
     set.mMax = *std::max_element( set.sizes.begin(), set.sizes.end() );
     return set;
 }
 
 /** The image of the set for the kernels: SET_IMAGE_BYTES bytes at `image` (4-byte aligned), laid out as described at
- * SET_TABLE_AT. */
+ * SET_TABLE_AT; with `fold`, the image of the set under foldAscii (whether or not the set itself was made with it). */
 inline void
-writeSetImage( const PatternSet& set, uint8_t* image )
+writeSetImage( const PatternSet& set, uint8_t* image, bool fold = false )
 {
     std::memset( image, 0, SET_IMAGE_BYTES );
     std::memcpy( image, set.bytes.data(), set.bytes.size() );
+    if ( fold ) {
+        for ( size_t i = 0; i < set.bytes.size(); ++i ) image[i] = foldAscii( image[i] );
+    }
     std::vector<uint32_t> order( set.count() );
     for ( uint32_t i = 0; i < set.count(); ++i ) order[i] = i;
-    std::stable_sort( order.begin(), order.end(), [&set] ( uint32_t a, uint32_t b ) { return set.pattern( a )[0] < set.pattern( b )[0]; } );
+    /* the image holds the bytes that are compared: ordered by their first one, equal first bytes by id */
+    std::stable_sort( order.begin(), order.end(), [&set, image] ( uint32_t a, uint32_t b ) { return image[set.offsets[a]] < image[set.offsets[b]]; } );
     auto* const table = reinterpret_cast<uint32_t*>( image + SET_TABLE_AT );
     auto* const first = reinterpret_cast<uint32_t*>( image + SET_FIRST_AT );
     for ( uint32_t e = 0; e < set.count(); ++e ) {
-        const uint32_t id = order[e], byte = set.pattern( id )[0];
+        const uint32_t id = order[e], byte = image[set.offsets[id]];
         table[e] = set.offsets[id] | ( ( set.sizes[id] - 1 ) << SET_ENTRY_SIZE_SHIFT ) | ( id << SET_ENTRY_ID_SHIFT );
         first[byte] = first[byte] == 0 ? ( e | ( 1u << 16 ) ) : first[byte] + ( 1u << 16 );
     }
@@ -261,9 +305,10 @@ planSearchSet( const std::vector<std::pair<uint64_t, uint64_t> >& map, uint64_t 
 /**
  * Every pair (p, i), in (p, i) order and once, with D[p : p + m_i] == P_i whose bytes lie inside the extents' union but not
  * inside a single extent.  `seams` as for seamMatches, each with its head and tail of seamLength( m_max, size ) bytes.
+ * With `fold`, equal reads equal under foldAscii.
  */
 inline std::vector<SetMatch>
-seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams )
+seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams, bool fold )
 {
     if ( !patternSetError( set.sizes.data(), set.count() ).empty() ) throw std::invalid_argument( "seamMatchesSet: not a set of patterns" );
     for ( size_t i = 0; i < seams.size(); ++i ) {
@@ -278,6 +323,8 @@ seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams )
     if ( set.mMax == 1 || seams.empty() ) return matches;
     const uint64_t unionEnd = seams.back().fileOffset + seams.back().size;
     const uint32_t reach = set.mMax - 1;
+    const auto folded = fold && !set.fold ? foldedBytes( set.bytes.data(), set.bytes.size(), true ) : std::vector<uint8_t>{};
+    const uint8_t* const compared = !fold ? set.bytes.data() : set.fold ? set.folded.data() : folded.data();
     std::vector<uint8_t> window;
     for ( size_t i = 0; i + 1 < seams.size(); ++i ) {
         const auto& extent = seams[i];
@@ -291,16 +338,26 @@ seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams )
         for ( size_t j = i + 1; j < seams.size() && window.size() - inFront < reach; ++j ) {
             window.insert( window.end(), seams[j].head.begin(), seams[j].head.end() );
         }
+        if ( fold ) {
+            for ( auto& byte : window ) byte = foldAscii( byte );
+        }
         /* ascending p, then ascending id: a pair starts in the tail, reaches behind b and fits into the window */
         for ( size_t at = 0; at < inFront; ++at ) {
             for ( uint32_t id = 0; id < set.count(); ++id ) {
                 const uint32_t m = set.sizes[id];
                 if ( at + m <= inFront || at + m > window.size() ) continue;
-                if ( std::memcmp( window.data() + at, set.pattern( id ), m ) == 0 ) matches.push_back( { b - inFront + at, id } );
+                if ( std::memcmp( window.data() + at, compared + set.offsets[id], m ) == 0 ) matches.push_back( { b - inFront + at, id } );
             }
         }
     }
     return matches;
+}
+
+/** seamMatchesSet as the set was made: folded if makePatternSet was given fold. */
+inline std::vector<SetMatch>
+seamMatchesSet( const PatternSet& set, const std::vector<ExtentSeam>& seams )
+{
+    return seamMatchesSet( set, seams, set.fold );
 }
 
 /** Of the pairs of one extent (ascending positions in D), how many have p + m_max <= the extent's end: each sorts in

@@ -26,6 +26,11 @@
  *                 written; a wave stops at the first tile whose prefix sum has reached the capacity (the prefix sums
  *                 ascend with the tiles).  No atomics, no sort: the same call gives the same arrays.
  *
+ * k_count_set and k_emit_set are templates over FOLD, as k_count_bytes is.  FOLD = true ignores the case of ASCII letters:
+ * writeSetImage( set, image, true ) stores the patterns folded and builds the buckets by folded first byte, every vector is
+ * folded once (fold16) where it is loaded, so that the table is indexed by the folded byte, and the verify folds the data
+ * byte it compares.  The addresses read are those of FOLD = false.
+ *
  * The pairs are recomputed by the emitting pass, not kept as a mask, as k_emit_bytes does and for the same reasons
  * (DESIGN.md).  k_seam_bytes of bz2_search.hip.h serves heads and tails of min( m_max - 1, size ) bytes.  Every loop is
  * bounded by the tile count, the tile's size, the bucket's length and m_i.
@@ -71,9 +76,9 @@ enum class SetWalk { COUNT_EACH, COUNT, WRITE };
 /**
  * The pairs that start in the 16 bytes d = out[a, a + 16), at the positions of `valid`, in (position, id) order; returns
  * their number.  COUNT_EACH adds every pair to histogram[id] (LDS), WRITE stores pair number n at place + n while that is
- * below the capacity.
+ * below the capacity.  FOLD: d and the set in LDS are folded, and the verify folds the bytes it reads.
  */
-template<SetWalk WALK>
+template<SetWalk WALK, bool FOLD>
 __device__ __forceinline__ uint32_t
 pairs16( const uint8_t* __restrict__ out, uint64_t a, uint4 d, uint32_t valid, uint64_t spanEnd, const uint8_t* lds,
          uint32_t* histogram, uint64_t place, uint64_t capacity, uint64_t* __restrict__ positions, uint32_t* __restrict__ ids )
@@ -97,7 +102,7 @@ pairs16( const uint8_t* __restrict__ out, uint64_t a, uint4 d, uint32_t valid, u
             if ( m > room ) continue;
             const uint8_t* const pattern = lds + ( entry & ( SET_MAX_BYTES - 1 ) );
             uint32_t j = 1;
-            while ( j < m && at[j] == pattern[j] ) ++j;
+            while ( j < m && foldByte<FOLD>( at[j] ) == pattern[j] ) ++j;
             if ( j != m ) continue;
             const uint32_t id = entry >> SET_ENTRY_ID_SHIFT;
             if constexpr ( WALK == SetWalk::COUNT_EACH ) atomicAdd( histogram + id, 1u );
@@ -112,6 +117,7 @@ pairs16( const uint8_t* __restrict__ out, uint64_t a, uint4 d, uint32_t valid, u
     return n;
 }
 
+template<bool FOLD>
 __global__ __launch_bounds__( SET_THREADS ) void
 k_count_set( const SetTile* __restrict__ tiles, uint32_t nTiles, const uint8_t* __restrict__ out,
              const uint8_t* __restrict__ image, uint32_t nBytes, uint32_t k, uint32_t* __restrict__ tileCounts,
@@ -132,8 +138,8 @@ k_count_set( const SetTile* __restrict__ tiles, uint32_t nTiles, const uint8_t* 
         uint32_t count = 0;
         for ( uint32_t i = lane; i < vectors; i += 64 ) {
             const uint64_t a = base + 16ull * i;
-            count += pairs16<SetWalk::COUNT_EACH>( out, a, v[i], validBytes16( a, begin, end ), t.end, lds, histogram, 0, 0,
-                                                   nullptr, nullptr );
+            count += pairs16<SetWalk::COUNT_EACH, FOLD>( out, a, fold16<FOLD>( v[i] ), validBytes16( a, begin, end ), t.end, lds,
+                                                         histogram, 0, 0, nullptr, nullptr );
         }
 #pragma unroll
         for ( uint32_t d = 32; d > 0; d >>= 1 ) count += __shfl_down( count, d );
@@ -148,6 +154,7 @@ k_count_set( const SetTile* __restrict__ tiles, uint32_t nTiles, const uint8_t* 
     }
 }
 
+template<bool FOLD>
 __global__ __launch_bounds__( SET_THREADS ) void
 k_emit_set( const SetTile* __restrict__ tiles, uint32_t nTiles, const uint8_t* __restrict__ out,
             const uint8_t* __restrict__ image, uint32_t nBytes, uint32_t k, const uint64_t* __restrict__ tileOffsets,
@@ -171,14 +178,14 @@ k_emit_set( const SetTile* __restrict__ tiles, uint32_t nTiles, const uint8_t* _
             uint4 d{ 0, 0, 0, 0 };
             uint32_t valid = 0, c = 0;
             if ( i < vectors ) {
-                d = v[i];
+                d = fold16<FOLD>( v[i] );
                 valid = validBytes16( a, begin, end );
-                c = pairs16<SetWalk::COUNT>( out, a, d, valid, t.end, lds, nullptr, 0, 0, nullptr, nullptr );
+                c = pairs16<SetWalk::COUNT, FOLD>( out, a, d, valid, t.end, lds, nullptr, 0, 0, nullptr, nullptr );
             }
             const uint32_t upTo = waveInclusiveScan( c, lane );
             const uint64_t mine = place + ( upTo - c );
             if ( c != 0 && mine < capacity ) {
-                pairs16<SetWalk::WRITE>( out, a, d, valid, t.end, lds, nullptr, mine, capacity, positions, ids );
+                pairs16<SetWalk::WRITE, FOLD>( out, a, d, valid, t.end, lds, nullptr, mine, capacity, positions, ids );
             }
             place += __shfl( upTo, 63 );
         }

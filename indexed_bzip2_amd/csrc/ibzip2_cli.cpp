@@ -41,7 +41,7 @@ struct Options
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
     bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false }, grep{ false }, lineNumber{ false };
-    bool grepFile{ false }, countMatchesFile{ false };
+    bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -99,7 +99,11 @@ printHelp()
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
-        "                                and ':'.\n\n"
+        "                                and ':'.\n"
+        "      --ignore-case             With --grep, --grep-file, --count-matches or --count-matches-file: ignore the\n"
+        "                                case of the ASCII letters A-Z and a-z, in the strings and in the data, as\n"
+        "                                LC_ALL=C grep -i does. Every other byte must be equal. There is no short\n"
+        "                                form: -i is --input.\n\n"
         " Advanced options:\n"
         "      --buffer-size arg         Controls the output buffer size. By default, the decoded data is written in\n"
         "                                one pass per block. (default: 0)\n\n"
@@ -117,7 +121,9 @@ printHelp()
         "Print the lines of a compressed file that contain a string, with their numbers:\n"
         "  ibzip2-mi355x --grep ERROR --line-number file.bz2\n\n"
         "Print the lines that contain any of the strings listed in a file:\n"
-        "  ibzip2-mi355x --grep-file codes.txt file.bz2\n";
+        "  ibzip2-mi355x --grep-file codes.txt file.bz2\n\n"
+        "Print the lines that contain a string in any case (error, Error, ERROR):\n"
+        "  ibzip2-mi355x --grep error --ignore-case file.bz2\n";
 }
 
 /** The patterns of --grep-file / --count-matches-file: the LF-separated lines of the file, concatenated, and their sizes.
@@ -233,6 +239,7 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
             else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
             else if ( name == "line-number" ) o.lineNumber = true;
+            else if ( name == "ignore-case" ) o.ignoreCase = true;
             else if ( name == "list-compressed-offsets" ) {
                 o.listCompressed = true;
                 if ( hasInline ) o.listCompressedPath = inlineValue; else optionalValue( i, o.listCompressedPath );
@@ -433,6 +440,11 @@ main( int argc, char** argv )
         std::cerr << "Option '--line-number' needs '--grep' or '--grep-file'\n";
         return 1;
     }
+    if ( o.ignoreCase && !o.grep && !o.grepFile && !o.countMatches && !o.countMatchesFile ) {
+        std::cerr << "Option '--ignore-case' needs '--grep', '--grep-file', '--count-matches' or '--count-matches-file'\n";
+        return 1;
+    }
+    const uint32_t searchFlags = o.ignoreCase ? MI355X_BZ2_SEARCH_IGNORE_CASE : 0u;
     if ( o.version ) {
         std::cout << "ibzip2-mi355x, CLI to the MI355X bzip2 block decoder (C ABI version " << mi355x_bz2_abi_version()
                   << "), option-compatible with ibzip2 of indexed-bzip2 1.7.0.\n";
@@ -496,8 +508,8 @@ main( int argc, char** argv )
             return 1;
         }
         uint64_t count = 0;
-        rc = mi355x_bz2_reader_search( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(), 0,
-                                       ~uint64_t( 0 ), 0, &count );
+        rc = mi355x_bz2_reader_search_ex( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(),
+                                          searchFlags, 0, ~uint64_t( 0 ), 0, &count );
         if ( rc != MI355X_BZ2_OK ) {
             const char* detail = mi355x_bz2_reader_last_error( reader );
             std::cerr << "Search failed: " << mi355x_bz2_status_string( rc );
@@ -529,8 +541,8 @@ main( int argc, char** argv )
             return 1;
         }
         uint64_t nLines = 0, total = 0;
-        rc = mi355x_bz2_reader_grep( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(), '\n',
-                                     0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0, &nLines, &total );
+        rc = mi355x_bz2_reader_grep_ex( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(),
+                                        searchFlags, '\n', 0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0, &nLines, &total );
         std::vector<uint64_t> numbers( nLines ), sizes( nLines );
         std::vector<char> bytes( total );
         if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );
@@ -583,10 +595,11 @@ main( int argc, char** argv )
         std::vector<uint64_t> numbers, sizes, each( patternSizes.size() );
         std::vector<char> bytes;
         if ( o.countMatchesFile ) {
-            rc = mi355x_bz2_reader_search_set( reader, set, patternSizes.data(), nPatterns, 0, ~uint64_t( 0 ), 0, &nMatches, each.data() );
+            rc = mi355x_bz2_reader_search_set_ex( reader, set, patternSizes.data(), nPatterns, searchFlags, 0, ~uint64_t( 0 ), 0,
+                                                  &nMatches, each.data() );
         } else {
-            rc = mi355x_bz2_reader_grep_set( reader, set, patternSizes.data(), nPatterns, '\n', 0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0,
-                                             &nLines, &total );
+            rc = mi355x_bz2_reader_grep_set_ex( reader, set, patternSizes.data(), nPatterns, searchFlags, '\n', 0, ~uint64_t( 0 ),
+                                                ~uint64_t( 0 ), 0, &nLines, &total );
             numbers.resize( nLines );
             sizes.resize( nLines );
             bytes.resize( total );

@@ -327,7 +327,13 @@ class _IndexedBzip2FileParallel:
         return data, torch.tensor(bounds, dtype=torch.int64)
 
     # -- search: a match of `pattern` (1 to 256 bytes) is every offset p with data[p:p + len(pattern)] == pattern,
-    # start <= p and p + len(pattern) <= end; start and end are clipped to the decoded size
+    # start <= p and p + len(pattern) <= end; start and end are clipped to the decoded size.  ignore_case=True (keyword
+    # only, on every search and grep method) compares data[p:p + len(pattern)].lower() with pattern.lower() instead: the
+    # ASCII letters fold on the GPU, every other byte -- 0x80 to 0xFF included -- must be equal (LC_ALL=C grep -i)
+    @staticmethod
+    def _flags(ignore_case):
+        return N.SEARCH_IGNORE_CASE if ignore_case else 0
+
     @staticmethod
     def _pattern(pattern):
         pattern = bytes(memoryview(pattern))     # TypeError for what is not bytes-like
@@ -335,26 +341,26 @@ class _IndexedBzip2FileParallel:
             raise ValueError(f"the pattern must have 1 to 256 bytes, not {len(pattern)}")
         return pattern
 
-    def _search(self, pattern, start, end, limit):
-        """Step 1 (mi355x_bz2_reader_search): the number of matches (limit 0), or of the positions now held."""
+    def _search(self, pattern, start, end, limit, ignore_case=False):
+        """Step 1 (mi355x_bz2_reader_search_ex): the number of matches (limit 0), or of the positions now held."""
         self._require()
         pattern = self._pattern(pattern)
         start, end = int(start), 2**64 - 1 if end is None else int(end)
         if start < 0 or end < 0:
             raise ValueError("start and end must not be negative")
         n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_search(self._h, pattern, len(pattern), min(start, 2**64 - 1),
-                                                     min(end, 2**64 - 1), limit, ctypes.byref(n)))
+        self._check(N.lib().mi355x_bz2_reader_search_ex(self._h, pattern, len(pattern), self._flags(ignore_case),
+                                                        min(start, 2**64 - 1), min(end, 2**64 - 1), limit, ctypes.byref(n)))
         return n.value
 
-    def count_matches(self, pattern, start=0, end=None):
+    def count_matches(self, pattern, start=0, end=None, *, ignore_case=False):
         """How often the byte string `pattern` occurs in data[start:end] of the decoded file.  Occurrences that overlap
         each other all count -- b"abab" occurs 3 times in b"abababab" -- unlike bytes.count, which says 2.  Every block
         that intersects the range is decoded once, the matches are found on the GPU and only their number leaves it.
-        Positionless."""
-        return self._search(pattern, start, end, 0)
+        ignore_case=True: the ASCII letters of pattern and data match in either case.  Positionless."""
+        return self._search(pattern, start, end, 0, ignore_case)
 
-    def find_all(self, pattern, start=0, end=None, limit=None):
+    def find_all(self, pattern, start=0, end=None, limit=None, *, ignore_case=False):
         """The offsets in the decoded file of the occurrences of `pattern` in data[start:end] (numpy uint64, ascending),
         at most `limit` of them (None: all).  With a limit, no launch is started once it has been reached.  Overlapping
         occurrences as in count_matches.  Positionless."""
@@ -364,14 +370,14 @@ class _IndexedBzip2FileParallel:
         if limit is not None and int(limit) == 0:
             self._pattern(pattern)
             return np.empty(0, dtype=np.uint64)
-        n = self._search(pattern, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1))
+        n = self._search(pattern, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1), ignore_case)
         out = (ctypes.c_uint64 * max(1, n))()
         self._check(N.lib().mi355x_bz2_reader_take_matches(self._h, out, n))
         return np.frombuffer(out, dtype=np.uint64, count=n).copy()
 
-    def find(self, pattern, start=0, end=None):
+    def find(self, pattern, start=0, end=None, *, ignore_case=False):
         """The offset of the first occurrence of `pattern` in data[start:end], or -1: find_all with limit=1."""
-        first = self.find_all(pattern, start, end, 1)
+        first = self.find_all(pattern, start, end, 1, ignore_case=ignore_case)
         return int(first[0]) if len(first) else -1
 
     # -- grep: the lines that hold a match.  A match belongs to the line of its first byte (the pattern may contain the
@@ -403,8 +409,8 @@ class _IndexedBzip2FileParallel:
             raise ValueError("start and end must not be negative")
         return pattern, nl, start, end
 
-    def _grep(self, pattern, start, end, limit, newline, on_device, any_of=False):
-        """Step 1 (mi355x_bz2_reader_grep, or _grep_set for a set of patterns) and the numbers and sizes of the held lines
+    def _grep(self, pattern, start, end, limit, newline, on_device, any_of=False, ignore_case=False):
+        """Step 1 (mi355x_bz2_reader_grep_ex, or _grep_set_ex for a set of patterns) and the numbers and sizes of the held lines
         (_take_grep): (numbers, sizes, total bytes); with limit 0 nothing is held and the number of matching lines comes
         back instead."""
         import numpy as np
@@ -413,13 +419,13 @@ class _IndexedBzip2FileParallel:
         n, total = ctypes.c_uint64(), ctypes.c_uint64()
         if any_of:
             data, sizes, k = pattern
-            self._check(N.lib().mi355x_bz2_reader_grep_set(self._h, data, sizes, k, nl, min(start, 2**64 - 1),
-                                                           min(end, 2**64 - 1), limit, 1 if on_device else 0,
-                                                           ctypes.byref(n), ctypes.byref(total)))
+            self._check(N.lib().mi355x_bz2_reader_grep_set_ex(self._h, data, sizes, k, self._flags(ignore_case), nl,
+                                                              min(start, 2**64 - 1), min(end, 2**64 - 1), limit,
+                                                              1 if on_device else 0, ctypes.byref(n), ctypes.byref(total)))
         else:
-            self._check(N.lib().mi355x_bz2_reader_grep(self._h, pattern, len(pattern), nl, min(start, 2**64 - 1),
-                                                       min(end, 2**64 - 1), limit, 1 if on_device else 0, ctypes.byref(n),
-                                                       ctypes.byref(total)))
+            self._check(N.lib().mi355x_bz2_reader_grep_ex(self._h, pattern, len(pattern), self._flags(ignore_case), nl,
+                                                          min(start, 2**64 - 1), min(end, 2**64 - 1), limit,
+                                                          1 if on_device else 0, ctypes.byref(n), ctypes.byref(total)))
         if limit == 0:
             return n.value
         numbers = (ctypes.c_uint64 * max(1, n.value))()
@@ -434,27 +440,30 @@ class _IndexedBzip2FileParallel:
             raise ValueError("limit must not be negative")
         return 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1)
 
-    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n"):
-        """The number of distinct lines that hold an occurrence of `pattern` in data[start:end] (`grep -c -F`)."""
-        return self._grep(pattern, start, end, 0, newline, False)
+    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n", *, ignore_case=False):
+        """The number of distinct lines that hold an occurrence of `pattern` in data[start:end] (`grep -c -F`, with
+        ignore_case `grep -c -F -i`)."""
+        return self._grep(pattern, start, end, 0, newline, False, False, ignore_case)
 
-    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """The lines that hold an occurrence of `pattern` in data[start:end] (`grep -n -F`) -> (numbers, lines): the
         0-based line numbers (numpy uint64, strictly ascending) and one bytes object per line, whole and with its
         delimiter (the unterminated tail as it is), at most `limit` lines (None: all).  An occurrence belongs to the
         line of its first byte; start and end bound the occurrences, not the lines.  Three passes on the GPU: the
         search, the line numbers of the matches (k_rank_byte), and the lines themselves; only numbers, sizes and the
-        lines' bytes leave it.  Releases matches and line ranges held by earlier calls.  Positionless."""
-        return self._grep_lines(pattern, start, end, limit, newline, False)
+        lines' bytes leave it.  Releases matches and line ranges held by earlier calls.  ignore_case=True
+        is `grep -n -F -i` in the C locale: it changes which occurrences the search pass finds and nothing else.
+        Positionless."""
+        return self._grep_lines(pattern, start, end, limit, newline, False, ignore_case)
 
-    def _grep_lines(self, pattern, start, end, limit, newline, any_of):
+    def _grep_lines(self, pattern, start, end, limit, newline, any_of, ignore_case=False):
         import numpy as np
         limit = self._line_limit(limit)
         if limit == 0:                                 # nothing is asked for: the arguments are checked, nothing runs
             self._require()
             self._grep_arguments(pattern, start, end, newline, any_of)
             return np.empty(0, dtype=np.uint64), []
-        numbers, sizes, total = self._grep(pattern, start, end, limit, newline, False, any_of)
+        numbers, sizes, total = self._grep(pattern, start, end, limit, newline, False, any_of, ignore_case)
         out = bytearray(total)
         dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
         self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
@@ -465,13 +474,13 @@ class _IndexedBzip2FileParallel:
             at += size
         return numbers, lines
 
-    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """grep into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), data and
         offsets laid out as read_line_ranges_to_tensor: line i is ``data[offsets[i]:offsets[i + 1]]``.  The lines' bytes
         never pass through the host."""
-        return self._grep_tensor(pattern, start, end, limit, newline, False)
+        return self._grep_tensor(pattern, start, end, limit, newline, False, ignore_case)
 
-    def _grep_tensor(self, pattern, start, end, limit, newline, any_of):
+    def _grep_tensor(self, pattern, start, end, limit, newline, any_of, ignore_case=False):
         import numpy as np
         import torch
         limit = self._line_limit(limit)
@@ -482,7 +491,7 @@ class _IndexedBzip2FileParallel:
         if limit == 0:
             numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
         else:
-            numbers, sizes, total = self._grep(pattern, start, end, limit, newline, True, any_of)
+            numbers, sizes, total = self._grep(pattern, start, end, limit, newline, True, any_of, ignore_case)
         data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
         if total:
             # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
@@ -495,9 +504,11 @@ class _IndexedBzip2FileParallel:
         return numbers, data, torch.tensor(bounds, dtype=torch.int64)
 
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
-    # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call
-    def _search_set(self, patterns, start, end, limit):
-        """Step 1 (mi355x_bz2_reader_search_set): (number of pairs, or of the pairs now held; per-pattern counts, which
+    # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
+    # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
+    # another, still report their own pairs
+    def _search_set(self, patterns, start, end, limit, ignore_case=False):
+        """Step 1 (mi355x_bz2_reader_search_set_ex): (number of pairs, or of the pairs now held; per-pattern counts, which
         the native call fills for limit 0 only)."""
         import numpy as np
         self._require()
@@ -507,19 +518,19 @@ class _IndexedBzip2FileParallel:
             raise ValueError("start and end must not be negative")
         n = ctypes.c_uint64()
         each = np.zeros(k, dtype=np.uint64)
-        self._check(N.lib().mi355x_bz2_reader_search_set(self._h, data, sizes, k, min(start, 2**64 - 1), min(end, 2**64 - 1),
-                                                         limit, ctypes.byref(n),
-                                                         each.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        self._check(N.lib().mi355x_bz2_reader_search_set_ex(self._h, data, sizes, k, self._flags(ignore_case),
+                                                            min(start, 2**64 - 1), min(end, 2**64 - 1), limit, ctypes.byref(n),
+                                                            each.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return n.value, each
 
-    def count_matches_each(self, patterns, start=0, end=None):
+    def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """How often each byte string of the sequence `patterns` (1 to 1 024 of them, 1 to 256 bytes each, at most 16 384
         bytes in total) occurs in data[start:end] -> numpy uint64, one count per pattern in the caller's order, each
         equal to count_matches of that pattern.  Equal patterns and prefixes of one another are allowed.  ONE decode of
         every block of the range whatever the number of patterns; only the counts leave the GPU.  Positionless."""
-        return self._search_set(patterns, start, end, 0)[1]
+        return self._search_set(patterns, start, end, 0, ignore_case)[1]
 
-    def find_all_any(self, patterns, start=0, end=None, limit=None):
+    def find_all_any(self, patterns, start=0, end=None, limit=None, *, ignore_case=False):
         """The occurrences of every pattern of `patterns` in data[start:end] -> (positions numpy uint64, ids numpy
         uint32): pairs (offset, index of the pattern that occurs there) by ascending offset, then ascending index, at
         most `limit` of them (None: all).  The pairs of pattern i are exactly find_all(patterns[i], start, end), and the
@@ -530,33 +541,33 @@ class _IndexedBzip2FileParallel:
         if limit is not None and int(limit) == 0:
             N.pattern_set(patterns)
             return np.empty(0, dtype=np.uint64), np.empty(0, dtype=np.uint32)
-        n, _ = self._search_set(patterns, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1))
+        n, _ = self._search_set(patterns, start, end, 2**64 - 1 if limit is None else min(int(limit), 2**64 - 1), ignore_case)
         positions, ids = np.empty(n, dtype=np.uint64), np.empty(n, dtype=np.uint32)
         self._check(N.lib().mi355x_bz2_reader_take_set_matches(
             self._h, positions.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if n else None,
             ids.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if n else None, n))
         return positions, ids
 
-    def find_any(self, patterns, start=0, end=None):
+    def find_any(self, patterns, start=0, end=None, *, ignore_case=False):
         """(offset, index) of the first occurrence of any pattern of `patterns` in data[start:end] -- the lowest index
         among those that occur at that offset --, or (-1, -1): find_all_any with limit=1."""
-        positions, ids = self.find_all_any(patterns, start, end, 1)
+        positions, ids = self.find_all_any(patterns, start, end, 1, ignore_case=ignore_case)
         return (int(positions[0]), int(ids[0])) if len(positions) else (-1, -1)
 
-    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """grep for a set of patterns (`grep -n -F -f FILE`) -> (numbers, lines): the lines that hold the first byte of an
         occurrence of at least one pattern, each once.  The set search is the first pass (one decode of the range
         whatever the number of patterns); the rank and line passes are grep's."""
-        return self._grep_lines(patterns, start, end, limit, newline, True)
+        return self._grep_lines(patterns, start, end, limit, newline, True, ignore_case)
 
-    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n"):
+    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n", *, ignore_case=False):
         """The number of distinct lines that hold an occurrence of at least one pattern (`grep -c -F -f FILE`)."""
-        return self._grep(patterns, start, end, 0, newline, False, True)
+        return self._grep(patterns, start, end, 0, newline, False, True, ignore_case)
 
-    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """grep_any into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), as
         grep_to_tensor."""
-        return self._grep_tensor(patterns, start, end, limit, newline, True)
+        return self._grep_tensor(patterns, start, end, limit, newline, True, ignore_case)
 
     def set_verify_stream_crc(self, enable: bool):
         """Check every end-of-stream CRC against the block CRCs in front of it (default: only with parallelization=1,
@@ -665,57 +676,57 @@ class IndexedBzip2File(io.BufferedReader):
         """See _IndexedBzip2FileParallel.read_line_ranges_to_tensor."""
         return self._open_reader().read_line_ranges_to_tensor(ranges, newline)
 
-    def count_matches(self, pattern, start=0, end=None):
+    def count_matches(self, pattern, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches."""
-        return self._open_reader().count_matches(pattern, start, end)
+        return self._open_reader().count_matches(pattern, start, end, ignore_case=ignore_case)
 
-    def find_all(self, pattern, start=0, end=None, limit=None):
+    def find_all(self, pattern, start=0, end=None, limit=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.find_all."""
-        return self._open_reader().find_all(pattern, start, end, limit)
+        return self._open_reader().find_all(pattern, start, end, limit, ignore_case=ignore_case)
 
-    def find(self, pattern, start=0, end=None):
+    def find(self, pattern, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.find."""
-        return self._open_reader().find(pattern, start, end)
+        return self._open_reader().find(pattern, start, end, ignore_case=ignore_case)
 
     def line_numbers(self, offsets, newline=b"\n"):
         """See _IndexedBzip2FileParallel.line_numbers."""
         return self._open_reader().line_numbers(offsets, newline)
 
-    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+    def grep(self, pattern, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep."""
-        return self._open_reader().grep(pattern, start, end, limit, newline)
+        return self._open_reader().grep(pattern, start, end, limit, newline, ignore_case=ignore_case)
 
-    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n"):
+    def count_matching_lines(self, pattern, start=0, end=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matching_lines."""
-        return self._open_reader().count_matching_lines(pattern, start, end, newline)
+        return self._open_reader().count_matching_lines(pattern, start, end, newline, ignore_case=ignore_case)
 
-    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep_to_tensor."""
-        return self._open_reader().grep_to_tensor(pattern, start, end, limit, newline)
+        return self._open_reader().grep_to_tensor(pattern, start, end, limit, newline, ignore_case=ignore_case)
 
-    def count_matches_each(self, patterns, start=0, end=None):
+    def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
-        return self._open_reader().count_matches_each(patterns, start, end)
+        return self._open_reader().count_matches_each(patterns, start, end, ignore_case=ignore_case)
 
-    def find_all_any(self, patterns, start=0, end=None, limit=None):
+    def find_all_any(self, patterns, start=0, end=None, limit=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.find_all_any."""
-        return self._open_reader().find_all_any(patterns, start, end, limit)
+        return self._open_reader().find_all_any(patterns, start, end, limit, ignore_case=ignore_case)
 
-    def find_any(self, patterns, start=0, end=None):
+    def find_any(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.find_any."""
-        return self._open_reader().find_any(patterns, start, end)
+        return self._open_reader().find_any(patterns, start, end, ignore_case=ignore_case)
 
-    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_any(self, patterns, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep_any."""
-        return self._open_reader().grep_any(patterns, start, end, limit, newline)
+        return self._open_reader().grep_any(patterns, start, end, limit, newline, ignore_case=ignore_case)
 
-    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n"):
+    def count_matching_lines_any(self, patterns, start=0, end=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matching_lines_any."""
-        return self._open_reader().count_matching_lines_any(patterns, start, end, newline)
+        return self._open_reader().count_matching_lines_any(patterns, start, end, newline, ignore_case=ignore_case)
 
-    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n"):
+    def grep_any_to_tensor(self, patterns, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep_any_to_tensor."""
-        return self._open_reader().grep_any_to_tensor(patterns, start, end, limit, newline)
+        return self._open_reader().grep_any_to_tensor(patterns, start, end, limit, newline, ignore_case=ignore_case)
 
 
 builtins_open = builtins.open
