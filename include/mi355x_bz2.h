@@ -223,7 +223,9 @@ int mi355x_bz2_debug_copy_stage( mi355x_bz2_ctx* ctx, uint32_t index, int stage,
  * is the `sizes[i]` bytes behind the pieces in front of it.  For consumers of decoded extents that sit on another GPU
  * (the gather of bench.py): the receiver recomputes every block's checksum over the bytes that ARRIVED and compares it
  * with the checksum the sender's block record carries.  `device_bytes` must be 16-byte aligned; runs on the context's
- * stream and waits for the result; no batch may be in flight on the context. */
+ * stream and waits for the result; no batch may be in flight on the context.  A piece may have any size that fits
+ * uint64_t, 2^32 bytes and more included: the checksum is exact.  One workgroup walks a piece serially, so the time
+ * of a call is that of its largest piece. */
 int mi355x_bz2_crc32_device( mi355x_bz2_ctx* ctx, const void* device_bytes, const uint64_t* sizes, uint32_t n_pieces,
                              uint32_t* crcs );
 

@@ -811,13 +811,14 @@ gf_mul( uint32_t a, uint32_t b )
     return r;
 }
 
-/** x^(8*nbytes) (or its inverse) by binary decomposition over the precomputed table. */
+/** x^(8*nbytes) (or its inverse) by binary decomposition over the precomputed table, for all 64 bits of nbytes: P is
+ * primitive, so x has order 2^32 - 1, x^(2^32) = x, and x^(8 * 2^k) = x^(8 * 2^(k - 32)) = table[k - 32] for k >= 32. */
 __device__ __forceinline__ uint32_t
 gf_pow8( const uint32_t* table, uint64_t nbytes )
 {
     uint32_t r = 0x00000001u;   /* the polynomial 1 */
-    for ( int k = 0; nbytes != 0 && k < 32; ++k, nbytes >>= 1 ) {
-        if ( nbytes & 1u ) r = gf_mul( r, table[k] );
+    for ( int k = 0; nbytes != 0; ++k, nbytes >>= 1 ) {
+        if ( nbytes & 1u ) r = gf_mul( r, table[k & 31] );
     }
     return r;
 }

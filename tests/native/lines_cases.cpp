@@ -9,7 +9,14 @@
  * Maps: hand-written ones with end-of-stream entries and two streams, an empty file, and seeded ones.  Cases: blocks
  * without any delimiter, a line spanning several blocks and a launch boundary, a delimiter on a block's last byte, first
  * equal to N and greater than N, count 0 and huge, cap 1, a file that ends with a delimiter, a file of delimiters only.
- * Also: line_starts plans, the checks of an imported index, and an index that lies.  Prints "lines ok". */
+ * Also: line_starts plans, the checks of an imported index, and an index that lies.
+ *
+ * Offsets at and across 2^32: the hand-written and some seeded cases once more behind a front block of 2^32 - k bytes
+ * without a delimiter.  Those bytes are never held in memory: a File knows its front, a launch's output is the list of the
+ * file's stretches it holds, and a range's bytes are compared as stretches of the file (every block is launched once, so
+ * equal stretches are equal bytes).  Line 0 then spans the front block, a launch that holds it puts every later span,
+ * query position and segment above 2^32, and the line index has entries on both sides.  Prints "lines ok". */
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <random>
@@ -36,12 +43,67 @@ const char* currentCase = "";
 using Map = std::vector<std::pair<uint64_t, uint64_t> >;
 constexpr uint8_t NL = '\n';
 
+/* the decoded file: `front` bytes 'x' that are not held in memory, then `tail` */
+struct File
+{
+    uint64_t front{ 0 };
+    std::vector<uint8_t> tail;
+    File() = default;
+    File( std::vector<uint8_t> bytes, uint64_t frontBytes = 0 ) : front( frontBytes ), tail( std::move( bytes ) ) {}
+    uint64_t size() const { return front + tail.size(); }
+    uint8_t operator[]( uint64_t p ) const { return p < front ? (uint8_t)'x' : tail[p - front]; }
+};
+
+using Stretches = std::vector<std::pair<uint64_t, uint64_t> >;   /* [from, to) of the file, in order; neighbours joined */
+
+void
+append( Stretches& stretches, uint64_t from, uint64_t to )
+{
+    if ( from == to ) return;
+    if ( !stretches.empty() && stretches.back().second == from ) {
+        stretches.back().second = to;
+    } else {
+        stretches.push_back( { from, to } );
+    }
+}
+
+/* a launch's ragged output: block by block, the stretch of the file it holds */
+struct Output
+{
+    std::vector<uint64_t> at, from, length;
+    uint64_t bytes{ 0 };
+    uint64_t size() const { return bytes; }
+    void add( uint64_t fileFrom, uint64_t n ) { at.push_back( bytes ); from.push_back( fileFrom ); length.push_back( n ); bytes += n; }
+    /* the part holding output byte x (x < size()) */
+    size_t partOf( uint64_t x ) const { return (size_t)( std::upper_bound( at.begin(), at.end(), x ) - at.begin() ) - 1; }
+    uint64_t fileOffset( uint64_t x ) const { const size_t k = partOf( x ); return from[k] + ( x - at[k] ); }
+    /* output bytes [src, src + n) as stretches of the file */
+    void stretches( uint64_t src, uint64_t n, Stretches& out ) const
+    {
+        while ( n > 0 ) {
+            const size_t k = partOf( src );
+            const uint64_t take = std::min( n, at[k] + length[k] - src );
+            append( out, from[k] + ( src - at[k] ), from[k] + ( src - at[k] ) + take );
+            src += take;
+            n -= take;
+        }
+    }
+};
+
 /* streams of data blocks (decoded sizes), each followed by its end-of-stream entry, then the end-of-file entry */
 Map
-makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes )
+makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes,
+         uint64_t frontBytes = 0, uint64_t frontBits = 0 )
 {
     Map map;
     uint64_t bits = 32, bytes = 0;
+    if ( frontBytes > 0 ) {
+        /* a stream of one block of frontBytes decoded bytes that ends at bit frontBits */
+        map.push_back( { bits, 0 } );
+        map.push_back( { frontBits - 80, frontBytes } );
+        bits = frontBits + 32;
+        bytes = frontBytes;
+    }
     for ( const auto& stream : streams ) {
         for ( const auto size : stream ) {
             map.push_back( { bits, bytes } );
@@ -77,7 +139,7 @@ blocksOf( const Map& map )
 }
 
 void
-indexOf( const Map& map, const std::vector<uint8_t>& file, std::vector<uint64_t>& bytes, std::vector<uint64_t>& lines )
+indexOf( const Map& map, const File& file, std::vector<uint64_t>& bytes, std::vector<uint64_t>& lines )
 {
     const auto blocks = blocksOf( map );
     bytes = blocks.starts;
@@ -85,7 +147,9 @@ indexOf( const Map& map, const std::vector<uint8_t>& file, std::vector<uint64_t>
     lines.assign( 1, 0 );
     for ( size_t b = 0; b < blocks.starts.size(); ++b ) {
         uint64_t count = 0;
-        for ( uint64_t x = blocks.starts[b]; x < blocks.starts[b] + blocks.lengths[b]; ++x ) count += file[x] == NL;
+        for ( uint64_t x = std::max( blocks.starts[b], file.front ); x < blocks.starts[b] + blocks.lengths[b]; ++x ) {
+            count += file[x] == NL;      /* (the front holds no delimiter) */
+        }
         lines.push_back( lines.back() + count );
     }
 }
@@ -102,14 +166,14 @@ blockHolding( const Blocks& blocks, uint64_t x )
 
 struct Executed
 {
-    std::vector<std::vector<uint8_t> > outputs;   /* per launch */
+    std::vector<Output> outputs;                  /* per launch */
     std::vector<uint64_t> positions;              /* per query */
     std::vector<uint64_t> launched;               /* bit offsets, in launch order */
 };
 
 /* what the GPU does with a plan: decode the launches, answer the queries */
 Executed
-execute( const LinePlan& plan, const Map& map, const std::vector<uint8_t>& file, size_t cap, bool packed )
+execute( const LinePlan& plan, const Map& map, const File& file, size_t cap, bool packed )
 {
     Executed run;
     for ( size_t l = 0; l < plan.launches.size(); ++l ) {
@@ -117,7 +181,7 @@ execute( const LinePlan& plan, const Map& map, const std::vector<uint8_t>& file,
         CHECK( !launch.bits.empty() && launch.bits.size() <= cap );
         if ( l + 1 < plan.launches.size() ) CHECK( launch.bits.size() == cap );
         CHECK( packed ? launch.packedBits.size() == launch.bits.size() && !launch.windows.empty() : launch.windows.empty() );
-        std::vector<uint8_t> out;
+        Output out;
         for ( size_t k = 0; k < launch.bits.size(); ++k ) {
             if ( !run.launched.empty() ) CHECK( run.launched.back() < launch.bits[k] );
             run.launched.push_back( launch.bits[k] );
@@ -125,7 +189,7 @@ execute( const LinePlan& plan, const Map& map, const std::vector<uint8_t>& file,
             while ( map[e].first != launch.bits[k] ) ++e;
             CHECK( launch.sizes[k] == map[e + 1].second - map[e].second );
             CHECK( launch.outOffsets[k] == out.size() );
-            out.insert( out.end(), file.begin() + map[e].second, file.begin() + map[e + 1].second );
+            out.add( map[e].second, map[e + 1].second - map[e].second );
         }
         CHECK( launch.outBytes == out.size() );
         run.outputs.push_back( std::move( out ) );
@@ -139,7 +203,14 @@ execute( const LinePlan& plan, const Map& map, const std::vector<uint8_t>& file,
             CHECK( q.spanOffset + q.spanSize <= out.size() );
             uint64_t seen = 0;
             for ( uint64_t x = q.spanOffset; x < q.spanOffset + q.spanSize && x < out.size(); ++x ) {
-                if ( out[x] == NL && ++seen == q.rank ) {
+                const uint64_t p = out.fileOffset( x );
+                if ( p < file.front ) {
+                    /* no delimiter in the front: on to its end, or to the end of this part of the output */
+                    const size_t k = out.partOf( x );
+                    x += std::min( file.front - p, out.at[k] + out.length[k] - x ) - 1;
+                    continue;
+                }
+                if ( file[p] == NL && ++seen == q.rank ) {
                     position = x;
                     break;
                 }
@@ -151,7 +222,7 @@ execute( const LinePlan& plan, const Map& map, const std::vector<uint8_t>& file,
 }
 
 void
-checkRanges( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& file, const std::vector<uint64_t>& first,
+checkRanges( const Map& map, uint64_t fileBytes, const File& file, const std::vector<uint64_t>& first,
              const std::vector<uint64_t>& count, size_t cap, bool packed )
 {
     std::vector<uint64_t> indexBytes, indexLines;
@@ -163,7 +234,7 @@ checkRanges( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& fil
 
     /* s(k) by a scan of the file */
     std::vector<uint64_t> s( 1, 0 );
-    for ( uint64_t x = 0; x < file.size(); ++x ) {
+    for ( uint64_t x = file.front; x < file.size(); ++x ) {
         if ( file[x] == NL ) s.push_back( x + 1 );
     }
     const uint64_t N = s.size() - 1;
@@ -191,7 +262,7 @@ checkRanges( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& fil
     }
 
     /* the ranges' bytes from the segments, in order */
-    std::vector<std::vector<uint8_t> > got( n );
+    std::vector<Stretches> got( n );
     uint32_t lastRange = 0;
     for ( const auto& segment : plan.segments ) {
         CHECK( segment.range < n && segment.range >= lastRange && segment.launch < run.outputs.size() );
@@ -204,21 +275,21 @@ checkRanges( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& fil
         const auto& out = run.outputs[segment.launch];
         CHECK( src + size <= out.size() );
         if ( src + size > out.size() ) continue;
-        got[segment.range].insert( got[segment.range].end(), out.begin() + src, out.begin() + src + size );
+        out.stretches( src, size, got[segment.range] );
     }
     for ( size_t i = 0; i < n; ++i ) {
-        std::vector<uint8_t> want;
+        Stretches want;
         if ( first[i] <= N && count[i] != 0 ) {
             const uint64_t from = s[first[i]];
             const uint64_t to = count[i] > N - first[i] ? file.size() : s[first[i] + count[i]];
-            want.assign( file.begin() + from, file.begin() + to );
+            append( want, from, to );
         }
         CHECK( got[i] == want );
     }
 }
 
 void
-checkStarts( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& file, const std::vector<uint64_t>& lines,
+checkStarts( const Map& map, uint64_t fileBytes, const File& file, const std::vector<uint64_t>& lines,
              size_t cap, bool packed )
 {
     std::vector<uint64_t> indexBytes, indexLines;
@@ -227,7 +298,7 @@ checkStarts( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& fil
     const auto plan = planLines( map, indexBytes.data(), indexLines.data(), indexBytes.size(), lines.data(), nullptr,
                                  lines.size(), true, cap, packed, fileBytes );
     std::vector<uint64_t> s( 1, 0 );
-    for ( uint64_t x = 0; x < file.size(); ++x ) {
+    for ( uint64_t x = file.front; x < file.size(); ++x ) {
         if ( file[x] == NL ) s.push_back( x + 1 );
     }
     const uint64_t N = s.size() - 1;
@@ -254,11 +325,11 @@ checkStarts( const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& fil
 }
 
 void
-runCases( const char* name, const Map& map, uint64_t fileBytes, const std::vector<uint8_t>& file, std::mt19937_64& rng )
+runCases( const char* name, const Map& map, uint64_t fileBytes, const File& file, std::mt19937_64& rng )
 {
     currentCase = name;
     uint64_t N = 0;
-    for ( const auto byte : file ) N += byte == NL;
+    for ( const auto byte : file.tail ) N += byte == NL;
     std::vector<uint64_t> first, count;
     const auto add = [&] ( uint64_t f, uint64_t c ) { first.push_back( f ); count.push_back( c ); };
     const uint64_t HUGE_COUNT = ~uint64_t( 0 );
@@ -330,6 +401,22 @@ main()
         /* every byte a delimiter */
         runCases( "delimiters only", map, fileBytes, std::vector<uint8_t>( 701, NL ), rng );
     }
+    /* the same behind a front block of 2^32 - k bytes without a delimiter (k: inside block 0, its last byte, block 1's first
+     * byte, inside the long line, in the second stream), the bit offsets of what follows from just below 2^32 on */
+    {
+        const uint64_t cut = uint64_t( 1 ) << 32;
+        for ( const uint64_t k : { 1, 50, 99, 100, 101, 300, 400, 450, 700 } ) {
+            const uint64_t front = cut - k;
+            const auto map = makeMap( { { 100, 250, 50 }, { 300, 1 } }, rng, &fileBytes, front, cut - 8 * ( 5 + k % 7 ) );
+            currentCase = "high: the layout";
+            CHECK( map[2].second == front && map.back().second == front + 701 && map.back().first > cut );
+            runCases( "high, two streams", map, fileBytes, File( fileWith( 701, { 10, 11, 99, 400, 450, 699 } ), front ), rng );
+            if ( k % 100 != 0 ) continue;
+            runCases( "high, ends with a delimiter", map, fileBytes, File( fileWith( 701, { 10, 99, 400, 700 } ), front ), rng );
+            runCases( "high, no delimiter", map, fileBytes, File( fileWith( 701, {} ), front ), rng );
+            runCases( "high, delimiters only", map, fileBytes, File( std::vector<uint8_t>( 701, NL ), front ), rng );
+        }
+    }
     /* a single one-byte block: a delimiter, and not */
     {
         const auto map = makeMap( { { 1 } }, rng, &fileBytes );
@@ -339,10 +426,10 @@ main()
     /* an empty file: the index is {0: 0}, every range is empty, nothing is launched */
     {
         const Map map = { { 32, 0 }, { 112, 0 } };
-        runCases( "empty file", map, 14, {}, rng );
+        runCases( "empty file", map, 14, File{}, rng );
         currentCase = "empty file";
         std::vector<uint64_t> indexBytes, indexLines;
-        indexOf( map, {}, indexBytes, indexLines );
+        indexOf( map, File{}, indexBytes, indexLines );
         CHECK( indexBytes == std::vector<uint64_t>{ 0 } && indexLines == std::vector<uint64_t>{ 0 } );
         const uint64_t first[2] = { 0, 5 }, count[2] = { 10, 1 };
         const auto plan = planLines( map, indexBytes.data(), indexLines.data(), 1, first, count, 2, false, 4, false, 14 );
@@ -372,6 +459,12 @@ main()
         }
         if ( m % 4 == 0 ) delimiters.push_back( total - 1 );
         runCases( "seeded", map, fileBytes, fileWith( total, delimiters ), rng );
+        if ( m % 4 == 1 ) {
+            /* the same blocks and delimiters behind a front block that ends a seeded number of bytes below 2^32 */
+            const uint64_t front = ( uint64_t( 1 ) << 32 ) - 1 - rng() % total;
+            const auto high = makeMap( streams, rng, &fileBytes, front, ( uint64_t( 1 ) << 32 ) - 8 * ( 5 + rng() % 50 ) );
+            runCases( "high, seeded", high, fileBytes, File( fileWith( total, delimiters ), front ), rng );
+        }
     }
 
     /* an imported index is checked against the map */

@@ -4,6 +4,8 @@
  * an empty file) and seeded random ones; ranges unsorted, overlapping, duplicated, empty, at and beyond the end of the
  * file, longer than a launch; caps 1, 2, 3 and 512.  With bounded residency the packed input is built from the windows
  * and every block's rebased bit offset must see the file's bytes from its magic word to the end of its slack.
+ * The same cases once more behind one block of 2^32 - k decoded bytes that no range touches, its successors' bit offsets
+ * starting just below 2^32 as well: blocks, extents, pieces and windows that lie below, across and above 2^32.
  * Prints "ranges ok". */
 #include <cstdio>
 #include <cstdlib>
@@ -159,10 +161,18 @@ checkPlan( const Map& map, const std::vector<uint64_t>& offsets, const std::vect
 /* a map from block sizes: streams of data blocks (decoded sizes), each followed by its end-of-stream entry, then the
  * end-of-file entry; compressed sizes of the blocks vary */
 Map
-makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes )
+makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes,
+         uint64_t frontBytes = 0, uint64_t frontBits = 0 )
 {
     Map map;
     uint64_t bits = 32, bytes = 0;
+    if ( frontBytes > 0 ) {
+        /* a stream of one block of frontBytes decoded bytes that ends at bit frontBits */
+        map.push_back( { bits, 0 } );
+        map.push_back( { frontBits - 80, frontBytes } );
+        bits = frontBits + 32;
+        bytes = frontBytes;
+    }
     for ( const auto& stream : streams ) {
         for ( const auto size : stream ) {
             map.push_back( { bits, bytes } );
@@ -178,14 +188,16 @@ makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rn
     return map;
 }
 
+/* `low`: the ranges keep to the decoded bytes from `low` on (the front block of a high map is never asked for: the
+ * restatement would walk its 2^32 bytes one by one) */
 void
-runCases( const char* name, const Map& map, uint64_t fileBytes, std::mt19937_64& rng )
+runCases( const char* name, const Map& map, uint64_t fileBytes, std::mt19937_64& rng, uint64_t low = 0 )
 {
     currentCase = name;
-    const uint64_t total = map.empty() ? 0 : map.back().second;
+    const uint64_t total = ( map.empty() ? 0 : map.back().second ) - low;
     std::vector<uint64_t> offsets, sizes;
     /* hand-picked: empty, at the end, beyond it, straddling it, the whole file, every block boundary +-1 */
-    const auto add = [&] ( uint64_t o, uint64_t s ) { offsets.push_back( o ); sizes.push_back( s ); };
+    const auto add = [&] ( uint64_t o, uint64_t s ) { offsets.push_back( low + o ); sizes.push_back( s ); };
     add( 0, 0 );
     add( total, 5 );
     add( total + 100, 7 );
@@ -193,7 +205,8 @@ runCases( const char* name, const Map& map, uint64_t fileBytes, std::mt19937_64&
     add( 0, total );
     add( 0, total + 1 );
     for ( size_t i = 0; i < map.size(); ++i ) {
-        const uint64_t b = map[i].second;
+        if ( map[i].second < low ) continue;
+        const uint64_t b = map[i].second - low;
         add( b > 0 ? b - 1 : 0, 2 );
         add( b, 1 );
         add( b, 0 );
@@ -212,7 +225,7 @@ runCases( const char* name, const Map& map, uint64_t fileBytes, std::mt19937_64&
     }
     /* few ranges: one range longer than a launch holds */
     for ( const size_t cap : { 1, 2 } ) {
-        checkPlan( map, { 1 }, { total }, cap, true, fileBytes );
+        checkPlan( map, { low + 1 }, { total }, cap, true, fileBytes );
     }
 }
 }  // namespace
@@ -254,6 +267,31 @@ main()
         }
         const auto map = makeMap( streams, rng, &fileBytes );
         runCases( "seeded", map, fileBytes, rng );
+    }
+
+    /* offsets at and across 2^32: the maps above behind a front block of 2^32 - k bytes, the bit offsets of what follows
+     * starting 8 * j bits below 2^32.  With k inside the first blocks, one block holds byte 2^32 - 1 and byte 2^32 (or ends
+     * exactly there: k = the first block's size), extents start below and end above it, and so do the packed windows */
+    {
+        const uint64_t cut = uint64_t( 1 ) << 32;
+        const std::vector<std::vector<uint64_t> > streams = { { 100, 250, 50 }, { 300, 1 } };
+        for ( const uint64_t k : { 1, 37, 100, 101, 349, 350, 400, 700 } ) {
+            for ( const uint64_t j : { 5, 61, 120 } ) {
+                const auto map = makeMap( streams, rng, &fileBytes, cut - k, cut - 8 * j );
+                currentCase = "high";
+                CHECK( map[2].second == cut - k && map[2].first < cut && map.back().first > cut && map.back().second > cut );
+                runCases( "high", map, fileBytes, rng, cut - k );
+            }
+        }
+        for ( int m = 0; m < 6; ++m ) {
+            std::vector<std::vector<uint64_t> > seeded( 1 + rng() % 4 );
+            for ( auto& stream : seeded ) {
+                stream.resize( 1 + rng() % 40 );
+                for ( auto& size : stream ) size = 1 + rng() % 400;
+            }
+            const auto map = makeMap( seeded, rng, &fileBytes, cut - 1 - rng() % 3000, cut - 8 * ( 1 + rng() % 3000 ) );
+            runCases( "high seeded", map, fileBytes, rng, map[2].second );
+        }
     }
 
     /* the requested sizes must add up within 64 bits; a cap of 0 is refused */

@@ -12,7 +12,12 @@
  * head and tail are cut from it, and the launches' matches merged with seamMatches' must be the matches of the file in
  * [start, end) -- with start and end cutting the first and the last extent, beyond the size, empty, and shorter than m.
  * The extents must lie back to back from the clipped start to the clipped end, inside their launches' outputs, and the
- * launches must hold exactly the blocks that intersect the range, once, at most `cap` each.  Prints "search ok". */
+ * launches must hold exactly the blocks that intersect the range, once, at most `cap` each.
+ *
+ * Offsets at and across 2^32: seamCase with the extents' file offsets shifted so that two of them meet exactly at 2^32 (and
+ * one byte to either side of it), and planCase on maps whose blocks lie behind a front block of 2^32 - k bytes that no
+ * range touches (`base`: the file offset of the bytes held), the bit offsets of what follows from just below 2^32 on:
+ * extents that start below and end above 2^32, matches that straddle it.  Prints "search ok". */
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -72,8 +77,9 @@ periodic( size_t size, size_t period, uint32_t m, std::mt19937_64& rng, Bytes& t
 
 int crossedKinds = 0;   /* bit 0: a match crossed exactly 1 boundary, bit 1: exactly 2, bit 2: 5 or more */
 
+/* `shift`: added to every extent's file offset, and so to every expected match */
 void
-seamCase( const Bytes& text, const Bytes& pattern, const std::vector<uint64_t>& sizes, uint64_t from )
+seamCase( const Bytes& text, const Bytes& pattern, const std::vector<uint64_t>& sizes, uint64_t from, uint64_t shift = 0 )
 {
     const auto m = (uint32_t)pattern.size();
     std::vector<ExtentSeam> seams;
@@ -99,6 +105,8 @@ seamCase( const Bytes& text, const Bytes& pattern, const std::vector<uint64_t>& 
             crossedKinds |= crossed == 1 ? 1 : crossed == 2 ? 2 : crossed >= 5 ? 4 : 0;
         }
     }
+    for ( auto& seam : seams ) seam.fileOffset += shift;
+    for ( auto& p : expected ) p += shift;
     const auto got = seamMatches( pattern.data(), m, seams );
     CHECK( got == expected );
 }
@@ -133,6 +141,14 @@ seamCases()
             seamCase( text, pattern, { 1000, 1, 1, 1, 1, 1, 1, 1000, 2, 3, 1000, 1, 0, 0, 1, 1000, 0, 1, 2, 1, 0 }, 11 );
             seamCase( text, pattern, std::vector<uint64_t>( 600, 1 ), 0 );
             seamCase( text, pattern, std::vector<uint64_t>( 300, 3 ), 5 );
+            currentCase = "two extents that meet at 2^32, and next to it";
+            for ( const uint64_t first : { (uint64_t)1000, (uint64_t)m, (uint64_t)1 } ) {
+                const uint64_t cut = uint64_t( 1 ) << 32;
+                for ( const uint64_t meet : { cut - 1, cut, cut + 1, cut + m - 1 } ) {
+                    /* the first extent ends at `meet`; rows of tiny ones and long ones follow */
+                    seamCase( text, pattern, { first, 1000, 1, 1, m, 2, 1000, 0, 1, 3ull * m + 17 }, 13, meet - 13 - first );
+                }
+            }
             currentCase = "one extent, no extent, empty extents only";
             seamCase( text, pattern, { 5000 }, 3 );
             seamCase( text, pattern, {}, 0 );
@@ -171,10 +187,18 @@ seamCases()
 
 /* streams of data blocks (decoded sizes), each followed by its end-of-stream entry, then the end-of-file entry */
 Map
-makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes )
+makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes,
+         uint64_t frontBytes = 0, uint64_t frontBits = 0 )
 {
     Map map;
     uint64_t bits = 32, bytes = 0;
+    if ( frontBytes > 0 ) {
+        /* a stream of one block of frontBytes decoded bytes that ends at bit frontBits */
+        map.push_back( { bits, 0 } );
+        map.push_back( { frontBits - 80, frontBytes } );
+        bits = frontBits + 32;
+        bytes = frontBytes;
+    }
     for ( const auto& stream : streams ) {
         for ( const auto size : stream ) {
             map.push_back( { bits, bytes } );
@@ -190,11 +214,14 @@ makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rn
     return map;
 }
 
+/* `base`: `file` holds the decoded bytes from file offset `base` on (a high map's front block is not held, and no range
+ * of such a case starts below `base`) */
 void
-planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Bytes& pattern, uint64_t start, uint64_t end, size_t cap )
+planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Bytes& pattern, uint64_t start, uint64_t end, size_t cap,
+          uint64_t base = 0 )
 {
     const auto m = (uint32_t)pattern.size();
-    const uint64_t total = file.size();
+    const uint64_t total = base + file.size();
     const uint64_t to = std::min( end, total ), from = std::min( start, to );
     for ( const bool packed : { false, true } ) {
         const auto plan = planSearch( map, start, end, m, cap, packed, fileBytes );
@@ -228,7 +255,7 @@ planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Bytes& pa
                 const auto& block = blockOfBits[launchedBits.size() < blockOfBits.size() ? launchedBits.size() : 0];
                 launchedBits.push_back( launch.bits[k] );
                 CHECK( launch.outOffsets[k] == output.size() && launch.sizes[k] == block.second );
-                output.insert( output.end(), file.begin() + block.first, file.begin() + block.first + block.second );
+                output.insert( output.end(), file.begin() + ( block.first - base ), file.begin() + ( block.first - base ) + block.second );
             }
             CHECK( launch.outBytes == output.size() );
             const auto& extent = plan.extents[l];
@@ -236,7 +263,9 @@ planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Bytes& pa
             CHECK( extent.src <= output.size() && extent.size <= output.size() - extent.src );
             if ( extent.src + extent.size > output.size() ) return;
             /* extent offset -> file offset is one addition */
-            CHECK( std::memcmp( output.data() + extent.src, file.data() + extent.fileOffset, extent.size ) == 0 );
+            CHECK( extent.fileOffset >= base );
+            if ( extent.fileOffset < base ) return;
+            CHECK( std::memcmp( output.data() + extent.src, file.data() + ( extent.fileOffset - base ), extent.size ) == 0 );
             /* only the first launch's extent may start, and only the last one's may end, inside the output */
             CHECK( l == 0 || extent.src == 0 );
             CHECK( l + 1 == plan.launches.size() || extent.src + extent.size == output.size() );
@@ -252,7 +281,9 @@ planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Bytes& pa
         const auto between = seamMatches( pattern.data(), m, seams );
         found.insert( found.end(), between.begin(), between.end() );
         std::sort( found.begin(), found.end() );
-        CHECK( found == matchesIn( file, from, to, pattern ) );
+        auto expected = matchesIn( file, from - base, to - base, pattern );
+        for ( auto& p : expected ) p += base;
+        CHECK( found == expected );
         CHECK( std::set<uint64_t>( found.begin(), found.end() ).size() == found.size() );
     }
 }
@@ -290,6 +321,36 @@ planCases()
                     for ( int k = 0; k < 12; ++k ) {
                         const uint64_t a = rng() % total, b = rng() % ( total + 3 );
                         planCase( map, fileBytes, file, pattern, std::min( a, b ), std::max( a, b ), cap );
+                    }
+                }
+            }
+        }
+    }
+    /* the layouts behind a front block of 2^32 - k bytes: k inside the first block, at its end, in a later block */
+    const uint64_t cut = uint64_t( 1 ) << 32;
+    for ( const auto& layout : layouts ) {
+        for ( const uint64_t k : { (uint64_t)1, (uint64_t)2, (uint64_t)300, (uint64_t)600 } ) {
+            uint64_t fileBytes = 0;
+            const uint64_t base = cut - k;
+            const auto map = makeMap( layout, rng, &fileBytes, base, cut - 8 * ( 5 + rng() % 100 ) );
+            const uint64_t total = map.back().second;
+            for ( const uint32_t m : { 1u, 2u, 16u, 256u } ) {
+                Bytes file, pattern;
+                periodic( total - base, m == 16 ? 7 : 3, m, rng, file, pattern );
+                for ( const size_t cap : { (size_t)1, (size_t)3, (size_t)512 } ) {
+                    currentCase = "high: everything behind the front, and beyond the size";
+                    planCase( map, fileBytes, file, pattern, base, total, cap, base );
+                    planCase( map, fileBytes, file, pattern, base, ~uint64_t( 0 ), cap, base );
+                    currentCase = "high: ranges that end and start at 2^32 and next to it";
+                    for ( const uint64_t edge : { cut - 1, cut, cut + 1, cut + m - 1, cut + m } ) {
+                        planCase( map, fileBytes, file, pattern, base, edge, cap, base );
+                        planCase( map, fileBytes, file, pattern, edge, total, cap, base );
+                        planCase( map, fileBytes, file, pattern, edge > base + m ? edge - m : base, edge, cap, base );
+                    }
+                    currentCase = "high: seeded ranges";
+                    for ( int r = 0; r < 8; ++r ) {
+                        const uint64_t a = base + rng() % ( total - base ), b = base + rng() % ( total - base + 3 );
+                        planCase( map, fileBytes, file, pattern, std::min( a, b ), std::max( a, b ), cap, base );
                     }
                 }
             }

@@ -8,7 +8,8 @@
  * and once each.  Extents of 1 to 3 bytes that a mixed-case match crosses several of; a match whose case differs from the
  * pattern's on both sides of a seam, asserted by name; m = 1; empty extents; patterns given in lower, upper and mixed case;
  * bytes next to the letters ('@', '[', '`', '{') and their counterparts above 0x80, which must not fold.  With the flag off
- * the same inputs must give what the exact functions give (and on text with mixed case that is less).
+ * the same inputs must give what the exact functions give (and on text with mixed case that is less).  The same cuts once
+ * more with the extents' file offsets shifted so that two extents meet exactly at 2^32, or one byte to either side.
  *
  * writeSetImage with fold: Err, eRR, err, [x and \xC5x land in the expected buckets, in id order, the stored bytes folded;
  * without fold the image is the exact one.  makePatternSet with fold changes neither ids, sizes nor m_min and m_max.
@@ -97,9 +98,10 @@ insideOne( const std::vector<ExtentSeam>& seams, uint64_t p, uint64_t m )
 
 size_t seamMatchesSeen = 0, foldOnlySeen = 0;
 
-/* both functions, fold on and off, for one cut of one text */
+/* both functions, fold on and off, for one cut of one text; `shift` is added to every extent's file offset, and so to
+ * every expected position */
 void
-seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_t>& sizes, uint64_t from )
+seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_t>& sizes, uint64_t from, uint64_t shift = 0 )
 {
     uint64_t to = from;
     for ( const auto size : sizes ) to += size;
@@ -122,6 +124,8 @@ seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_
             for ( uint64_t p = from; p + m <= to; ++p ) {
                 if ( equalAt( text, p, pattern, fold ) && !insideOne( seams, p, m ) ) expected.push_back( p );
             }
+            for ( auto& seam : seams ) seam.fileOffset += shift;
+            for ( auto& p : expected ) p += shift;
             const auto got = seamMatches( pattern.data(), m, seams, fold );
             CHECK( got == expected );
             if ( !fold ) CHECK( got == seamMatches( pattern.data(), m, seams ) );    /* the default is the exact search */
@@ -144,6 +148,8 @@ seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_
                 if ( p + m <= to && equalAt( text, p, patterns[i], fold ) && !insideOne( seams, p, m ) ) expected.push_back( { p, i } );
             }
         }
+        for ( auto& seam : seams ) seam.fileOffset += shift;
+        for ( auto& pair : expected ) pair.first += shift;
         const auto made = setOf( patterns, fold );
         const auto plain = setOf( patterns, false );
         CHECK( made.fold == fold && made.sizes == plain.sizes && made.offsets == plain.offsets && made.bytes == plain.bytes
@@ -236,6 +242,13 @@ seamCases()
         seamCase( text, patterns, { 0, 0, 0 }, 5 );
         seamCase( text, patterns, {}, 0 );
         seamCase( text, patterns, { 1000 }, 9 );
+        currentCase = "extents that meet at 2^32, and next to it";
+        for ( const uint64_t first : { (uint64_t)1000, (uint64_t)40, (uint64_t)1 } ) {
+            const uint64_t cut = uint64_t( 1 ) << 32;
+            for ( const uint64_t meet : { cut - 1, cut, cut + 1, cut + 39 } ) {
+                seamCase( text, patterns, { first, 1000, 1, 2, 3, 1, 40, 0, 39, 500 }, 13, meet - 13 - first );
+            }
+        }
         currentCase = "seeded extent sizes";
         const std::vector<uint64_t> kinds{ 0, 1, 2, 3, 39, 40, 41, 137, 1000 };
         for ( int round = 0; round < 6; ++round ) {

@@ -15,6 +15,11 @@
  * that holds `limit` safe pairs gives the first `limit` pairs of the whole result -- for every limit of a case in which
  * a long pattern crosses a boundary in front of a short one inside.
  *
+ * Offsets at and across 2^32: seamCase with the extents' file offsets shifted so that two of them meet at 2^32 and next to
+ * it; planCase on maps whose blocks lie behind a front block of 2^32 - k bytes that no range touches (`base`: the file
+ * offset of the bytes held), the bit offsets of what follows from just below 2^32 on; and the limit rule with the first
+ * front's end exactly at 2^32 -- the long pattern crosses it -- and with the limit reached above it.
+ *
  * writeSetImage: every pattern is found again through the first-byte table, the buckets in id order.  patternSetError:
  * every limit.  Prints "search set ok". */
 #include <cstdio>
@@ -96,8 +101,9 @@ slice( const Bytes& text, size_t at, size_t n )
 
 size_t mostCrossed = 0;
 
+/* `shift`: added to every extent's file offset, and so to every expected pair's position */
 void
-seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_t>& sizes, uint64_t from )
+seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_t>& sizes, uint64_t from, uint64_t shift = 0 )
 {
     const auto set = setOf( patterns );
     std::vector<ExtentSeam> seams;
@@ -124,6 +130,8 @@ seamCase( const Bytes& text, const Patterns& patterns, const std::vector<uint64_
             mostCrossed = std::max( mostCrossed, crossed );
         }
     }
+    for ( auto& seam : seams ) seam.fileOffset += shift;
+    for ( auto& pair : expected ) pair.first += shift;
     const auto got = seamMatchesSet( set, seams );
     CHECK( got == expected );
 }
@@ -165,6 +173,13 @@ seamCases()
             seamCase( text, patterns, { 1000, 1, 1, 1, 1, 1, 1, 1000, 2, 3, 1000, 1, 0, 0, 1, 1000, 0, 1, 2, 1, 0 }, 11 );
             seamCase( text, patterns, std::vector<uint64_t>( 600, 1 ), 0 );
             seamCase( text, patterns, std::vector<uint64_t>( 300, 3 ), 5 );
+            currentCase = "two extents that meet at 2^32, and next to it";
+            for ( const uint64_t first : { (uint64_t)1000, mMax, (uint64_t)1 } ) {
+                const uint64_t cut = uint64_t( 1 ) << 32;
+                for ( const uint64_t meet : { cut - 1, cut, cut + 1, cut + mMax - 1 } ) {
+                    seamCase( text, patterns, { first, 1000, 1, 1, mMax, 2, 1000, 0, 1, 3 * mMax + 17 }, 13, meet - 13 - first );
+                }
+            }
             currentCase = "one extent, no extent, empty extents only";
             seamCase( text, patterns, { 5000 }, 3 );
             seamCase( text, patterns, {}, 0 );
@@ -215,10 +230,18 @@ seamCases()
 
 /* streams of data blocks (decoded sizes), each followed by its end-of-stream entry, then the end-of-file entry */
 Map
-makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes )
+makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rng, uint64_t* fileBytes,
+         uint64_t frontBytes = 0, uint64_t frontBits = 0 )
 {
     Map map;
     uint64_t bits = 32, bytes = 0;
+    if ( frontBytes > 0 ) {
+        /* a stream of one block of frontBytes decoded bytes that ends at bit frontBits */
+        map.push_back( { bits, 0 } );
+        map.push_back( { frontBits - 80, frontBytes } );
+        bits = frontBits + 32;
+        bytes = frontBytes;
+    }
     for ( const auto& stream : streams ) {
         for ( const auto size : stream ) {
             map.push_back( { bits, bytes } );
@@ -234,10 +257,21 @@ makeMap( const std::vector<std::vector<uint64_t> >& streams, std::mt19937_64& rn
     return map;
 }
 
-/* The merged result of a plan, as the reader computes it.  With a limit: the launches are taken in order until the front
- * holds `limit` safe pairs, the rest is skipped, and the merge is cut. */
+/* pairsIn over file offsets [from, to) of a file whose bytes are held from file offset `base` on */
 std::vector<SetMatch>
-execute( const SearchPlan& plan, const Bytes& file, const Patterns& patterns, const PatternSet& set, uint64_t limit, size_t* used )
+pairsAt( const Bytes& file, uint64_t base, uint64_t from, uint64_t to, const Patterns& patterns )
+{
+    auto found = pairsIn( file, from - base, to - base, patterns );
+    for ( auto& pair : found ) pair.first += base;
+    return found;
+}
+
+/* The merged result of a plan, as the reader computes it.  With a limit: the launches are taken in order until the front
+ * holds `limit` safe pairs, the rest is skipped, and the merge is cut.  `base`: `file` holds the decoded bytes from file
+ * offset `base` on (a high map's front block is not held, and no range of such a case starts below `base`). */
+std::vector<SetMatch>
+execute( const SearchPlan& plan, const Bytes& file, const Patterns& patterns, const PatternSet& set, uint64_t limit, size_t* used,
+         uint64_t base = 0 )
 {
     std::vector<ExtentSeam> seams;
     std::vector<SetMatch> inside;
@@ -245,12 +279,13 @@ execute( const SearchPlan& plan, const Bytes& file, const Patterns& patterns, co
     size_t l = 0;
     for ( ; l < plan.extents.size() && ( limit == 0 || safe < limit ); ++l ) {
         const auto& extent = plan.extents[l];
-        const auto own = pairsIn( file, extent.fileOffset, extent.fileOffset + extent.size, patterns );
+        const auto own = pairsAt( file, base, extent.fileOffset, extent.fileOffset + extent.size, patterns );
         std::vector<uint64_t> positions;
         for ( const auto& pair : own ) positions.push_back( pair.first );
         safe += safePairs( positions.data(), positions.size(), extent.fileOffset + extent.size, set.mMax );
         inside.insert( inside.end(), own.begin(), own.end() );
-        seams.push_back( seamOf( file, extent.fileOffset, extent.size, set.mMax ) );
+        seams.push_back( seamOf( file, extent.fileOffset - base, extent.size, set.mMax ) );
+        seams.back().fileOffset = extent.fileOffset;
     }
     *used = l;
     const auto between = seamMatchesSet( set, seams );
@@ -261,10 +296,11 @@ execute( const SearchPlan& plan, const Bytes& file, const Patterns& patterns, co
 }
 
 void
-planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Patterns& patterns, uint64_t start, uint64_t end, size_t cap )
+planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Patterns& patterns, uint64_t start, uint64_t end, size_t cap,
+          uint64_t base = 0 )
 {
     const auto set = setOf( patterns );
-    const uint64_t total = file.size();
+    const uint64_t total = base + file.size();
     const uint64_t to = std::min( end, total ), from = std::min( start, to );
     for ( const bool packed : { false, true } ) {
         const auto plan = planSearchSet( map, start, end, set, cap, packed, fileBytes );
@@ -285,9 +321,9 @@ planCase( const Map& map, uint64_t fileBytes, const Bytes& file, const Patterns&
         }
         CHECK( at == to );
         size_t used = 0;
-        const auto all = execute( plan, file, patterns, set, 0, &used );
+        const auto all = execute( plan, file, patterns, set, 0, &used, base );
         CHECK( used == plan.extents.size() );
-        CHECK( all == pairsIn( file, from, to, patterns ) );
+        CHECK( all == pairsAt( file, base, from, to, patterns ) );
         CHECK( std::set<SetMatch>( all.begin(), all.end() ).size() == all.size() );
     }
 }
@@ -340,6 +376,40 @@ planCases()
             }
         }
     }
+    /* the layouts behind a front block of 2^32 - k bytes: k inside the first block, at its end, in a later block */
+    const uint64_t cut = uint64_t( 1 ) << 32;
+    for ( const auto& layout : layouts ) {
+        for ( const uint64_t k : { (uint64_t)1, (uint64_t)2, (uint64_t)300, (uint64_t)600 } ) {
+            uint64_t fileBytes = 0;
+            const uint64_t base = cut - k;
+            const auto map = makeMap( layout, rng, &fileBytes, base, cut - 8 * ( 5 + rng() % 100 ) );
+            const uint64_t total = map.back().second;
+            const Bytes file = periodic( total - base, 3, rng );
+            const std::vector<Patterns> sets{
+                { slice( file, 0, 3 ), slice( file, 0, 16 ), slice( file, 0, 3 ), slice( file, 1, 2 ) },
+                { slice( file, 0, 1 ), slice( file, 0, 256 ) },
+            };
+            for ( const auto& patterns : sets ) {
+                const uint64_t mMax = setOf( patterns ).mMax;
+                for ( const size_t cap : { (size_t)1, (size_t)3, (size_t)512 } ) {
+                    currentCase = "high: everything behind the front, and beyond the size";
+                    planCase( map, fileBytes, file, patterns, base, total, cap, base );
+                    planCase( map, fileBytes, file, patterns, base, ~uint64_t( 0 ), cap, base );
+                    currentCase = "high: ranges that end and start at 2^32 and next to it";
+                    for ( const uint64_t edge : { cut - 1, cut, cut + 1, cut + mMax - 1, cut + mMax } ) {
+                        planCase( map, fileBytes, file, patterns, base, edge, cap, base );
+                        planCase( map, fileBytes, file, patterns, edge, total, cap, base );
+                        planCase( map, fileBytes, file, patterns, edge > base + mMax ? edge - mMax : base, edge, cap, base );
+                    }
+                    currentCase = "high: seeded ranges";
+                    for ( int r = 0; r < 6; ++r ) {
+                        const uint64_t a = base + rng() % ( total - base ), b = base + rng() % ( total - base + 3 );
+                        planCase( map, fileBytes, file, patterns, std::min( a, b ), std::max( a, b ), cap, base );
+                    }
+                }
+            }
+        }
+    }
     currentCase = "an empty file";
     const Map empty{ { 32, 0 }, { 80, 0 } };
     planCase( empty, 14, {}, { { 'a' } }, 0, 10, 4 );
@@ -352,6 +422,45 @@ planCases()
         thrown = true;
     }
     CHECK( thrown );
+}
+
+/* The limit rule on blocks of 1000 bytes, one per launch, that start at decoded offset `base` (0, or behind a front block that
+ * ends there): L (200 bytes) crosses the first boundary from base + 900, S = L[50:52] lies inside the first extent at
+ * base + 950 and elsewhere: (base + 900, L) sorts in front of (base + 950, S) but only the second launch shows it. */
+void
+limitRule( uint64_t base, std::mt19937_64& rng )
+{
+    const uint64_t cut = uint64_t( 1 ) << 32;
+    uint64_t fileBytes = 0;
+    const auto map = base == 0 ? makeMap( { { 1000, 1000, 1000, 1000, 500 } }, rng, &fileBytes )
+                               : makeMap( { { 1000, 1000, 1000, 1000, 500 } }, rng, &fileBytes, base, cut - 8 * 9 );
+    Bytes file( 4500 );
+    for ( size_t i = 0; i < file.size(); ++i ) file[i] = (uint8_t)( 'a' + ( i * 7 + i / 13 ) % 23 );
+    Bytes big( 200 );
+    for ( size_t i = 0; i < big.size(); ++i ) big[i] = (uint8_t)( 'A' + i % 26 );
+    std::copy( big.begin(), big.end(), file.begin() + 900 );
+    std::copy( big.begin(), big.end(), file.begin() + 2950 );
+    const Bytes tiny = slice( big, 50, 2 );
+    for ( const size_t at : { (size_t)100, (size_t)200, (size_t)300, (size_t)700, (size_t)1500, (size_t)1700, (size_t)2500, (size_t)3990 } ) std::copy( tiny.begin(), tiny.end(), file.begin() + at );
+    for ( const bool longFirst : { true, false } ) {
+        const Patterns patterns = longFirst ? Patterns{ big, tiny } : Patterns{ tiny, big };
+        const auto set = setOf( patterns );
+        for ( const size_t cap : { (size_t)1, (size_t)2 } ) {
+            const auto plan = planSearchSet( map, base, ~uint64_t( 0 ), set, cap, false, fileBytes );
+            size_t used = 0;
+            const auto all = execute( plan, file, patterns, set, 0, &used, base );
+            CHECK( all == pairsAt( file, base, base, base + file.size(), patterns ) && all.size() >= 10 );
+            CHECK( base == 0 || ( all.front().first < cut && all.back().first > cut ) );
+            bool skipped = false;
+            for ( uint64_t limit = 1; limit <= all.size() + 1; ++limit ) {
+                const auto some = execute( plan, file, patterns, set, limit, &used, base );
+                const auto n = (size_t)std::min<uint64_t>( limit, all.size() );
+                CHECK( some == std::vector<SetMatch>( all.begin(), all.begin() + n ) );
+                skipped = skipped || used < plan.extents.size();
+            }
+            CHECK( skipped );    /* the rule does stop launches */
+        }
+    }
 }
 
 void
@@ -371,36 +480,10 @@ limitCases()
     }
 
     currentCase = "the limit rule";
-    /* blocks of 1000 bytes, one per launch; L (200 bytes) crosses the first boundary from 900, S = L[50:52] lies inside the
-     * first extent at 950 and elsewhere: (900, L) sorts in front of (950, S) but only the second launch shows it */
-    uint64_t fileBytes = 0;
-    const auto map = makeMap( { { 1000, 1000, 1000, 1000, 500 } }, rng, &fileBytes );
-    Bytes file( 4500 );
-    for ( size_t i = 0; i < file.size(); ++i ) file[i] = (uint8_t)( 'a' + ( i * 7 + i / 13 ) % 23 );
-    Bytes big( 200 );
-    for ( size_t i = 0; i < big.size(); ++i ) big[i] = (uint8_t)( 'A' + i % 26 );
-    std::copy( big.begin(), big.end(), file.begin() + 900 );
-    std::copy( big.begin(), big.end(), file.begin() + 2950 );
-    const Bytes tiny = slice( big, 50, 2 );
-    for ( const size_t at : { (size_t)100, (size_t)200, (size_t)300, (size_t)700, (size_t)1500, (size_t)1700, (size_t)2500, (size_t)3990 } ) std::copy( tiny.begin(), tiny.end(), file.begin() + at );
-    for ( const bool longFirst : { true, false } ) {
-        const Patterns patterns = longFirst ? Patterns{ big, tiny } : Patterns{ tiny, big };
-        const auto set = setOf( patterns );
-        for ( const size_t cap : { (size_t)1, (size_t)2 } ) {
-            const auto plan = planSearchSet( map, 0, ~uint64_t( 0 ), set, cap, false, fileBytes );
-            size_t used = 0;
-            const auto all = execute( plan, file, patterns, set, 0, &used );
-            CHECK( all == pairsIn( file, 0, file.size(), patterns ) && all.size() >= 10 );
-            bool skipped = false;
-            for ( uint64_t limit = 1; limit <= all.size() + 1; ++limit ) {
-                const auto some = execute( plan, file, patterns, set, limit, &used );
-                const auto n = (size_t)std::min<uint64_t>( limit, all.size() );
-                CHECK( some == std::vector<SetMatch>( all.begin(), all.begin() + n ) );
-                skipped = skipped || used < plan.extents.size();
-            }
-            CHECK( skipped );    /* the rule does stop launches */
-        }
-    }
+    /* base 0, and behind a front block: the first block ends exactly at 2^32 (L crosses 2^32 from 2^32 - 100), the third
+     * does (the second L crosses it, and limits are reached above it), and 2^32 lies inside the first block */
+    const uint64_t cut = uint64_t( 1 ) << 32;
+    for ( const uint64_t base : { (uint64_t)0, cut - 1000, cut - 3000, cut - 500 } ) limitRule( base, rng );
 }
 
 void
