@@ -338,6 +338,50 @@ int mi355x_bz2_find_bytes_set_ex( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_spa
                                   uint32_t flags, uint64_t* positions, uint32_t* ids, uint64_t capacity, uint64_t* counts,
                                   uint64_t* per_pattern );
 
+/* A regular expression, compiled to a small DFA on the host (no GPU is needed), and the lines of spans of the last batch's
+ * output that match it.  D, nl and lines as under line access below; the CONTENT of a line is its bytes without the
+ * closing nl, and the unterminated tail is a line only if it is non-empty.  A line matches iff Python's
+ * re.search( pattern, content, re.DOTALL ) on bytes finds a match; with MI355X_BZ2_SEARCH_IGNORE_CASE in `flags`,
+ * re.IGNORECASE as well (ASCII letters only, 0x80 .. 0xFF never fold).  One difference: `$` is the end of the content
+ * only, where Python's also matches in front of a final "\n" of the content (which a content has only if nl is not "\n").
+ * Accepted syntax, every construct with Python's meaning: literal bytes, 0x80 .. 0xFF included; a backslash in front of
+ * ASCII punctuation; \n \r \t \f \v \0 \xHH; \d \D \w \W \s \S; `.` (any byte); [...] and [^...] with ranges, escapes and
+ * \d \w \s inside (a `]` must be escaped); ( ) and (?: ), both only grouping; |; * + ? {m} {m,} {m,n} {,n} with counts
+ * <= 255; ^ and $ anywhere.  Refused with MI355X_BZ2_ERR_INVALID_ARGUMENT and a sentence in `error` (at most
+ * error_capacity bytes with the final 0; may be NULL) that names the construct and its offset in the pattern:
+ * back-references, look-around, inline flags, named groups, lazy and possessive quantifiers, \b \B \A \Z and every other
+ * escape, a `{` that opens no repetition, an empty pattern, a pattern over 4096 bytes, any flag bit but
+ * MI355X_BZ2_SEARCH_* ("unknown flag bits", as _search_ex), and a pattern whose minimal DFA has more than
+ * MI355X_BZ2_REGEX_MAX_STATES states (the sentence gives the count; the construction stops at 2048 states before
+ * minimisation).
+ * The DFA: transitions[n][256] and accepts_at_end[n], n = _regex_states.  State 0 is the start of a line -- no transition
+ * leads to it --, state 1 is "this line has matched" and is absorbing.  `^` holds in state 0 only, `$` is accepts_at_end.
+ * The table does not know nl: transitions on nl are never taken.
+ *   _regex_table        copies both arrays (n * 256 and n bytes).
+ *   _regex_chunk_bytes  the bytes one GPU lane walks (bz2_regex.hip.h says why 256): of interest to tests and tuning.
+ *   _match_lines        over spans as for _find_bytes (inside the last batch's output, no batch in flight, a span given
+ *                       twice is searched twice).  Per span i, with the span read as a stretch of D that a line may enter
+ *                       and leave: head_maps[64 i + q] = the state behind the span's HEAD (its bytes in front of its first
+ *                       nl, all of them if it has none) entered in state q (0 for q >= n); has_delimiter[i]; exit_states[i]
+ *                       = the state behind the bytes that follow the span's last nl (0 without one); counts[i] = the lines
+ *                       that START inside the span and are seen to match inside it, and positions[] = one offset of the
+ *                       output inside each of them (the byte that completes the first match, or the closing nl where only
+ *                       the end of the line decides), span by span in caller order and ascending within a span, the first
+ *                       `capacity` of them; capacity 0 runs no emitting pass.  The span's head line is not among them:
+ *                       whether it matches depends on the state the span is entered in, which the caller composes
+ *                       (bz2_regex.hpp: stitchSummaries).  k_regex_chunks, k_regex_link, k_scan_tiles, k_regex_emit. */
+#define MI355X_BZ2_REGEX_MAX_STATES 64
+typedef struct mi355x_bz2_regex mi355x_bz2_regex;
+int mi355x_bz2_regex_compile( const uint8_t* pattern, uint64_t size, uint32_t flags, mi355x_bz2_regex** re, char* error,
+                              uint64_t error_capacity );
+void mi355x_bz2_regex_free( mi355x_bz2_regex* re );
+uint32_t mi355x_bz2_regex_states( const mi355x_bz2_regex* re );
+int mi355x_bz2_regex_table( const mi355x_bz2_regex* re, uint8_t* transitions, uint8_t* accepts_at_end );
+uint32_t mi355x_bz2_regex_chunk_bytes( void );
+int mi355x_bz2_match_lines( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, const mi355x_bz2_regex* re,
+                            uint8_t nl, uint8_t* head_maps, uint8_t* has_delimiter, uint8_t* exit_states, uint64_t* positions,
+                            uint64_t capacity, uint64_t* counts );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -620,6 +664,16 @@ int mi355x_bz2_reader_grep_set( mi355x_bz2_reader* r, const uint8_t* patterns, c
 int mi355x_bz2_reader_grep_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns, const uint32_t* pattern_sizes,
                                    uint32_t n_patterns, uint32_t flags, uint8_t nl, uint64_t start, uint64_t end,
                                    uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+
+/* ---- grep for a regular expression (bzgrep PATTERN, grep -n): _grep with a DFA run as its first pass.  `re` comes from
+ * mi355x_bz2_regex_compile, which also says which lines match.  The whole file is searched: there is no start / end.
+ * The launches are those of _search over [0, size); each runs mi355x_bz2_match_lines on its part on the context that
+ * decoded it, the host composes the parts' summaries (lines that cross launches, `^` and `$` included) into one offset per
+ * matching line, and the rank and line passes of _grep follow.  max_lines == 0 counts only: no emitting pass, no rank
+ * pass, nothing held.  Otherwise the first min( max_lines, all ) matching lines are held; _take_grep and
+ * _take_line_ranges serve them unchanged.  Positionless; holds and releases as _grep does, same failure rules. */
+int mi355x_bz2_reader_grep_regex( mi355x_bz2_reader* r, const mi355x_bz2_regex* re, uint8_t nl, uint64_t max_lines,
+                                  int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

@@ -11,7 +11,9 @@ and which lines hold it (grep, count_matching_lines, grep_to_tensor: the lines o
 whole, with their 0-based numbers).  The same for a set of up to 1 024 byte strings with one decode of the file per call
 (count_matches_each, find_all_any, find_any, grep_any, count_matching_lines_any, grep_any_to_tensor).  Every one of these
 search and grep methods takes the keyword-only ignore_case=True, which folds the ASCII letters of pattern and data on the
-GPU (bytes.lower() on both sides, `LC_ALL=C grep -i`; the bytes 0x80 to 0xFF are never folded).
+GPU (bytes.lower() on both sides, `LC_ALL=C grep -i`; the bytes 0x80 to 0xFF are never folded).  And the lines that match
+a regular expression (grep_regex, count_matching_lines_regex, grep_regex_to_tensor): compile_regex turns a subset of
+Python's bytes `re` syntax into a DFA of at most 64 states on the host, and the GPU runs it over the decoded file.
 """
 __version__ = "0.1.0"
 
@@ -24,8 +26,8 @@ import os as _os
 # existing setting wins
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from ._native import (Bz2Error, Decoder, find_magic, lib, plan_compress_blocks, status_string,  # noqa: F401
-                      warmup)
+from ._native import (Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib,  # noqa: F401
+                      plan_compress_blocks, status_string, warmup)
 from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
                       decompress_many_to_tensor)
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401

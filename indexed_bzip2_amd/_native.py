@@ -17,6 +17,7 @@ OK = 0
 ERR_CRC = 15
 ERR_STREAM_CRC = 17
 ERR_NO_DEVICE = 102
+ERR_INVALID_ARGUMENT = 103
 
 
 class Config(ctypes.Structure):
@@ -173,6 +174,15 @@ SYMBOLS = [
     ("mi355x_bz2_find_bytes_set_ex", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_char_p, _u32p,
                                                      ctypes.c_uint32, ctypes.c_uint32, _u64p, _u32p, ctypes.c_uint64, _u64p,
                                                      _u64p]),
+    ("mi355x_bz2_regex_compile", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.POINTER(_vp),
+                                                 ctypes.c_char_p, ctypes.c_uint64]),
+    ("mi355x_bz2_regex_free", None, [_vp]),
+    ("mi355x_bz2_regex_states", ctypes.c_uint32, [_vp]),
+    ("mi355x_bz2_regex_table", ctypes.c_int, [_vp, _vp, _vp]),
+    ("mi355x_bz2_regex_chunk_bytes", ctypes.c_uint32, []),
+    ("mi355x_bz2_match_lines", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, _vp, ctypes.c_uint8, _vp, _vp,
+                                               _vp, _u64p, ctypes.c_uint64, _u64p]),
+    ("mi355x_bz2_reader_grep_regex", ctypes.c_int, [_vp, _vp, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -318,6 +328,58 @@ SET_MAX_PATTERNS, SET_MAX_PATTERN_BYTES, SET_MAX_BYTES = 1024, 256, 16384
 
 
 SEARCH_IGNORE_CASE = 1          # MI355X_BZ2_SEARCH_IGNORE_CASE
+
+
+REGEX_MAX_STATES = 64           # MI355X_BZ2_REGEX_MAX_STATES
+
+
+class CompiledRegex:
+    """A regular expression compiled to the DFA the GPU runs (compile_regex).  .states is the number n of states,
+    .transitions a numpy uint8 array [n, 256], .accepts_at_end a numpy uint8 array [n]: state 0 is the start of a line,
+    state 1 is "this line has matched" and absorbing, `^` holds in state 0 only and `$` is accepts_at_end."""
+
+    def __init__(self, pattern, ignore_case=False):
+        import numpy as np
+        if isinstance(pattern, str):
+            raise TypeError("the pattern must be a bytes-like object, not str")
+        self.pattern = bytes(_byte_view(pattern))
+        self.ignore_case = bool(ignore_case)
+        self._h = None
+        handle = ctypes.c_void_p()
+        error = ctypes.create_string_buffer(512)
+        rc = lib().mi355x_bz2_regex_compile(self.pattern, len(self.pattern), SEARCH_IGNORE_CASE if ignore_case else 0,
+                                            ctypes.byref(handle), error, len(error))
+        if rc == ERR_INVALID_ARGUMENT:
+            raise ValueError(error.value.decode("latin-1"))
+        if rc != OK:
+            raise Bz2Error(rc, error.value.decode("latin-1"))
+        self._h = handle
+        self.states = int(lib().mi355x_bz2_regex_states(handle))
+        self.transitions = np.empty((self.states, 256), dtype=np.uint8)
+        self.accepts_at_end = np.empty(self.states, dtype=np.uint8)
+        lib().mi355x_bz2_regex_table(handle, self.transitions.ctypes.data, self.accepts_at_end.ctypes.data)
+        self.transitions.setflags(write=False)
+        self.accepts_at_end.setflags(write=False)
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and _lib is not None:
+            _lib.mi355x_bz2_regex_free(self._h)
+            self._h = None
+
+    def __repr__(self):
+        return f"CompiledRegex({self.pattern!r}, ignore_case={self.ignore_case}, states={self.states})"
+
+
+def compile_regex(pattern, ignore_case=False):
+    """Compile `pattern` (bytes-like; a subset of Python's bytes `re` syntax, every accepted pattern with Python's meaning
+    under re.DOTALL) for grep_regex and Decoder.match_lines.  Needs no GPU.  A pattern outside the subset, or one whose
+    DFA needs more than 64 states, is a ValueError that names the construct and its offset."""
+    return CompiledRegex(pattern, ignore_case)
+
+
+def regex_chunk_bytes():
+    """The bytes of a span that one GPU lane walks in match_lines (mi355x_bz2_regex_chunk_bytes)."""
+    return int(lib().mi355x_bz2_regex_chunk_bytes())
 
 
 def pattern_set(patterns, check=True):
@@ -615,6 +677,39 @@ class Decoder:
                                                        counts, None))
         found = min(capacity, sum(counts[:len(spans)]))
         return list(positions[:found]), list(ids[:found]), list(counts[:len(spans)])
+
+    def match_lines(self, spans, regex, newline=b"\n", capacity=None):
+        """k_regex_chunks, k_regex_link, k_scan_tiles, k_regex_emit: the summary of every span [(offset, size)] of the last
+        batch's output under `regex` (compile_regex, or a pattern to compile), read as a stretch of lines that a line may
+        enter and leave -> (head_maps, has_delimiter, exit_states, positions, counts): head_maps a numpy uint8 array
+        [spans, 64] (the state behind the span's first line for every entry state), has_delimiter and exit_states one
+        value per span, positions one offset inside every line that starts in its span and matches there, span by span
+        and ascending, the first `capacity` of them (None: all; 0: no emitting pass), counts their true number per span."""
+        import numpy as np
+        if not isinstance(regex, CompiledRegex):
+            regex = compile_regex(regex)
+        nl = bytes(newline)
+        if len(nl) != 1:
+            raise ValueError("newline must be exactly one byte")
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        head_maps = np.zeros((len(spans), REGEX_MAX_STATES), dtype=np.uint8)
+        has_delimiter = np.zeros(max(1, len(spans)), dtype=np.uint8)
+        exit_states = np.zeros(max(1, len(spans)), dtype=np.uint8)
+        counts = (ctypes.c_uint64 * max(1, len(spans)))()
+
+        def call(positions, room):
+            self._check(lib().mi355x_bz2_match_lines(self._h, arr, len(spans), regex._h, nl[0],
+                                                     head_maps.ctypes.data if len(spans) else None,
+                                                     has_delimiter.ctypes.data, exit_states.ctypes.data, positions, room, counts))
+        if capacity is None:
+            call(None, 0)
+            capacity = sum(counts[:len(spans)])
+        positions = (ctypes.c_uint64 * max(1, capacity))()
+        call(positions, capacity)
+        found = min(capacity, sum(counts[:len(spans)]))
+        return (head_maps, [bool(v) for v in has_delimiter[:len(spans)]], [int(v) for v in exit_states[:len(spans)]],
+                list(positions[:found]), list(counts[:len(spans)]))
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -9,7 +9,14 @@
 #include <vector>
 
 #include "../../include/mi355x_bz2.h"
+#include "bz2_regex.hpp"
 #include "bz2_search.hpp"
+
+/** What mi355x_bz2_regex_compile hands out (bz2_regex.cpp). */
+struct mi355x_bz2_regex
+{
+    bz2gpu::Regex dfa;
+};
 
 namespace mi355x
 {
@@ -42,6 +49,12 @@ int searchOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const
 int searchOutputSet( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const bz2gpu::PatternSet& set, uint64_t limit,
                      std::vector<uint64_t>* positions, std::vector<uint32_t>* ids, uint64_t* count, uint64_t* perPattern,
                      uint8_t* seamBytes );
+
+/** The reader's regular-expression pass in one launch: mi355x_bz2_match_lines with `extent` as its one span.  *summary
+ * receives the extent's summary and the true count of its body witnesses; with limit > 0 its witnesses are the first
+ * min( count, limit ) of them as offsets in the output (0: count only, no emitting pass). */
+int matchLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const bz2gpu::Regex& regex, uint8_t nl,
+                      uint64_t limit, bz2gpu::StretchSummary* summary );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

@@ -28,6 +28,7 @@
 #include "bz2_lines.hip.h"
 #include "bz2_search.hip.h"
 #include "bz2_search_set.hip.h"
+#include "bz2_regex.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -35,6 +36,7 @@
 #include "bz2_scratch.hpp"
 #include "bz2_lanes.hpp"
 #include "bz2_ctx.hpp"
+#include "bz2_regex.hpp"
 
 using namespace bz2gpu;
 
@@ -213,7 +215,8 @@ struct mi355x_bz2_ctx : Scratch
     GrowBuffer hSelect{ nullptr, 0, true }, dSelect;
 
     /* mi355x_bz2_count_bytes / _find_bytes: tiles, pattern, counts and seam bytes of one call, page-locked and on the
-     * device, and the positions of the emitting pass on the device (searchBytes lays them out) */
+     * device, and the positions of the emitting pass on the device (searchBytes lays them out).  mi355x_bz2_match_lines
+     * uses the same three for its tiles, table, summaries and witnesses (matchLines lays them out) */
     GrowBuffer hSearch{ nullptr, 0, true }, dSearch, dSearchPositions;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
@@ -2102,6 +2105,127 @@ searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span*
     return MI355X_BZ2_OK;
 }
 
+static_assert( REGEX_STATES == REGEX_MAX_STATES && REGEX_CHUNK == REGEX_CHUNK_BYTES, "the kernels' constants are the compiler's" );
+
+/**
+ * mi355x_bz2_match_lines and the reader's launches.  Every span is cut into tiles of COUNT_TILE bytes = REGEX_THREADS
+ * chunks; k_regex_chunks summarises every chunk, k_regex_link -- one workgroup per span -- gives the chunks their entry
+ * states and head hits and writes the spans' summaries and counts, which come back in one D2H.  With positions wanted,
+ * k_scan_tiles turns the chunk counts into places, k_regex_emit writes min( total, capacity ) witnesses and a second D2H
+ * brings them to `positions`, or to `grown` resized to their number.  An empty span has the identity for its headMap.
+ */
+int
+matchLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const Regex& regex, uint8_t nl,
+            uint8_t* headMaps, uint8_t* hasDelimiter, uint8_t* exitStates, bool wantPositions, uint64_t capacity,
+            uint64_t* positions, std::vector<uint64_t>* grown, uint64_t* counts )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    if ( regex.n < 2 || regex.n > REGEX_MAX_STATES || regex.transitions.size() != (size_t)regex.n * 256
+         || regex.acceptsAtEnd.size() != regex.n ) {
+        c->lastError = std::string( what ) + ": not a compiled regular expression";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    uint64_t nTiles = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
+    }
+    if ( grown != nullptr ) grown->clear();
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles * REGEX_THREADS > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][spans][table][accepts] up, [span maps][span info][span counts] down; device only, behind
+     * them: [chunk maps][chunk info][chunk counts][chunk places] */
+    const uint64_t slots = nTiles * REGEX_THREADS, stride = regexMapStride( regex.n );
+    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
+    const uint64_t spansAt = nTiles * sizeof( CountTile ), tableAt = aligned( spansAt + n * sizeof( RegexSpan ) );
+    const uint64_t acceptsAt = tableAt + (uint64_t)regex.n * 256, resultsAt = aligned( acceptsAt + REGEX_STATES );
+    const uint64_t spanInfoAt = resultsAt + (uint64_t)n * REGEX_STATES, spanCountsAt = aligned( spanInfoAt + n * sizeof( uint32_t ) );
+    const uint64_t mapsAt = aligned( spanCountsAt + n * sizeof( uint64_t ) ), infoAt = mapsAt + slots * stride;
+    const uint64_t countsAt = infoAt + slots * sizeof( uint32_t ), placesAt = aligned( countsAt + slots * sizeof( uint32_t ) );
+    const uint64_t bytes = placesAt + slots * sizeof( uint64_t );
+    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
+    /* the previous call's lists have been consumed (every call waits for its kernels) */
+    /* the host holds what goes up and comes down, not the per-chunk arrays */
+    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, mapsAt );
+    HIP_TRY( c, c->hSearch.grow( c, mapsAt, hostCap, hostCap ) );
+    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
+    uint8_t* const h = c->hSearch.bytes;
+    auto* const hTiles = reinterpret_cast<CountTile*>( h );
+    auto* const hSpans = reinterpret_cast<RegexSpan*>( h + spansAt );
+    uint64_t tile = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        hSpans[s] = { (uint32_t)( tile * REGEX_THREADS ), (uint32_t)( ( spans[s].size + REGEX_CHUNK - 1 ) / REGEX_CHUNK ) };
+        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
+            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
+        }
+    }
+    std::memcpy( h + tableAt, regex.transitions.data(), (size_t)regex.n * 256 );
+    std::memset( h + acceptsAt, 0, resultsAt - acceptsAt );
+    std::memcpy( h + acceptsAt, regex.acceptsAtEnd.data(), regex.n );
+    uint8_t* const d = c->dSearch.bytes;
+    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
+    auto* const dInfo = reinterpret_cast<uint32_t*>( d + infoAt );
+    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_regex_chunks, dim3( (uint32_t)nTiles ), dim3( REGEX_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            d + tableAt, d + acceptsAt, regex.n, (uint32_t)nl, d + mapsAt, dInfo, dCounts );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_regex_link, dim3( n ), dim3( REGEX_THREADS ), 0, c->stream,
+                        reinterpret_cast<const RegexSpan*>( d + spansAt ), d + acceptsAt, regex.n, d + mapsAt, dInfo, dCounts,
+                        d + resultsAt, reinterpret_cast<uint32_t*>( d + spanInfoAt ),
+                        reinterpret_cast<unsigned long long*>( d + spanCountsAt ) );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, mapsAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    uint64_t total = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const uint32_t info = reinterpret_cast<const uint32_t*>( h + spanInfoAt )[i];
+        std::memcpy( headMaps + (size_t)i * REGEX_STATES, h + resultsAt + (size_t)i * REGEX_STATES, REGEX_STATES );
+        hasDelimiter[i] = ( info & REGEX_HAS_DELIMITER ) != 0 ? 1 : 0;
+        exitStates[i] = (uint8_t)( info >> REGEX_EXIT_SHIFT );
+        counts[i] = reinterpret_cast<const uint64_t*>( h + spanCountsAt )[i];
+        total += counts[i];
+    }
+    const uint64_t wanted = wantPositions ? std::min( total, capacity ) : 0;
+    if ( wanted == 0 ) return MI355X_BZ2_OK;
+
+    if ( grown != nullptr ) {
+        try {
+            grown->resize( wanted );
+        } catch ( const std::exception& ) {
+            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " positions";
+            return MI355X_BZ2_ERR_DEVICE;
+        }
+        positions = grown->data();
+    }
+    const uint64_t need = wanted * sizeof( uint64_t );
+    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
+    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
+    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
+    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_regex_emit, dim3( (uint32_t)nTiles ), dim3( REGEX_THREADS ), 0, c->stream, dTiles, c->dOut,
+                        d + tableAt, d + acceptsAt, regex.n, (uint32_t)nl, dInfo, dPlaces, wanted, dPositions );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, need, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -2139,6 +2263,20 @@ mi355x::searchOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, con
     if ( c == nullptr || pattern == nullptr || count == nullptr || seamBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return searchBytes( c, "search", &extent, 1, pattern, m, flags, positions != nullptr, limit, nullptr, positions, count,
                         &extent, seamBytes );
+}
+
+int
+mi355x::matchLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const bz2gpu::Regex& regex, uint8_t nl,
+                          uint64_t limit, bz2gpu::StretchSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    uint8_t hasDelimiter = 0, exitState = 0;
+    summary->witnesses.clear();
+    const int status = matchLines( c, "grep_regex", &extent, 1, regex, nl, summary->headMap.data(), &hasDelimiter, &exitState,
+                                   limit > 0, limit, nullptr, &summary->witnesses, &summary->count );
+    summary->hasDelimiter = hasDelimiter != 0;
+    summary->exit = exitState;
+    return status;
 }
 
 int
@@ -2232,6 +2370,20 @@ mi355x_bz2_find_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uin
                        uint32_t patternSize, uint64_t* positions, uint64_t capacity, uint64_t* counts )
 {
     return mi355x_bz2_find_bytes_ex( c, spans, n, pattern, patternSize, 0, positions, capacity, counts );
+}
+
+int
+mi355x_bz2_match_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const mi355x_bz2_regex* re, uint8_t nl,
+                        uint8_t* headMaps, uint8_t* hasDelimiter, uint8_t* exitStates, uint64_t* positions, uint64_t capacity,
+                        uint64_t* counts )
+{
+    if ( c == nullptr || re == nullptr
+         || ( n > 0 && ( spans == nullptr || headMaps == nullptr || hasDelimiter == nullptr || exitStates == nullptr || counts == nullptr ) )
+         || ( capacity > 0 && positions == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return matchLines( c, "match_lines", spans, n, re->dfa, nl, headMaps, hasDelimiter, exitStates, capacity > 0, capacity,
+                       positions, nullptr, counts );
 }
 
 int

@@ -1677,6 +1677,43 @@ public:
         grepPositions( positions, nl, maxLines, keepOnDevice, nLines, totalBytes );
     }
 
+    /** mi355x_bz2_reader_grep_regex: grep with a DFA run as its first pass.  The launches are planSearch's over the whole
+     * file; each summarises its extent (matchLinesOutput), stitchSummaries composes the summaries into one offset inside
+     * every matching line, and the rank and line passes are grep's.  Only the number of lines wanted: the count of
+     * witnesses is the answer, nothing is emitted or ranked. */
+    void
+    grepRegex( const bz2gpu::Regex& regex, uint8_t nl, uint64_t maxLines, bool keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "grep_regex on a closed reader" );
+        m_matches.reset();
+        const uint64_t everything = std::numeric_limits<uint64_t>::max();
+        indexUpTo( everything );
+        const auto map = knownMap();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planSearch( map, 0, everything, 1, m_batch, packed, m_source->size() );
+        } );
+        std::vector<bz2gpu::Stretch> stretches( plan.launches.size() );
+        for ( size_t l = 0; l < stretches.size(); ++l ) {
+            stretches[l].fileOffset = plan.extents[l].fileOffset;
+            stretches[l].size = plan.extents[l].size;
+        }
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [&regex, nl, maxLines, extent = plan.extents[l], stretch = &stretches[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+                checkDevice( ctx, matchLinesOutput( ctx, { extent.src, extent.size }, regex, nl, maxLines, &stretch->summary ) );
+                for ( auto& witness : stretch->summary.witnesses ) witness = extent.fileOffset + ( witness - extent.src );
+            };
+        } );
+        if ( maxLines == 0 ) {
+            dropHeldLines();
+            *nLines = bz2gpu::stitchSummaries( regex, stretches, nullptr );
+            *totalBytes = 0;
+            return;
+        }
+        std::vector<uint64_t> positions;
+        bz2gpu::stitchSummaries( regex, stretches, &positions );
+        grepPositions( positions, nl, maxLines, keepOnDevice, nLines, totalBytes );
+    }
+
     /** The rank and line passes of grep, from the ascending positions of the matches' first bytes. */
     void
     grepPositions( const std::vector<uint64_t>& positions, uint8_t nl, uint64_t maxLines, bool keepOnDevice, uint64_t* nLines,
@@ -2525,6 +2562,16 @@ mi355x_bz2_reader_take_set_matches( mi355x_bz2_reader* r, uint64_t* positions, u
 {
     if ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeSetMatches( positions, ids, capacity ); } );
+}
+
+int
+mi355x_bz2_reader_grep_regex( mi355x_bz2_reader* r, const mi355x_bz2_regex* re, uint8_t nl, uint64_t maxLines, int keepOnDevice,
+                              uint64_t* nLines, uint64_t* totalBytes )
+{
+    if ( re == nullptr || nLines == nullptr || totalBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.grepRegex( re->dfa, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
+    } );
 }
 
 int

@@ -23,6 +23,7 @@
 #include <fstream>
 #include <iostream>
 #include <iterator>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -41,8 +42,8 @@ struct Options
     bool quiet{ false }, version{ false };
     int verbose{ 0 };
     bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false }, grep{ false }, lineNumber{ false };
-    bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false };
-    std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile;
+    bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false }, grepRegex{ false };
+    std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
     int device{ -1 };
@@ -96,6 +97,12 @@ printHelp()
         "                                bytes in total; a final empty line is ignored, any other empty line refused).\n"
         "                                A line that contains several of them is printed once. The data is decoded\n"
         "                                once for the search whatever the number of strings.\n"
+        "      --grep-regex arg          As --grep, for a regular expression (bzgrep PATTERN): print the lines whose\n"
+        "                                content matches it. The syntax is a subset of Python's bytes re syntax with\n"
+        "                                re.DOTALL: literals, . [...] [^...] \\d \\w \\s \\D \\W \\S \\n \\t \\xHH, ( ) (?: ) |,\n"
+        "                                * + ? {m} {m,} {m,n} {,n}, ^ and $. Back-references, look-around, lazy\n"
+        "                                quantifiers, \\b and patterns that need more than 64 DFA states are refused.\n"
+        "                                --line-number and --ignore-case apply as for --grep.\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -123,7 +130,9 @@ printHelp()
         "Print the lines that contain any of the strings listed in a file:\n"
         "  ibzip2-mi355x --grep-file codes.txt file.bz2\n\n"
         "Print the lines that contain a string in any case (error, Error, ERROR):\n"
-        "  ibzip2-mi355x --grep error --ignore-case file.bz2\n";
+        "  ibzip2-mi355x --grep error --ignore-case file.bz2\n\n"
+        "Print the lines that start with a date and report an error:\n"
+        "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
 
 /** The patterns of --grep-file / --count-matches-file: the LF-separated lines of the file, concatenated, and their sizes.
@@ -236,6 +245,7 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "count-lines" ) o.countLines = true;
             else if ( name == "count-matches" ) { if ( !need( o.pattern ) ) return 1; o.countMatches = true; }
             else if ( name == "grep" ) { if ( !need( o.pattern ) ) return 1; o.grep = true; }
+            else if ( name == "grep-regex" ) { if ( !need( o.regex ) ) return 1; o.grepRegex = true; }
             else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
             else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
             else if ( name == "line-number" ) o.lineNumber = true;
@@ -436,11 +446,15 @@ main( int argc, char** argv )
         std::cerr << "Options '--grep', '--count-matches', '--grep-file' and '--count-matches-file' cannot be combined\n";
         return 1;
     }
-    if ( o.lineNumber && !o.grep && !o.grepFile ) {
+    if ( o.grepRegex && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile ) ) {
+        std::cerr << "Option '--grep-regex' cannot be combined with '--grep', '--count-matches', '--grep-file' or '--count-matches-file'\n";
+        return 1;
+    }
+    if ( o.lineNumber && !o.grep && !o.grepFile && !o.grepRegex ) {
         std::cerr << "Option '--line-number' needs '--grep' or '--grep-file'\n";
         return 1;
     }
-    if ( o.ignoreCase && !o.grep && !o.grepFile && !o.countMatches && !o.countMatchesFile ) {
+    if ( o.ignoreCase && !o.grep && !o.grepFile && !o.countMatches && !o.countMatchesFile && !o.grepRegex ) {
         std::cerr << "Option '--ignore-case' needs '--grep', '--grep-file', '--count-matches' or '--count-matches-file'\n";
         return 1;
     }
@@ -523,8 +537,20 @@ main( int argc, char** argv )
         return 0;
     }
 
-    /* likewise: the lines that hold a match (bzgrep -F), from the reader's grep; 0 also when no line matched */
-    if ( o.grep ) {
+    /* likewise: the lines that hold a match (bzgrep -F), from the reader's grep, or that match a regular expression
+     * (bzgrep), from its grep_regex; 0 also when no line matched */
+    if ( o.grep || o.grepRegex ) {
+        mi355x_bz2_regex* regex = nullptr;
+        if ( o.grepRegex ) {
+            /* before anything is opened: a pattern outside the syntax is the user's to fix */
+            char why[512];
+            if ( mi355x_bz2_regex_compile( reinterpret_cast<const uint8_t*>( o.regex.data() ), o.regex.size(), searchFlags, &regex,
+                                           why, sizeof( why ) ) != MI355X_BZ2_OK ) {
+                std::cerr << "Invalid regular expression: " << why << "\n";
+                return 1;
+            }
+        }
+        const std::unique_ptr<mi355x_bz2_regex, void ( * )( mi355x_bz2_regex* )> regexOwner( regex, mi355x_bz2_regex_free );
         Input in;
         if ( !in.open( o.input ) ) {
             std::cerr << "Could not open '" << o.input << "'\n";
@@ -541,8 +567,10 @@ main( int argc, char** argv )
             return 1;
         }
         uint64_t nLines = 0, total = 0;
-        rc = mi355x_bz2_reader_grep_ex( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(),
-                                        searchFlags, '\n', 0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0, &nLines, &total );
+        rc = o.grepRegex
+             ? mi355x_bz2_reader_grep_regex( reader, regex, '\n', ~uint64_t( 0 ), 0, &nLines, &total )
+             : mi355x_bz2_reader_grep_ex( reader, reinterpret_cast<const uint8_t*>( o.pattern.data() ), (uint32_t)o.pattern.size(),
+                                          searchFlags, '\n', 0, ~uint64_t( 0 ), ~uint64_t( 0 ), 0, &nLines, &total );
         std::vector<uint64_t> numbers( nLines ), sizes( nLines );
         std::vector<char> bytes( total );
         if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );

@@ -503,6 +503,86 @@ class _IndexedBzip2FileParallel:
             bounds.append(bounds[-1] + size)
         return numbers, data, torch.tensor(bounds, dtype=torch.int64)
 
+    # -- grep for a regular expression: a line matches iff re.search(pattern, content, re.DOTALL) finds a match in its
+    # content (the line without its delimiter; the unterminated tail is a line only if it is non-empty).  The pattern is
+    # compiled on the host to a DFA of at most 64 states (N.compile_regex names the syntax), the GPU runs it over the whole
+    # decoded file, and the rank and line passes are grep's.  There is no start / end
+    @staticmethod
+    def _regex(pattern, ignore_case):
+        if isinstance(pattern, N.CompiledRegex):
+            if ignore_case and not pattern.ignore_case:
+                raise ValueError("ignore_case is a property of the compiled regex: compile_regex(pattern, ignore_case=True)")
+            return pattern
+        return N.compile_regex(pattern, ignore_case)
+
+    def _grep_regex(self, regex, limit, nl, on_device):
+        """Step 1 (mi355x_bz2_reader_grep_regex) and the numbers and sizes of the held lines, as _grep."""
+        import numpy as np
+        n, total = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_grep_regex(self._h, regex._h, nl, limit, 1 if on_device else 0,
+                                                         ctypes.byref(n), ctypes.byref(total)))
+        if limit == 0:
+            return n.value
+        numbers = (ctypes.c_uint64 * max(1, n.value))()
+        sizes = (ctypes.c_uint64 * max(1, n.value))()
+        self._check(N.lib().mi355x_bz2_reader_take_grep(self._h, numbers, sizes, n.value))
+        return (np.frombuffer(numbers, dtype=np.uint64, count=n.value).copy(), [sizes[i] for i in range(n.value)],
+                total.value)
+
+    def count_matching_lines_regex(self, pattern, newline=b"\n", *, ignore_case=False):
+        """The number of lines whose content matches the regular expression `pattern` (`grep -c`, with ignore_case
+        `grep -c -i`): bytes-like, or compiled by compile_regex.  One pass on the GPU, only counts leave it."""
+        self._require()
+        regex, nl = self._regex(pattern, ignore_case), self._newline(newline)
+        return self._grep_regex(regex, 0, nl, False)
+
+    def grep_regex(self, pattern, limit=None, newline=b"\n", *, ignore_case=False):
+        """The lines whose content matches the regular expression `pattern` (`bzgrep -n PATTERN`) -> (numbers, lines), as
+        grep returns them: 0-based line numbers (numpy uint64, strictly ascending) and one bytes object per line, whole
+        and with its delimiter, at most `limit` lines (None: all).  `pattern` is bytes-like or compiled by compile_regex;
+        a pattern outside the supported syntax is a ValueError before anything is launched.  The whole file is searched.
+        Positionless; releases matches and line ranges held by earlier calls."""
+        import numpy as np
+        limit = self._line_limit(limit)
+        self._require()
+        regex, nl = self._regex(pattern, ignore_case), self._newline(newline)
+        if limit == 0:                                 # nothing is asked for: the arguments are checked, nothing runs
+            return np.empty(0, dtype=np.uint64), []
+        numbers, sizes, total = self._grep_regex(regex, limit, nl, False)
+        out = bytearray(total)
+        dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
+        self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
+        del dst
+        lines, at = [], 0
+        for size in sizes:
+            lines.append(bytes(out[at:at + size]))
+            at += size
+        return numbers, lines
+
+    def grep_regex_to_tensor(self, pattern, limit=None, newline=b"\n", *, ignore_case=False):
+        """grep_regex into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets), as
+        grep_to_tensor."""
+        import numpy as np
+        import torch
+        limit = self._line_limit(limit)
+        self._require()
+        regex, nl = self._regex(pattern, ignore_case), self._newline(newline)
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        if limit == 0:
+            numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
+        else:
+            numbers, sizes, total = self._grep_regex(regex, limit, nl, True)
+        data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+        if total:
+            torch.cuda.current_stream(data.device).synchronize()
+        if limit != 0:
+            self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, ctypes.c_void_p(data.data_ptr()) if total else None, 1))
+        bounds = [0]
+        for size in sizes:
+            bounds.append(bounds[-1] + size)
+        return numbers, data, torch.tensor(bounds, dtype=torch.int64)
+
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
     # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
     # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
@@ -703,6 +783,18 @@ class IndexedBzip2File(io.BufferedReader):
     def grep_to_tensor(self, pattern, start=0, end=None, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep_to_tensor."""
         return self._open_reader().grep_to_tensor(pattern, start, end, limit, newline, ignore_case=ignore_case)
+
+    def grep_regex(self, pattern, limit=None, newline=b"\n", *, ignore_case=False):
+        """See _IndexedBzip2FileParallel.grep_regex."""
+        return self._open_reader().grep_regex(pattern, limit, newline, ignore_case=ignore_case)
+
+    def count_matching_lines_regex(self, pattern, newline=b"\n", *, ignore_case=False):
+        """See _IndexedBzip2FileParallel.count_matching_lines_regex."""
+        return self._open_reader().count_matching_lines_regex(pattern, newline, ignore_case=ignore_case)
+
+    def grep_regex_to_tensor(self, pattern, limit=None, newline=b"\n", *, ignore_case=False):
+        """See _IndexedBzip2FileParallel.grep_regex_to_tensor."""
+        return self._open_reader().grep_regex_to_tensor(pattern, limit, newline, ignore_case=ignore_case)
 
     def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
