@@ -382,6 +382,38 @@ int mi355x_bz2_match_lines( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spa
                             uint8_t nl, uint8_t* head_maps, uint8_t* has_delimiter, uint8_t* exit_states, uint64_t* positions,
                             uint64_t capacity, uint64_t* counts );
 
+/* One 61-bit hash per line.  p = 2^61 - 1; splitmix64( s ): z = s + 0x9E3779B97F4A7C15, z = ( z ^ z >> 30 ) *
+ * 0xBF58476D1CE4E5B9, z = ( z ^ z >> 27 ) * 0x94D049BB133111EB, z ^ z >> 31, all mod 2^64; the base of a 64-bit seed is
+ * x = 256 + splitmix64( seed ) mod ( p - 256 ).  The hash of a line is the hash of its CONTENT (its bytes without the
+ * closing nl): h = 0, then h = ( h * x + b + 1 ) mod p for every byte b, the canonical value in [0, p).  The empty line
+ * hashes to 0, and "\0" and "\0\0" differ.  Two distinct contents of at most L bytes have the same hash for at most L of
+ * the p - 256 bases: equal hashes say "the same line" with that probability, not with certainty, "distinct" below means
+ * "of distinct hash", and a second seed is an independent check.  Lines are numbered as grep numbers them: line k is
+ * closed by the k-th nl, counted from 0; a non-empty unterminated tail is one more line, an empty one is none.
+ *   _line_hash        the hash of `size` bytes of content; host only, no GPU is needed.
+ *   _line_hash_chunk_bytes  the bytes one GPU lane walks: of interest to tests and tuning.
+ *   _hash_lines       over spans as for _find_bytes (inside the last batch's output, no batch in flight).  With
+ *                     xl = x^length mod p beside a hash, ( h1, xl1 ) followed by ( h2, xl2 ) is ( h1 * xl2 + h2,
+ *                     xl1 * xl2 ).  Per span i, read as a stretch of D that a line may enter and leave: head = ( h, xl ) of
+ *                     its bytes in front of its first nl (all of them if it has none); has_delimiter; tail = ( h, xl ) of
+ *                     the bytes behind its last nl (( 0, 1 ) without one); tail_non_empty = the span is not empty and its
+ *                     last byte is not nl; count = the lines the span closes.  hashes_device[] (DEVICE memory, uint64,
+ *                     room for `capacity`) receives the hashes of the closed lines, span by span in caller order and in
+ *                     line order within a span, the first `capacity` of them; nothing is written at or beyond `capacity`,
+ *                     and capacity 0 runs no emitting pass.  The first closed line of a span is hashed as if the span
+ *                     were entered with hash 0: the caller that knows the carry ( h, xl ) in front of the span replaces
+ *                     it by carry.h * head_xl + head_hash (bz2_linehash.hpp: stitchSummaries).  The call returns when
+ *                     the hashes are written.  k_linehash_chunks, k_linehash_link, k_scan_tiles, k_linehash_emit. */
+typedef struct mi355x_bz2_line_hash_summary
+{
+    uint64_t head_hash, head_xl, tail_hash, tail_xl, count;
+    uint32_t has_delimiter, tail_non_empty;
+} mi355x_bz2_line_hash_summary;
+uint64_t mi355x_bz2_line_hash( const uint8_t* bytes, uint64_t size, uint64_t seed );
+uint32_t mi355x_bz2_line_hash_chunk_bytes( void );
+int mi355x_bz2_hash_lines( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t seed,
+                           mi355x_bz2_line_hash_summary* summaries, uint64_t* hashes_device, uint64_t capacity );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -674,6 +706,36 @@ int mi355x_bz2_reader_grep_set_ex( mi355x_bz2_reader* r, const uint8_t* patterns
  * _take_line_ranges serve them unchanged.  Positionless; holds and releases as _grep does, same failure rules. */
 int mi355x_bz2_reader_grep_regex( mi355x_bz2_reader* r, const mi355x_bz2_regex* re, uint8_t nl, uint64_t max_lines,
                                   int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+
+/* ---- line hashes (mi355x_bz2_line_hash says what the hash of a line is, and how lines are numbered).
+ *   _line_hashes      the hashes of lines [first, first + count), count clipped at the last line; *n_lines = their number.
+ *                     Needs the line index for `nl` (built on first use, as _read_line_ranges).  Only the blocks that hold
+ *                     those lines are decoded, each once, in the launches of _read_line_ranges for the range (first,
+ *                     count), with its residency and failure rules; each launch hashes its blocks on the context that
+ *                     decoded them (mi355x_bz2_hash_lines' kernels) straight into one device buffer of the reader's, and
+ *                     the host stitches the launches' summaries and patches the one line per launch that crosses a seam.
+ *                     The buffer is allocated before anything is launched: a failed allocation is
+ *                     MI355X_BZ2_ERR_DEVICE with a message.  The hashes are held until the next _line_hashes or
+ *                     _distinct_lines or the close.  Positionless; releases line ranges held by earlier calls.
+ *   _take_line_hashes the first min( capacity, n_lines ) held hashes (uint64 each) to `dst`, host memory or, with
+ *                     dst_is_device, device memory; they stay held.
+ *   _line_hashes_device  the held hashes on the GPU (uint64[n_lines]; NULL if none are held or keep_on_device was 0);
+ *                     valid until the next _line_hashes or _distinct_lines or the close.
+ *   _distinct_lines   *n_distinct = the number of distinct hashes among all lines of the file.  The hashes of the whole
+ *                     file go into one device buffer as for _line_hashes( 0, all ); a stable radix sort (rocPRIM) of
+ *                     (hash, line number) over 61 bits, a flag on the first element of every run of equal hashes, and
+ *                     their count.  With want_numbers != 0 the flagged line numbers are selected and sorted ascending:
+ *                     the first occurrence of every distinct line (awk '!seen[$0]++'), held for _take_distinct_lines.
+ *                     Every device buffer is allocated before the pass that fills it; a failed allocation is
+ *                     MI355X_BZ2_ERR_DEVICE with a message.  Nothing of _line_hashes stays held.
+ *   _take_distinct_lines  the first min( capacity, n_distinct ) held line numbers, ascending; they stay held until the
+ *                     next _distinct_lines, _line_hashes or the close. */
+int mi355x_bz2_reader_line_hashes( mi355x_bz2_reader* r, uint8_t nl, uint64_t seed, uint64_t first, uint64_t count,
+                                   int keep_on_device, uint64_t* n_lines );
+int mi355x_bz2_reader_take_line_hashes( mi355x_bz2_reader* r, void* dst, uint64_t capacity, int dst_is_device );
+const uint64_t* mi355x_bz2_reader_line_hashes_device( mi355x_bz2_reader* r );
+int mi355x_bz2_reader_distinct_lines( mi355x_bz2_reader* r, uint8_t nl, uint64_t seed, int want_numbers, uint64_t* n_distinct );
+int mi355x_bz2_reader_take_distinct_lines( mi355x_bz2_reader* r, uint64_t* line_numbers, uint64_t capacity );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

@@ -13,7 +13,11 @@ whole, with their 0-based numbers).  The same for a set of up to 1 024 byte stri
 search and grep methods takes the keyword-only ignore_case=True, which folds the ASCII letters of pattern and data on the
 GPU (bytes.lower() on both sides, `LC_ALL=C grep -i`; the bytes 0x80 to 0xFF are never folded).  And the lines that match
 a regular expression (grep_regex, count_matching_lines_regex, grep_regex_to_tensor): compile_regex turns a subset of
-Python's bytes `re` syntax into a DFA of at most 64 states on the host, and the GPU runs it over the decoded file.
+Python's bytes `re` syntax into a DFA of at most 64 states on the host, and the GPU runs it over the decoded file.  And
+which lines are the same: line_hashes and line_hashes_to_tensor give one 61-bit polynomial hash per line (line_hash says
+which, and computes it on the CPU), count_distinct_lines and first_occurrences sort them on the GPU (`sort -u | wc -l`,
+`awk '!seen[$0]++'`).  Distinct lines have distinct hashes with overwhelming probability, not with certainty: two contents
+of at most L bytes collide for at most L of the 2^61 bases a seed selects, and a second seed is an independent check.
 """
 __version__ = "0.1.0"
 
@@ -26,7 +30,7 @@ import os as _os
 # existing setting wins
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from ._native import (Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib,  # noqa: F401
+from ._native import (Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib, line_hash,  # noqa: F401
                       plan_compress_blocks, status_string, warmup)
 from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
                       decompress_many_to_tensor)

@@ -183,6 +183,16 @@ SYMBOLS = [
     ("mi355x_bz2_match_lines", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, _vp, ctypes.c_uint8, _vp, _vp,
                                                _vp, _u64p, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_grep_regex", ctypes.c_int, [_vp, _vp, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_line_hash", ctypes.c_uint64, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
+    ("mi355x_bz2_line_hash_chunk_bytes", ctypes.c_uint32, []),
+    ("mi355x_bz2_hash_lines", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint64,
+                                              _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_line_hashes", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                      ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_take_line_hashes", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_reader_line_hashes_device", ctypes.c_void_p, [_vp]),
+    ("mi355x_bz2_reader_distinct_lines", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_take_distinct_lines", ctypes.c_int, [_vp, _u64p, ctypes.c_uint64]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -380,6 +390,30 @@ def compile_regex(pattern, ignore_case=False):
 def regex_chunk_bytes():
     """The bytes of a span that one GPU lane walks in match_lines (mi355x_bz2_regex_chunk_bytes)."""
     return int(lib().mi355x_bz2_regex_chunk_bytes())
+
+
+class LineHashSummary(ctypes.Structure):
+    """mi355x_bz2_line_hash_summary"""
+    _fields_ = [("head_hash", ctypes.c_uint64), ("head_xl", ctypes.c_uint64), ("tail_hash", ctypes.c_uint64),
+                ("tail_xl", ctypes.c_uint64), ("count", ctypes.c_uint64), ("has_delimiter", ctypes.c_uint32),
+                ("tail_non_empty", ctypes.c_uint32)]
+
+
+def line_hash(content, seed=0):
+    """The hash line_hashes gives a line with this content (bytes-like, without the delimiter), on the CPU: p = 2^61 - 1,
+    x = 256 + splitmix64(seed) % (p - 256), h = 0 and h = (h * x + b + 1) % p for every byte b.  Needs no GPU."""
+    if isinstance(content, str):
+        raise TypeError("the content must be a bytes-like object, not str")
+    seed = int(seed)
+    if seed < 0 or seed >= 2**64:
+        raise ValueError("seed must not be negative and must fit 64 bits")
+    data = bytes(_byte_view(content))
+    return int(lib().mi355x_bz2_line_hash(data, len(data), seed))
+
+
+def line_hash_chunk_bytes():
+    """The bytes of a span that one GPU lane walks in hash_lines (mi355x_bz2_line_hash_chunk_bytes)."""
+    return int(lib().mi355x_bz2_line_hash_chunk_bytes())
 
 
 def pattern_set(patterns, check=True):
@@ -710,6 +744,47 @@ class Decoder:
         found = min(capacity, sum(counts[:len(spans)]))
         return (head_maps, [bool(v) for v in has_delimiter[:len(spans)]], [int(v) for v in exit_states[:len(spans)]],
                 list(positions[:found]), list(counts[:len(spans)]))
+
+    def hash_lines(self, spans, newline=b"\n", seed=0, capacity=None, room=None):
+        """k_linehash_chunks, k_linehash_link, k_scan_tiles, k_linehash_emit: the summary of every span [(offset, size)] of
+        the last batch's output, read as a stretch of lines that a line may enter and leave, and the hashes of the lines
+        the spans close -> (summaries, hashes): one dict per span (head and tail as (h, xl), has_delimiter,
+        tail_non_empty, count) and a numpy uint64 array of `room` values (default: capacity) that were all ones before the
+        call and of which the call may write the first `capacity` (None: as many as there are closed lines)."""
+        import numpy as np
+        nl = bytes(newline)
+        if len(nl) != 1:
+            raise ValueError("newline must be exactly one byte")
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        summaries = (LineHashSummary * max(1, len(spans)))()
+
+        def call(device, capacity):
+            self._check(lib().mi355x_bz2_hash_lines(self._h, arr, len(spans), nl[0], int(seed), summaries, device, capacity))
+        if capacity is None:
+            call(None, 0)
+            capacity = sum(s.count for s in summaries[:len(spans)])
+        room = capacity if room is None else max(int(room), capacity)
+        hashes = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        hip.hipFree.argtypes = [ctypes.c_void_p]
+        device = ctypes.c_void_p()
+        if hip.hipMalloc(ctypes.byref(device), hashes.nbytes) != 0:
+            raise Bz2Error(101, f"hash_lines: no device memory for {hashes.nbytes} bytes")
+        try:
+            if hip.hipMemcpy(device, hashes.ctypes.data, hashes.nbytes, 1) != 0:         # hipMemcpyHostToDevice
+                raise Bz2Error(101, "hash_lines: the copy to the device failed")
+            call(device, capacity)
+            if hip.hipMemcpy(hashes.ctypes.data, device, hashes.nbytes, 2) != 0:         # hipMemcpyDeviceToHost
+                raise Bz2Error(101, "hash_lines: the copy from the device failed")
+        finally:
+            hip.hipFree(device)
+        out = [{"head": (s.head_hash, s.head_xl), "tail": (s.tail_hash, s.tail_xl), "has_delimiter": bool(s.has_delimiter),
+                "tail_non_empty": bool(s.tail_non_empty), "count": int(s.count)} for s in summaries[:len(spans)]]
+        return out, hashes[:room]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mi355x_bz2.h"
+#include "bz2_linehash.hpp"
 #include "bz2_regex.hpp"
 #include "bz2_search.hpp"
 
@@ -55,6 +56,26 @@ int searchOutputSet( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, co
  * min( count, limit ) of them as offsets in the output (0: count only, no emitting pass). */
 int matchLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, const bz2gpu::Regex& regex, uint8_t nl,
                       uint64_t limit, bz2gpu::StretchSummary* summary );
+
+/** The reader's hashing pass in one launch: mi355x_bz2_hash_lines with `extent` as its one span and the base x instead of
+ * the seed.  *summary receives the extent's summary and the count of the lines it closes, no hashes; the hashes of its
+ * closed lines [skip, skip + take) go to dHashes[0, ...), device memory (take 0: no emitting pass). */
+int hashLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint8_t nl, uint64_t x, uint64_t skip, uint64_t take,
+                     uint64_t* dHashes, bz2gpu::HashSummary* summary );
+
+/** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
+ * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies
+ * to device memory instead. */
+void* deviceAllocate( int device, uint64_t bytes, std::string* error );
+void deviceRelease( void* pointer );
+bool deviceToHost( int device, void* dst, const void* src, uint64_t bytes, bool dstIsDevice, std::string* error );
+bool hostToDevice( int device, void* dst, const void* src, uint64_t bytes, std::string* error );
+
+/** The distinct values among dHashes[0, n) (device memory, left as it is): *nDistinct = their number and, if `numbers` is
+ * given, the index of the first occurrence of each, ascending.  False with *error set if an allocation or a launch
+ * fails; every buffer is allocated before the pass that fills it. */
+bool distinctHashes( int device, const uint64_t* dHashes, uint64_t n, uint64_t* nDistinct, std::vector<uint64_t>* numbers,
+                     std::string* error );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

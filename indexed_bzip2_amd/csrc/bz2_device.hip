@@ -29,6 +29,7 @@
 #include "bz2_search.hip.h"
 #include "bz2_search_set.hip.h"
 #include "bz2_regex.hip.h"
+#include "bz2_linehash.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -37,6 +38,7 @@
 #include "bz2_lanes.hpp"
 #include "bz2_ctx.hpp"
 #include "bz2_regex.hpp"
+#include "bz2_linehash.hpp"
 
 using namespace bz2gpu;
 
@@ -216,7 +218,8 @@ struct mi355x_bz2_ctx : Scratch
 
     /* mi355x_bz2_count_bytes / _find_bytes: tiles, pattern, counts and seam bytes of one call, page-locked and on the
      * device, and the positions of the emitting pass on the device (searchBytes lays them out).  mi355x_bz2_match_lines
-     * uses the same three for its tiles, table, summaries and witnesses (matchLines lays them out) */
+     * uses the same three for its tiles, table, summaries and witnesses (matchLines lays them out), mi355x_bz2_hash_lines
+     * the first two for its tiles and summaries (hashLines lays them out) */
     GrowBuffer hSearch{ nullptr, 0, true }, dSearch, dSearchPositions;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
@@ -2226,6 +2229,100 @@ matchLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spa
     return MI355X_BZ2_OK;
 }
 
+static_assert( LINEHASH_CHUNK == LINEHASH_CHUNK_BYTES && LINEHASH_PRIME == LINEHASH_P, "the kernels' constants are the host's" );
+
+/**
+ * mi355x_bz2_hash_lines and the reader's launches.  Every span is cut into tiles of COUNT_TILE bytes = LINEHASH_THREADS
+ * chunks; k_linehash_chunks summarises every chunk and scans each tile, k_linehash_link -- one workgroup per span --
+ * scans the tiles and writes the spans' summaries and counts, which come back in one D2H.  With hashes wanted,
+ * k_scan_tiles turns the chunk counts into places and k_linehash_emit writes the hashes of the closed lines [skip,
+ * skip + capacity) -- numbered over all spans in caller order -- to dHashes[0, ...), device memory of the caller's.
+ */
+int
+hashLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t x,
+           mi355x_bz2_line_hash_summary* summaries, uint64_t skip, uint64_t capacity, uint64_t* dHashes )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    uint64_t nTiles = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
+    }
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles * LINEHASH_THREADS > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][spans] up, [span summaries] down; device only, behind them: [tile summaries]
+     * [chunk prefixes][chunk places][chunk counts] */
+    const uint64_t slots = nTiles * LINEHASH_THREADS;
+    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
+    const uint64_t spansAt = aligned( nTiles * sizeof( CountTile ) ), resultsAt = aligned( spansAt + n * sizeof( LineHashSpan ) );
+    const uint64_t tilesAt = aligned( resultsAt + n * sizeof( LineHashSpanSummary ) );
+    const uint64_t prefixesAt = aligned( tilesAt + nTiles * sizeof( LineHashTile ) );
+    const uint64_t placesAt = prefixesAt + slots * sizeof( ulonglong2 ), countsAt = placesAt + slots * sizeof( uint64_t );
+    const uint64_t bytes = countsAt + slots * sizeof( uint32_t );
+    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
+    /* the previous call's lists have been consumed (every call waits for its kernels); the host holds what goes up and
+     * comes down, not the per-tile and per-chunk arrays */
+    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, tilesAt );
+    HIP_TRY( c, c->hSearch.grow( c, tilesAt, hostCap, hostCap ) );
+    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
+    uint8_t* const h = c->hSearch.bytes;
+    auto* const hTiles = reinterpret_cast<CountTile*>( h );
+    auto* const hSpans = reinterpret_cast<LineHashSpan*>( h + spansAt );
+    uint64_t tile = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        hSpans[s] = { tile, ( spans[s].size + COUNT_TILE - 1 ) / COUNT_TILE };
+        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
+            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
+        }
+    }
+    uint8_t* const d = c->dSearch.bytes;
+    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
+    auto* const dTileSummaries = reinterpret_cast<LineHashTile*>( d + tilesAt );
+    auto* const dPrefixes = reinterpret_cast<ulonglong2*>( d + prefixesAt );
+    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_linehash_chunks, dim3( (uint32_t)nTiles ), dim3( LINEHASH_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            x, (uint32_t)nl, dPrefixes, dCounts, dTileSummaries );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_linehash_link, dim3( n ), dim3( LINEHASH_THREADS ), 0, c->stream,
+                        reinterpret_cast<const LineHashSpan*>( d + spansAt ), dTileSummaries,
+                        reinterpret_cast<LineHashSpanSummary*>( d + resultsAt ) );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, tilesAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    uint64_t total = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& from = reinterpret_cast<const LineHashSpanSummary*>( h + resultsAt )[i];
+        summaries[i] = { from.headH, from.headXl, from.tailH, from.tailXl, from.count,
+                         ( from.info & LINEHASH_HAS_DELIMITER ) != 0 ? 1u : 0u, ( from.info & LINEHASH_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
+        total += from.count;
+    }
+    if ( capacity == 0 || skip >= total || nTiles == 0 ) return MI355X_BZ2_OK;
+
+    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
+    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_linehash_emit, dim3( (uint32_t)nTiles ), dim3( LINEHASH_THREADS ), 0, c->stream, dTiles, c->dOut, x,
+                        (uint32_t)nl, dPrefixes, dTileSummaries, dPlaces, skip, capacity, dHashes );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -2276,6 +2373,22 @@ mi355x::matchLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent,
                                    limit > 0, limit, nullptr, &summary->witnesses, &summary->count );
     summary->hasDelimiter = hasDelimiter != 0;
     summary->exit = exitState;
+    return status;
+}
+
+int
+mi355x::hashLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint8_t nl, uint64_t x, uint64_t skip,
+                         uint64_t take, uint64_t* dHashes, bz2gpu::HashSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr || ( take > 0 && dHashes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    mi355x_bz2_line_hash_summary s{};
+    const int status = hashLines( c, "line_hashes", &extent, 1, nl, x, &s, skip, take, dHashes );
+    summary->head = { s.head_hash, s.head_xl };
+    summary->tail = { s.tail_hash, s.tail_xl };
+    summary->hasDelimiter = s.has_delimiter != 0;
+    summary->tailNonEmpty = s.tail_non_empty != 0;
+    summary->count = s.count;
+    summary->hashes.clear();
     return status;
 }
 
@@ -2384,6 +2497,16 @@ mi355x_bz2_match_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, ui
     }
     return matchLines( c, "match_lines", spans, n, re->dfa, nl, headMaps, hasDelimiter, exitStates, capacity > 0, capacity,
                        positions, nullptr, counts );
+}
+
+int
+mi355x_bz2_hash_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t seed,
+                       mi355x_bz2_line_hash_summary* summaries, uint64_t* hashesDevice, uint64_t capacity )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) ) || ( capacity > 0 && hashesDevice == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return hashLines( c, "hash_lines", spans, n, nl, lineHashBase( seed ), summaries, 0, capacity, hashesDevice );
 }
 
 int

@@ -1,0 +1,192 @@
+/**
+ * bz2_distinct.hip -- the distinct values among the line hashes of a file (mi355x_bz2_reader_distinct_lines), and the
+ * device memory the reader keeps those hashes in.
+ *
+ *   k_iota            numbers[i] = i
+ *   rocPRIM           a stable radix sort of ( hash, line number ) over the 61 bits of a hash: equal hashes stay in line
+ *                     order, so the first element of a run is the line's first occurrence
+ *   k_flag_runs       flags[i] = i == 0 || hash[i] != hash[i - 1], and the number of flags (one atomic per workgroup)
+ *   rocPRIM           with the numbers wanted: select the flagged line numbers, sort them ascending
+ *
+ * The null stream and buffers of the call's own: it comes when the reader's launches are through.  Every buffer is
+ * allocated before the pass that fills it, so that a failed allocation loses no result.
+ */
+#include <hip/hip_runtime.h>
+
+#include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_select.hpp>
+
+#include <algorithm>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "bz2_ctx.hpp"
+
+namespace
+{
+constexpr uint32_t DISTINCT_THREADS = 256;
+
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_iota( uint64_t* __restrict__ numbers, uint64_t n )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( i < n ) numbers[i] = i;
+}
+
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_flag_runs( const uint64_t* __restrict__ sorted, uint64_t n, uint8_t* __restrict__ flags, unsigned long long* __restrict__ count )
+{
+    __shared__ uint32_t inBlock;
+    if ( threadIdx.x == 0 ) inBlock = 0;
+    __syncthreads();
+    const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( i < n ) {
+        const bool first = i == 0 || sorted[i] != sorted[i - 1];
+        flags[i] = first ? 1 : 0;
+        if ( first ) atomicAdd( &inBlock, 1u );
+    }
+    __syncthreads();
+    if ( threadIdx.x == 0 && inBlock != 0 ) atomicAdd( count, (unsigned long long)inBlock );
+}
+
+/** Device allocations of one call, freed when it returns. */
+struct Buffers
+{
+    std::vector<void*> pointers;
+
+    ~Buffers()
+    {
+        for ( auto* const pointer : pointers ) (void)hipFree( pointer );
+    }
+    template<typename T>
+    bool
+    get( T** pointer, uint64_t bytes, const char* what, std::string* error )
+    {
+        void* raw = nullptr;
+        const hipError_t err = hipMalloc( &raw, bytes > 0 ? bytes : 1 );
+        if ( err != hipSuccess ) {
+            (void)hipGetLastError();
+            *error = std::string( "distinct_lines: no device memory for " ) + what + " (" + std::to_string( bytes ) + " bytes): "
+                     + hipGetErrorString( err );
+            return false;
+        }
+        pointers.push_back( raw );
+        *pointer = static_cast<T*>( raw );
+        return true;
+    }
+};
+
+bool
+tried( hipError_t err, const char* what, std::string* error )
+{
+    if ( err == hipSuccess ) return true;
+    *error = std::string( what ) + ": " + hipGetErrorString( err );
+    return false;
+}
+
+#define DISTINCT_TRY( expr ) \
+    do { if ( !tried( ( expr ), #expr, error ) ) return false; } while ( 0 )
+}  // namespace
+
+void*
+mi355x::deviceAllocate( int device, uint64_t bytes, std::string* error )
+{
+    void* pointer = nullptr;
+    hipError_t err = device >= 0 ? hipSetDevice( device ) : hipSuccess;
+    if ( err == hipSuccess ) err = hipMalloc( &pointer, bytes > 0 ? bytes : 1 );
+    if ( err != hipSuccess ) {
+        (void)hipGetLastError();
+        *error = "no device memory for " + std::to_string( bytes ) + " bytes of line hashes: " + hipGetErrorString( err );
+        return nullptr;
+    }
+    return pointer;
+}
+
+void
+mi355x::deviceRelease( void* pointer )
+{
+    if ( pointer != nullptr ) (void)hipFree( pointer );
+}
+
+bool
+mi355x::deviceToHost( int device, void* dst, const void* src, uint64_t bytes, bool dstIsDevice, std::string* error )
+{
+    if ( bytes == 0 ) return true;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    DISTINCT_TRY( hipMemcpy( dst, src, bytes, dstIsDevice ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost ) );
+    return true;
+}
+
+bool
+mi355x::hostToDevice( int device, void* dst, const void* src, uint64_t bytes, std::string* error )
+{
+    if ( bytes == 0 ) return true;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    DISTINCT_TRY( hipMemcpy( dst, src, bytes, hipMemcpyHostToDevice ) );
+    return true;
+}
+
+bool
+mi355x::distinctHashes( int device, const uint64_t* dHashes, uint64_t n, uint64_t* nDistinct, std::vector<uint64_t>* numbers,
+                        std::string* error )
+{
+    *nDistinct = 0;
+    if ( numbers != nullptr ) numbers->clear();
+    if ( n == 0 ) return true;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    const hipStream_t stream = nullptr;
+    const uint32_t blocks = (uint32_t)( ( n + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS );
+    if ( (uint64_t)blocks * DISTINCT_THREADS < n ) {
+        *error = "distinct_lines: too many lines";
+        return false;
+    }
+
+    Buffers buffers;
+    uint64_t *dNumbers = nullptr, *dSortedHashes = nullptr, *dSortedNumbers = nullptr;
+    uint8_t* dFlags = nullptr;
+    unsigned long long* dCount = nullptr;
+    void* dTemp = nullptr;
+    size_t sortBytes = 0;
+    DISTINCT_TRY( rocprim::radix_sort_pairs( nullptr, sortBytes, dHashes, dSortedHashes, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+    if ( !buffers.get( &dNumbers, n * 8, "the line numbers", error ) || !buffers.get( &dSortedHashes, n * 8, "the sorted hashes", error )
+         || !buffers.get( &dSortedNumbers, n * 8, "the sorted line numbers", error ) || !buffers.get( &dFlags, n, "the flags", error )
+         || !buffers.get( &dCount, 2 * sizeof( unsigned long long ), "the count", error )
+         || !buffers.get( &dTemp, sortBytes, "the sort", error ) ) {
+        return false;
+    }
+    DISTINCT_TRY( hipMemsetAsync( dCount, 0, 2 * sizeof( unsigned long long ), stream ) );
+    hipLaunchKernelGGL( k_iota, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dNumbers, n );
+    DISTINCT_TRY( hipGetLastError() );
+    DISTINCT_TRY( rocprim::radix_sort_pairs( dTemp, sortBytes, dHashes, dSortedHashes, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+    hipLaunchKernelGGL( k_flag_runs, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dSortedHashes, n, dFlags, dCount );
+    DISTINCT_TRY( hipGetLastError() );
+    unsigned long long count = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &count, dCount, sizeof( count ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    *nDistinct = count;
+    if ( numbers == nullptr ) return true;
+
+    /* the selected numbers go where the unsorted ones were, their sorted form where the sorted hashes were */
+    try {
+        numbers->resize( (size_t)count );
+    } catch ( const std::exception& ) {
+        *error = "distinct_lines: no host memory for " + std::to_string( count ) + " line numbers";
+        return false;
+    }
+    uint64_t* const dSelected = dNumbers;
+    uint64_t* const dAscending = dSortedHashes;
+    size_t selectBytes = 0, secondSortBytes = 0;
+    DISTINCT_TRY( rocprim::select( nullptr, selectBytes, dSortedNumbers, dFlags, dSelected, dCount + 1, (size_t)n, stream ) );
+    DISTINCT_TRY( rocprim::radix_sort_keys( nullptr, secondSortBytes, dSelected, dAscending, (size_t)count, 0, 64, stream ) );
+    void* dTemp2 = dTemp;
+    if ( std::max( selectBytes, secondSortBytes ) > sortBytes
+         && !buffers.get( &dTemp2, std::max( selectBytes, secondSortBytes ), "the selection", error ) ) {
+        return false;
+    }
+    DISTINCT_TRY( rocprim::select( dTemp2, selectBytes, dSortedNumbers, dFlags, dSelected, dCount + 1, (size_t)n, stream ) );
+    DISTINCT_TRY( rocprim::radix_sort_keys( dTemp2, secondSortBytes, dSelected, dAscending, (size_t)count, 0, 64, stream ) );
+    DISTINCT_TRY( hipMemcpyAsync( numbers->data(), dAscending, count * 8, hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    return true;
+}

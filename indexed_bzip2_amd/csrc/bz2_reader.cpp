@@ -42,6 +42,7 @@
 #include "bz2_host.hpp"
 #include "bz2_ctx.hpp"
 #include "bz2_lines.hpp"
+#include "bz2_linehash.hpp"
 #include "bz2_search.hpp"
 #include "bz2_ranges.hpp"
 
@@ -1230,6 +1231,7 @@ public:
     close()
     {
         dropHeldLines();
+        dropHeldHashes();
         m_matches.reset();
         m_setMatches.reset();
         m_scheduler.reset();
@@ -1823,6 +1825,130 @@ public:
         }
     }
 
+    /** mi355x_bz2_reader_line_hashes: the launches of planLineHashes, each hashing its stretch (hashLinesOutput) on the
+     * context that decoded it, straight into the reader's device buffer -- the line index says how many lines every
+     * stretch closes, so every launch knows its place before any has run; then stitchSummaries, and one 8-byte copy for
+     * every line that crosses a seam and for the unterminated tail. */
+    void
+    lineHashes( uint8_t nl, uint64_t seed, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
+    {
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        dropHeldHashes();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLineHashes( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
+                                           count, m_batch, packed, m_source->size() );
+        } );
+        *nLines = 0;
+        HeldHashes held;
+        held.onDevice = keepOnDevice;
+        if ( plan.count == 0 ) {
+            m_hashes = std::move( held );
+            return;
+        }
+        /* per stretch: the lines it closes (from the index), which of them are wanted, and where they go */
+        struct Work { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
+        std::vector<Work> works( plan.stretches.size() );
+        std::vector<bz2gpu::HashStretch> stretches( plan.stretches.size() );
+        std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
+        const uint64_t wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;   /* but for the tail */
+        uint64_t closedBefore = plan.firstClosed;
+        for ( size_t k = 0; k < works.size(); ++k ) {
+            const auto& piece = plan.stretches[k];
+            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
+            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
+            auto& work = works[k];
+            work.closed = index.lines[to] - index.lines[from];
+            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
+            if ( end > begin ) {
+                work.skip = begin - closedBefore;
+                work.take = end - begin;
+                work.at = begin - first;
+            }
+            closedBefore += work.closed;
+            stretches[k].fileOffset = piece.fileOffset;
+            stretches[k].size = piece.size;
+            ofLaunch[piece.launch].push_back( k );
+        }
+        std::string why;
+        held.device = m_device;
+        held.capacity = plan.count;
+        held.dHashes = static_cast<uint64_t*>( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
+        if ( held.dHashes == nullptr ) fail( MI355X_BZ2_ERR_DEVICE, "line_hashes: " + why );
+        const uint64_t x = bz2gpu::lineHashBase( seed );
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [&plan, &works, &stretches, mine = &ofLaunch[l], nl, x, to = held.dHashes] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+                for ( const auto k : *mine ) {
+                    const auto& piece = plan.stretches[k];
+                    const auto& work = works[k];
+                    checkDevice( ctx, hashLinesOutput( ctx, { piece.src, piece.size }, nl, x, work.skip, work.take, to + work.at,
+                                                       &stretches[k].summary ) );
+                    if ( stretches[k].summary.count != work.closed ) {
+                        failLyingLineIndex( piece.fileOffset, work.closed, stretches[k].summary.count );
+                    }
+                }
+            };
+        } );
+        /* the first closed line of a stretch is line firstClosed + k of the file */
+        std::vector<std::pair<uint64_t, uint64_t> > patches;
+        const auto stitched = bz2gpu::stitchSummaries( stretches, [&] ( uint64_t k, uint64_t hash ) {
+            const uint64_t line = plan.firstClosed + k;
+            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, hash );
+        } );
+        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
+        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tailHash );
+        for ( const auto& [at, hash] : patches ) {
+            if ( !hostToDevice( m_device, held.dHashes + at, &hash, sizeof( hash ), &why ) ) fail( MI355X_BZ2_ERR_DEVICE, "line_hashes: " + why );
+        }
+        held.n = n;
+        *nLines = n;
+        m_hashes = std::move( held );
+    }
+
+    /** mi355x_bz2_reader_take_line_hashes. */
+    void
+    takeLineHashes( void* hashes, uint64_t capacity, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_line_hashes on a closed reader" );
+        if ( !m_hashes ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_line_hashes: no hashes are held (line_hashes first)" );
+        std::string why;
+        if ( !deviceToHost( m_hashes->device, hashes, m_hashes->dHashes, std::min( capacity, m_hashes->n ) * sizeof( uint64_t ),
+                            dstIsDevice, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, "take_line_hashes: " + why );
+        }
+    }
+
+    [[nodiscard]] const uint64_t*
+    lineHashesDevice() const
+    {
+        return m_hashes && m_hashes->onDevice && m_hashes->n > 0 ? m_hashes->dHashes : nullptr;
+    }
+
+    /** mi355x_bz2_reader_distinct_lines: lineHashes over the whole file, then bz2_distinct.hip. */
+    void
+    distinctLines( uint8_t nl, uint64_t seed, bool wantNumbers, uint64_t* nDistinct )
+    {
+        uint64_t n = 0;
+        lineHashes( nl, seed, 0, std::numeric_limits<uint64_t>::max(), false, &n );
+        std::vector<uint64_t> numbers;
+        std::string why;
+        const bool done = distinctHashes( m_device, m_hashes->dHashes, n, nDistinct, wantNumbers ? &numbers : nullptr, &why );
+        dropHeldHashes();
+        if ( !done ) fail( MI355X_BZ2_ERR_DEVICE, why );
+        if ( wantNumbers ) m_distinct = std::move( numbers );
+    }
+
+    /** mi355x_bz2_reader_take_distinct_lines. */
+    void
+    takeDistinctLines( uint64_t* lineNumbers, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_distinct_lines on a closed reader" );
+        if ( !m_distinct ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_distinct_lines: no line numbers are held (distinct_lines with want_numbers first)" );
+        }
+        std::copy_n( m_distinct->begin(), (size_t)std::min<uint64_t>( capacity, m_distinct->size() ), lineNumbers );
+    }
+
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
 
     [[nodiscard]] OffsetMap
@@ -1900,6 +2026,41 @@ private:
     {
         std::vector<uint64_t> numbers, sizes;              /* per matching line; the bytes are m_held's */
     };
+
+    /** The hashes of line_hashes, in device memory of the reader's own. */
+    struct HeldHashes
+    {
+        uint64_t* dHashes{ nullptr };
+        uint64_t n{ 0 }, capacity{ 0 };
+        int device{ -1 };
+        bool onDevice{ false };
+
+        HeldHashes() = default;
+        HeldHashes( const HeldHashes& ) = delete;
+        HeldHashes& operator=( const HeldHashes& ) = delete;
+        HeldHashes( HeldHashes&& other ) noexcept { *this = std::move( other ); }
+        HeldHashes&
+        operator=( HeldHashes&& other ) noexcept
+        {
+            if ( this != &other ) {
+                deviceRelease( dHashes );
+                dHashes = std::exchange( other.dHashes, nullptr );
+                n = other.n;
+                capacity = other.capacity;
+                device = other.device;
+                onDevice = other.onDevice;
+            }
+            return *this;
+        }
+        ~HeldHashes() { deviceRelease( dHashes ); }
+    };
+
+    void
+    dropHeldHashes()
+    {
+        m_hashes.reset();
+        m_distinct.reset();
+    }
 
     void
     dropHeldLines()
@@ -2187,6 +2348,8 @@ private:
     std::optional<HeldSetMatches> m_setMatches;        /* between search_set (with a limit) and take_set_matches */
     std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
+    std::optional<HeldHashes> m_hashes;   /* between line_hashes and the next line_hashes / distinct_lines */
+    std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
 
@@ -2572,6 +2735,43 @@ mi355x_bz2_reader_grep_regex( mi355x_bz2_reader* r, const mi355x_bz2_regex* re, 
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
         reader.grepRegex( re->dfa, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
     } );
+}
+
+int
+mi355x_bz2_reader_line_hashes( mi355x_bz2_reader* r, uint8_t nl, uint64_t seed, uint64_t first, uint64_t count, int keepOnDevice,
+                               uint64_t* nLines )
+{
+    if ( nLines == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.lineHashes( nl, seed, first, count, keepOnDevice != 0, nLines ); } );
+}
+
+int
+mi355x_bz2_reader_take_line_hashes( mi355x_bz2_reader* r, void* hashes, uint64_t capacity, int dstIsDevice )
+{
+    if ( capacity > 0 && hashes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeLineHashes( hashes, capacity, dstIsDevice != 0 ); } );
+}
+
+const uint64_t*
+mi355x_bz2_reader_line_hashes_device( mi355x_bz2_reader* r )
+{
+    return r != nullptr && r->reader ? r->reader->lineHashesDevice() : nullptr;
+}
+
+int
+mi355x_bz2_reader_distinct_lines( mi355x_bz2_reader* r, uint8_t nl, uint64_t seed, int wantNumbers, uint64_t* nDistinct )
+{
+    if ( nDistinct == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nDistinct = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.distinctLines( nl, seed, wantNumbers != 0, nDistinct ); } );
+}
+
+int
+mi355x_bz2_reader_take_distinct_lines( mi355x_bz2_reader* r, uint64_t* lineNumbers, uint64_t capacity )
+{
+    if ( capacity > 0 && lineNumbers == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeDistinctLines( lineNumbers, capacity ); } );
 }
 
 int

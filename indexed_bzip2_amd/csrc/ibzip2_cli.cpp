@@ -43,6 +43,8 @@ struct Options
     int verbose{ 0 };
     bool listCompressed{ false }, listOffsets{ false }, countLines{ false }, countMatches{ false }, grep{ false }, lineNumber{ false };
     bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false }, grepRegex{ false };
+    bool lineHashes{ false }, countDistinctLines{ false }, hasSeed{ false };
+    uint64_t seed{ 0 };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -103,6 +105,14 @@ printHelp()
         "                                * + ? {m} {m,} {m,n} {,n}, ^ and $. Back-references, look-around, lazy\n"
         "                                quantifiers, \\b and patterns that need more than 64 DFA states are refused.\n"
         "                                --line-number and --ignore-case apply as for --grep.\n"
+        "      --line-hashes             Print one hash per line of the decoded data, 16 lower-case hexadecimal digits\n"
+        "                                each: h = (h * x + byte + 1) mod (2^61 - 1) over the line without its newline,\n"
+        "                                x chosen by --seed. Equal lines have equal hashes; the data stays on the GPU.\n"
+        "      --count-distinct-lines    Print the number of distinct line hashes (sort -u | wc -l). Distinct lines\n"
+        "                                have distinct hashes with overwhelming probability, not with certainty: run\n"
+        "                                again with another --seed for an independent check.\n"
+        "      --seed arg                With --line-hashes or --count-distinct-lines: the 64-bit seed of the hash's\n"
+        "                                base. (default: 0)\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -131,6 +141,8 @@ printHelp()
         "  ibzip2-mi355x --grep-file codes.txt file.bz2\n\n"
         "Print the lines that contain a string in any case (error, Error, ERROR):\n"
         "  ibzip2-mi355x --grep error --ignore-case file.bz2\n\n"
+        "Count the distinct lines of a file:\n"
+        "  ibzip2-mi355x --count-distinct-lines file.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -186,6 +198,22 @@ parseUnsigned( const char* text, unsigned& value )
     const unsigned long v = std::strtoul( text, &end, 10 );
     if ( errno != 0 || *end != '\0' || v > 0xFFFFFFFFul ) return false;
     value = (unsigned)v;
+    return true;
+}
+
+/** A 64-bit seed: decimal digits only, no sign, no overflow. */
+bool
+parseSeed( const char* text, uint64_t& value )
+{
+    if ( text == nullptr || *text == '\0' ) return false;
+    uint64_t v = 0;
+    for ( const char* c = text; *c != '\0'; ++c ) {
+        if ( *c < '0' || *c > '9' ) return false;
+        const uint64_t digit = (uint64_t)( *c - '0' );
+        if ( v > ( ~uint64_t( 0 ) - digit ) / 10 ) return false;
+        v = v * 10 + digit;
+    }
+    value = v;
     return true;
 }
 
@@ -246,6 +274,12 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "count-matches" ) { if ( !need( o.pattern ) ) return 1; o.countMatches = true; }
             else if ( name == "grep" ) { if ( !need( o.pattern ) ) return 1; o.grep = true; }
             else if ( name == "grep-regex" ) { if ( !need( o.regex ) ) return 1; o.grepRegex = true; }
+            else if ( name == "line-hashes" ) o.lineHashes = true;
+            else if ( name == "count-distinct-lines" ) o.countDistinctLines = true;
+            else if ( name == "seed" ) {
+                if ( !need( value ) || !parseSeed( value.c_str(), o.seed ) ) { std::cerr << "Bad value for --seed\n"; return 1; }
+                o.hasSeed = true;
+            }
             else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
             else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
             else if ( name == "line-number" ) o.lineNumber = true;
@@ -458,6 +492,20 @@ main( int argc, char** argv )
         std::cerr << "Option '--ignore-case' needs '--grep', '--grep-file', '--count-matches' or '--count-matches-file'\n";
         return 1;
     }
+    if ( o.lineHashes && o.countDistinctLines ) {
+        std::cerr << "Options '--line-hashes' and '--count-distinct-lines' cannot be combined\n";
+        return 1;
+    }
+    if ( ( o.lineHashes || o.countDistinctLines )
+         && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines ) ) {
+        std::cerr << "Options '--line-hashes' and '--count-distinct-lines' cannot be combined with '--count-lines', '--grep', "
+                     "'--grep-regex', '--count-matches', '--grep-file' or '--count-matches-file'\n";
+        return 1;
+    }
+    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines ) {
+        std::cerr << "Option '--seed' needs '--line-hashes' or '--count-distinct-lines'\n";
+        return 1;
+    }
     const uint32_t searchFlags = o.ignoreCase ? MI355X_BZ2_SEARCH_IGNORE_CASE : 0u;
     if ( o.version ) {
         std::cout << "ibzip2-mi355x, CLI to the MI355X bzip2 block decoder (C ABI version " << mi355x_bz2_abi_version()
@@ -501,6 +549,54 @@ main( int argc, char** argv )
         }
         mi355x_bz2_reader_close( reader );
         std::cout << lines.back() << "\n";
+        return 0;
+    }
+
+    /* likewise actions of their own: one hash per line, from the reader's line_hashes, or the number of distinct ones,
+     * from its distinct_lines */
+    if ( o.lineHashes || o.countDistinctLines ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t n = 0;
+        std::vector<uint64_t> hashes;
+        if ( o.countDistinctLines ) {
+            rc = mi355x_bz2_reader_distinct_lines( reader, '\n', o.seed, 0, &n );
+        } else {
+            rc = mi355x_bz2_reader_line_hashes( reader, '\n', o.seed, 0, ~uint64_t( 0 ), 0, &n );
+            hashes.resize( n );
+            if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_line_hashes( reader, hashes.data(), n, 0 );
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        if ( o.countDistinctLines ) {
+            std::cout << n << "\n";
+            return 0;
+        }
+        std::string text( hashes.size() * 17, '\n' );
+        for ( size_t i = 0; i < hashes.size(); ++i ) {
+            for ( int digit = 0; digit < 16; ++digit ) text[i * 17 + digit] = "0123456789abcdef"[( hashes[i] >> ( 60 - 4 * digit ) ) & 15];
+        }
+        std::cout << text;
         return 0;
     }
 

@@ -583,6 +583,67 @@ class _IndexedBzip2FileParallel:
             bounds.append(bounds[-1] + size)
         return numbers, data, torch.tensor(bounds, dtype=torch.int64)
 
+    # -- line hashes: one 61-bit polynomial hash per line (N.line_hash says which), computed where the decoded bytes lie.
+    # Lines are numbered as grep numbers them; a non-empty unterminated tail is the last line.  Equal contents have equal
+    # hashes; two distinct contents of at most L bytes have equal hashes for at most L of the 2^61 bases a seed can give,
+    # so "distinct" below means "of distinct hash", and a second seed is an independent check
+    def _line_hash_arguments(self, first, count, newline, seed):
+        self._require()
+        nl = self._newline(newline)
+        (first, seed), _ = self._u64([first, seed], "first and seed")
+        (count,), _ = self._u64([2**64 - 1 if count is None else count], "count")
+        return nl, first, count, seed
+
+    def line_hashes(self, first=0, count=None, newline=b"\n", seed=0):
+        """The hashes of lines [first, first + count) (count None: to the last line; clipped there) -> numpy uint64, one
+        value below 2^61 per line, equal to line_hash(content, seed).  Only the blocks that hold those lines are decoded,
+        each once; the hashes are computed on the GPU and 8 bytes per line come back.  Builds the line index first if
+        the reader does not hold one for `newline`.  Positionless."""
+        import numpy as np
+        nl, first, count, seed = self._line_hash_arguments(first, count, newline, seed)
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_line_hashes(self._h, nl, seed, first, count, 0, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint64)
+        self._check(N.lib().mi355x_bz2_reader_take_line_hashes(self._h, out.ctypes.data if n.value else None, n.value, 0))
+        return out
+
+    def line_hashes_to_tensor(self, first=0, count=None, newline=b"\n", seed=0):
+        """line_hashes as a torch.int64 tensor on the reader's device; the hashes never pass through the host.  A hash
+        is below 2^61, so torch.unique, sort and isin order and compare it as the unsigned value."""
+        import torch
+        nl, first, count, seed = self._line_hash_arguments(first, count, newline, seed)
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_line_hashes(self._h, nl, seed, first, count, 1, ctypes.byref(n)))
+        out = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
+        if n.value:
+            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(out.device).synchronize()
+            self._check(N.lib().mi355x_bz2_reader_take_line_hashes(self._h, ctypes.c_void_p(out.data_ptr()), n.value, 1))
+        return out
+
+    def _distinct_lines(self, newline, seed, want_numbers):
+        nl, _, _, seed = self._line_hash_arguments(0, None, newline, seed)
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_distinct_lines(self._h, nl, seed, 1 if want_numbers else 0, ctypes.byref(n)))
+        return n.value
+
+    def count_distinct_lines(self, newline=b"\n", seed=0):
+        """The number of distinct lines (`sort -u | wc -l`): of distinct hashes, see above.  The whole file is hashed
+        and the hashes are sorted on the GPU; one number comes back."""
+        return self._distinct_lines(newline, seed, False)
+
+    def first_occurrences(self, newline=b"\n", seed=0):
+        """The numbers of the lines that are the first of their content (`awk '!seen[$0]++'`) -> numpy uint64, ascending,
+        ready for read_line_ranges([(k, 1) for k in ...])."""
+        import numpy as np
+        n = self._distinct_lines(newline, seed, True)
+        out = np.empty(n, dtype=np.uint64)
+        self._check(N.lib().mi355x_bz2_reader_take_distinct_lines(
+            self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if n else None, n))
+        return out
+
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
     # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
     # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
@@ -795,6 +856,22 @@ class IndexedBzip2File(io.BufferedReader):
     def grep_regex_to_tensor(self, pattern, limit=None, newline=b"\n", *, ignore_case=False):
         """See _IndexedBzip2FileParallel.grep_regex_to_tensor."""
         return self._open_reader().grep_regex_to_tensor(pattern, limit, newline, ignore_case=ignore_case)
+
+    def line_hashes(self, first=0, count=None, newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.line_hashes."""
+        return self._open_reader().line_hashes(first, count, newline, seed)
+
+    def line_hashes_to_tensor(self, first=0, count=None, newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.line_hashes_to_tensor."""
+        return self._open_reader().line_hashes_to_tensor(first, count, newline, seed)
+
+    def count_distinct_lines(self, newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.count_distinct_lines."""
+        return self._open_reader().count_distinct_lines(newline, seed)
+
+    def first_occurrences(self, newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.first_occurrences."""
+        return self._open_reader().first_occurrences(newline, seed)
 
     def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
