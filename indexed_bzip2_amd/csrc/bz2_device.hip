@@ -436,7 +436,7 @@ allowLargeLds()
     };
     allow( reinterpret_cast<const void*>( &k_mtf<MTF_LANE_STRIDE, MTF_THREADS, REGS_MTF> ), sizeof( MtfShared<MTF_LANE_STRIDE, MTF_THREADS> ) );
     allow( reinterpret_cast<const void*>( &k_mtf<MTF_LANE_STRIDE, 512> ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ) );
-    allow( reinterpret_cast<const void*>( &k_mtf<MTF_SMALL_STRIDE, 512> ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ) );
+    allow( reinterpret_cast<const void*>( &k_mtf<MTF_SMALL_STRIDE, 512, REGS_MTF> ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ) );
     allow( reinterpret_cast<const void*>( &k_mtf<MTF_SMALL_STRIDE, 1024> ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ) );
     allow( reinterpret_cast<const void*>( &k_link2 ), sizeof( LinkShared ) );
     return ok;
@@ -466,6 +466,7 @@ readSwitches()
     s.plan.scanWaves = positive( "MI355X_BZ2_SCAN_WAVES" );   /* 1 = k_hscan<1>, 4 / 8 = k_hscan_spec<4 / 8> */
     s.plan.bwtSplit = positive( "MI355X_BZ2_BWT_SPLIT" );     /* workgroups per block of the table build (1, 2, 4, 8) */
     s.plan.mtfNarrow = one( "MI355X_BZ2_MTF_NARROW" );        /* 256 lanes per block in k_mtf */
+    s.plan.mtfSerial = one( "MI355X_BZ2_MTF_SERIAL" );        /* the serial pass B of k_mtf for every block */
     s.plan.noSplit = one( "MI355X_BZ2_NO_SPLIT" );
     s.trace = one( "MI355X_BZ2_TRACE" );
     s.readerTrace = std::getenv( "MI355X_BZ2_READER_TRACE" ) != nullptr;
@@ -1099,9 +1100,10 @@ mi355x::decodeBatchBegin( mi355x_bz2_ctx* c, const uint64_t* offsets, const uint
             HSYM( SYM_GROUPS );
 #undef HSYM
         }
+        const uint32_t serial = plan.mtfSerial ? 1u : 0u;
 #define MTF256( STRIDE, STREAM, INDEX ) \
         TIMED_LAUNCH( c, g, STREAM, INDEX, ( k_mtf<STRIDE, MTF_THREADS, REGS_MTF> ), dim3( m ), dim3( MTF_THREADS ), \
-                      sizeof( MtfShared<STRIDE, MTF_THREADS> ), STREAM, meta, hmeta, sym, stb, lcol, m, order )
+                      sizeof( MtfShared<STRIDE, MTF_THREADS> ), STREAM, meta, hmeta, sym, stb, lcol, m, order, serial )
         /* every block belongs to one of the two k_mtf instances (by its symbol count), the other returns at once.  Small
          * batches (plan.mtfSide) run them side by side when the layout gives the second one a lane */
         const hipStream_t side = layout.sideLaneOf[g] >= 0 ? streamOfLane( layout.sideLaneOf[g] ) : q;
@@ -1110,15 +1112,15 @@ mi355x::decodeBatchBegin( mi355x_bz2_ctx* c, const uint64_t* offsets, const uint
             HIP_TRY( c, hipStreamWaitEvent( side, c->evFork[g], 0 ) );
         }
         if ( plan.mtfSmallLanes == 1024 ) {
-            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order );
+            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 1024> ), dim3( m ), dim3( 1024 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 1024> ), side, meta, hmeta, sym, stb, lcol, m, order, serial );
         } else if ( plan.mtfSmallLanes == 512 ) {
-            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order );
+            TIMED_LAUNCH( c, g, side, 11, ( k_mtf<MTF_SMALL_STRIDE, 512, REGS_MTF> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_SMALL_STRIDE, 512> ), side, meta, hmeta, sym, stb, lcol, m, order, serial );
         } else {
             MTF256( MTF_SMALL_STRIDE, side, 11 );
         }
         if ( side != q ) HIP_TRY( c, hipEventRecord( c->evJoin[g], side ) );
         if ( plan.mtfSmallLanes > 256 ) {
-            TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order );
+            TIMED_LAUNCH( c, g, q, 1, ( k_mtf<MTF_LANE_STRIDE, 512> ), dim3( m ), dim3( 512 ), sizeof( MtfShared<MTF_LANE_STRIDE, 512> ), q, meta, hmeta, sym, stb, lcol, m, order, serial );
         } else {
             MTF256( MTF_LANE_STRIDE, q, 1 );
         }

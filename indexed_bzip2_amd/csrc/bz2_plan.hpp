@@ -31,7 +31,7 @@ constexpr uint32_t WALK_CHUNK = 256;         /* segments per queue grab */
 constexpr uint32_t WALK_WGS_PER_XCD = 128;   /* one or two contexts */
 constexpr uint32_t WALK_WGS_CROWD = 32;      /* three or more contexts alive, with claims of 4 x WALK_CHUNK */
 
-/** Kernel forms a test asks for whatever the batch size (MI355X_BZ2_SCAN_WAVES, _BWT_SPLIT, _MTF_NARROW), and
+/** Kernel forms a test asks for whatever the batch size (MI355X_BZ2_SCAN_WAVES, _BWT_SPLIT, _MTF_NARROW, _MTF_SERIAL), and
  * MI355X_BZ2_NO_SPLIT (one group for the whole batch). */
 struct PlanOverrides
 {
@@ -39,6 +39,7 @@ struct PlanOverrides
     uint32_t bwtSplit{ 0 };    /* workgroups per block of the table build (1, 2, 4, 8); 0: by batch size */
     bool mtfNarrow{ false };   /* 256 lanes per block in k_mtf */
     bool noSplit{ false };
+    bool mtfSerial{ false };   /* every block through k_mtf's serial pass B, which otherwise sees damaged blocks only */
 };
 
 struct BatchPlan
@@ -53,6 +54,7 @@ struct BatchPlan
     std::vector<uint32_t> order;           /* by slot: group-relative slots, largest block first */
     bool mtfSide{ false };                 /* the two k_mtf instances of a group side by side on two streams */
     uint32_t mtfSmallLanes{ 256 };         /* lanes per block of k_mtf<MTF_SMALL_STRIDE>: 1 024, 512 or 256 */
+    bool mtfSerial{ false };               /* k_mtf's forceSerial argument */
     uint32_t bwtSlices{ 1 };               /* 1: k_bwt_build; more: k_bwt_count + k_bwt_rank with that many per block */
     uint32_t walkWgsPerXcd{ 0 };
     uint32_t walkChunk{ 0 };               /* segments per claim of k_walk */
@@ -150,6 +152,7 @@ planBatch( const uint64_t* offsets, uint32_t n, uint64_t inSizeBytes, bool crowd
      * four side by side 11.9 -> 12.1 ms per batch.  The 128-entry lists of 1 024 lanes still fit the LDS of a CU: 152 KB) */
     p.mtfSide = n <= 1280;
     if ( p.mtfSide && n <= ( crowd ? 256u : 640u ) && !knobs.mtfNarrow ) p.mtfSmallLanes = n <= 64 ? 1024u : 512u;
+    p.mtfSerial = knobs.mtfSerial;
 
     /* table build: one workgroup per block when the batch fills the GPU with that (1 024 threads each: 512 at a time);
      * fewer blocks are spread over 2, 4 or 8 workgroups each (a lone block: 1.0 -> 0.3 ms) */
