@@ -414,6 +414,42 @@ uint32_t mi355x_bz2_line_hash_chunk_bytes( void );
 int mi355x_bz2_hash_lines( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t seed,
                            mi355x_bz2_line_hash_summary* summaries, uint64_t* hashes_device, uint64_t capacity );
 
+/* Where field `field` of every line lies.  D = the decoded data, nl = the one byte between lines, dl = the one byte
+ * between fields, dl != nl.  Lines are numbered as for mi355x_bz2_line_hash: line k is closed by the k-th nl, counted from
+ * 0; a non-empty unterminated tail is one more line, an empty one is none.  C = a line's content, without its nl, s = the
+ * offset of its first byte.  parts = C split at every dl, as Python's bytes.split splits: the empty content has one field,
+ * the empty one.  Field j, counted from 0, is present iff j < len( parts ); then start = s + sum( len( p ) + 1 for p in
+ * parts[:j] ) and size = len( parts[j] ).  A missing field has start = s + len( C ) -- the offset of the closing nl, or of
+ * the end of D for the tail -- and size = -1.  0 <= field <= 1023.  There is no quoting and no escaping: this is cut -f /
+ * awk -F / bytes.split, not a CSV parser.
+ *   _field_chunk_bytes  the bytes one GPU lane walks: of interest to tests and tuning.
+ *   _field_spans      over spans as for _hash_lines (inside the last batch's output, no batch in flight).  dl == nl or
+ *                     field > 1023 is MI355X_BZ2_ERR_INVALID_ARGUMENT, before anything is launched.  Per span i, read as
+ *                     a stretch of D that a line may enter and leave, all positions relative to the span: count = the
+ *                     lines it closes; has_delimiter; first_nl = its first nl (UINT64_MAX without one); head_delims = the
+ *                     dl bytes in front of first_nl (in all of the span without an nl), saturated at field + 1, and
+ *                     head_positions[i * ( field + 1 ) + k], k < head_delims, the position of the k-th of them (host
+ *                     memory, room for n * ( field + 1 ); may be NULL); tail_start = the byte behind its last nl (0
+ *                     without one); tail_delims = the dl bytes from there on, saturated at field + 1; tail_field_start,
+ *                     tail_field_end = where the field of the line that begins at tail_start starts and ends,
+ *                     UINT64_MAX where the span does not reach that; tail_non_empty = the span is not empty and its
+ *                     last byte is not nl.  starts_device[] (uint64) and sizes_device[] (int64; both DEVICE memory, room
+ *                     for `capacity`) receive start and size of the field in the closed lines, span by span in caller
+ *                     order and in line order within a span, the first `capacity` of them, a start being an offset in
+ *                     the batch's output; nothing is written at or beyond `capacity`.  The first closed line of a span
+ *                     is computed as if the span were entered at a line start: the caller that knows the line's bytes
+ *                     in front of the span replaces it (bz2_fields.hpp: stitchFields).  The call returns when
+ *                     everything is written.  k_field_chunks, k_field_link, k_scan_tiles, k_field_emit, k_field_sizes. */
+typedef struct mi355x_bz2_field_summary
+{
+    uint64_t count, first_nl, tail_start, tail_field_start, tail_field_end;
+    uint32_t head_delims, tail_delims, has_delimiter, tail_non_empty;
+} mi355x_bz2_field_summary;
+uint32_t mi355x_bz2_field_chunk_bytes( void );
+int mi355x_bz2_field_spans( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl,
+                            uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* head_positions,
+                            uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -736,6 +772,24 @@ int mi355x_bz2_reader_take_line_hashes( mi355x_bz2_reader* r, void* dst, uint64_
 const uint64_t* mi355x_bz2_reader_line_hashes_device( mi355x_bz2_reader* r );
 int mi355x_bz2_reader_distinct_lines( mi355x_bz2_reader* r, uint8_t nl, uint64_t seed, int want_numbers, uint64_t* n_distinct );
 int mi355x_bz2_reader_take_distinct_lines( mi355x_bz2_reader* r, uint64_t* line_numbers, uint64_t capacity );
+
+/* ---- fields (mi355x_bz2_field_spans says what field j of a line is, and how lines are numbered).
+ *   _field_spans      where field `field` lies in lines [first, first + count), count clipped at the last line; *n_lines =
+ *                     their number.  dl == nl or field > 1023 is MI355X_BZ2_ERR_INVALID_ARGUMENT, before anything is
+ *                     launched.  Needs the line index for `nl` (built on first use, as _read_line_ranges).  Only the
+ *                     blocks that hold those lines are decoded, each once, in the launches of _line_hashes for the same
+ *                     range, with their residency and failure rules; each launch runs mi355x_bz2_field_spans' kernels on
+ *                     the context that decoded its blocks, straight into two device buffers of the reader's, and the host
+ *                     stitches the launches' summaries and patches the one line per launch that crosses a seam, and the
+ *                     tail.  The buffers are allocated before anything is launched: a failed allocation is
+ *                     MI355X_BZ2_ERR_DEVICE with a message.  The spans are held until the next _field_spans or the
+ *                     close.  Positionless; releases line ranges held by earlier calls.
+ *   _take_field_spans the first min( capacity, n_lines ) held starts (uint64 each, offsets in the decoded file) and sizes
+ *                     (int64 each, -1 for a missing field) to `starts` and `sizes`, host memory or, with dst_is_device,
+ *                     device memory; they stay held. */
+int mi355x_bz2_reader_field_spans( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
+                                   int keep_on_device, uint64_t* n_lines );
+int mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* sizes, uint64_t capacity, int dst_is_device );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

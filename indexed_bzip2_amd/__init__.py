@@ -18,6 +18,10 @@ which lines are the same: line_hashes and line_hashes_to_tensor give one 61-bit 
 which, and computes it on the CPU), count_distinct_lines and first_occurrences sort them on the GPU (`sort -u | wc -l`,
 `awk '!seen[$0]++'`).  Distinct lines have distinct hashes with overwhelming probability, not with certainty: two contents
 of at most L bytes collide for at most L of the 2^61 bases a seed selects, and a second seed is an independent check.
+And what a line holds: field_spans and field_spans_to_tensor say where field j of every line lies when the line is split at
+a delimiter byte exactly as bytes.split splits it (size -1 where a line has fewer fields), read_fields and
+read_fields_to_tensor bring those bytes and nothing else (`cut -f`, `awk -F`); there is no quoting or escaping, this is not
+a CSV parser.
 """
 __version__ = "0.1.0"
 

@@ -193,6 +193,12 @@ SYMBOLS = [
     ("mi355x_bz2_reader_line_hashes_device", ctypes.c_void_p, [_vp]),
     ("mi355x_bz2_reader_distinct_lines", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint64, ctypes.c_int, _u64p]),
     ("mi355x_bz2_reader_take_distinct_lines", ctypes.c_int, [_vp, _u64p, ctypes.c_uint64]),
+    ("mi355x_bz2_field_chunk_bytes", ctypes.c_uint32, []),
+    ("mi355x_bz2_field_spans", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
+                                               ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_field_spans", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                                                      ctypes.c_uint64, ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_take_field_spans", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -414,6 +420,18 @@ def line_hash(content, seed=0):
 def line_hash_chunk_bytes():
     """The bytes of a span that one GPU lane walks in hash_lines (mi355x_bz2_line_hash_chunk_bytes)."""
     return int(lib().mi355x_bz2_line_hash_chunk_bytes())
+
+
+class FieldSummary(ctypes.Structure):
+    """mi355x_bz2_field_summary"""
+    _fields_ = [("count", ctypes.c_uint64), ("first_nl", ctypes.c_uint64), ("tail_start", ctypes.c_uint64),
+                ("tail_field_start", ctypes.c_uint64), ("tail_field_end", ctypes.c_uint64), ("head_delims", ctypes.c_uint32),
+                ("tail_delims", ctypes.c_uint32), ("has_delimiter", ctypes.c_uint32), ("tail_non_empty", ctypes.c_uint32)]
+
+
+def field_chunk_bytes():
+    """The bytes of a span that one GPU lane walks in field_spans (mi355x_bz2_field_chunk_bytes)."""
+    return int(lib().mi355x_bz2_field_chunk_bytes())
 
 
 def pattern_set(patterns, check=True):
@@ -785,6 +803,68 @@ class Decoder:
         out = [{"head": (s.head_hash, s.head_xl), "tail": (s.tail_hash, s.tail_xl), "has_delimiter": bool(s.has_delimiter),
                 "tail_non_empty": bool(s.tail_non_empty), "count": int(s.count)} for s in summaries[:len(spans)]]
         return out, hashes[:room]
+
+    def field_spans(self, spans, field, delimiter=b"\t", newline=b"\n", capacity=None, room=None):
+        """k_field_chunks, k_field_link, k_scan_tiles, k_field_emit, k_field_sizes: the summary for field `field` of every
+        span [(offset, size)] of the last batch's output, read as a stretch of lines that a line may enter and leave, and
+        where the field lies in the lines the spans close -> (summaries, starts, sizes): one dict per span (count,
+        has_delimiter, first_nl, head_positions, tail_start, tail_delims, tail_field_start, tail_field_end,
+        tail_non_empty; None for a position the span does not reach) and two numpy arrays, uint64 and int64, of `room`
+        values (default: capacity) that were all ones before the call and of which the call may write the first
+        `capacity` (None: as many as there are closed lines).  A start is an offset in the output."""
+        import numpy as np
+        nl, dl = bytes(newline), bytes(delimiter)
+        if len(nl) != 1 or len(dl) != 1:
+            raise ValueError("newline and delimiter must be exactly one byte each")
+        field = int(field)
+        if field < 0 or field > 1023:
+            raise ValueError("field must be between 0 and 1023")
+        if nl == dl:
+            raise ValueError("delimiter and newline must differ")
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        summaries = (FieldSummary * max(1, len(spans)))()
+        heads = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
+
+        def call(starts, sizes, capacity):
+            self._check(lib().mi355x_bz2_field_spans(self._h, arr, len(spans), nl[0], dl[0], field, summaries, heads.ctypes.data,
+                                                     starts, sizes, capacity))
+        if capacity is None:
+            call(None, None, 0)
+            capacity = sum(s.count for s in summaries[:len(spans)])
+        room = capacity if room is None else max(int(room), capacity)
+        starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
+        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        hip.hipFree.argtypes = [ctypes.c_void_p]
+        device = ctypes.c_void_p()
+        if hip.hipMalloc(ctypes.byref(device), 2 * starts.nbytes) != 0:
+            raise Bz2Error(101, f"field_spans: no device memory for {2 * starts.nbytes} bytes")
+        try:
+            second = ctypes.c_void_p(device.value + starts.nbytes)
+            if (hip.hipMemcpy(device, starts.ctypes.data, starts.nbytes, 1) != 0            # hipMemcpyHostToDevice
+                    or hip.hipMemcpy(second, sizes.ctypes.data, sizes.nbytes, 1) != 0):
+                raise Bz2Error(101, "field_spans: the copy to the device failed")
+            call(device, second, capacity)
+            if (hip.hipMemcpy(starts.ctypes.data, device, starts.nbytes, 2) != 0            # hipMemcpyDeviceToHost
+                    or hip.hipMemcpy(sizes.ctypes.data, second, sizes.nbytes, 2) != 0):
+                raise Bz2Error(101, "field_spans: the copy from the device failed")
+        finally:
+            hip.hipFree(device)
+        none = 2**64 - 1
+        out = []
+        for i, s in enumerate(summaries[:len(spans)]):
+            out.append({"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
+                        "first_nl": None if s.first_nl == none else int(s.first_nl),
+                        "head_positions": [int(v) for v in heads[i * (field + 1):i * (field + 1) + s.head_delims]],
+                        "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
+                        "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
+                        "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
+                        "tail_non_empty": bool(s.tail_non_empty)})
+        return out, starts[:room], sizes[:room]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

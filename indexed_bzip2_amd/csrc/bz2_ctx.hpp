@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/mi355x_bz2.h"
+#include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_regex.hpp"
 #include "bz2_search.hpp"
@@ -62,6 +63,13 @@ int matchLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, c
  * closed lines [skip, skip + take) go to dHashes[0, ...), device memory (take 0: no emitting pass). */
 int hashLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint8_t nl, uint64_t x, uint64_t skip, uint64_t take,
                      uint64_t* dHashes, bz2gpu::HashSummary* summary );
+
+/** The reader's field pass in one launch: mi355x_bz2_field_spans with `extent` as its one span, whose first byte is
+ * offset `fileOffset` of the decoded file.  *summary receives the extent's summary for `field` and the count of the
+ * lines it closes, none of them listed; start and size of the field in its closed lines [skip, skip + take) go to
+ * dStarts[0, ...) and dSizes[0, ...), device memory, the starts as offsets in the file. */
+int fieldSpansOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                      uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes, bz2gpu::FieldSummary* summary );
 
 /** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
  * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies

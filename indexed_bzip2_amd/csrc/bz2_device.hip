@@ -30,6 +30,7 @@
 #include "bz2_search_set.hip.h"
 #include "bz2_regex.hip.h"
 #include "bz2_linehash.hip.h"
+#include "bz2_fields.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -39,6 +40,7 @@
 #include "bz2_ctx.hpp"
 #include "bz2_regex.hpp"
 #include "bz2_linehash.hpp"
+#include "bz2_fields.hpp"
 
 using namespace bz2gpu;
 
@@ -219,7 +221,7 @@ struct mi355x_bz2_ctx : Scratch
     /* mi355x_bz2_count_bytes / _find_bytes: tiles, pattern, counts and seam bytes of one call, page-locked and on the
      * device, and the positions of the emitting pass on the device (searchBytes lays them out).  mi355x_bz2_match_lines
      * uses the same three for its tiles, table, summaries and witnesses (matchLines lays them out), mi355x_bz2_hash_lines
-     * the first two for its tiles and summaries (hashLines lays them out) */
+     * and mi355x_bz2_field_spans the first two for their tiles and summaries (hashLines and fieldSpans lay them out) */
     GrowBuffer hSearch{ nullptr, 0, true }, dSearch, dSearchPositions;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
@@ -2325,6 +2327,119 @@ hashLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* span
     return MI355X_BZ2_OK;
 }
 
+static_assert( FIELD_CHUNK == FIELD_CHUNK_BYTES && FIELD_NOT_REACHED == FIELD_UNKNOWN, "the kernels' constants are the host's" );
+
+/**
+ * mi355x_bz2_field_spans and the reader's launches.  The tiling is hashLines'; k_field_chunks gives every chunk its
+ * element and scans each tile, k_field_link -- one workgroup per span -- scans the tiles, k_scan_tiles turns the chunk
+ * counts into places, k_field_emit writes starts and ends of field `field` in the closed lines [skip, skip + capacity)
+ * -- numbered over all spans in caller order -- to dStarts[0, ...) and dSizes[0, ...), device memory of the caller's, and
+ * completes the spans' summaries and head positions, and k_field_sizes turns the ends into sizes.  The kernels queue
+ * behind one another and the summaries come back in one D2H behind them.  The first byte of span i counts as offset
+ * bases[i] (nullptr: its offset in the output).  k_field_emit runs whatever the capacity: the summaries need it.
+ */
+int
+fieldSpans( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, const uint64_t* bases, uint32_t n, uint8_t nl,
+            uint8_t dl, uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* headPositions, uint64_t skip,
+            uint64_t capacity, uint64_t* dStarts, int64_t* dSizes )
+{
+    const std::scoped_lock lock( c->mutex );
+    const auto why = fieldArgumentsError( nl, dl, field );
+    if ( !why.empty() ) {
+        c->lastError = std::string( what ) + ": " + why;
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    if ( c->pendingBlocks != 0 ) {
+        c->lastError = std::string( what ) + ": a batch is in flight";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    uint64_t nTiles = 0, bytesInSpans = 0;
+    for ( uint32_t i = 0; i < n; ++i ) {
+        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
+            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
+        bytesInSpans += spans[i].size;
+    }
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    if ( nTiles * FIELD_THREADS > 0x7FFFFFFFu ) {
+        c->lastError = std::string( what ) + ": too many spans";
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    /* host and device: [tiles][spans] up, [span summaries][head positions] down; device only, behind them:
+     * [tile summaries][chunk places][chunk prefixes][chunk counts] */
+    const uint64_t slots = nTiles * FIELD_THREADS, cap = (uint64_t)field + 1;
+    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
+    const uint64_t spansAt = aligned( nTiles * sizeof( CountTile ) ), resultsAt = aligned( spansAt + n * sizeof( FieldSpanTiles ) );
+    const uint64_t headsAt = aligned( resultsAt + n * sizeof( FieldSpanSummary ) );
+    const uint64_t tilesAt = aligned( headsAt + n * cap * sizeof( uint64_t ) );
+    const uint64_t placesAt = aligned( tilesAt + nTiles * sizeof( FieldTile ) );
+    const uint64_t prefixesAt = placesAt + slots * sizeof( uint64_t ), countsAt = prefixesAt + slots * sizeof( uint32_t );
+    const uint64_t bytes = countsAt + slots * sizeof( uint32_t );
+    const uint64_t deviceCap = std::max( 2 * c->dSearch.capacity, bytes );
+    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, tilesAt );
+    HIP_TRY( c, c->hSearch.grow( c, tilesAt, hostCap, hostCap ) );
+    HIP_TRY( c, c->dSearch.grow( c, bytes, deviceCap, deviceCap ) );
+    uint8_t* const h = c->hSearch.bytes;
+    auto* const hTiles = reinterpret_cast<CountTile*>( h );
+    auto* const hSpans = reinterpret_cast<FieldSpanTiles*>( h + spansAt );
+    uint64_t tile = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        hSpans[s] = { tile, ( spans[s].size + COUNT_TILE - 1 ) / COUNT_TILE, bases != nullptr ? bases[s] : spans[s].offset };
+        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
+            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
+        }
+    }
+    uint8_t* const d = c->dSearch.bytes;
+    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
+    const auto* const dSpans = reinterpret_cast<const FieldSpanTiles*>( d + spansAt );
+    auto* const dSummaries = reinterpret_cast<FieldSpanSummary*>( d + resultsAt );
+    auto* const dTileSummaries = reinterpret_cast<FieldTile*>( d + tilesAt );
+    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
+    auto* const dPrefixes = reinterpret_cast<uint32_t*>( d + prefixesAt );
+    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_field_chunks, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, (uint32_t)cap, dPrefixes, dCounts, dTileSummaries );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_field_link, dim3( n ), dim3( FIELD_THREADS ), 0, c->stream, dSpans, dTileSummaries, dSummaries, field );
+    HIP_TRY( c, hipGetLastError() );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+        HIP_TRY( c, hipGetLastError() );
+        hipLaunchKernelGGL( k_field_emit, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, field, dSpans, dPrefixes, dTileSummaries, dPlaces, dSummaries,
+                            reinterpret_cast<uint64_t*>( d + headsAt ), skip, capacity, dStarts, dSizes );
+        HIP_TRY( c, hipGetLastError() );
+        /* a span closes at most one line per byte */
+        const uint64_t most = std::min( capacity, bytesInSpans );
+        if ( most > 0 ) {
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( most + FIELD_SIZES_THREADS - 1 ) / FIELD_SIZES_THREADS, FIELD_SIZES_BLOCKS );
+            hipLaunchKernelGGL( k_field_sizes, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
+                                skip, capacity, dStarts, dSizes );
+            HIP_TRY( c, hipGetLastError() );
+        }
+    }
+    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, tilesAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& from = reinterpret_cast<const FieldSpanSummary*>( h + resultsAt )[i];
+        summaries[i] = { from.count, from.firstNl, from.tailStart, from.tailFieldStart, from.tailFieldEnd, from.headDelims,
+                         from.tailDelims, ( from.info & FIELD_HAS_DELIMITER ) != 0 ? 1u : 0u,
+                         ( from.info & FIELD_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
+        if ( headPositions != nullptr ) {
+            std::copy_n( reinterpret_cast<const uint64_t*>( h + headsAt ) + i * cap, std::min<uint64_t>( from.headDelims, cap ),
+                         headPositions + i * cap );
+        }
+    }
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -2391,6 +2506,33 @@ mi355x::hashLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, 
     summary->tailNonEmpty = s.tail_non_empty != 0;
     summary->count = s.count;
     summary->hashes.clear();
+    return status;
+}
+
+int
+mi355x::fieldSpansOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                          uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes,
+                          bz2gpu::FieldSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr || field > FIELD_MAX || ( take > 0 && ( dStarts == nullptr || dSizes == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    mi355x_bz2_field_summary s{};
+    std::vector<uint64_t> heads( (size_t)field + 1 );
+    const int status = fieldSpans( c, "field_spans", &extent, &fileOffset, 1, nl, dl, field, &s, heads.data(), skip, take, dStarts, dSizes );
+    *summary = bz2gpu::emptyFieldSummary( field );
+    if ( status != MI355X_BZ2_OK ) return status;
+    summary->size = extent.size;
+    summary->hasDelimiter = s.has_delimiter != 0;
+    summary->tailNonEmpty = s.tail_non_empty != 0;
+    summary->count = s.count;
+    summary->firstNl = s.first_nl;
+    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
+    summary->headPositions = std::move( heads );
+    summary->tailStart = s.tail_start;
+    summary->tailDelims = s.tail_delims;
+    summary->tailFieldStart = s.tail_field_start;
+    summary->tailFieldEnd = s.tail_field_end;
     return status;
 }
 
@@ -2509,6 +2651,19 @@ mi355x_bz2_hash_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uin
         return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     }
     return hashLines( c, "hash_lines", spans, n, nl, lineHashBase( seed ), summaries, 0, capacity, hashesDevice );
+}
+
+int
+mi355x_bz2_field_spans( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl, uint32_t field,
+                        mi355x_bz2_field_summary* summaries, uint64_t* headPositions, uint64_t* startsDevice,
+                        int64_t* sizesDevice, uint64_t capacity )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) )
+         || ( capacity > 0 && ( startsDevice == nullptr || sizesDevice == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return fieldSpans( c, "field_spans", spans, nullptr, n, nl, dl, field, summaries, headPositions, 0, capacity, startsDevice,
+                       sizesDevice );
 }
 
 int

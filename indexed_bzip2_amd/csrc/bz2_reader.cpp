@@ -43,6 +43,7 @@
 #include "bz2_ctx.hpp"
 #include "bz2_lines.hpp"
 #include "bz2_linehash.hpp"
+#include "bz2_fields.hpp"
 #include "bz2_search.hpp"
 #include "bz2_ranges.hpp"
 
@@ -1232,6 +1233,7 @@ public:
     {
         dropHeldLines();
         dropHeldHashes();
+        m_fields.reset();
         m_matches.reset();
         m_setMatches.reset();
         m_scheduler.reset();
@@ -1949,6 +1951,105 @@ public:
         std::copy_n( m_distinct->begin(), (size_t)std::min<uint64_t>( capacity, m_distinct->size() ), lineNumbers );
     }
 
+    /** mi355x_bz2_reader_field_spans: lineHashes' launches and places with fieldSpansOutput in place of the hashing pass;
+     * then stitchFields, and one start and one size copied for every line that crosses a seam and for the unterminated
+     * tail. */
+    void
+    fieldSpans( uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "field_spans: " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        m_fields.reset();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planFields( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
+                                       count, m_batch, packed, m_source->size() );
+        } );
+        *nLines = 0;
+        HeldFields held;
+        held.onDevice = keepOnDevice;
+        if ( plan.count == 0 ) {
+            m_fields = std::move( held );
+            return;
+        }
+        /* per stretch: the lines it closes (from the index), which of them are wanted, and where they go */
+        struct Work { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
+        std::vector<Work> works( plan.stretches.size() );
+        std::vector<bz2gpu::FieldStretch> stretches( plan.stretches.size() );
+        std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
+        const uint64_t wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;   /* but for the tail */
+        uint64_t closedBefore = plan.firstClosed;
+        for ( size_t k = 0; k < works.size(); ++k ) {
+            const auto& piece = plan.stretches[k];
+            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
+            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
+            auto& work = works[k];
+            work.closed = index.lines[to] - index.lines[from];
+            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
+            if ( end > begin ) {
+                work.skip = begin - closedBefore;
+                work.take = end - begin;
+                work.at = begin - first;
+            }
+            closedBefore += work.closed;
+            stretches[k].fileOffset = piece.fileOffset;
+            stretches[k].summary.size = piece.size;
+            ofLaunch[piece.launch].push_back( k );
+        }
+        std::string why;
+        held.device = m_device;
+        held.starts.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
+        if ( held.starts ) held.sizes.reset( deviceAllocate( m_device, plan.count * sizeof( int64_t ), &why ) );
+        if ( !held.starts || !held.sizes ) fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
+        auto* const dStarts = static_cast<uint64_t*>( held.starts.get() );
+        auto* const dSizes = static_cast<int64_t*>( held.sizes.get() );
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [&plan, &works, &stretches, mine = &ofLaunch[l], nl, dl, field, dStarts, dSizes] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+                for ( const auto k : *mine ) {
+                    const auto& piece = plan.stretches[k];
+                    const auto& work = works[k];
+                    checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, work.skip,
+                                                        work.take, dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
+                    if ( stretches[k].summary.count != work.closed ) {
+                        failLyingLineIndex( piece.fileOffset, work.closed, stretches[k].summary.count );
+                    }
+                }
+            };
+        } );
+        /* the first closed line of a stretch is line firstClosed + k of the file */
+        std::vector<std::pair<uint64_t, bz2gpu::FieldSpan> > patches;
+        const auto stitched = bz2gpu::stitchFields( stretches, field, [&] ( uint64_t k, const bz2gpu::FieldSpan& span ) {
+            const uint64_t line = plan.firstClosed + k;
+            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, span );
+        } );
+        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
+        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tail );
+        for ( const auto& [at, span] : patches ) {
+            if ( !hostToDevice( m_device, dStarts + at, &span.start, sizeof( span.start ), &why )
+                 || !hostToDevice( m_device, dSizes + at, &span.size, sizeof( span.size ), &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
+            }
+        }
+        held.n = n;
+        *nLines = n;
+        m_fields = std::move( held );
+    }
+
+    /** mi355x_bz2_reader_take_field_spans. */
+    void
+    takeFieldSpans( void* starts, void* sizes, uint64_t capacity, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_spans on a closed reader" );
+        if ( !m_fields ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_spans: no field spans are held (field_spans first)" );
+        std::string why;
+        const uint64_t bytes = std::min( capacity, m_fields->n ) * sizeof( uint64_t );
+        if ( !deviceToHost( m_fields->device, starts, m_fields->starts.get(), bytes, dstIsDevice, &why )
+             || !deviceToHost( m_fields->device, sizes, m_fields->sizes.get(), bytes, dstIsDevice, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, "take_field_spans: " + why );
+        }
+    }
+
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
 
     [[nodiscard]] OffsetMap
@@ -2053,6 +2154,16 @@ private:
             return *this;
         }
         ~HeldHashes() { deviceRelease( dHashes ); }
+    };
+
+    /** The starts and sizes of field_spans, in device memory of the reader's own. */
+    struct HeldFields
+    {
+        struct Release { void operator()( void* pointer ) const { deviceRelease( pointer ); } };
+        std::unique_ptr<void, Release> starts, sizes;
+        uint64_t n{ 0 };
+        int device{ -1 };
+        bool onDevice{ false };
     };
 
     void
@@ -2349,6 +2460,7 @@ private:
     std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
     std::optional<HeldHashes> m_hashes;   /* between line_hashes and the next line_hashes / distinct_lines */
+    std::optional<HeldFields> m_fields;   /* between field_spans and the next field_spans */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
@@ -2757,6 +2869,22 @@ const uint64_t*
 mi355x_bz2_reader_line_hashes_device( mi355x_bz2_reader* r )
 {
     return r != nullptr && r->reader ? r->reader->lineHashesDevice() : nullptr;
+}
+
+int
+mi355x_bz2_reader_field_spans( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
+                               int keepOnDevice, uint64_t* nLines )
+{
+    if ( nLines == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.fieldSpans( nl, dl, field, first, count, keepOnDevice != 0, nLines ); } );
+}
+
+int
+mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* sizes, uint64_t capacity, int dstIsDevice )
+{
+    if ( capacity > 0 && ( starts == nullptr || sizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldSpans( starts, sizes, capacity, dstIsDevice != 0 ); } );
 }
 
 int

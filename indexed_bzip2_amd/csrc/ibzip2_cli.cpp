@@ -45,6 +45,9 @@ struct Options
     bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false }, grepRegex{ false };
     bool lineHashes{ false }, countDistinctLines{ false }, hasSeed{ false };
     uint64_t seed{ 0 };
+    bool cutField{ false }, hasFieldDelimiter{ false };
+    unsigned field{ 0 };
+    uint8_t fieldDelimiter{ '\t' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -113,6 +116,13 @@ printHelp()
         "                                again with another --seed for an independent check.\n"
         "      --seed arg                With --line-hashes or --count-distinct-lines: the 64-bit seed of the hash's\n"
         "                                base. (default: 0)\n"
+        "      --cut-field arg           Print field N (counted from 0, at most 1023) of every line of the decoded\n"
+        "                                data, one per line, and an empty line where a line has no such field (cut -f,\n"
+        "                                awk -F): a line is split at every --field-delimiter byte; there is no quoting\n"
+        "                                and no escaping, this is not a CSV parser. The fields are found on the GPU and\n"
+        "                                only their bytes are copied to the host.\n"
+        "      --field-delimiter arg     With --cut-field: the byte between fields, as itself (',') or as \\t, \\0 or\n"
+        "                                \\xHH; not the newline. (default: \\t)\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -143,6 +153,8 @@ printHelp()
         "  ibzip2-mi355x --grep error --ignore-case file.bz2\n\n"
         "Count the distinct lines of a file:\n"
         "  ibzip2-mi355x --count-distinct-lines file.bz2\n\n"
+        "Print the third column of a tab-separated file:\n"
+        "  ibzip2-mi355x --cut-field 2 file.tsv.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -217,6 +229,20 @@ parseSeed( const char* text, uint64_t& value )
     return true;
 }
 
+/** One byte for --field-delimiter: the argument itself if it is one byte, or \\t, \\0, \\xHH. */
+bool
+parseByte( const std::string& text, uint8_t& value )
+{
+    const auto hex = [] ( char c ) { return c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1; };
+    if ( text.size() == 1 ) value = (uint8_t)text[0];
+    else if ( text == "\\t" ) value = '\t';
+    else if ( text == "\\0" ) value = 0;
+    else if ( text.size() == 4 && text[0] == '\\' && text[1] == 'x' && hex( text[2] ) >= 0 && hex( text[3] ) >= 0 ) {
+        value = (uint8_t)( hex( text[2] ) * 16 + hex( text[3] ) );
+    } else return false;
+    return true;
+}
+
 /** Returns 0 on success.  An option with an optional value (-l, -L) takes the next argument unless that starts with '-'
  * or is the last argument while no input has been seen (then it is the positional input file, the ambiguity the
  * reference warns about, ibzip2.cpp:175-178, resolved the way its examples are written: "-l file -- input"). */
@@ -279,6 +305,22 @@ parseArguments( int argc, char** argv, Options& o )
             else if ( name == "seed" ) {
                 if ( !need( value ) || !parseSeed( value.c_str(), o.seed ) ) { std::cerr << "Bad value for --seed\n"; return 1; }
                 o.hasSeed = true;
+            }
+            else if ( name == "cut-field" ) {
+                uint64_t field = 0;     /* digits only, as --seed */
+                if ( !need( value ) || !parseSeed( value.c_str(), field ) || field > 1023 ) {
+                    std::cerr << "Bad value for --cut-field\n";
+                    return 1;
+                }
+                o.field = (unsigned)field;
+                o.cutField = true;
+            }
+            else if ( name == "field-delimiter" ) {
+                if ( !need( value ) || !parseByte( value, o.fieldDelimiter ) || o.fieldDelimiter == '\n' ) {
+                    std::cerr << "Bad value for --field-delimiter\n";
+                    return 1;
+                }
+                o.hasFieldDelimiter = true;
             }
             else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
             else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
@@ -506,6 +548,16 @@ main( int argc, char** argv )
         std::cerr << "Option '--seed' needs '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
+    if ( o.cutField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
+                         || o.countDistinctLines ) ) {
+        std::cerr << "Option '--cut-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
+                     "'--grep-file', '--count-matches-file', '--line-hashes' or '--count-distinct-lines'\n";
+        return 1;
+    }
+    if ( o.hasFieldDelimiter && !o.cutField ) {
+        std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
+        return 1;
+    }
     const uint32_t searchFlags = o.ignoreCase ? MI355X_BZ2_SEARCH_IGNORE_CASE : 0u;
     if ( o.version ) {
         std::cout << "ibzip2-mi355x, CLI to the MI355X bzip2 block decoder (C ABI version " << mi355x_bz2_abi_version()
@@ -597,6 +649,66 @@ main( int argc, char** argv )
             for ( int digit = 0; digit < 16; ++digit ) text[i * 17 + digit] = "0123456789abcdef"[( hashes[i] >> ( 60 - 4 * digit ) ) & 15];
         }
         std::cout << text;
+        return 0;
+    }
+
+    /* likewise an action of its own: one field of every line, from the reader's field_spans and read_ranges, in windows
+     * of lines so that the memory is bounded whatever the file */
+    if ( o.cutField ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        constexpr uint64_t WINDOW = uint64_t( 1 ) << 20;
+        std::vector<uint64_t> starts, lengths, got;
+        std::vector<int64_t> sizes;
+        std::string bytes, text;
+        for ( uint64_t first = 0; rc == MI355X_BZ2_OK; first += WINDOW ) {
+            uint64_t n = 0;
+            rc = mi355x_bz2_reader_field_spans( reader, '\n', o.fieldDelimiter, o.field, first, WINDOW, 0, &n );
+            if ( rc != MI355X_BZ2_OK || n == 0 ) break;
+            starts.resize( n );
+            sizes.resize( n );
+            lengths.resize( n );
+            got.resize( n );
+            rc = mi355x_bz2_reader_take_field_spans( reader, starts.data(), sizes.data(), n, 0 );
+            if ( rc != MI355X_BZ2_OK ) break;
+            uint64_t total = 0;
+            for ( uint64_t i = 0; i < n; ++i ) total += lengths[i] = sizes[i] > 0 ? (uint64_t)sizes[i] : 0;
+            bytes.resize( total );
+            rc = mi355x_bz2_reader_read_ranges( reader, starts.data(), lengths.data(), (uint32_t)n, bytes.data(), 0, got.data() );
+            if ( rc != MI355X_BZ2_OK ) break;
+            text.clear();
+            text.reserve( total + n );
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < n; ++i ) {
+                text.append( bytes, at, lengths[i] );
+                text.push_back( '\n' );
+                at += lengths[i];
+            }
+            std::cout << text;
+            if ( n < WINDOW ) break;
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
         return 0;
     }
 

@@ -644,6 +644,106 @@ class _IndexedBzip2FileParallel:
             self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)) if n else None, n))
         return out
 
+    # -- fields: where field j of every line lies and what it holds.  A line's content (the line without `newline`) is
+    # split at every `delimiter` byte exactly as bytes.split(delimiter) splits it; field j, 0-based, is missing in a line
+    # with fewer than j delimiters.  There is no quoting and no escaping: this is `cut -f` / `awk -F`, not a CSV parser.
+    # Lines are numbered as line_hashes numbers them; a non-empty unterminated tail is the last line
+    def _field_arguments(self, field, first, count, delimiter, newline):
+        self._require()
+        nl = self._newline(newline)
+        if not isinstance(delimiter, (bytes, bytearray)) or len(delimiter) != 1:
+            raise ValueError("delimiter must be exactly one byte, e.g. b'\\t'")
+        if delimiter[0] == nl:
+            raise ValueError("delimiter and newline must differ")
+        field = int(field)
+        if field < 0 or field > 1023:
+            raise ValueError("field must be between 0 and 1023")
+        (first,), _ = self._u64([first], "first")
+        (count,), _ = self._u64([2**64 - 1 if count is None else count], "count")
+        return nl, delimiter[0], field, first, count
+
+    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """Where field `field` (0-based, at most 1023) lies in lines [first, first + count) (count None: to the last
+        line; clipped there) -> (starts numpy uint64, sizes numpy int64), one pair per line: data[start:start + size] ==
+        content.split(delimiter)[field].  A line with fewer fields has size -1 and start = the offset at which its
+        content ends.  No quoting, no escaping: `cut -f`, not a CSV parser.  Only the blocks that hold those lines are
+        decoded, each once; the spans are computed on the GPU and 16 bytes per line come back.  Builds the line index
+        first if the reader does not hold one for `newline`.  Positionless."""
+        import numpy as np
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, 0, ctypes.byref(n)))
+        starts, sizes = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.int64)
+        self._check(N.lib().mi355x_bz2_reader_take_field_spans(self._h, starts.ctypes.data if n.value else None,
+                                                                sizes.ctypes.data if n.value else None, n.value, 0))
+        return starts, sizes
+
+    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """field_spans as two torch.int64 tensors (starts, sizes) on the reader's device; nothing passes through the
+        host.  A start is below 2^63, so int64 holds it as it is."""
+        import torch
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, 1, ctypes.byref(n)))
+        starts = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
+        sizes = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
+        if n.value:
+            # the new tensors' memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(starts.device).synchronize()
+            self._check(N.lib().mi355x_bz2_reader_take_field_spans(self._h, ctypes.c_void_p(starts.data_ptr()),
+                                                                    ctypes.c_void_p(sizes.data_ptr()), n.value, 1))
+        return starts, sizes
+
+    def _read_fields(self, field, first, count, delimiter, newline, make):
+        """field_spans, then the existing read_ranges over the present fields; make(total) -> (destination, pointer,
+        is_device).  Returns (sizes numpy int64, bounds numpy int64 of n + 1, destination)."""
+        import numpy as np
+        starts, sizes = self.field_spans(field, first, count, delimiter, newline)
+        n = len(starts)
+        lengths = np.maximum(sizes, 0).astype(np.uint64)
+        bounds = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(lengths, out=bounds[1:])
+        out, dst, device = make(int(bounds[-1]))
+        if n:
+            got = np.empty(n, dtype=np.uint64)
+            u64p = ctypes.POINTER(ctypes.c_uint64)
+            self._check(N.lib().mi355x_bz2_reader_read_ranges(self._h, starts.ctypes.data_as(u64p), lengths.ctypes.data_as(u64p),
+                                                               n, dst, device, got.ctypes.data_as(u64p)))
+        return sizes, bounds, out
+
+    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """Field `field` of lines [first, first + count) -> a list with one bytes object per line, content.split(
+        delimiter)[field], and None where the line has no such field.  No quoting, no escaping: `cut -f`, not a CSV
+        parser.  field_spans finds the fields on the GPU; then the blocks that hold them are decoded a second time and
+        only the fields' bytes are copied out.  Positionless."""
+        def make(total):
+            out = bytearray(total)
+            return out, ((ctypes.c_char * total).from_buffer(out) if total else None), 0
+        sizes, bounds, out = self._read_fields(field, first, count, delimiter, newline, make)
+        data = bytes(out)
+        return [data[bounds[i]:bounds[i + 1]] if sizes[i] >= 0 else None for i in range(len(sizes))]
+
+    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """read_fields into ONE contiguous torch.uint8 tensor on the reader's device -> (data, offsets) as
+        read_line_ranges_to_tensor shapes them: line i's field is ``data[offsets[i]:offsets[i + 1]]``, `offsets` an
+        int64 CPU tensor of n + 1 boundaries; a missing field has size 0 (field_spans tells it from an empty one).  The
+        fields' bytes never pass through the host."""
+        import torch
+        self._field_arguments(field, first, count, delimiter, newline)      # refused before the GPU is touched
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+
+        def make(total):
+            data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+            if total:
+                # the new tensor's memory may still be in use by work queued on torch's stream: the gather comes after it
+                torch.cuda.current_stream(data.device).synchronize()
+            return data, (ctypes.c_void_p(data.data_ptr()) if total else None), 1
+        _, bounds, data = self._read_fields(field, first, count, delimiter, newline, make)
+        return data, torch.from_numpy(bounds)
+
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
     # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
     # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
@@ -872,6 +972,22 @@ class IndexedBzip2File(io.BufferedReader):
     def first_occurrences(self, newline=b"\n", seed=0):
         """See _IndexedBzip2FileParallel.first_occurrences."""
         return self._open_reader().first_occurrences(newline, seed)
+
+    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.field_spans."""
+        return self._open_reader().field_spans(field, first, count, delimiter, newline)
+
+    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.field_spans_to_tensor."""
+        return self._open_reader().field_spans_to_tensor(field, first, count, delimiter, newline)
+
+    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_fields."""
+        return self._open_reader().read_fields(field, first, count, delimiter, newline)
+
+    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_fields_to_tensor."""
+        return self._open_reader().read_fields_to_tensor(field, first, count, delimiter, newline)
 
     def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
