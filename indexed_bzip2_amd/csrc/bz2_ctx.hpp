@@ -1,6 +1,8 @@
 /**
- * bz2_ctx.hpp -- entry points of the decoder context (bz2_device.hip) that other host code of the library uses but the
- * C ABI does not export.
+ * bz2_ctx.hpp -- entry points of the decoder context that other host code of the library uses but the C ABI does not
+ * export: the batch, its buffers and the encoder's slot (bz2_device.hip), the reader's one-span forms of the calls that
+ * read a batch's output (bz2_queries.hip.h, in the same translation unit), and device memory of nobody's context
+ * (bz2_distinct.hip).
  */
 #pragma once
 

@@ -6,6 +6,8 @@
  * stream.  Per-block scratch lives in HBM and is sized for the largest block the format allows (900 000 symbols):
  *   L column 0.9 MB, packed LF table 4 MiB, pre-RLE1 stream 0.9 MB, selectors 32 KiB, segment records ~100 KB.
  * There is NO CPU fallback: without a usable gfx950 device every entry point fails with MI355X_BZ2_ERR_NO_DEVICE.
+ * The calls that read a finished batch's output are in bz2_queries.hip.h, included below: ONE translation unit, because
+ * the kernel headers define their __global__ functions and the context's layout names device record types.
  */
 #include <hip/hip_runtime.h>
 
@@ -214,14 +216,15 @@ struct mi355x_bz2_ctx : Scratch
      * list (page-locked and on the device) and, for a host destination, the packed pieces (device and page-locked) */
     GrowBuffer hGatherTiles{ nullptr, 0, true }, dGatherTiles, hGatherStage{ nullptr, 0, true }, dGatherStage;
 
-    /* mi355x_bz2_count_byte / _find_byte: tiles, queries, tile counts and results of one call, page-locked and on the
-     * device (selectBytes lays them out) */
+    /* mi355x_bz2_count_byte / _find_byte / _rank_byte: tiles, queries, tile counts and results of one call, page-locked
+     * and on the device (laySelect and layRank of bz2_query_layout.hpp lay them out) */
     GrowBuffer hSelect{ nullptr, 0, true }, dSelect;
 
-    /* mi355x_bz2_count_bytes / _find_bytes: tiles, pattern, counts and seam bytes of one call, page-locked and on the
-     * device, and the positions of the emitting pass on the device (searchBytes lays them out).  mi355x_bz2_match_lines
-     * uses the same three for its tiles, table, summaries and witnesses (matchLines lays them out), mi355x_bz2_hash_lines
-     * and mi355x_bz2_field_spans the first two for their tiles and summaries (hashLines and fieldSpans lay them out) */
+    /* mi355x_bz2_count_bytes / _find_bytes and their _set forms: tiles, pattern or set, counts and seam bytes of one call,
+     * page-locked and on the device, and the positions of the emitting pass on the device (emitListed).
+     * mi355x_bz2_match_lines uses the same three for its tiles, table, summaries and witnesses, mi355x_bz2_hash_lines and
+     * mi355x_bz2_field_spans the first two for their tiles and summaries.  bz2_query_layout.hpp has a layout function for
+     * each of them; the launchers are in bz2_queries.hip.h */
     GrowBuffer hSearch{ nullptr, 0, true }, dSearch, dSearchPositions;
 
     /* mi355x_bz2_decompress_buffers: the buffers' bytes back to back (mi355x::resultBuffer) */
@@ -1580,1136 +1583,9 @@ mi355x_bz2_crc32_device( mi355x_bz2_ctx* c, const void* deviceBytes, const uint6
 
 }  // extern "C"
 
-namespace
-{
-/** k_gather over pieces of the `srcSize` bytes at `src` (device memory of the context), see mi355x_bz2_gather_output.
- * The caller holds the context's lock. */
-int
-gatherPieces( mi355x_bz2_ctx* c, const uint8_t* src, uint64_t srcSize, const mi355x_bz2_gather_piece* pieces,
-              uint32_t nPieces, void* dst, int dstIsDevice )
-{
-    /* every piece inside the source; tiles of at most GATHER_TILE bytes */
-    uint64_t nTiles = 0, total = 0;
-    for ( uint32_t i = 0; i < nPieces; ++i ) {
-        const auto& p = pieces[i];
-        if ( p.size > srcSize || p.src_offset > srcSize - p.size || p.dst_offset > ~uint64_t( 0 ) - p.size ) {
-            c->lastError = "gather_output: piece " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        nTiles += ( p.size + GATHER_TILE - 1 ) / GATHER_TILE;
-        total += p.size;
-    }
-    if ( total == 0 ) return MI355X_BZ2_OK;
-    if ( dst == nullptr || nTiles > 0x7FFFFFFFu ) {
-        c->lastError = "gather_output: no destination, or too many pieces";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-    /* the previous call's tile list has been consumed (every call waits for its kernel) */
-    const uint64_t tileBytes = nTiles * sizeof( GatherTile ), tileCap = std::max( 2 * c->dGatherTiles.capacity, tileBytes );
-    HIP_TRY( c, c->hGatherTiles.grow( c, tileBytes, tileCap, tileCap ) );
-    HIP_TRY( c, c->dGatherTiles.grow( c, tileBytes, tileCap, tileCap ) );
-    const bool toHost = dstIsDevice == 0;
-    if ( toHost ) {
-        const uint64_t cap = std::max( c->dGatherStage.capacity + c->dGatherStage.capacity / 2, total );
-        HIP_TRY( c, c->hGatherStage.grow( c, total, cap, cap ) );
-        HIP_TRY( c, c->dGatherStage.grow( c, total, cap, cap ) );
-    }
-    GatherTile* const hTiles = reinterpret_cast<GatherTile*>( c->hGatherTiles.bytes );
-    GatherTile* const dTiles = reinterpret_cast<GatherTile*>( c->dGatherTiles.bytes );
-    /* a host destination gets the pieces packed back to back in the staging buffer, one D2H copy of exactly the requested
-     * bytes, and then each piece copied to its place: bytes of `dst` between the pieces are never written */
-    uint64_t tile = 0, staged = 0;
-    for ( uint32_t i = 0; i < nPieces; ++i ) {
-        const auto& p = pieces[i];
-        const uint64_t at = toHost ? staged : p.dst_offset;
-        for ( uint64_t k = 0; k < p.size; k += GATHER_TILE ) {
-            hTiles[tile++] = { p.src_offset + k, at + k, std::min<uint64_t>( GATHER_TILE, p.size - k ) };
-        }
-        staged += p.size;
-    }
-    HIP_TRY( c, hipMemcpyAsync( dTiles, hTiles, tileBytes, hipMemcpyHostToDevice, c->stream ) );
-    hipLaunchKernelGGL( k_gather, dim3( (uint32_t)nTiles ), dim3( GATHER_THREADS ), 0, c->stream, dTiles, src,
-                        toHost ? c->dGatherStage.bytes : static_cast<uint8_t*>( dst ) );
-    HIP_TRY( c, hipGetLastError() );
-    if ( toHost ) {
-        HIP_TRY( c, hipMemcpyAsync( c->hGatherStage.bytes, c->dGatherStage.bytes, total, hipMemcpyDeviceToHost, c->stream ) );
-    }
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    if ( toHost ) {
-        staged = 0;
-        for ( uint32_t i = 0; i < nPieces; ++i ) {
-            std::memcpy( static_cast<uint8_t*>( dst ) + pieces[i].dst_offset, c->hGatherStage.bytes + staged, pieces[i].size );
-            staged += pieces[i].size;
-        }
-    }
-    return MI355X_BZ2_OK;
-}
-
-/**
- * Both byte calls: the distinct spans are cut into tiles, k_count_byte counts every tile, and either the spans' sums or
- * (ranks given) the positions k_find_byte finds come back.  One page-locked and one device allocation hold the tiles,
- * the queries, the tile counts and the results of the call.
- */
-int
-selectBytes( mi355x_bz2_ctx* c, const char* what, uint8_t value, uint32_t n, const uint64_t* offsets, const uint64_t* sizes,
-             const uint64_t* ranks, uint64_t* results )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    /* every span inside the last batch's output; a span named several times is counted once */
-    std::map<std::pair<uint64_t, uint64_t>, uint32_t> known;
-    std::vector<uint32_t> spanOf( n );
-    std::vector<std::pair<uint64_t, uint64_t> > spans;
-    std::vector<uint64_t> firstTile;
-    uint64_t nTiles = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( sizes[i] > c->outSize || offsets[i] > c->outSize - sizes[i] || ( ranks != nullptr && ranks[i] == 0 ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i )
-                           + " lies outside the last batch's output, or its rank is 0";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        const auto [entry, isNew] = known.emplace( std::make_pair( offsets[i], sizes[i] ), (uint32_t)spans.size() );
-        spanOf[i] = entry->second;
-        if ( isNew ) {
-            spans.push_back( entry->first );
-            firstTile.push_back( nTiles );
-            nTiles += ( sizes[i] + COUNT_TILE - 1 ) / COUNT_TILE;
-        }
-    }
-    firstTile.push_back( nTiles );
-    const bool find = ranks != nullptr;
-    for ( uint32_t i = 0; i < n; ++i ) results[i] = find ? FIND_NONE : 0;
-    if ( nTiles == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][queries][results]; device only: [tile counts] behind them */
-    const uint64_t nResults = find ? n : spans.size();
-    const uint64_t tilesAt = 0, queriesAt = tilesAt + nTiles * sizeof( CountTile );
-    const uint64_t resultsAt = queriesAt + ( find ? n * sizeof( FindQuery ) : 0 );
-    const uint64_t countsAt = resultsAt + nResults * sizeof( uint64_t ), bytes = countsAt + nTiles * sizeof( uint32_t );
-    const uint64_t cap = std::max( 2 * c->dSelect.capacity, bytes );
-    /* the previous call's lists have been consumed (every call waits for its kernels) */
-    HIP_TRY( c, c->hSelect.grow( c, countsAt, cap, cap ) );
-    HIP_TRY( c, c->dSelect.grow( c, bytes, cap, cap ) );
-    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSelect.bytes + tilesAt );
-    auto* const hQueries = reinterpret_cast<FindQuery*>( c->hSelect.bytes + queriesAt );
-    auto* const hResults = reinterpret_cast<uint64_t*>( c->hSelect.bytes + resultsAt );
-    uint64_t tile = 0;
-    for ( size_t s = 0; s < spans.size(); ++s ) {
-        for ( uint64_t k = 0; k < spans[s].second; k += COUNT_TILE ) {
-            hTiles[tile++] = { spans[s].first + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].second - k ), (uint32_t)s };
-        }
-    }
-    for ( uint32_t i = 0; find && i < n; ++i ) {
-        hQueries[i] = { ranks[i], (uint32_t)firstTile[spanOf[i]], (uint32_t)( firstTile[spanOf[i] + 1] - firstTile[spanOf[i]] ) };
-    }
-    uint8_t* const d = c->dSelect.bytes;
-    HIP_TRY( c, hipMemcpyAsync( d, c->hSelect.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    if ( !find ) HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, nResults * sizeof( uint64_t ), c->stream ) );
-    const uint32_t pattern = 0x01010101u * value;
-    hipLaunchKernelGGL( k_count_byte, dim3( (uint32_t)nTiles ), dim3( COUNT_THREADS ), 0, c->stream,
-                        reinterpret_cast<const CountTile*>( d + tilesAt ), c->dOut, pattern,
-                        reinterpret_cast<uint32_t*>( d + countsAt ),
-                        find ? nullptr : reinterpret_cast<unsigned long long*>( d + resultsAt ) );
-    HIP_TRY( c, hipGetLastError() );
-    if ( find ) {
-        hipLaunchKernelGGL( k_find_byte, dim3( n ), dim3( FIND_THREADS ), 0, c->stream,
-                            reinterpret_cast<const FindQuery*>( d + queriesAt ), reinterpret_cast<const CountTile*>( d + tilesAt ),
-                            reinterpret_cast<const uint32_t*>( d + countsAt ), c->dOut, pattern,
-                            reinterpret_cast<uint64_t*>( d + resultsAt ) );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    HIP_TRY( c, hipMemcpyAsync( hResults, d + resultsAt, nResults * sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    for ( uint32_t i = 0; i < n; ++i ) results[i] = find ? hResults[i] : hResults[spanOf[i]];
-    return MI355X_BZ2_OK;
-}
-
-/**
- * mi355x_bz2_rank_byte: the distinct spans are cut into tiles and counted as in selectBytes; the positions are sorted
- * span by span and grouped by tile, and k_rank_byte runs one wave per tile that holds a position.  A position at a
- * span's first byte is answered here (0); a position at a tile's first byte is the end of the tile in front of it, so
- * that a position at the span's end needs no tile behind the span.
- */
-constexpr uint64_t RANK_LIST_DOUBLING = 64ull << 20;
-
-int
-rankBytes( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, uint32_t n, uint8_t value, uint64_t* ranks )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = "rank_byte: a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    std::map<std::pair<uint64_t, uint64_t>, uint32_t> known;
-    std::vector<std::pair<uint64_t, uint64_t> > spans;
-    std::vector<uint64_t> firstTile;
-    struct Asked { uint64_t tile; uint32_t end, input; };   /* tile in the list, bytes of it in front of the position */
-    std::vector<Asked> asked;
-    asked.reserve( n );
-    uint64_t nTiles = 0;
-    /* nothing is written before every query has passed */
-    for ( uint32_t i = 0; i < n; ++i ) {
-        const auto& q = queries[i];
-        if ( q.size > c->outSize || q.offset > c->outSize - q.size || q.position < q.offset || q.position - q.offset > q.size ) {
-            c->lastError = "rank_byte: query " + std::to_string( i )
-                           + " names a span outside the last batch's output, or a position outside its span";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-    }
-    for ( uint32_t i = 0; i < n; ++i ) {
-        const auto& q = queries[i];
-        const auto [entry, isNew] = known.emplace( std::make_pair( q.offset, q.size ), (uint32_t)spans.size() );
-        if ( isNew ) {
-            spans.push_back( entry->first );
-            firstTile.push_back( nTiles );
-            nTiles += ( q.size + COUNT_TILE - 1 ) / COUNT_TILE;
-        }
-        ranks[i] = 0;
-        const uint64_t in = q.position - q.offset;
-        if ( in == 0 ) continue;
-        asked.push_back( { firstTile[entry->second] + ( in - 1 ) / COUNT_TILE, (uint32_t)( ( in - 1 ) % COUNT_TILE ) + 1, i } );
-    }
-    if ( asked.empty() ) return MI355X_BZ2_OK;
-    if ( nTiles > 0x7FFFFFFFu ) {
-        c->lastError = "rank_byte: too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    std::sort( asked.begin(), asked.end(), [] ( const Asked& a, const Asked& b ) {
-        return a.tile != b.tile ? a.tile < b.tile : a.end < b.end;
-    } );
-    uint64_t nWork = 0;
-    for ( size_t k = 0; k < asked.size(); ++k ) nWork += k == 0 || asked[k].tile != asked[k - 1].tile ? 1 : 0;
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][tiles with queries][ends, padded to 8 bytes][ranks]; device only: [tile counts] behind */
-    const uint64_t nAsked = asked.size();
-    const uint64_t tilesAt = 0, workAt = tilesAt + nTiles * sizeof( CountTile ), endsAt = workAt + nWork * sizeof( RankTile );
-    const uint64_t resultsAt = endsAt + ( ( nAsked + 1 ) & ~uint64_t( 1 ) ) * sizeof( uint32_t );
-    const uint64_t countsAt = resultsAt + nAsked * sizeof( uint64_t ), bytes = countsAt + nTiles * sizeof( uint32_t );
-    /* the lists of this call can be orders of magnitude larger than the other byte calls' (12 bytes per position, and a
-     * search hands over millions): a need of up to RANK_LIST_DOUBLING doubles the device buffer as the other calls do, a
-     * larger one gets the need and an eighth.  One capacity for both buffers, derived from the device's, which holds
-     * all the host's holds and the tile counts: it is at least `bytes`, and the host needs `countsAt` < `bytes` */
-    const uint64_t cap = bytes <= RANK_LIST_DOUBLING ? std::max( 2 * c->dSelect.capacity, bytes ) : bytes + bytes / 8;
-    /* the previous call's lists have been consumed (every call waits for its kernels) */
-    HIP_TRY( c, c->hSelect.grow( c, countsAt, cap, cap ) );
-    HIP_TRY( c, c->dSelect.grow( c, bytes, cap, cap ) );
-    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSelect.bytes + tilesAt );
-    auto* const hWork = reinterpret_cast<RankTile*>( c->hSelect.bytes + workAt );
-    auto* const hEnds = reinterpret_cast<uint32_t*>( c->hSelect.bytes + endsAt );
-    auto* const hResults = reinterpret_cast<uint64_t*>( c->hSelect.bytes + resultsAt );
-    uint64_t tile = 0;
-    std::vector<uint32_t> spanOfTile( nTiles );
-    for ( size_t s = 0; s < spans.size(); ++s ) {
-        for ( uint64_t k = 0; k < spans[s].second; k += COUNT_TILE ) {
-            spanOfTile[tile] = (uint32_t)s;
-            hTiles[tile++] = { spans[s].first + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].second - k ), (uint32_t)s };
-        }
-    }
-    uint64_t work = 0;
-    for ( size_t k = 0; k < asked.size(); ++k ) {
-        if ( k == 0 || asked[k].tile != asked[k - 1].tile ) {
-            hWork[work++] = { (uint32_t)asked[k].tile, (uint32_t)firstTile[spanOfTile[asked[k].tile]], (uint32_t)k, 0 };
-        }
-        ++hWork[work - 1].nQueries;
-        hEnds[k] = asked[k].end;
-    }
-    if ( ( nAsked & 1 ) != 0 ) hEnds[nAsked] = 0;
-    uint8_t* const d = c->dSelect.bytes;
-    HIP_TRY( c, hipMemcpyAsync( d, c->hSelect.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    const uint32_t pattern = 0x01010101u * value;
-    hipLaunchKernelGGL( k_count_byte, dim3( (uint32_t)nTiles ), dim3( COUNT_THREADS ), 0, c->stream,
-                        reinterpret_cast<const CountTile*>( d + tilesAt ), c->dOut, pattern,
-                        reinterpret_cast<uint32_t*>( d + countsAt ), nullptr );
-    HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( k_rank_byte, dim3( (uint32_t)nWork ), dim3( FIND_THREADS ), 0, c->stream,
-                        reinterpret_cast<const RankTile*>( d + workAt ), reinterpret_cast<const CountTile*>( d + tilesAt ),
-                        reinterpret_cast<const uint32_t*>( d + countsAt ), reinterpret_cast<const uint32_t*>( d + endsAt ),
-                        c->dOut, pattern, reinterpret_cast<uint64_t*>( d + resultsAt ) );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( hResults, d + resultsAt, nAsked * sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    for ( size_t k = 0; k < asked.size(); ++k ) ranks[asked[k].input] = hResults[k];
-    return MI355X_BZ2_OK;
-}
-
-static_assert( SEARCH_IGNORE_CASE == MI355X_BZ2_SEARCH_IGNORE_CASE, "the planner's flag is the C ABI's" );
-
-/** True, with lastError set, if `flags` has a bit that no search knows.  The caller holds the context's mutex. */
-bool
-unknownSearchFlags( mi355x_bz2_ctx* c, const char* what, uint32_t flags )
-{
-    if ( ( flags & ~SEARCH_KNOWN_FLAGS ) == 0 ) return false;
-    char bits[16];
-    std::snprintf( bits, sizeof( bits ), "0x%X", flags & ~SEARCH_KNOWN_FLAGS );
-    c->lastError = std::string( what ) + ": unknown flag bits " + bits;
-    return true;
-}
-
-/**
- * Both string calls.  The start positions every span allows are cut into tiles (spans in caller order, a span given twice
- * is searched twice: its positions are wanted twice), k_count_bytes counts every tile and adds to its span's counter, and
- * the counts -- with the seam bytes of `seam`, if given -- come back in one D2H.  With positions wanted, min( total,
- * capacity ) of them are then made room for on the device (a failure to allocate fails the call), k_scan_tiles turns the
- * tile counts into places, k_emit_bytes writes the positions and a second D2H brings them to `positions`, or to `grown`
- * resized to their number.  With MI355X_BZ2_SEARCH_IGNORE_CASE in `flags` the pattern is uploaded under foldAscii and the
- * folding instantiations of the two kernels run; the seam bytes come back raw.
- */
-int
-searchBytes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-             uint32_t m, uint32_t flags, bool wantPositions, uint64_t capacity, uint64_t* positions,
-             std::vector<uint64_t>* grown, uint64_t* counts, const mi355x_bz2_byte_span* seam, uint8_t* seamBytes )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( unknownSearchFlags( c, what, flags ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    const bool fold = ( flags & SEARCH_IGNORE_CASE ) != 0;
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    if ( m == 0 || m > SEARCH_MAX_PATTERN ) {
-        c->lastError = std::string( what ) + ": the pattern must have 1 to " + std::to_string( SEARCH_MAX_PATTERN ) + " bytes";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    const auto inside = [c] ( const mi355x_bz2_byte_span& span ) {
-        return span.size <= c->outSize && span.offset <= c->outSize - span.size;
-    };
-    uint64_t nTiles = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( !inside( spans[i] ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        counts[i] = 0;
-        if ( spans[i].size >= m ) nTiles += ( spans[i].size - m + 1 + SEARCH_TILE - 1 ) / SEARCH_TILE;
-    }
-    if ( seam != nullptr && !inside( *seam ) ) {
-        c->lastError = std::string( what ) + ": the seam span lies outside the last batch's output";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    const uint32_t seamN = seam != nullptr ? (uint32_t)std::min<uint64_t>( m - 1, seam->size ) : 0u;
-    if ( grown != nullptr ) grown->clear();
-    if ( nTiles == 0 && seamN == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][pattern][span counts][seam bytes]; device only: [tile counts][tile places] behind them */
-    const uint64_t patternAt = nTiles * sizeof( CountTile ), resultsAt = patternAt + SEARCH_MAX_PATTERN;
-    const uint64_t seamAt = resultsAt + n * sizeof( uint64_t ), countsAt = seamAt + 2 * SEARCH_MAX_PATTERN;
-    const uint64_t placesAt = countsAt + ( ( nTiles * sizeof( uint32_t ) + 7 ) & ~uint64_t( 7 ) );
-    const uint64_t bytes = placesAt + nTiles * sizeof( uint64_t );
-    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
-    /* the previous call's lists have been consumed (every call waits for its kernels) */
-    HIP_TRY( c, c->hSearch.grow( c, countsAt, cap, cap ) );
-    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
-    auto* const hTiles = reinterpret_cast<CountTile*>( c->hSearch.bytes );
-    uint64_t tile = 0;
-    for ( uint32_t s = 0; s < n; ++s ) {
-        if ( spans[s].size < m ) continue;
-        const uint64_t starts = spans[s].size - m + 1;
-        for ( uint64_t k = 0; k < starts; k += SEARCH_TILE ) {
-            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( SEARCH_TILE, starts - k ), s };
-        }
-    }
-    std::memset( c->hSearch.bytes + patternAt, 0, SEARCH_MAX_PATTERN );
-    for ( uint32_t j = 0; j < m; ++j ) c->hSearch.bytes[patternAt + j] = fold ? foldAscii( pattern[j] ) : pattern[j];
-    uint8_t* const d = c->dSearch.bytes;
-    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
-    auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
-    HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( fold ? k_count_bytes<true> : k_count_bytes<false>, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ),
-                            0, c->stream, dTiles, c->dOut, d + patternAt, m, dTileCounts,
-                            reinterpret_cast<unsigned long long*>( d + resultsAt ) );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    if ( seamN > 0 ) {
-        hipLaunchKernelGGL( k_seam_bytes, dim3( 1 ), dim3( 2 * SEARCH_MAX_PATTERN ), 0, c->stream, c->dOut, seam->offset,
-                            seam->size, seamN, d + seamAt );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    HIP_TRY( c, hipMemcpyAsync( c->hSearch.bytes + resultsAt, d + resultsAt, countsAt - resultsAt, hipMemcpyDeviceToHost,
-                                c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    uint64_t total = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        counts[i] = reinterpret_cast<const uint64_t*>( c->hSearch.bytes + resultsAt )[i];
-        total += counts[i];
-    }
-    if ( seamN > 0 ) {
-        std::memcpy( seamBytes, c->hSearch.bytes + seamAt, seamN );
-        std::memcpy( seamBytes + SEARCH_MAX_PATTERN, c->hSearch.bytes + seamAt + SEARCH_MAX_PATTERN, seamN );
-    }
-    const uint64_t wanted = wantPositions ? std::min( total, capacity ) : 0;
-    if ( wanted == 0 ) return MI355X_BZ2_OK;
-
-    if ( grown != nullptr ) {
-        try {
-            grown->resize( wanted );
-        } catch ( const std::exception& ) {
-            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " positions";
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-        positions = grown->data();
-    }
-    const uint64_t need = wanted * sizeof( uint64_t );
-    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
-    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
-    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
-    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
-    HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( fold ? k_emit_bytes<true> : k_emit_bytes<false>, dim3( (uint32_t)nTiles ), dim3( SEARCH_THREADS ), 0,
-                        c->stream, dTiles, c->dOut, d + patternAt, m, dPlaces, wanted, dPositions );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, need, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    return MI355X_BZ2_OK;
-}
-
-/**
- * Both set calls: searchBytes for a set of patterns.  The start positions every span allows for the shortest pattern are
- * cut into tiles that carry their span's end, k_count_set counts the pairs of every tile, of every span and of every
- * pattern, and the counts -- with the seam bytes of `seam`, if given: min( m_max - 1, size ) each -- come back in one
- * D2H.  With pairs wanted, k_scan_tiles and k_emit_set write min( total, capacity ) positions and ids, which a second D2H
- * brings to `positions` and `ids`, or to `grownPositions` and `grownIds` resized to their number.  perPattern (may be
- * null) receives the count of every pattern over all spans.  A set made with fold gets its image under foldAscii and the
- * folding instantiations of the two kernels.
- */
-int
-searchBytesSet( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const PatternSet& set,
-                bool wantPairs, uint64_t capacity, uint64_t* positions, uint32_t* ids, std::vector<uint64_t>* grownPositions,
-                std::vector<uint32_t>* grownIds, uint64_t* counts, uint64_t* perPattern, const mi355x_bz2_byte_span* seam,
-                uint8_t* seamBytes )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    const auto inside = [c] ( const mi355x_bz2_byte_span& span ) {
-        return span.size <= c->outSize && span.offset <= c->outSize - span.size;
-    };
-    const uint32_t k = set.count(), mMin = set.mMin;
-    const bool fold = set.fold;
-    uint64_t nTiles = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( !inside( spans[i] ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        counts[i] = 0;
-        if ( spans[i].size >= mMin ) nTiles += ( spans[i].size - mMin + 1 + SEARCH_TILE - 1 ) / SEARCH_TILE;
-    }
-    if ( seam != nullptr && !inside( *seam ) ) {
-        c->lastError = std::string( what ) + ": the seam span lies outside the last batch's output";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    const uint32_t seamN = seam != nullptr ? seamLength( set.mMax, seam->size ) : 0u;
-    if ( perPattern != nullptr ) std::fill_n( perPattern, k, uint64_t( 0 ) );
-    if ( grownPositions != nullptr ) grownPositions->clear();
-    if ( grownIds != nullptr ) grownIds->clear();
-    if ( nTiles == 0 && seamN == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][set image, at a multiple of 16][span counts][pattern counts][seam bytes]; device only:
-     * [tile counts][tile places] behind them */
-    const uint64_t imageAt = ( nTiles * sizeof( SetTile ) + 15 ) & ~uint64_t( 15 ), resultsAt = imageAt + SET_IMAGE_BYTES;
-    const uint64_t eachAt = resultsAt + n * sizeof( uint64_t ), seamAt = eachAt + k * sizeof( uint64_t );
-    const uint64_t countsAt = seamAt + 2 * SEARCH_MAX_PATTERN;
-    const uint64_t placesAt = countsAt + ( ( nTiles * sizeof( uint32_t ) + 7 ) & ~uint64_t( 7 ) );
-    const uint64_t bytes = placesAt + nTiles * sizeof( uint64_t );
-    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
-    /* the previous call's lists have been consumed (every call waits for its kernels) */
-    HIP_TRY( c, c->hSearch.grow( c, countsAt, cap, cap ) );
-    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
-    auto* const hTiles = reinterpret_cast<SetTile*>( c->hSearch.bytes );
-    uint64_t tile = 0;
-    for ( uint32_t s = 0; s < n; ++s ) {
-        if ( spans[s].size < mMin ) continue;
-        const uint64_t starts = spans[s].size - mMin + 1;
-        for ( uint64_t at = 0; at < starts; at += SEARCH_TILE ) {
-            hTiles[tile++] = { spans[s].offset + at, spans[s].offset + spans[s].size,
-                               (uint32_t)std::min<uint64_t>( SEARCH_TILE, starts - at ), s };
-        }
-    }
-    writeSetImage( set, c->hSearch.bytes + imageAt, fold );
-    uint8_t* const d = c->dSearch.bytes;
-    const auto* const dTiles = reinterpret_cast<const SetTile*>( d );
-    auto* const dTileCounts = reinterpret_cast<uint32_t*>( d + countsAt );
-    const auto nBytes = (uint32_t)set.bytes.size();
-    const auto groups = (uint32_t)std::min<uint64_t>( ( nTiles + SET_WAVES - 1 ) / SET_WAVES, SET_MAX_GROUPS );
-    HIP_TRY( c, hipMemcpyAsync( d, c->hSearch.bytes, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    HIP_TRY( c, hipMemsetAsync( d + resultsAt, 0, countsAt - resultsAt, c->stream ) );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( fold ? k_count_set<true> : k_count_set<false>, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
-                            d + imageAt, nBytes, k, dTileCounts, reinterpret_cast<unsigned long long*>( d + resultsAt ),
-                            reinterpret_cast<unsigned long long*>( d + eachAt ) );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    if ( seamN > 0 ) {
-        hipLaunchKernelGGL( k_seam_bytes, dim3( 1 ), dim3( 2 * SEARCH_MAX_PATTERN ), 0, c->stream, c->dOut, seam->offset,
-                            seam->size, seamN, d + seamAt );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    HIP_TRY( c, hipMemcpyAsync( c->hSearch.bytes + resultsAt, d + resultsAt, countsAt - resultsAt, hipMemcpyDeviceToHost,
-                                c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    uint64_t total = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        counts[i] = reinterpret_cast<const uint64_t*>( c->hSearch.bytes + resultsAt )[i];
-        total += counts[i];
-    }
-    if ( perPattern != nullptr ) std::memcpy( perPattern, c->hSearch.bytes + eachAt, k * sizeof( uint64_t ) );
-    if ( seamN > 0 ) {
-        std::memcpy( seamBytes, c->hSearch.bytes + seamAt, seamN );
-        std::memcpy( seamBytes + SEARCH_MAX_PATTERN, c->hSearch.bytes + seamAt + SEARCH_MAX_PATTERN, seamN );
-    }
-    const uint64_t wanted = wantPairs ? std::min( total, capacity ) : 0;
-    if ( wanted == 0 ) return MI355X_BZ2_OK;
-
-    if ( grownPositions != nullptr ) {
-        try {
-            grownPositions->resize( wanted );
-            grownIds->resize( wanted );
-        } catch ( const std::exception& ) {
-            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " pairs";
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-        positions = grownPositions->data();
-        ids = grownIds->data();
-    }
-    /* the positions, then the ids */
-    const uint64_t idsAt = wanted * sizeof( uint64_t ), need = idsAt + wanted * sizeof( uint32_t );
-    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
-    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
-    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
-    auto* const dIds = reinterpret_cast<uint32_t*>( c->dSearchPositions.bytes + idsAt );
-    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dTileCounts, (uint32_t)nTiles, dPlaces );
-    HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( fold ? k_emit_set<true> : k_emit_set<false>, dim3( groups ), dim3( SET_THREADS ), 0, c->stream, dTiles, (uint32_t)nTiles, c->dOut,
-                        d + imageAt, nBytes, k, dPlaces, wanted, dPositions, dIds );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, idsAt, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipMemcpyAsync( ids, dIds, wanted * sizeof( uint32_t ), hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    return MI355X_BZ2_OK;
-}
-
-static_assert( REGEX_STATES == REGEX_MAX_STATES && REGEX_CHUNK == REGEX_CHUNK_BYTES, "the kernels' constants are the compiler's" );
-
-/**
- * mi355x_bz2_match_lines and the reader's launches.  Every span is cut into tiles of COUNT_TILE bytes = REGEX_THREADS
- * chunks; k_regex_chunks summarises every chunk, k_regex_link -- one workgroup per span -- gives the chunks their entry
- * states and head hits and writes the spans' summaries and counts, which come back in one D2H.  With positions wanted,
- * k_scan_tiles turns the chunk counts into places, k_regex_emit writes min( total, capacity ) witnesses and a second D2H
- * brings them to `positions`, or to `grown` resized to their number.  An empty span has the identity for its headMap.
- */
-int
-matchLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, const Regex& regex, uint8_t nl,
-            uint8_t* headMaps, uint8_t* hasDelimiter, uint8_t* exitStates, bool wantPositions, uint64_t capacity,
-            uint64_t* positions, std::vector<uint64_t>* grown, uint64_t* counts )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    if ( regex.n < 2 || regex.n > REGEX_MAX_STATES || regex.transitions.size() != (size_t)regex.n * 256
-         || regex.acceptsAtEnd.size() != regex.n ) {
-        c->lastError = std::string( what ) + ": not a compiled regular expression";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    uint64_t nTiles = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
-    }
-    if ( grown != nullptr ) grown->clear();
-    if ( n == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles * REGEX_THREADS > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][spans][table][accepts] up, [span maps][span info][span counts] down; device only, behind
-     * them: [chunk maps][chunk info][chunk counts][chunk places] */
-    const uint64_t slots = nTiles * REGEX_THREADS, stride = regexMapStride( regex.n );
-    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
-    const uint64_t spansAt = nTiles * sizeof( CountTile ), tableAt = aligned( spansAt + n * sizeof( RegexSpan ) );
-    const uint64_t acceptsAt = tableAt + (uint64_t)regex.n * 256, resultsAt = aligned( acceptsAt + REGEX_STATES );
-    const uint64_t spanInfoAt = resultsAt + (uint64_t)n * REGEX_STATES, spanCountsAt = aligned( spanInfoAt + n * sizeof( uint32_t ) );
-    const uint64_t mapsAt = aligned( spanCountsAt + n * sizeof( uint64_t ) ), infoAt = mapsAt + slots * stride;
-    const uint64_t countsAt = infoAt + slots * sizeof( uint32_t ), placesAt = aligned( countsAt + slots * sizeof( uint32_t ) );
-    const uint64_t bytes = placesAt + slots * sizeof( uint64_t );
-    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
-    /* the previous call's lists have been consumed (every call waits for its kernels) */
-    /* the host holds what goes up and comes down, not the per-chunk arrays */
-    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, mapsAt );
-    HIP_TRY( c, c->hSearch.grow( c, mapsAt, hostCap, hostCap ) );
-    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
-    uint8_t* const h = c->hSearch.bytes;
-    auto* const hTiles = reinterpret_cast<CountTile*>( h );
-    auto* const hSpans = reinterpret_cast<RegexSpan*>( h + spansAt );
-    uint64_t tile = 0;
-    for ( uint32_t s = 0; s < n; ++s ) {
-        hSpans[s] = { (uint32_t)( tile * REGEX_THREADS ), (uint32_t)( ( spans[s].size + REGEX_CHUNK - 1 ) / REGEX_CHUNK ) };
-        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
-            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
-        }
-    }
-    std::memcpy( h + tableAt, regex.transitions.data(), (size_t)regex.n * 256 );
-    std::memset( h + acceptsAt, 0, resultsAt - acceptsAt );
-    std::memcpy( h + acceptsAt, regex.acceptsAtEnd.data(), regex.n );
-    uint8_t* const d = c->dSearch.bytes;
-    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
-    auto* const dInfo = reinterpret_cast<uint32_t*>( d + infoAt );
-    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
-    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_regex_chunks, dim3( (uint32_t)nTiles ), dim3( REGEX_THREADS ), 0, c->stream, dTiles, c->dOut,
-                            d + tableAt, d + acceptsAt, regex.n, (uint32_t)nl, d + mapsAt, dInfo, dCounts );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    hipLaunchKernelGGL( k_regex_link, dim3( n ), dim3( REGEX_THREADS ), 0, c->stream,
-                        reinterpret_cast<const RegexSpan*>( d + spansAt ), d + acceptsAt, regex.n, d + mapsAt, dInfo, dCounts,
-                        d + resultsAt, reinterpret_cast<uint32_t*>( d + spanInfoAt ),
-                        reinterpret_cast<unsigned long long*>( d + spanCountsAt ) );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, mapsAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    uint64_t total = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        const uint32_t info = reinterpret_cast<const uint32_t*>( h + spanInfoAt )[i];
-        std::memcpy( headMaps + (size_t)i * REGEX_STATES, h + resultsAt + (size_t)i * REGEX_STATES, REGEX_STATES );
-        hasDelimiter[i] = ( info & REGEX_HAS_DELIMITER ) != 0 ? 1 : 0;
-        exitStates[i] = (uint8_t)( info >> REGEX_EXIT_SHIFT );
-        counts[i] = reinterpret_cast<const uint64_t*>( h + spanCountsAt )[i];
-        total += counts[i];
-    }
-    const uint64_t wanted = wantPositions ? std::min( total, capacity ) : 0;
-    if ( wanted == 0 ) return MI355X_BZ2_OK;
-
-    if ( grown != nullptr ) {
-        try {
-            grown->resize( wanted );
-        } catch ( const std::exception& ) {
-            c->lastError = std::string( what ) + ": no host memory for " + std::to_string( wanted ) + " positions";
-            return MI355X_BZ2_ERR_DEVICE;
-        }
-        positions = grown->data();
-    }
-    const uint64_t need = wanted * sizeof( uint64_t );
-    HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
-    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
-    auto* const dPositions = reinterpret_cast<uint64_t*>( c->dSearchPositions.bytes );
-    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
-    HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( k_regex_emit, dim3( (uint32_t)nTiles ), dim3( REGEX_THREADS ), 0, c->stream, dTiles, c->dOut,
-                        d + tableAt, d + acceptsAt, regex.n, (uint32_t)nl, dInfo, dPlaces, wanted, dPositions );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( positions, dPositions, need, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    return MI355X_BZ2_OK;
-}
-
-static_assert( LINEHASH_CHUNK == LINEHASH_CHUNK_BYTES && LINEHASH_PRIME == LINEHASH_P, "the kernels' constants are the host's" );
-
-/**
- * mi355x_bz2_hash_lines and the reader's launches.  Every span is cut into tiles of COUNT_TILE bytes = LINEHASH_THREADS
- * chunks; k_linehash_chunks summarises every chunk and scans each tile, k_linehash_link -- one workgroup per span --
- * scans the tiles and writes the spans' summaries and counts, which come back in one D2H.  With hashes wanted,
- * k_scan_tiles turns the chunk counts into places and k_linehash_emit writes the hashes of the closed lines [skip,
- * skip + capacity) -- numbered over all spans in caller order -- to dHashes[0, ...), device memory of the caller's.
- */
-int
-hashLines( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t x,
-           mi355x_bz2_line_hash_summary* summaries, uint64_t skip, uint64_t capacity, uint64_t* dHashes )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    uint64_t nTiles = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
-    }
-    if ( n == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles * LINEHASH_THREADS > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][spans] up, [span summaries] down; device only, behind them: [tile summaries]
-     * [chunk prefixes][chunk places][chunk counts] */
-    const uint64_t slots = nTiles * LINEHASH_THREADS;
-    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
-    const uint64_t spansAt = aligned( nTiles * sizeof( CountTile ) ), resultsAt = aligned( spansAt + n * sizeof( LineHashSpan ) );
-    const uint64_t tilesAt = aligned( resultsAt + n * sizeof( LineHashSpanSummary ) );
-    const uint64_t prefixesAt = aligned( tilesAt + nTiles * sizeof( LineHashTile ) );
-    const uint64_t placesAt = prefixesAt + slots * sizeof( ulonglong2 ), countsAt = placesAt + slots * sizeof( uint64_t );
-    const uint64_t bytes = countsAt + slots * sizeof( uint32_t );
-    const uint64_t cap = std::max( 2 * c->dSearch.capacity, bytes );
-    /* the previous call's lists have been consumed (every call waits for its kernels); the host holds what goes up and
-     * comes down, not the per-tile and per-chunk arrays */
-    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, tilesAt );
-    HIP_TRY( c, c->hSearch.grow( c, tilesAt, hostCap, hostCap ) );
-    HIP_TRY( c, c->dSearch.grow( c, bytes, cap, cap ) );
-    uint8_t* const h = c->hSearch.bytes;
-    auto* const hTiles = reinterpret_cast<CountTile*>( h );
-    auto* const hSpans = reinterpret_cast<LineHashSpan*>( h + spansAt );
-    uint64_t tile = 0;
-    for ( uint32_t s = 0; s < n; ++s ) {
-        hSpans[s] = { tile, ( spans[s].size + COUNT_TILE - 1 ) / COUNT_TILE };
-        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
-            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
-        }
-    }
-    uint8_t* const d = c->dSearch.bytes;
-    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
-    auto* const dTileSummaries = reinterpret_cast<LineHashTile*>( d + tilesAt );
-    auto* const dPrefixes = reinterpret_cast<ulonglong2*>( d + prefixesAt );
-    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
-    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_linehash_chunks, dim3( (uint32_t)nTiles ), dim3( LINEHASH_THREADS ), 0, c->stream, dTiles, c->dOut,
-                            x, (uint32_t)nl, dPrefixes, dCounts, dTileSummaries );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    hipLaunchKernelGGL( k_linehash_link, dim3( n ), dim3( LINEHASH_THREADS ), 0, c->stream,
-                        reinterpret_cast<const LineHashSpan*>( d + spansAt ), dTileSummaries,
-                        reinterpret_cast<LineHashSpanSummary*>( d + resultsAt ) );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, tilesAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    uint64_t total = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        const auto& from = reinterpret_cast<const LineHashSpanSummary*>( h + resultsAt )[i];
-        summaries[i] = { from.headH, from.headXl, from.tailH, from.tailXl, from.count,
-                         ( from.info & LINEHASH_HAS_DELIMITER ) != 0 ? 1u : 0u, ( from.info & LINEHASH_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
-        total += from.count;
-    }
-    if ( capacity == 0 || skip >= total || nTiles == 0 ) return MI355X_BZ2_OK;
-
-    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
-    hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
-    HIP_TRY( c, hipGetLastError() );
-    hipLaunchKernelGGL( k_linehash_emit, dim3( (uint32_t)nTiles ), dim3( LINEHASH_THREADS ), 0, c->stream, dTiles, c->dOut, x,
-                        (uint32_t)nl, dPrefixes, dTileSummaries, dPlaces, skip, capacity, dHashes );
-    HIP_TRY( c, hipGetLastError() );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    return MI355X_BZ2_OK;
-}
-
-static_assert( FIELD_CHUNK == FIELD_CHUNK_BYTES && FIELD_NOT_REACHED == FIELD_UNKNOWN, "the kernels' constants are the host's" );
-
-/**
- * mi355x_bz2_field_spans and the reader's launches.  The tiling is hashLines'; k_field_chunks gives every chunk its
- * element and scans each tile, k_field_link -- one workgroup per span -- scans the tiles, k_scan_tiles turns the chunk
- * counts into places, k_field_emit writes starts and ends of field `field` in the closed lines [skip, skip + capacity)
- * -- numbered over all spans in caller order -- to dStarts[0, ...) and dSizes[0, ...), device memory of the caller's, and
- * completes the spans' summaries and head positions, and k_field_sizes turns the ends into sizes.  The kernels queue
- * behind one another and the summaries come back in one D2H behind them.  The first byte of span i counts as offset
- * bases[i] (nullptr: its offset in the output).  k_field_emit runs whatever the capacity: the summaries need it.
- */
-int
-fieldSpans( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, const uint64_t* bases, uint32_t n, uint8_t nl,
-            uint8_t dl, uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* headPositions, uint64_t skip,
-            uint64_t capacity, uint64_t* dStarts, int64_t* dSizes )
-{
-    const std::scoped_lock lock( c->mutex );
-    const auto why = fieldArgumentsError( nl, dl, field );
-    if ( !why.empty() ) {
-        c->lastError = std::string( what ) + ": " + why;
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = std::string( what ) + ": a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    uint64_t nTiles = 0, bytesInSpans = 0;
-    for ( uint32_t i = 0; i < n; ++i ) {
-        if ( !( spans[i].size <= c->outSize && spans[i].offset <= c->outSize - spans[i].size ) ) {
-            c->lastError = std::string( what ) + ": span " + std::to_string( i ) + " lies outside the last batch's output";
-            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-        }
-        nTiles += ( spans[i].size + COUNT_TILE - 1 ) / COUNT_TILE;
-        bytesInSpans += spans[i].size;
-    }
-    if ( n == 0 ) return MI355X_BZ2_OK;
-    if ( nTiles * FIELD_THREADS > 0x7FFFFFFFu ) {
-        c->lastError = std::string( what ) + ": too many spans";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    HIP_TRY( c, hipSetDevice( c->device ) );
-
-    /* host and device: [tiles][spans] up, [span summaries][head positions] down; device only, behind them:
-     * [tile summaries][chunk places][chunk prefixes][chunk counts] */
-    const uint64_t slots = nTiles * FIELD_THREADS, cap = (uint64_t)field + 1;
-    const auto aligned = [] ( uint64_t at ) { return ( at + 15 ) & ~uint64_t( 15 ); };
-    const uint64_t spansAt = aligned( nTiles * sizeof( CountTile ) ), resultsAt = aligned( spansAt + n * sizeof( FieldSpanTiles ) );
-    const uint64_t headsAt = aligned( resultsAt + n * sizeof( FieldSpanSummary ) );
-    const uint64_t tilesAt = aligned( headsAt + n * cap * sizeof( uint64_t ) );
-    const uint64_t placesAt = aligned( tilesAt + nTiles * sizeof( FieldTile ) );
-    const uint64_t prefixesAt = placesAt + slots * sizeof( uint64_t ), countsAt = prefixesAt + slots * sizeof( uint32_t );
-    const uint64_t bytes = countsAt + slots * sizeof( uint32_t );
-    const uint64_t deviceCap = std::max( 2 * c->dSearch.capacity, bytes );
-    const uint64_t hostCap = std::max( 2 * c->hSearch.capacity, tilesAt );
-    HIP_TRY( c, c->hSearch.grow( c, tilesAt, hostCap, hostCap ) );
-    HIP_TRY( c, c->dSearch.grow( c, bytes, deviceCap, deviceCap ) );
-    uint8_t* const h = c->hSearch.bytes;
-    auto* const hTiles = reinterpret_cast<CountTile*>( h );
-    auto* const hSpans = reinterpret_cast<FieldSpanTiles*>( h + spansAt );
-    uint64_t tile = 0;
-    for ( uint32_t s = 0; s < n; ++s ) {
-        hSpans[s] = { tile, ( spans[s].size + COUNT_TILE - 1 ) / COUNT_TILE, bases != nullptr ? bases[s] : spans[s].offset };
-        for ( uint64_t k = 0; k < spans[s].size; k += COUNT_TILE ) {
-            hTiles[tile++] = { spans[s].offset + k, (uint32_t)std::min<uint64_t>( COUNT_TILE, spans[s].size - k ), s };
-        }
-    }
-    uint8_t* const d = c->dSearch.bytes;
-    const auto* const dTiles = reinterpret_cast<const CountTile*>( d );
-    const auto* const dSpans = reinterpret_cast<const FieldSpanTiles*>( d + spansAt );
-    auto* const dSummaries = reinterpret_cast<FieldSpanSummary*>( d + resultsAt );
-    auto* const dTileSummaries = reinterpret_cast<FieldTile*>( d + tilesAt );
-    auto* const dPlaces = reinterpret_cast<uint64_t*>( d + placesAt );
-    auto* const dPrefixes = reinterpret_cast<uint32_t*>( d + prefixesAt );
-    auto* const dCounts = reinterpret_cast<uint32_t*>( d + countsAt );
-    HIP_TRY( c, hipMemcpyAsync( d, h, resultsAt, hipMemcpyHostToDevice, c->stream ) );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_field_chunks, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
-                            (uint32_t)nl, (uint32_t)dl, (uint32_t)cap, dPrefixes, dCounts, dTileSummaries );
-        HIP_TRY( c, hipGetLastError() );
-    }
-    hipLaunchKernelGGL( k_field_link, dim3( n ), dim3( FIELD_THREADS ), 0, c->stream, dSpans, dTileSummaries, dSummaries, field );
-    HIP_TRY( c, hipGetLastError() );
-    if ( nTiles > 0 ) {
-        hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
-        HIP_TRY( c, hipGetLastError() );
-        hipLaunchKernelGGL( k_field_emit, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
-                            (uint32_t)nl, (uint32_t)dl, field, dSpans, dPrefixes, dTileSummaries, dPlaces, dSummaries,
-                            reinterpret_cast<uint64_t*>( d + headsAt ), skip, capacity, dStarts, dSizes );
-        HIP_TRY( c, hipGetLastError() );
-        /* a span closes at most one line per byte */
-        const uint64_t most = std::min( capacity, bytesInSpans );
-        if ( most > 0 ) {
-            const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( most + FIELD_SIZES_THREADS - 1 ) / FIELD_SIZES_THREADS, FIELD_SIZES_BLOCKS );
-            hipLaunchKernelGGL( k_field_sizes, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
-                                skip, capacity, dStarts, dSizes );
-            HIP_TRY( c, hipGetLastError() );
-        }
-    }
-    HIP_TRY( c, hipMemcpyAsync( h + resultsAt, d + resultsAt, tilesAt - resultsAt, hipMemcpyDeviceToHost, c->stream ) );
-    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
-    for ( uint32_t i = 0; i < n; ++i ) {
-        const auto& from = reinterpret_cast<const FieldSpanSummary*>( h + resultsAt )[i];
-        summaries[i] = { from.count, from.firstNl, from.tailStart, from.tailFieldStart, from.tailFieldEnd, from.headDelims,
-                         from.tailDelims, ( from.info & FIELD_HAS_DELIMITER ) != 0 ? 1u : 0u,
-                         ( from.info & FIELD_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
-        if ( headPositions != nullptr ) {
-            std::copy_n( reinterpret_cast<const uint64_t*>( h + headsAt ) + i * cap, std::min<uint64_t>( from.headDelims, cap ),
-                         headPositions + i * cap );
-        }
-    }
-    return MI355X_BZ2_OK;
-}
-
-/** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
-bool
-takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
-         PatternSet* set )
-{
-    const std::scoped_lock lock( c->mutex );
-    if ( unknownSearchFlags( c, what, flags ) ) return false;
-    const auto why = patternSetError( sizes, n );
-    if ( !why.empty() ) {
-        c->lastError = std::string( what ) + ": " + why;
-        return false;
-    }
-    *set = makePatternSet( patterns, sizes, n, ( flags & SEARCH_IGNORE_CASE ) != 0 );
-    return true;
-}
-}  // namespace
-
-int
-mi355x::searchOutputSet( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const bz2gpu::PatternSet& set, uint64_t limit,
-                         std::vector<uint64_t>* positions, std::vector<uint32_t>* ids, uint64_t* count, uint64_t* perPattern,
-                         uint8_t* seamBytes )
-{
-    if ( c == nullptr || count == nullptr || seamBytes == nullptr || ( positions == nullptr ) != ( ids == nullptr )
-         || !patternSetError( set.sizes.data(), set.count() ).empty() ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return searchBytesSet( c, "search_set", &extent, 1, set, positions != nullptr, limit, nullptr, nullptr, positions, ids,
-                           count, perPattern, &extent, seamBytes );
-}
-
-int
-mi355x::searchOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const uint8_t* pattern, uint32_t m,
-                      uint32_t flags, uint64_t limit, std::vector<uint64_t>* positions, uint64_t* count, uint8_t* seamBytes )
-{
-    if ( c == nullptr || pattern == nullptr || count == nullptr || seamBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytes( c, "search", &extent, 1, pattern, m, flags, positions != nullptr, limit, nullptr, positions, count,
-                        &extent, seamBytes );
-}
-
-int
-mi355x::matchLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, const bz2gpu::Regex& regex, uint8_t nl,
-                          uint64_t limit, bz2gpu::StretchSummary* summary )
-{
-    if ( c == nullptr || summary == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    uint8_t hasDelimiter = 0, exitState = 0;
-    summary->witnesses.clear();
-    const int status = matchLines( c, "grep_regex", &extent, 1, regex, nl, summary->headMap.data(), &hasDelimiter, &exitState,
-                                   limit > 0, limit, nullptr, &summary->witnesses, &summary->count );
-    summary->hasDelimiter = hasDelimiter != 0;
-    summary->exit = exitState;
-    return status;
-}
-
-int
-mi355x::hashLinesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint8_t nl, uint64_t x, uint64_t skip,
-                         uint64_t take, uint64_t* dHashes, bz2gpu::HashSummary* summary )
-{
-    if ( c == nullptr || summary == nullptr || ( take > 0 && dHashes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    mi355x_bz2_line_hash_summary s{};
-    const int status = hashLines( c, "line_hashes", &extent, 1, nl, x, &s, skip, take, dHashes );
-    summary->head = { s.head_hash, s.head_xl };
-    summary->tail = { s.tail_hash, s.tail_xl };
-    summary->hasDelimiter = s.has_delimiter != 0;
-    summary->tailNonEmpty = s.tail_non_empty != 0;
-    summary->count = s.count;
-    summary->hashes.clear();
-    return status;
-}
-
-int
-mi355x::fieldSpansOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
-                          uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes,
-                          bz2gpu::FieldSummary* summary )
-{
-    if ( c == nullptr || summary == nullptr || field > FIELD_MAX || ( take > 0 && ( dStarts == nullptr || dSizes == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    mi355x_bz2_field_summary s{};
-    std::vector<uint64_t> heads( (size_t)field + 1 );
-    const int status = fieldSpans( c, "field_spans", &extent, &fileOffset, 1, nl, dl, field, &s, heads.data(), skip, take, dStarts, dSizes );
-    *summary = bz2gpu::emptyFieldSummary( field );
-    if ( status != MI355X_BZ2_OK ) return status;
-    summary->size = extent.size;
-    summary->hasDelimiter = s.has_delimiter != 0;
-    summary->tailNonEmpty = s.tail_non_empty != 0;
-    summary->count = s.count;
-    summary->firstNl = s.first_nl;
-    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
-    summary->headPositions = std::move( heads );
-    summary->tailStart = s.tail_start;
-    summary->tailDelims = s.tail_delims;
-    summary->tailFieldStart = s.tail_field_start;
-    summary->tailFieldEnd = s.tail_field_end;
-    return status;
-}
-
-int
-mi355x::gatherResult( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice )
-{
-    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    const std::scoped_lock lock( c->mutex );
-    return gatherPieces( c, c->result.bytes, c->result.capacity, pieces, nPieces, dst, dstIsDevice );
-}
+#include "bz2_queries.hip.h"   /* gatherPieces ... mi355x_bz2_find_bytes_set */
 
 extern "C" {
-
-int
-mi355x_bz2_gather_output( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst,
-                          int dstIsDevice )
-{
-    if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    const std::scoped_lock lock( c->mutex );
-    if ( c->pendingBlocks != 0 ) {
-        c->lastError = "gather_output: a batch is in flight";
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return gatherPieces( c, c->dOut, c->outSize, pieces, nPieces, dst, dstIsDevice );
-}
-
-int
-mi355x_bz2_count_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t value, uint64_t* counts )
-{
-    if ( c == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    std::vector<uint64_t> offsets( n ), sizes( n );
-    for ( uint32_t i = 0; i < n; ++i ) {
-        offsets[i] = spans[i].offset;
-        sizes[i] = spans[i].size;
-    }
-    return selectBytes( c, "count_byte", value, n, offsets.data(), sizes.data(), nullptr, counts );
-}
-
-int
-mi355x_bz2_find_byte( mi355x_bz2_ctx* c, const mi355x_bz2_byte_query* queries, uint32_t n, uint8_t value,
-                      uint64_t* positions )
-{
-    if ( c == nullptr || ( n > 0 && ( queries == nullptr || positions == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    std::vector<uint64_t> offsets( n ), sizes( n ), ranks( n );
-    for ( uint32_t i = 0; i < n; ++i ) {
-        offsets[i] = queries[i].offset;
-        sizes[i] = queries[i].size;
-        ranks[i] = queries[i].rank;
-    }
-    return selectBytes( c, "find_byte", value, n, offsets.data(), sizes.data(), ranks.data(), positions );
-}
-
-int
-mi355x_bz2_rank_byte( mi355x_bz2_ctx* c, const mi355x_bz2_rank_query* queries, uint32_t n, uint8_t value, uint64_t* ranks )
-{
-    if ( c == nullptr || ( n > 0 && ( queries == nullptr || ranks == nullptr ) ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return rankBytes( c, queries, n, value, ranks );
-}
-
-int
-mi355x_bz2_count_bytes_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-                           uint32_t patternSize, uint32_t flags, uint64_t* counts )
-{
-    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return searchBytes( c, "count_bytes", spans, n, pattern, patternSize, flags, false, 0, nullptr, nullptr, counts, nullptr,
-                        nullptr );
-}
-
-int
-mi355x_bz2_count_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-                        uint32_t patternSize, uint64_t* counts )
-{
-    return mi355x_bz2_count_bytes_ex( c, spans, n, pattern, patternSize, 0, counts );
-}
-
-int
-mi355x_bz2_find_bytes_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-                          uint32_t patternSize, uint32_t flags, uint64_t* positions, uint64_t capacity, uint64_t* counts )
-{
-    if ( c == nullptr || pattern == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
-         || ( capacity > 0 && positions == nullptr ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return searchBytes( c, "find_bytes", spans, n, pattern, patternSize, flags, true, capacity, positions, nullptr, counts,
-                        nullptr, nullptr );
-}
-
-int
-mi355x_bz2_find_bytes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* pattern,
-                       uint32_t patternSize, uint64_t* positions, uint64_t capacity, uint64_t* counts )
-{
-    return mi355x_bz2_find_bytes_ex( c, spans, n, pattern, patternSize, 0, positions, capacity, counts );
-}
-
-int
-mi355x_bz2_match_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const mi355x_bz2_regex* re, uint8_t nl,
-                        uint8_t* headMaps, uint8_t* hasDelimiter, uint8_t* exitStates, uint64_t* positions, uint64_t capacity,
-                        uint64_t* counts )
-{
-    if ( c == nullptr || re == nullptr
-         || ( n > 0 && ( spans == nullptr || headMaps == nullptr || hasDelimiter == nullptr || exitStates == nullptr || counts == nullptr ) )
-         || ( capacity > 0 && positions == nullptr ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return matchLines( c, "match_lines", spans, n, re->dfa, nl, headMaps, hasDelimiter, exitStates, capacity > 0, capacity,
-                       positions, nullptr, counts );
-}
-
-int
-mi355x_bz2_hash_lines( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint64_t seed,
-                       mi355x_bz2_line_hash_summary* summaries, uint64_t* hashesDevice, uint64_t capacity )
-{
-    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) ) || ( capacity > 0 && hashesDevice == nullptr ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return hashLines( c, "hash_lines", spans, n, nl, lineHashBase( seed ), summaries, 0, capacity, hashesDevice );
-}
-
-int
-mi355x_bz2_field_spans( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl, uint32_t field,
-                        mi355x_bz2_field_summary* summaries, uint64_t* headPositions, uint64_t* startsDevice,
-                        int64_t* sizesDevice, uint64_t capacity )
-{
-    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) )
-         || ( capacity > 0 && ( startsDevice == nullptr || sizesDevice == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    return fieldSpans( c, "field_spans", spans, nullptr, n, nl, dl, field, summaries, headPositions, 0, capacity, startsDevice,
-                       sizesDevice );
-}
-
-int
-mi355x_bz2_count_bytes_set_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
-                               const uint32_t* patternSizes, uint32_t nPatterns, uint32_t flags, uint64_t* counts,
-                               uint64_t* perPattern )
-{
-    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    PatternSet set;
-    if ( !takeSet( c, "count_bytes_set", patterns, patternSizes, nPatterns, flags, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytesSet( c, "count_bytes_set", spans, n, set, false, 0, nullptr, nullptr, nullptr, nullptr, counts, perPattern,
-                           nullptr, nullptr );
-}
-
-int
-mi355x_bz2_count_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
-                            const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* counts, uint64_t* perPattern )
-{
-    return mi355x_bz2_count_bytes_set_ex( c, spans, n, patterns, patternSizes, nPatterns, 0, counts, perPattern );
-}
-
-int
-mi355x_bz2_find_bytes_set_ex( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
-                              const uint32_t* patternSizes, uint32_t nPatterns, uint32_t flags, uint64_t* positions,
-                              uint32_t* ids, uint64_t capacity, uint64_t* counts, uint64_t* perPattern )
-{
-    if ( c == nullptr || patterns == nullptr || patternSizes == nullptr || ( n > 0 && ( spans == nullptr || counts == nullptr ) )
-         || ( capacity > 0 && ( positions == nullptr || ids == nullptr ) ) ) {
-        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    }
-    PatternSet set;
-    if ( !takeSet( c, "find_bytes_set", patterns, patternSizes, nPatterns, flags, &set ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
-    return searchBytesSet( c, "find_bytes_set", spans, n, set, true, capacity, positions, ids, nullptr, nullptr, counts,
-                           perPattern, nullptr, nullptr );
-}
-
-int
-mi355x_bz2_find_bytes_set( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, const uint8_t* patterns,
-                           const uint32_t* patternSizes, uint32_t nPatterns, uint64_t* positions, uint32_t* ids,
-                           uint64_t capacity, uint64_t* counts, uint64_t* perPattern )
-{
-    return mi355x_bz2_find_bytes_set_ex( c, spans, n, patterns, patternSizes, nPatterns, 0, positions, ids, capacity, counts,
-                                         perPattern );
-}
 
 int
 mi355x_bz2_debug_copy_stage( mi355x_bz2_ctx* c, uint32_t index, int stage, void* hostDst, uint64_t capacity )

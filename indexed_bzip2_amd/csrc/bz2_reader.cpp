@@ -1828,9 +1828,8 @@ public:
     }
 
     /** mi355x_bz2_reader_line_hashes: the launches of planLineHashes, each hashing its stretch (hashLinesOutput) on the
-     * context that decoded it, straight into the reader's device buffer -- the line index says how many lines every
-     * stretch closes, so every launch knows its place before any has run; then stitchSummaries, and one 8-byte copy for
-     * every line that crosses a seam and for the unterminated tail. */
+     * context that decoded it, straight into the reader's device buffer (runLineColumn); then stitchSummaries, and one
+     * 8-byte copy for every line that crosses a seam and for the unterminated tail. */
     void
     lineHashes( uint8_t nl, uint64_t seed, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
     {
@@ -1848,29 +1847,10 @@ public:
             m_hashes = std::move( held );
             return;
         }
-        /* per stretch: the lines it closes (from the index), which of them are wanted, and where they go */
-        struct Work { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
-        std::vector<Work> works( plan.stretches.size() );
         std::vector<bz2gpu::HashStretch> stretches( plan.stretches.size() );
-        std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
-        const uint64_t wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;   /* but for the tail */
-        uint64_t closedBefore = plan.firstClosed;
-        for ( size_t k = 0; k < works.size(); ++k ) {
-            const auto& piece = plan.stretches[k];
-            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
-            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
-            auto& work = works[k];
-            work.closed = index.lines[to] - index.lines[from];
-            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
-            if ( end > begin ) {
-                work.skip = begin - closedBefore;
-                work.take = end - begin;
-                work.at = begin - first;
-            }
-            closedBefore += work.closed;
-            stretches[k].fileOffset = piece.fileOffset;
-            stretches[k].size = piece.size;
-            ofLaunch[piece.launch].push_back( k );
+        for ( size_t k = 0; k < stretches.size(); ++k ) {
+            stretches[k].fileOffset = plan.stretches[k].fileOffset;
+            stretches[k].size = plan.stretches[k].size;
         }
         std::string why;
         held.device = m_device;
@@ -1878,18 +1858,10 @@ public:
         held.dHashes = static_cast<uint64_t*>( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
         if ( held.dHashes == nullptr ) fail( MI355X_BZ2_ERR_DEVICE, "line_hashes: " + why );
         const uint64_t x = bz2gpu::lineHashBase( seed );
-        runJobs( plan.launches, [&] ( size_t l ) {
-            return [&plan, &works, &stretches, mine = &ofLaunch[l], nl, x, to = held.dHashes] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
-                for ( const auto k : *mine ) {
-                    const auto& piece = plan.stretches[k];
-                    const auto& work = works[k];
-                    checkDevice( ctx, hashLinesOutput( ctx, { piece.src, piece.size }, nl, x, work.skip, work.take, to + work.at,
-                                                       &stretches[k].summary ) );
-                    if ( stretches[k].summary.count != work.closed ) {
-                        failLyingLineIndex( piece.fileOffset, work.closed, stretches[k].summary.count );
-                    }
-                }
-            };
+        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, x, to = held.dHashes]
+                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
+            checkDevice( ctx, hashLinesOutput( ctx, { piece.src, piece.size }, nl, x, work.skip, work.take, to + work.at, &stretches[k].summary ) );
+            return stretches[k].summary.count;
         } );
         /* the first closed line of a stretch is line firstClosed + k of the file */
         std::vector<std::pair<uint64_t, uint64_t> > patches;
@@ -1973,29 +1945,10 @@ public:
             m_fields = std::move( held );
             return;
         }
-        /* per stretch: the lines it closes (from the index), which of them are wanted, and where they go */
-        struct Work { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
-        std::vector<Work> works( plan.stretches.size() );
         std::vector<bz2gpu::FieldStretch> stretches( plan.stretches.size() );
-        std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
-        const uint64_t wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;   /* but for the tail */
-        uint64_t closedBefore = plan.firstClosed;
-        for ( size_t k = 0; k < works.size(); ++k ) {
-            const auto& piece = plan.stretches[k];
-            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
-            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
-            auto& work = works[k];
-            work.closed = index.lines[to] - index.lines[from];
-            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
-            if ( end > begin ) {
-                work.skip = begin - closedBefore;
-                work.take = end - begin;
-                work.at = begin - first;
-            }
-            closedBefore += work.closed;
-            stretches[k].fileOffset = piece.fileOffset;
-            stretches[k].summary.size = piece.size;
-            ofLaunch[piece.launch].push_back( k );
+        for ( size_t k = 0; k < stretches.size(); ++k ) {
+            stretches[k].fileOffset = plan.stretches[k].fileOffset;
+            stretches[k].summary.size = plan.stretches[k].size;
         }
         std::string why;
         held.device = m_device;
@@ -2004,18 +1957,11 @@ public:
         if ( !held.starts || !held.sizes ) fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
         auto* const dStarts = static_cast<uint64_t*>( held.starts.get() );
         auto* const dSizes = static_cast<int64_t*>( held.sizes.get() );
-        runJobs( plan.launches, [&] ( size_t l ) {
-            return [&plan, &works, &stretches, mine = &ofLaunch[l], nl, dl, field, dStarts, dSizes] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
-                for ( const auto k : *mine ) {
-                    const auto& piece = plan.stretches[k];
-                    const auto& work = works[k];
-                    checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, work.skip,
-                                                        work.take, dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
-                    if ( stretches[k].summary.count != work.closed ) {
-                        failLyingLineIndex( piece.fileOffset, work.closed, stretches[k].summary.count );
-                    }
-                }
-            };
+        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, dl, field, dStarts, dSizes]
+                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
+            checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, work.skip, work.take,
+                                                dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
+            return stretches[k].summary.count;
         } );
         /* the first closed line of a stretch is line firstClosed + k of the file */
         std::vector<std::pair<uint64_t, bz2gpu::FieldSpan> > patches;
@@ -2288,6 +2234,44 @@ private:
                 runLineWork( ctx, launch, *work, m_heldBytes );
             };
         } );
+    }
+
+    /** What lineHashes and fieldSpans share, columns with one entry per line: per stretch of `plan` the lines it closes --
+     * the line index says how many, so every launch knows its place before any has run --, which of them are wanted
+     * (skip, take) and where they go (at); then the launches, in which perStretch( ctx, k, stretch, work ) does stretch k on
+     * the context that decoded it and returns the number of lines it found the stretch to close, which has to be the
+     * index's.  Returns the number of wanted lines but for the tail. */
+    struct ColumnWork { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
+
+    template<typename PerStretch>
+    uint64_t
+    runLineColumn( const LineIndex& index, const bz2gpu::LineHashPlan& plan, const PerStretch& perStretch )
+    {
+        std::vector<ColumnWork> works( plan.stretches.size() );
+        std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
+        const uint64_t first = plan.first, wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;
+        uint64_t closedBefore = plan.firstClosed;
+        for ( size_t k = 0; k < works.size(); ++k ) {
+            const auto& piece = plan.stretches[k];
+            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
+            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
+            auto& work = works[k];
+            work.closed = index.lines[to] - index.lines[from];
+            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
+            if ( end > begin ) work = { begin - closedBefore, end - begin, begin - first, work.closed };
+            closedBefore += work.closed;
+            ofLaunch[piece.launch].push_back( k );
+        }
+        runJobs( plan.launches, [&] ( size_t l ) {
+            return [&plan, &works, &perStretch, mine = &ofLaunch[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+                for ( const auto k : *mine ) {
+                    const auto& piece = plan.stretches[k];
+                    const uint64_t counted = perStretch( ctx, k, piece, works[k] );
+                    if ( counted != works[k].closed ) failLyingLineIndex( piece.fileOffset, works[k].closed, counted );
+                }
+            };
+        } );
+        return wantedClosed;
     }
 
     /** The line index for `nl`: the one the reader holds, or a new one.  The block map is completed first if it has to
