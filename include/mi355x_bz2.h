@@ -450,6 +450,34 @@ int mi355x_bz2_field_spans( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spa
                             uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* head_positions,
                             uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
 
+/* The hash of field `field` of every line: the KEY of a line is mi355x_bz2_line_hash's hash (same seed, same base) of
+ * content.split( dl )[field], the field mi355x_bz2_field_spans finds; a line with fewer fields has the key
+ * MI355X_BZ2_FIELD_MISSING = 2^61 - 1, the hash's modulus, which no hash takes; an empty field is present and hashes
+ * to 0.  "Equal key" stands for "equal field" with the collision bound of mi355x_bz2_line_hash.
+ *   _field_hashes     over spans as for _field_spans, with the same refusals before anything is launched.  Per span i,
+ *                     summaries[i] holds _field_spans' summary, head_hash / head_xl / tail_hash / tail_xl as
+ *                     _hash_lines' summary, and tail_start_hash, tail_end_hash = the hash of the bytes from tail_start up
+ *                     to tail_field_start and to tail_field_end, where those are reached; head_hashes[i * ( field + 1 )
+ *                     + k], k < head_delims, is the hash of the span's bytes in front of head_positions[...] (host
+ *                     memory, room for n * ( field + 1 ) each; may be NULL).  hashes_device[] (uint64, DEVICE memory, room
+ *                     for `capacity`) receives the keys of the closed lines in _field_spans' order, the first `capacity`
+ *                     of them; starts_device[] and sizes_device[] receive what _field_spans writes, or are both NULL.
+ *                     The first closed line of a span is computed as if the span were entered at a line start
+ *                     (bz2_fieldhash.hpp: stitchFieldHashes).  The call returns when everything is written.
+ *                     k_field_chunks, k_field_link, k_linehash_chunks, k_linehash_link, k_scan_tiles, k_fieldhash_emit,
+ *                     k_fieldhash_finish. */
+#define MI355X_BZ2_FIELD_MISSING 0x1FFFFFFFFFFFFFFFull
+typedef struct mi355x_bz2_field_hash_summary
+{
+    uint64_t count, first_nl, tail_start, tail_field_start, tail_field_end;
+    uint64_t head_hash, head_xl, tail_hash, tail_xl, tail_start_hash, tail_end_hash;
+    uint32_t head_delims, tail_delims, has_delimiter, tail_non_empty;
+} mi355x_bz2_field_hash_summary;
+int mi355x_bz2_field_hashes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl,
+                             uint32_t field, uint64_t seed, mi355x_bz2_field_hash_summary* summaries, uint64_t* head_positions,
+                             uint64_t* head_hashes, uint64_t* hashes_device, uint64_t* starts_device, int64_t* sizes_device,
+                             uint64_t capacity );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -790,6 +818,34 @@ int mi355x_bz2_reader_take_distinct_lines( mi355x_bz2_reader* r, uint64_t* line_
 int mi355x_bz2_reader_field_spans( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
                                    int keep_on_device, uint64_t* n_lines );
 int mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* sizes, uint64_t capacity, int dst_is_device );
+
+/* ---- field hashes and groups (mi355x_bz2_field_hashes says what the key of a line is).
+ *   _field_hashes     the keys of lines [first, first + count), count clipped at the last line; *n_lines = their number.
+ *                     Refusals, line index, launches, residency and failure rules are _field_spans': every needed block
+ *                     is decoded once per call, each launch runs mi355x_bz2_field_hashes' kernels on the context that
+ *                     decoded its blocks, straight into three device buffers of the reader's (keys, starts, sizes)
+ *                     allocated before anything is launched, and the host stitches the launches' summaries and patches
+ *                     one key and one span per seam and for the tail.  Keys and spans are held until the next
+ *                     _field_hashes or _field_groups or the close.  Positionless; releases line ranges held by earlier
+ *                     calls.
+ *   _take_field_hashes  the first min( capacity, n_lines ) held keys (uint64 each) to `dst`, host memory or, with
+ *                     dst_is_device, device memory; they stay held.
+ *   _field_groups     the lines [first, first + count) grouped by key: _field_hashes, then on the GPU a stable radix sort
+ *                     (rocPRIM) of (key, line) over 61 bits, a flag on the first element of every run, the run starts
+ *                     selected, and per run its length, its first line and that line's field span; the run of
+ *                     MI355X_BZ2_FIELD_MISSING is dropped and its length is *n_missing; the others, *n_groups of them,
+ *                     are sorted by first line.  32 bytes per group come to the host and nothing per line.  Nothing of
+ *                     _field_hashes stays held; the groups are held until the next call of this family or the close.
+ *   _take_field_groups  of the first min( capacity, n_groups ) held groups, ascending by first line: lines[] = the first
+ *                     line (numbered in the file), counts[] = the number of lines with that key, starts[] / sizes[] = the
+ *                     field in that first line.  Any of the four may be NULL. */
+int mi355x_bz2_reader_field_hashes( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first,
+                                    uint64_t count, int keep_on_device, uint64_t* n_lines );
+int mi355x_bz2_reader_take_field_hashes( mi355x_bz2_reader* r, void* dst, uint64_t capacity, int dst_is_device );
+int mi355x_bz2_reader_field_groups( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first,
+                                    uint64_t count, uint64_t* n_groups, uint64_t* n_missing );
+int mi355x_bz2_reader_take_field_groups( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts,
+                                         int64_t* sizes, uint64_t capacity );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

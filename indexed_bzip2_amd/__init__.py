@@ -21,7 +21,9 @@ of at most L bytes collide for at most L of the 2^61 bases a seed selects, and a
 And what a line holds: field_spans and field_spans_to_tensor say where field j of every line lies when the line is split at
 a delimiter byte exactly as bytes.split splits it (size -1 where a line has fewer fields), read_fields and
 read_fields_to_tensor bring those bytes and nothing else (`cut -f`, `awk -F`); there is no quoting or escaping, this is not
-a CSV parser.
+a CSV parser.  And how often each value of a column occurs: field_hashes and field_hashes_to_tensor give the hash of
+field j of every line (FIELD_MISSING, 2^61 - 1, where a line has no such field), count_by_field groups the lines by it on
+the GPU and value_counts adds the values (`cut -f3 | sort | uniq -c | sort -rn`).
 """
 __version__ = "0.1.0"
 
@@ -34,8 +36,8 @@ import os as _os
 # existing setting wins
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from ._native import (Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib, line_hash,  # noqa: F401
-                      plan_compress_blocks, status_string, warmup)
+from ._native import (FIELD_MISSING, Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib,  # noqa: F401
+                      line_hash, plan_compress_blocks, status_string, warmup)
 from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
                       decompress_many_to_tensor)
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401

@@ -199,6 +199,14 @@ SYMBOLS = [
     ("mi355x_bz2_reader_field_spans", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
                                                       ctypes.c_uint64, ctypes.c_int, _u64p]),
     ("mi355x_bz2_reader_take_field_spans", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_field_hashes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
+                                                ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_field_hashes", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                                                       ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_take_field_hashes", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_reader_field_groups", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                                                       ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_field_groups", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -432,6 +440,18 @@ class FieldSummary(ctypes.Structure):
 def field_chunk_bytes():
     """The bytes of a span that one GPU lane walks in field_spans (mi355x_bz2_field_chunk_bytes)."""
     return int(lib().mi355x_bz2_field_chunk_bytes())
+
+
+FIELD_MISSING = 2**61 - 1      # MI355X_BZ2_FIELD_MISSING: the key of a line that has no such field
+
+
+class FieldHashSummary(ctypes.Structure):
+    """mi355x_bz2_field_hash_summary"""
+    _fields_ = [("count", ctypes.c_uint64), ("first_nl", ctypes.c_uint64), ("tail_start", ctypes.c_uint64),
+                ("tail_field_start", ctypes.c_uint64), ("tail_field_end", ctypes.c_uint64), ("head_hash", ctypes.c_uint64),
+                ("head_xl", ctypes.c_uint64), ("tail_hash", ctypes.c_uint64), ("tail_xl", ctypes.c_uint64),
+                ("tail_start_hash", ctypes.c_uint64), ("tail_end_hash", ctypes.c_uint64), ("head_delims", ctypes.c_uint32),
+                ("tail_delims", ctypes.c_uint32), ("has_delimiter", ctypes.c_uint32), ("tail_non_empty", ctypes.c_uint32)]
 
 
 def pattern_set(patterns, check=True):
@@ -865,6 +885,78 @@ class Decoder:
                         "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
                         "tail_non_empty": bool(s.tail_non_empty)})
         return out, starts[:room], sizes[:room]
+
+    def field_hashes(self, spans, field, delimiter=b"\t", newline=b"\n", seed=0, capacity=None, room=None):
+        """k_field_chunks, k_field_link, k_linehash_chunks, k_linehash_link, k_scan_tiles, k_fieldhash_emit,
+        k_fieldhash_finish: field_spans with the key of the field beside its span -> (summaries, keys, starts, sizes).  A
+        summary is field_spans' dict with head and tail as (h, xl) of hash_lines, head_hashes (one per head position: the
+        hash of the span's bytes in front of it) and tail_start_hash, tail_end_hash (None where the tail's field does not
+        reach them).  keys is a numpy uint64 array shaped and filled like starts and sizes: `room` values that were all
+        ones before the call, of which the call may write the first `capacity`."""
+        import numpy as np
+        nl, dl = bytes(newline), bytes(delimiter)
+        if len(nl) != 1 or len(dl) != 1:
+            raise ValueError("newline and delimiter must be exactly one byte each")
+        field = int(field)
+        if field < 0 or field > 1023:
+            raise ValueError("field must be between 0 and 1023")
+        if nl == dl:
+            raise ValueError("delimiter and newline must differ")
+        seed = int(seed)
+        if seed < 0 or seed >= 2**64:
+            raise ValueError("seed must not be negative and must fit 64 bits")
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        summaries = (FieldHashSummary * max(1, len(spans)))()
+        heads = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
+        head_hashes = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
+
+        def call(keys, starts, sizes, capacity):
+            self._check(lib().mi355x_bz2_field_hashes(self._h, arr, len(spans), nl[0], dl[0], field, seed, summaries,
+                                                      heads.ctypes.data, head_hashes.ctypes.data, keys, starts, sizes, capacity))
+        if capacity is None:
+            call(None, None, None, 0)
+            capacity = sum(s.count for s in summaries[:len(spans)])
+        room = capacity if room is None else max(int(room), capacity)
+        keys = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
+        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
+        hip = ctypes.CDLL("libamdhip64.so")
+        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        hip.hipFree.argtypes = [ctypes.c_void_p]
+        device = ctypes.c_void_p()
+        if hip.hipMalloc(ctypes.byref(device), 3 * keys.nbytes) != 0:
+            raise Bz2Error(101, f"field_hashes: no device memory for {3 * keys.nbytes} bytes")
+        try:
+            columns = [(keys, device), (starts, ctypes.c_void_p(device.value + keys.nbytes)),
+                       (sizes, ctypes.c_void_p(device.value + 2 * keys.nbytes))]
+            for host, pointer in columns:
+                if hip.hipMemcpy(pointer, host.ctypes.data, host.nbytes, 1) != 0:       # hipMemcpyHostToDevice
+                    raise Bz2Error(101, "field_hashes: the copy to the device failed")
+            call(columns[0][1], columns[1][1], columns[2][1], capacity)
+            for host, pointer in columns:
+                if hip.hipMemcpy(host.ctypes.data, pointer, host.nbytes, 2) != 0:       # hipMemcpyDeviceToHost
+                    raise Bz2Error(101, "field_hashes: the copy from the device failed")
+        finally:
+            hip.hipFree(device)
+        none = 2**64 - 1
+        out = []
+        for i, s in enumerate(summaries[:len(spans)]):
+            at = i * (field + 1)
+            out.append({"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
+                        "first_nl": None if s.first_nl == none else int(s.first_nl),
+                        "head_positions": [int(v) for v in heads[at:at + s.head_delims]],
+                        "head_hashes": [int(v) for v in head_hashes[at:at + s.head_delims]],
+                        "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
+                        "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
+                        "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
+                        "tail_start_hash": None if s.tail_field_start == none else int(s.tail_start_hash),
+                        "tail_end_hash": None if s.tail_field_end == none else int(s.tail_end_hash),
+                        "head": (int(s.head_hash), int(s.head_xl)), "tail": (int(s.tail_hash), int(s.tail_xl)),
+                        "tail_non_empty": bool(s.tail_non_empty)})
+        return out, keys[:room], starts[:room], sizes[:room]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/mi355x_bz2.h"
+#include "bz2_fieldhash.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_regex.hpp"
@@ -73,6 +74,14 @@ int hashLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, ui
 int fieldSpansOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
                       uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes, bz2gpu::FieldSummary* summary );
 
+/** The reader's field-hash pass in one launch: mi355x_bz2_field_hashes with `extent` as its one span, whose first byte is
+ * offset `fileOffset` of the decoded file, and the base x instead of the seed.  *summary receives the extent's summary
+ * and the count of the lines it closes, none of them listed; key, start and size of the field in its closed lines [skip,
+ * skip + take) go to dKeys[0, ...), dStarts[0, ...) and dSizes[0, ...), device memory, the starts as offsets in the file. */
+int fieldHashesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                       uint32_t field, uint64_t x, uint64_t skip, uint64_t take, uint64_t* dKeys, uint64_t* dStarts, int64_t* dSizes,
+                       bz2gpu::FieldHashSummary* summary );
+
 /** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
  * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies
  * to device memory instead. */
@@ -86,6 +95,20 @@ bool hostToDevice( int device, void* dst, const void* src, uint64_t bytes, std::
  * fails; every buffer is allocated before the pass that fills it. */
 bool distinctHashes( int device, const uint64_t* dHashes, uint64_t n, uint64_t* nDistinct, std::vector<uint64_t>* numbers,
                      std::string* error );
+
+/** One group of lines with the same key: its first line, its size, and the field in that first line. */
+struct FieldGroup
+{
+    uint64_t line{ 0 }, count{ 0 }, start{ 0 };
+    int64_t size{ 0 };
+};
+
+/** The lines 0 .. n - 1 grouped by dKeys[0, n), with dStarts / dSizes their fields (device memory, left as it is):
+ * *groups = one FieldGroup per distinct key but `missing`, ascending by first line; *nMissing = the lines with the key
+ * `missing`.  False with *error set if an allocation or a launch fails; every buffer is allocated before the pass that
+ * fills it. */
+bool groupHashes( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t missing,
+                  std::vector<FieldGroup>* groups, uint64_t* nMissing, std::string* error );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

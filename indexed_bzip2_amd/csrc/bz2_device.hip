@@ -33,6 +33,7 @@
 #include "bz2_regex.hip.h"
 #include "bz2_linehash.hip.h"
 #include "bz2_fields.hip.h"
+#include "bz2_fieldhash.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -43,6 +44,7 @@
 #include "bz2_regex.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_fields.hpp"
+#include "bz2_fieldhash.hpp"
 
 using namespace bz2gpu;
 

@@ -8,6 +8,15 @@
  *   k_flag_runs       flags[i] = i == 0 || hash[i] != hash[i - 1], and the number of flags (one atomic per workgroup)
  *   rocPRIM           with the numbers wanted: select the flagged line numbers, sort them ascending
  *
+ * and the groups of the lines of a range by the key of a field (mi355x_bz2_reader_field_groups), with the same sort:
+ *
+ *   rocPRIM           the stable sort of ( key, line ) and k_flag_runs as above; select the flagged POSITIONS: run starts
+ *   k_group_runs      per run: its length (to the next run's start), its first line (stability: the run's first element),
+ *                     that line's field span gathered from the span column; the last run's length goes aside if its key
+ *                     is the one that stands for a missing field, the largest 61-bit value
+ *   rocPRIM           sort ( first line, run ) ascending
+ *   k_group_order     the groups in that order, 32 bytes each, for the one D2H
+ *
  * The null stream and buffers of the call's own: it comes when the reader's launches are through.  Every buffer is
  * allocated before the pass that fills it, so that a failed allocation loses no result.
  */
@@ -15,6 +24,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_select.hpp>
+#include <rocprim/iterator/counting_iterator.hpp>
 
 #include <algorithm>
 #include <cstdint>
@@ -50,10 +60,37 @@ k_flag_runs( const uint64_t* __restrict__ sorted, uint64_t n, uint8_t* __restric
     if ( threadIdx.x == 0 && inBlock != 0 ) atomicAdd( count, (unsigned long long)inBlock );
 }
 
+/** One lane per run of equal keys in the sorted column; runStarts ascend. */
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_group_runs( const uint64_t* __restrict__ runStarts, uint64_t nRuns, uint64_t n, const uint64_t* __restrict__ sortedKeys,
+              const uint64_t* __restrict__ sortedNumbers, const uint64_t* __restrict__ starts, const int64_t* __restrict__ sizes,
+              uint64_t missing, mi355x::FieldGroup* __restrict__ groups, uint64_t* __restrict__ firstLines,
+              uint64_t* __restrict__ runs, unsigned long long* __restrict__ nMissing )
+{
+    const uint64_t r = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( r >= nRuns ) return;
+    const uint64_t begin = runStarts[r], end = r + 1 < nRuns ? runStarts[r + 1] : n;
+    const uint64_t line = sortedNumbers[begin];
+    groups[r] = { line, end - begin, starts[line], sizes[line] };
+    firstLines[r] = line;
+    runs[r] = r;
+    /* the keys ascend and `missing` is the largest there is */
+    if ( r + 1 == nRuns && sortedKeys[begin] == missing ) *nMissing = end - begin;
+}
+
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_group_order( const mi355x::FieldGroup* __restrict__ groups, const uint64_t* __restrict__ order, uint64_t nGroups,
+               mi355x::FieldGroup* __restrict__ ordered )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( i < nGroups ) ordered[i] = groups[order[i]];
+}
+
 /** Device allocations of one call, freed when it returns. */
 struct Buffers
 {
     std::vector<void*> pointers;
+    const char* who{ "distinct_lines" };
 
     ~Buffers()
     {
@@ -67,7 +104,7 @@ struct Buffers
         const hipError_t err = hipMalloc( &raw, bytes > 0 ? bytes : 1 );
         if ( err != hipSuccess ) {
             (void)hipGetLastError();
-            *error = std::string( "distinct_lines: no device memory for " ) + what + " (" + std::to_string( bytes ) + " bytes): "
+            *error = std::string( who ) + ": no device memory for " + what + " (" + std::to_string( bytes ) + " bytes): "
                      + hipGetErrorString( err );
             return false;
         }
@@ -187,6 +224,89 @@ mi355x::distinctHashes( int device, const uint64_t* dHashes, uint64_t n, uint64_
     DISTINCT_TRY( rocprim::select( dTemp2, selectBytes, dSortedNumbers, dFlags, dSelected, dCount + 1, (size_t)n, stream ) );
     DISTINCT_TRY( rocprim::radix_sort_keys( dTemp2, secondSortBytes, dSelected, dAscending, (size_t)count, 0, 64, stream ) );
     DISTINCT_TRY( hipMemcpyAsync( numbers->data(), dAscending, count * 8, hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    return true;
+}
+
+bool
+mi355x::groupHashes( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t missing,
+                     std::vector<FieldGroup>* groups, uint64_t* nMissing, std::string* error )
+{
+    static_assert( sizeof( FieldGroup ) == 32, "32 bytes per group come to the host" );
+    groups->clear();
+    *nMissing = 0;
+    if ( n == 0 ) return true;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    const hipStream_t stream = nullptr;
+    const uint32_t blocks = (uint32_t)( ( n + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS );
+    if ( (uint64_t)blocks * DISTINCT_THREADS < n ) {
+        *error = "field_groups: too many lines";
+        return false;
+    }
+
+    Buffers buffers;
+    buffers.who = "field_groups";
+    uint64_t *dNumbers = nullptr, *dSortedKeys = nullptr, *dSortedNumbers = nullptr;
+    uint8_t* dFlags = nullptr;
+    unsigned long long* dCount = nullptr;     /* runs, selected, lines with a missing field */
+    void* dTemp = nullptr;
+    size_t sortBytes = 0, selectBytes = 0;
+    const rocprim::counting_iterator<uint64_t> positions( 0 );
+    DISTINCT_TRY( rocprim::radix_sort_pairs( nullptr, sortBytes, dKeys, dSortedKeys, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+    DISTINCT_TRY( rocprim::select( nullptr, selectBytes, positions, dFlags, dNumbers, dCount + 1, (size_t)n, stream ) );
+    if ( !buffers.get( &dNumbers, n * 8, "the line numbers", error ) || !buffers.get( &dSortedKeys, n * 8, "the sorted keys", error )
+         || !buffers.get( &dSortedNumbers, n * 8, "the sorted line numbers", error ) || !buffers.get( &dFlags, n, "the flags", error )
+         || !buffers.get( &dCount, 3 * sizeof( unsigned long long ), "the counts", error )
+         || !buffers.get( &dTemp, std::max( sortBytes, selectBytes ), "the sort", error ) ) {
+        return false;
+    }
+    DISTINCT_TRY( hipMemsetAsync( dCount, 0, 3 * sizeof( unsigned long long ), stream ) );
+    hipLaunchKernelGGL( k_iota, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dNumbers, n );
+    DISTINCT_TRY( hipGetLastError() );
+    DISTINCT_TRY( rocprim::radix_sort_pairs( dTemp, sortBytes, dKeys, dSortedKeys, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+    hipLaunchKernelGGL( k_flag_runs, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dSortedKeys, n, dFlags, dCount );
+    DISTINCT_TRY( hipGetLastError() );
+    /* the run starts go where the unsorted numbers were */
+    uint64_t* const dRunStarts = dNumbers;
+    DISTINCT_TRY( rocprim::select( dTemp, selectBytes, positions, dFlags, dRunStarts, dCount + 1, (size_t)n, stream ) );
+    unsigned long long nRuns = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &nRuns, dCount, sizeof( nRuns ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+
+    FieldGroup *dGroups = nullptr, *dOrdered = nullptr;
+    uint64_t *dFirstLines = nullptr, *dRuns = nullptr, *dSortedLines = nullptr, *dOrder = nullptr;
+    void* dTemp2 = nullptr;
+    size_t orderBytes = 0;
+    DISTINCT_TRY( rocprim::radix_sort_pairs( nullptr, orderBytes, dFirstLines, dSortedLines, dRuns, dOrder, (size_t)nRuns, 0, 64, stream ) );
+    if ( !buffers.get( &dGroups, nRuns * sizeof( FieldGroup ), "the groups", error )
+         || !buffers.get( &dOrdered, nRuns * sizeof( FieldGroup ), "the ordered groups", error )
+         || !buffers.get( &dFirstLines, nRuns * 8, "the first lines", error ) || !buffers.get( &dRuns, nRuns * 8, "the runs", error )
+         || !buffers.get( &dSortedLines, nRuns * 8, "the sorted first lines", error )
+         || !buffers.get( &dOrder, nRuns * 8, "the order", error ) || !buffers.get( &dTemp2, orderBytes, "the second sort", error ) ) {
+        return false;
+    }
+    const uint32_t runBlocks = (uint32_t)( ( nRuns + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS );
+    hipLaunchKernelGGL( k_group_runs, dim3( runBlocks ), dim3( DISTINCT_THREADS ), 0, stream, dRunStarts, (uint64_t)nRuns, n, dSortedKeys,
+                        dSortedNumbers, dStarts, dSizes, missing, dGroups, dFirstLines, dRuns, dCount + 2 );
+    DISTINCT_TRY( hipGetLastError() );
+    unsigned long long missingLines = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &missingLines, dCount + 2, sizeof( missingLines ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    *nMissing = missingLines;
+    /* the run of the missing key is the last one: the groups are the runs in front of it */
+    const uint64_t nGroups = nRuns - ( missingLines != 0 ? 1 : 0 );
+    if ( nGroups == 0 ) return true;
+    try {
+        groups->resize( (size_t)nGroups );
+    } catch ( const std::exception& ) {
+        *error = "field_groups: no host memory for " + std::to_string( nGroups ) + " groups";
+        return false;
+    }
+    DISTINCT_TRY( rocprim::radix_sort_pairs( dTemp2, orderBytes, dFirstLines, dSortedLines, dRuns, dOrder, (size_t)nGroups, 0, 64, stream ) );
+    hipLaunchKernelGGL( k_group_order, dim3( (uint32_t)( ( nGroups + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS ) ), dim3( DISTINCT_THREADS ),
+                        0, stream, dGroups, dOrder, nGroups, dOrdered );
+    DISTINCT_TRY( hipGetLastError() );
+    DISTINCT_TRY( hipMemcpyAsync( groups->data(), dOrdered, nGroups * sizeof( FieldGroup ), hipMemcpyDeviceToHost, stream ) );
     DISTINCT_TRY( hipStreamSynchronize( stream ) );
     return true;
 }

@@ -1,6 +1,6 @@
 /**
  * bz2_queries.hip.h -- the host side of the calls that read a finished batch's output: gather, count / find / rank of a
- * byte, search for a string or a set of strings, regular expressions, line hashes and field spans, their
+ * byte, search for a string or a set of strings, regular expressions, line hashes, field spans and field hashes, their
  * mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's translation unit
  * (the context's layout names device record types), included below the context's definition and HIP_TRY.
  *
@@ -748,6 +748,115 @@ fieldSpans( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spa
     return MI355X_BZ2_OK;
 }
 
+static_assert( sizeof( FieldHashTail ) == 16 && FIELDHASH_MISSING == FIELD_MISSING, "the layout's tail hashes; the host's constant" );
+static_assert( FIELD_MISSING == MI355X_BZ2_FIELD_MISSING, "the C ABI's constant" );
+
+/**
+ * mi355x_bz2_field_hashes and the reader's launches.  The tiling is fieldSpans'; k_field_chunks / k_field_link and
+ * k_linehash_chunks / k_linehash_link run as they are, each with its own lists, and the spans' counts and hash summaries
+ * come back: the number of lines says how many prefixes have to be kept.  Then k_scan_tiles, k_fieldhash_emit and
+ * k_fieldhash_finish write keys, starts and sizes of the closed lines [skip, skip + capacity) -- numbered over all spans
+ * in caller order -- to dKeys, dStarts and dSizes, device memory of the caller's (dStarts and dSizes may both be null:
+ * they then lie beside the prefixes in dSearchPositions), and the field summaries, tail hashes, head positions and head
+ * hashes come back in one D2H.  The first byte of span i counts as offset bases[i] (nullptr: its offset in the output).
+ */
+int
+fieldHashes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, const uint64_t* bases, uint32_t n, uint8_t nl,
+             uint8_t dl, uint32_t field, uint64_t x, mi355x_bz2_field_hash_summary* summaries, uint64_t* headPositions,
+             uint64_t* headHashes, uint64_t skip, uint64_t capacity, uint64_t* dKeys, uint64_t* dStarts, int64_t* dSizes )
+{
+    const std::scoped_lock lock( c->mutex );
+    const auto why = fieldArgumentsError( nl, dl, field );
+    if ( !why.empty() ) return refuse( c, what, why );
+    if ( const int status = refuseQuery( c, what, spans, n ) ) return status;
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    const auto firstTile = firstTiles( spans, n, COUNT_TILE, 1 );
+    const uint64_t nTiles = firstTile.back(), slots = nTiles * FIELD_THREADS, cap = (uint64_t)field + 1;
+    if ( slots > 0x7FFFFFFFu ) return refuse( c, what, "too many spans" );
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    const FieldHashLayout l = layFieldHashes( QUERY_SIZES, nTiles, n, field );
+    if ( const int status = growLineStaging( c, l.tileSummariesAt, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    writeCountTiles( at<CountTile>( h, l.tilesAt ), spans, n, COUNT_TILE, 1 );
+    for ( uint32_t s = 0; s < n; ++s ) {
+        const uint64_t base = bases != nullptr ? bases[s] : spans[s].offset;
+        at<FieldSpanTiles>( h, l.spansAt )[s] = { firstTile[s], firstTile[s + 1] - firstTile[s], base };
+        at<LineHashSpan>( h, l.hashSpansAt )[s] = { firstTile[s], firstTile[s + 1] - firstTile[s] };
+    }
+    const auto* const dTiles = at<const CountTile>( d, l.tilesAt );
+    const auto* const dSpans = at<const FieldSpanTiles>( d, l.spansAt );
+    auto* const dSummaries = at<FieldSpanSummary>( d, l.resultsAt );
+    auto* const dTileSummaries = at<FieldTile>( d, l.tileSummariesAt );
+    auto* const dHashTiles = at<LineHashTile>( d, l.hashTilesAt );
+    auto* const dPlaces = at<uint64_t>( d, l.placesAt );
+    auto* const dHashPrefixes = at<ulonglong2>( d, l.hashPrefixesAt );
+    auto* const dPrefixes = at<uint32_t>( d, l.prefixesAt );
+    auto* const dCounts = at<uint32_t>( d, l.countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, h, l.resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    /* the tail of a span that no event reaches starts, for field 0, at its first byte with hash 0 */
+    HIP_TRY( c, hipMemsetAsync( d + l.tailsAt, 0, l.headsAt - l.tailsAt, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_field_chunks, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, (uint32_t)cap, dPrefixes, dCounts, dTileSummaries );
+        HIP_TRY( c, hipGetLastError() );
+        hipLaunchKernelGGL( k_linehash_chunks, dim3( (uint32_t)nTiles ), dim3( LINEHASH_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            x, (uint32_t)nl, dHashPrefixes, at<uint32_t>( d, l.hashCountsAt ), dHashTiles );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_field_link, dim3( n ), dim3( FIELD_THREADS ), 0, c->stream, dSpans, dTileSummaries, dSummaries, field );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_linehash_link, dim3( n ), dim3( LINEHASH_THREADS ), 0, c->stream, at<const LineHashSpan>( d, l.hashSpansAt ),
+                        dHashTiles, at<LineHashSpanSummary>( d, l.hashSummariesAt ) );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( h + l.hashSummariesAt, d + l.hashSummariesAt, l.tailsAt - l.hashSummariesAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    uint64_t total = 0;
+    for ( uint32_t i = 0; i < n; ++i ) total += at<const LineHashSpanSummary>( h, l.hashSummariesAt )[i].count;
+    const uint64_t wanted = total > skip ? std::min( capacity, total - skip ) : 0;
+
+    if ( nTiles > 0 ) {
+        /* P( start ) per wanted line, and starts and sizes where the caller wants none */
+        const bool ownSpans = dStarts == nullptr || dSizes == nullptr;
+        const uint64_t need = wanted * sizeof( uint64_t ) * ( ownSpans ? 3 : 1 );
+        HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
+        auto* const dPStarts = at<uint64_t>( c->dSearchPositions.bytes, 0 );
+        if ( ownSpans ) {
+            dStarts = dPStarts + wanted;
+            dSizes = reinterpret_cast<int64_t*>( dPStarts + 2 * wanted );
+        }
+        hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+        HIP_TRY( c, hipGetLastError() );
+        hipLaunchKernelGGL( k_fieldhash_emit, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut, x,
+                            (uint32_t)nl, (uint32_t)dl, field, dSpans, dPrefixes, dTileSummaries, dHashPrefixes, dHashTiles, dPlaces,
+                            dSummaries, at<FieldHashTail>( d, l.tailsAt ), at<uint64_t>( d, l.headsAt ),
+                            at<uint64_t>( d, l.headHashesAt ), skip, wanted, dStarts, dSizes, dPStarts, dKeys );
+        HIP_TRY( c, hipGetLastError() );
+        if ( wanted > 0 ) {
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( wanted + FIELD_SIZES_THREADS - 1 ) / FIELD_SIZES_THREADS, FIELD_SIZES_BLOCKS );
+            hipLaunchKernelGGL( k_fieldhash_finish, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
+                                skip, wanted, x, dStarts, dSizes, dPStarts, dKeys );
+            HIP_TRY( c, hipGetLastError() );
+        }
+    }
+    HIP_TRY( c, hipMemcpyAsync( h + l.resultsAt, d + l.resultsAt, l.tileSummariesAt - l.resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& from = at<const FieldSpanSummary>( h, l.resultsAt )[i];
+        const auto& hashes = at<const LineHashSpanSummary>( h, l.hashSummariesAt )[i];
+        const auto& tail = at<const FieldHashTail>( h, l.tailsAt )[i];
+        summaries[i] = { from.count, from.firstNl, from.tailStart, from.tailFieldStart, from.tailFieldEnd,
+                         hashes.headH, hashes.headXl, hashes.tailH, hashes.tailXl, tail.startHash, tail.endHash, from.headDelims,
+                         from.tailDelims, ( from.info & FIELD_HAS_DELIMITER ) != 0 ? 1u : 0u,
+                         ( from.info & FIELD_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
+        const uint64_t listed = std::min<uint64_t>( from.headDelims, cap );
+        if ( headPositions != nullptr ) std::copy_n( at<const uint64_t>( h, l.headsAt ) + i * cap, listed, headPositions + i * cap );
+        if ( headHashes != nullptr ) std::copy_n( at<const uint64_t>( h, l.headHashesAt ) + i * cap, listed, headHashes + i * cap );
+    }
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -841,6 +950,42 @@ mi355x::fieldSpansOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent,
     summary->tailDelims = s.tail_delims;
     summary->tailFieldStart = s.tail_field_start;
     summary->tailFieldEnd = s.tail_field_end;
+    return status;
+}
+
+int
+mi355x::fieldHashesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                           uint32_t field, uint64_t x, uint64_t skip, uint64_t take, uint64_t* dKeys, uint64_t* dStarts,
+                           int64_t* dSizes, bz2gpu::FieldHashSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr || field > FIELD_MAX
+         || ( take > 0 && ( dKeys == nullptr || dStarts == nullptr || dSizes == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    mi355x_bz2_field_hash_summary s{};
+    std::vector<uint64_t> heads( (size_t)field + 1 ), headHashes( (size_t)field + 1 );
+    const int status = fieldHashes( c, "field_hashes", &extent, &fileOffset, 1, nl, dl, field, x, &s, heads.data(), headHashes.data(),
+                                    skip, take, dKeys, dStarts, dSizes );
+    *summary = bz2gpu::emptyFieldHashSummary( field );
+    if ( status != MI355X_BZ2_OK ) return status;
+    auto& f = summary->fields;
+    f.size = extent.size;
+    f.hasDelimiter = s.has_delimiter != 0;
+    f.tailNonEmpty = s.tail_non_empty != 0;
+    f.count = s.count;
+    f.firstNl = s.first_nl;
+    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
+    headHashes.resize( heads.size() );
+    f.headPositions = std::move( heads );
+    f.tailStart = s.tail_start;
+    f.tailDelims = s.tail_delims;
+    f.tailFieldStart = s.tail_field_start;
+    f.tailFieldEnd = s.tail_field_end;
+    summary->headHashes = std::move( headHashes );
+    summary->head = { s.head_hash, s.head_xl };
+    summary->tail = { s.tail_hash, s.tail_xl };
+    summary->tailStartHash = s.tail_start_hash;
+    summary->tailEndHash = s.tail_end_hash;
     return status;
 }
 
@@ -963,6 +1108,19 @@ mi355x_bz2_field_spans( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, ui
     }
     return fieldSpans( c, "field_spans", spans, nullptr, n, nl, dl, field, summaries, headPositions, 0, capacity, startsDevice,
                        sizesDevice );
+}
+
+int
+mi355x_bz2_field_hashes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl, uint32_t field,
+                         uint64_t seed, mi355x_bz2_field_hash_summary* summaries, uint64_t* headPositions, uint64_t* headHashes,
+                         uint64_t* hashesDevice, uint64_t* startsDevice, int64_t* sizesDevice, uint64_t capacity )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) ) || ( capacity > 0 && hashesDevice == nullptr )
+         || ( startsDevice == nullptr ) != ( sizesDevice == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return fieldHashes( c, "field_hashes", spans, nullptr, n, nl, dl, field, lineHashBase( seed ), summaries, headPositions, headHashes,
+                        0, capacity, hashesDevice, startsDevice, sizesDevice );
 }
 
 int

@@ -156,4 +156,25 @@ layFields( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field )
              r.add( n * ( field + 1 ) * 8, 16 ), r.add( nTiles * s.fieldTile, 16 ), r.add( slots * 8, 16 ), r.add( slots * 4 ),
              r.add( slots * 4 ), r.size() };
 }
+
+/* field_hashes for field `field`: field_spans' and hash_lines' lists side by side, since both first passes run as they
+ * are: [tiles][field spans][hash spans] up, [field summaries][hash summaries][tail hashes, 16 bytes per span]
+ * [head positions][head hashes, field + 1 per span each] down; [field tile summaries][hash tile summaries][chunk places]
+ * [hash prefixes][field prefixes][field counts][hash counts] */
+struct FieldHashLayout
+{
+    uint64_t tilesAt, spansAt, hashSpansAt, resultsAt, hashSummariesAt, tailsAt, headsAt, headHashesAt, tileSummariesAt,
+             hashTilesAt, placesAt, hashPrefixesAt, prefixesAt, countsAt, hashCountsAt, bytes;
+};
+inline FieldHashLayout
+layFieldHashes( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field )
+{
+    const uint64_t slots = nTiles * s.chunksPerTile;
+    Regions r;
+    return { r.add( nTiles * s.countTile ), r.add( n * s.fieldSpan, 16 ), r.add( n * s.lineHashSpan, 16 ),
+             r.add( n * s.fieldSummary, 16 ), r.add( n * s.lineHashSummary, 16 ), r.add( n * 16, 16 ),
+             r.add( n * ( field + 1 ) * 8, 16 ), r.add( n * ( field + 1 ) * 8, 16 ),
+             r.add( nTiles * s.fieldTile, 16 ), r.add( nTiles * s.lineHashTile, 16 ), r.add( slots * 8, 16 ),
+             r.add( slots * s.lineHashPrefix, 16 ), r.add( slots * 4 ), r.add( slots * 4 ), r.add( slots * 4 ), r.size() };
+}
 }  // namespace bz2gpu

@@ -1234,6 +1234,7 @@ public:
         dropHeldLines();
         dropHeldHashes();
         m_fields.reset();
+        dropHeldFieldHashes();
         m_matches.reset();
         m_setMatches.reset();
         m_scheduler.reset();
@@ -1996,6 +1997,121 @@ public:
         }
     }
 
+    /** mi355x_bz2_reader_field_hashes: fieldSpans' launches and places with fieldHashesOutput in place of its pass, a
+     * column of keys beside the two of the spans; then stitchFieldHashes, and one key and one span copied for every line
+     * that crosses a seam and for the unterminated tail. */
+    void
+    fieldHashes( uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first, uint64_t count, bool keepOnDevice,
+                 uint64_t* nLines, const char* what = "field_hashes" )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        dropHeldFieldHashes();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planFields( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
+                                       count, m_batch, packed, m_source->size() );
+        } );
+        *nLines = 0;
+        HeldFieldHashes held;
+        held.first = first;
+        held.spans.onDevice = keepOnDevice;
+        if ( plan.count == 0 ) {
+            m_fieldHashes = std::move( held );
+            return;
+        }
+        std::vector<bz2gpu::FieldHashStretch> stretches( plan.stretches.size() );
+        for ( size_t k = 0; k < stretches.size(); ++k ) {
+            stretches[k].fileOffset = plan.stretches[k].fileOffset;
+            stretches[k].summary.fields.size = plan.stretches[k].size;
+        }
+        std::string why;
+        held.spans.device = m_device;
+        held.keys.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
+        if ( held.keys ) held.spans.starts.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
+        if ( held.spans.starts ) held.spans.sizes.reset( deviceAllocate( m_device, plan.count * sizeof( int64_t ), &why ) );
+        if ( !held.keys || !held.spans.starts || !held.spans.sizes ) fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
+        auto* const dKeys = static_cast<uint64_t*>( held.keys.get() );
+        auto* const dStarts = static_cast<uint64_t*>( held.spans.starts.get() );
+        auto* const dSizes = static_cast<int64_t*>( held.spans.sizes.get() );
+        const uint64_t x = bz2gpu::lineHashBase( seed );
+        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, dl, field, x, dKeys, dStarts, dSizes]
+                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
+            checkDevice( ctx, fieldHashesOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, x, work.skip, work.take,
+                                                 dKeys + work.at, dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
+            return stretches[k].summary.fields.count;
+        } );
+        /* the first closed line of a stretch is line firstClosed + k of the file */
+        std::vector<std::pair<uint64_t, bz2gpu::FieldKey> > patches;
+        const auto stitched = bz2gpu::stitchFieldHashes( stretches, x, dl, field, [&] ( uint64_t k, const bz2gpu::FieldKey& key ) {
+            const uint64_t line = plan.firstClosed + k;
+            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, key );
+        } );
+        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
+        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tail );
+        for ( const auto& [at, key] : patches ) {
+            if ( !hostToDevice( m_device, dKeys + at, &key.key, sizeof( key.key ), &why )
+                 || !hostToDevice( m_device, dStarts + at, &key.field.start, sizeof( key.field.start ), &why )
+                 || !hostToDevice( m_device, dSizes + at, &key.field.size, sizeof( key.field.size ), &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
+            }
+        }
+        held.spans.n = n;
+        *nLines = n;
+        m_fieldHashes = std::move( held );
+    }
+
+    /** mi355x_bz2_reader_take_field_hashes. */
+    void
+    takeFieldHashes( void* keys, uint64_t capacity, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_hashes on a closed reader" );
+        if ( !m_fieldHashes ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_hashes: no field hashes are held (field_hashes first)" );
+        std::string why;
+        const uint64_t bytes = std::min( capacity, m_fieldHashes->spans.n ) * sizeof( uint64_t );
+        if ( !deviceToHost( m_fieldHashes->spans.device, keys, m_fieldHashes->keys.get(), bytes, dstIsDevice, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, "take_field_hashes: " + why );
+        }
+    }
+
+    /** mi355x_bz2_reader_field_groups: fieldHashes over the range, then bz2_distinct.hip's groupHashes. */
+    void
+    fieldGroups( uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first, uint64_t count, uint64_t* nGroups,
+                 uint64_t* nMissing )
+    {
+        uint64_t n = 0;
+        fieldHashes( nl, dl, field, seed, first, count, false, &n, "field_groups" );
+        std::vector<FieldGroup> groups;
+        std::string why;
+        const auto& held = *m_fieldHashes;
+        const bool done = groupHashes( m_device, static_cast<const uint64_t*>( held.keys.get() ),
+                                       static_cast<const uint64_t*>( held.spans.starts.get() ),
+                                       static_cast<const int64_t*>( held.spans.sizes.get() ), n, bz2gpu::FIELD_MISSING, &groups,
+                                       nMissing, &why );
+        dropHeldFieldHashes();
+        if ( !done ) fail( MI355X_BZ2_ERR_DEVICE, why );
+        for ( auto& group : groups ) group.line += first;
+        *nGroups = groups.size();
+        m_fieldGroups = std::move( groups );
+    }
+
+    /** mi355x_bz2_reader_take_field_groups. */
+    void
+    takeFieldGroups( uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_groups on a closed reader" );
+        if ( !m_fieldGroups ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_groups: no groups are held (field_groups first)" );
+        const size_t n = (size_t)std::min<uint64_t>( capacity, m_fieldGroups->size() );
+        for ( size_t i = 0; i < n; ++i ) {
+            const auto& group = ( *m_fieldGroups )[i];
+            if ( lines != nullptr ) lines[i] = group.line;
+            if ( counts != nullptr ) counts[i] = group.count;
+            if ( starts != nullptr ) starts[i] = group.start;
+            if ( sizes != nullptr ) sizes[i] = group.size;
+        }
+    }
+
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
 
     [[nodiscard]] OffsetMap
@@ -2111,6 +2227,21 @@ private:
         int device{ -1 };
         bool onDevice{ false };
     };
+
+    /** The keys of field_hashes beside their spans, in device memory of the reader's own; `first` is the line of keys[0]. */
+    struct HeldFieldHashes
+    {
+        std::unique_ptr<void, HeldFields::Release> keys;
+        HeldFields spans;
+        uint64_t first{ 0 };
+    };
+
+    void
+    dropHeldFieldHashes()
+    {
+        m_fieldHashes.reset();
+        m_fieldGroups.reset();
+    }
 
     void
     dropHeldHashes()
@@ -2445,6 +2576,8 @@ private:
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
     std::optional<HeldHashes> m_hashes;   /* between line_hashes and the next line_hashes / distinct_lines */
     std::optional<HeldFields> m_fields;   /* between field_spans and the next field_spans */
+    std::optional<HeldFieldHashes> m_fieldHashes;             /* between field_hashes and the next call of its family */
+    std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
@@ -2869,6 +3002,41 @@ mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* si
 {
     if ( capacity > 0 && ( starts == nullptr || sizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldSpans( starts, sizes, capacity, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_field_hashes( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first,
+                                uint64_t count, int keepOnDevice, uint64_t* nLines )
+{
+    if ( nLines == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldHashes( nl, dl, field, seed, first, count, keepOnDevice != 0, nLines );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_field_hashes( mi355x_bz2_reader* r, void* keys, uint64_t capacity, int dstIsDevice )
+{
+    if ( capacity > 0 && keys == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldHashes( keys, capacity, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_field_groups( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first,
+                                uint64_t count, uint64_t* nGroups, uint64_t* nMissing )
+{
+    if ( nGroups == nullptr || nMissing == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nGroups = 0;
+    *nMissing = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.fieldGroups( nl, dl, field, seed, first, count, nGroups, nMissing ); } );
+}
+
+int
+mi355x_bz2_reader_take_field_groups( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes,
+                                     uint64_t capacity )
+{
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldGroups( lines, counts, starts, sizes, capacity ); } );
 }
 
 int

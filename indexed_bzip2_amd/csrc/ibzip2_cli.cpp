@@ -45,7 +45,7 @@ struct Options
     bool grepFile{ false }, countMatchesFile{ false }, ignoreCase{ false }, grepRegex{ false };
     bool lineHashes{ false }, countDistinctLines{ false }, hasSeed{ false };
     uint64_t seed{ 0 };
-    bool cutField{ false }, hasFieldDelimiter{ false };
+    bool cutField{ false }, hasFieldDelimiter{ false }, countByField{ false };
     unsigned field{ 0 };
     uint8_t fieldDelimiter{ '\t' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
@@ -123,6 +123,14 @@ printHelp()
         "                                only their bytes are copied to the host.\n"
         "      --field-delimiter arg     With --cut-field: the byte between fields, as itself (',') or as \\t, \\0 or\n"
         "                                \\xHH; not the newline. (default: \\t)\n"
+        "      --count-by-field arg      Print how often every value of field N (as for --cut-field) occurs, one line\n"
+        "                                'count<TAB>value' per distinct value, the most frequent first and values of\n"
+        "                                equal count in the order of their first occurrence (cut -f | sort | uniq -c |\n"
+        "                                sort -rn); lines without the field are not counted. The lines are grouped on\n"
+        "                                the GPU by a hash of the field (--seed chooses its base): distinct values have\n"
+        "                                distinct hashes with overwhelming probability, not with certainty. Only the\n"
+        "                                values' bytes are copied to the host. --field-delimiter applies; this is not a\n"
+        "                                CSV parser.\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -155,6 +163,8 @@ printHelp()
         "  ibzip2-mi355x --count-distinct-lines file.bz2\n\n"
         "Print the third column of a tab-separated file:\n"
         "  ibzip2-mi355x --cut-field 2 file.tsv.bz2\n\n"
+        "Print how often each value of the third column occurs, the most frequent first:\n"
+        "  ibzip2-mi355x --count-by-field 2 file.tsv.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -314,6 +324,15 @@ parseArguments( int argc, char** argv, Options& o )
                 }
                 o.field = (unsigned)field;
                 o.cutField = true;
+            }
+            else if ( name == "count-by-field" ) {
+                uint64_t field = 0;     /* digits only, as --cut-field */
+                if ( !need( value ) || !parseSeed( value.c_str(), field ) || field > 1023 ) {
+                    std::cerr << "Bad value for --count-by-field\n";
+                    return 1;
+                }
+                o.field = (unsigned)field;
+                o.countByField = true;
             }
             else if ( name == "field-delimiter" ) {
                 if ( !need( value ) || !parseByte( value, o.fieldDelimiter ) || o.fieldDelimiter == '\n' ) {
@@ -544,7 +563,13 @@ main( int argc, char** argv )
                      "'--grep-regex', '--count-matches', '--grep-file' or '--count-matches-file'\n";
         return 1;
     }
-    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines ) {
+    if ( o.countByField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
+                             || o.countDistinctLines || o.cutField ) ) {
+        std::cerr << "Option '--count-by-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
+                     "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines' or '--cut-field'\n";
+        return 1;
+    }
+    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines && !o.countByField ) {
         std::cerr << "Option '--seed' needs '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
@@ -554,7 +579,7 @@ main( int argc, char** argv )
                      "'--grep-file', '--count-matches-file', '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
-    if ( o.hasFieldDelimiter && !o.cutField ) {
+    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField ) {
         std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
         return 1;
     }
@@ -699,6 +724,72 @@ main( int argc, char** argv )
             }
             std::cout << text;
             if ( n < WINDOW ) break;
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        return 0;
+    }
+
+    /* likewise an action of its own: the distinct values of one field with their counts, from the reader's field_groups;
+     * the values of the groups come by read_ranges, in windows of groups */
+    if ( o.countByField ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t n = 0, missing = 0;
+        rc = mi355x_bz2_reader_field_groups( reader, '\n', o.fieldDelimiter, o.field, o.seed, 0, ~uint64_t( 0 ), &n, &missing );
+        std::vector<uint64_t> counts( n ), starts( n );
+        std::vector<int64_t> sizes( n );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_field_groups( reader, nullptr, counts.data(), starts.data(), sizes.data(), n );
+        /* the groups ascend by first line: a stable sort by descending count keeps that order among equal counts */
+        std::vector<uint64_t> order( n );
+        for ( uint64_t i = 0; i < n; ++i ) order[i] = i;
+        std::stable_sort( order.begin(), order.end(), [&counts] ( uint64_t a, uint64_t b ) { return counts[a] > counts[b]; } );
+        constexpr uint64_t WINDOW = uint64_t( 1 ) << 20;
+        std::vector<uint64_t> offsets, lengths, got;
+        std::string bytes, text;
+        for ( uint64_t first = 0; rc == MI355X_BZ2_OK && first < n; first += WINDOW ) {
+            const uint64_t m = std::min( WINDOW, n - first );
+            offsets.resize( m );
+            lengths.resize( m );
+            got.resize( m );
+            uint64_t total = 0;
+            for ( uint64_t i = 0; i < m; ++i ) {
+                offsets[i] = starts[order[first + i]];
+                total += lengths[i] = (uint64_t)sizes[order[first + i]];
+            }
+            bytes.resize( total );
+            rc = mi355x_bz2_reader_read_ranges( reader, offsets.data(), lengths.data(), (uint32_t)m, bytes.data(), 0, got.data() );
+            if ( rc != MI355X_BZ2_OK ) break;
+            text.clear();
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < m; ++i ) {
+                text += std::to_string( counts[order[first + i]] );
+                text.push_back( '\t' );
+                text.append( bytes, at, lengths[i] );
+                text.push_back( '\n' );
+                at += lengths[i];
+            }
+            std::cout << text;
         }
         if ( rc != MI355X_BZ2_OK ) {
             const char* detail = mi355x_bz2_reader_last_error( reader );

@@ -744,6 +744,84 @@ class _IndexedBzip2FileParallel:
         _, bounds, data = self._read_fields(field, first, count, delimiter, newline, make)
         return data, torch.from_numpy(bounds)
 
+    # -- field hashes and groups: the KEY of a line is N.line_hash(content.split(delimiter)[field], seed), computed where the
+    # decoded bytes lie; a line with fewer fields has the key N.FIELD_MISSING = 2^61 - 1, which no hash takes, and an
+    # empty field is present and hashes to 0.  "Distinct value" below means "of distinct key", with the collision bound
+    # of line_hashes; a second seed is an independent check.  No quoting, no escaping: `cut -f`, not a CSV parser
+    def _field_hash_arguments(self, field, first, count, delimiter, newline, seed):
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        (seed,), _ = self._u64([seed], "seed")
+        return nl, dl, field, first, count, seed
+
+    def field_hashes(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """The keys of lines [first, first + count) (count None: to the last line; clipped there) -> numpy uint64, one
+        per line: line_hash(content.split(delimiter)[field], seed), or FIELD_MISSING where the line has no such field.
+        Only the blocks that hold those lines are decoded, each once; field and hash are found on the GPU in shared
+        passes and 8 bytes per line come back.  Builds the line index first if the reader does not hold one for
+        `newline`.  Not a CSV parser.  Positionless."""
+        import numpy as np
+        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_hashes(self._h, nl, dl, field, seed, first, count, 0, ctypes.byref(n)))
+        out = np.empty(n.value, dtype=np.uint64)
+        self._check(N.lib().mi355x_bz2_reader_take_field_hashes(self._h, out.ctypes.data if n.value else None, n.value, 0))
+        return out
+
+    def field_hashes_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """field_hashes as a torch.int64 tensor on the reader's device; the keys never pass through the host.  A key is
+        below 2^61 and FIELD_MISSING is 2^61 - 1, so torch.unique, sort and isin order and compare them as they are:
+        join keys for torch.isin."""
+        import torch
+        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
+        torch.cuda.init()
+        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        n = ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_hashes(self._h, nl, dl, field, seed, first, count, 1, ctypes.byref(n)))
+        out = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
+        if n.value:
+            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(out.device).synchronize()
+            self._check(N.lib().mi355x_bz2_reader_take_field_hashes(self._h, ctypes.c_void_p(out.data_ptr()), n.value, 1))
+        return out
+
+    def _field_groups(self, field, first, count, delimiter, newline, seed):
+        """mi355x_bz2_reader_field_groups and its take -> (lines, counts, starts, sizes, missing)."""
+        import numpy as np
+        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
+        n, missing = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_groups(self._h, nl, dl, field, seed, first, count, ctypes.byref(n),
+                                                            ctypes.byref(missing)))
+        lines, counts, starts = (np.empty(n.value, dtype=np.uint64) for _ in range(3))
+        sizes = np.empty(n.value, dtype=np.int64)
+        if n.value:
+            self._check(N.lib().mi355x_bz2_reader_take_field_groups(self._h, lines.ctypes.data, counts.ctypes.data,
+                                                                     starts.ctypes.data, sizes.ctypes.data, n.value))
+        return lines, counts, starts, sizes, missing.value
+
+    def count_by_field(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """Lines [first, first + count) grouped by field `field` (`cut -f | sort | uniq -c`) -> (lines, counts, missing):
+        `lines` (numpy uint64, ascending) holds the file's line number of the first line of every distinct value,
+        `counts` (numpy uint64) how many lines of the range have that value, `missing` the number of lines without such a
+        field: counts.sum() + missing is the number of lines in the range.  field_hashes, then a sort of the keys on the
+        GPU; 32 bytes per distinct value come back and nothing per line.  Not a CSV parser.  Positionless."""
+        lines, counts, _, _, missing = self._field_groups(field, first, count, delimiter, newline, seed)
+        return lines, counts, missing
+
+    def value_counts(self, field, limit=None, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """count_by_field with the values themselves (`cut -f | sort | uniq -c | sort -rn | head`) -> a list of (value
+        bytes, count) by descending count, then by first occurrence, at most `limit` entries (None: all).  The values
+        are fetched by read_ranges over the chosen groups' spans, so only those bytes leave the GPU.  Lines without the
+        field are in no entry.  Not a CSV parser.  Positionless."""
+        import numpy as np
+        limit = self._line_limit(limit)
+        _, counts, starts, sizes, _ = self._field_groups(field, first, count, delimiter, newline, seed)
+        # the groups ascend by first line: a stable sort by descending count keeps that order among equal counts
+        chosen = np.argsort(-counts.astype(np.int64), kind="stable")[:limit]
+        if len(chosen) == 0:
+            return []
+        values = self.read_ranges([(int(starts[i]), int(sizes[i])) for i in chosen])
+        return [(value, int(counts[i])) for value, i in zip(values, chosen)]
+
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
     # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
     # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
@@ -980,6 +1058,22 @@ class IndexedBzip2File(io.BufferedReader):
     def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """See _IndexedBzip2FileParallel.field_spans_to_tensor."""
         return self._open_reader().field_spans_to_tensor(field, first, count, delimiter, newline)
+
+    def field_hashes(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.field_hashes."""
+        return self._open_reader().field_hashes(field, first, count, delimiter, newline, seed)
+
+    def field_hashes_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.field_hashes_to_tensor."""
+        return self._open_reader().field_hashes_to_tensor(field, first, count, delimiter, newline, seed)
+
+    def count_by_field(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.count_by_field."""
+        return self._open_reader().count_by_field(field, first, count, delimiter, newline, seed)
+
+    def value_counts(self, field, limit=None, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.value_counts."""
+        return self._open_reader().value_counts(field, limit, first, count, delimiter, newline, seed)
 
     def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """See _IndexedBzip2FileParallel.read_fields."""
