@@ -11,13 +11,23 @@ decoded and in bits -- comes from arithmetic on the way the streams are stitched
   * the bit offsets inside ONE copy of a stream come from a plain search for the two 48-bit magics (magic_offsets).
 
 The runs (fillers) have byte values of 0x80 and above: no ASCII pattern, folded or not, holds one, and none is a newline.
-VirtualRaw asserts both for every question it answers, so everything is computed from the literal parts alone."""
+VirtualRaw asserts both for every question it answers, so everything is computed from the literal parts alone.
+
+The same holds for the four line queries (regex, line hashes, field spans, field hashes): newlines and delimiters come from
+the literals alone, a hash over a run comes in closed form (fieldhash.run_part), and a regular expression sees a line that
+holds runs with every run cut to RUN_SHRINK bytes.  That last step is exact only under the rule written at
+VirtualRaw.regex_lines; FAR_PATTERNS is the list of patterns the tests use, all inside it."""
+import bisect
 import bz2
 import functools
+import re
 
 import numpy as np
 
 import datagen
+import fieldhash
+import fields
+import linehash
 
 MAGIC_BLOCK = 0x314159265359
 MAGIC_EOS = 0x177245385090
@@ -189,6 +199,199 @@ class VirtualRaw:
         if limit is not None:
             numbers = numbers[:limit]
         return numbers, self.line_ranges([(k, 1) for k in numbers], newline)
+
+    # ---------------------------------------------------------------------------------- lines, hashes, fields, regex
+    # Lines are numbered as line_hashes, field_spans and grep_regex number them: a non-empty unterminated tail is one
+    # more line.  Everything below is arithmetic on the parts; nothing calls the code under test.
+
+    def byte_offsets(self, value):
+        """Every offset that holds byte `value` (not a run's), ascending, as a numpy uint64 array; computed once."""
+        assert 0 <= value < 256 and value not in self.run_values, "a run value is asked for as a delimiter"
+        cache = self.__dict__.setdefault("_byte_offsets", {})
+        if value not in cache:
+            cache[value] = self.newline_offsets(bytes([value]))
+        return cache[value]
+
+    def _within(self, positions, start, end):
+        """positions (sorted) inside [start, end), as Python integers."""
+        lo, hi = np.searchsorted(positions, np.uint64(start), "left"), np.searchsorted(positions, np.uint64(max(start, end)), "left")
+        return [int(p) for p in positions[lo:hi]]
+
+    def line_bounds(self, newline=b"\n"):
+        """[(start, end of content)] of every line."""
+        cache = self.__dict__.setdefault("_line_bounds", {})
+        if newline[0] not in cache:
+            cuts = [int(p) for p in self.byte_offsets(newline[0])]
+            starts = [0] + [c + 1 for c in cuts]
+            bounds = list(zip(starts, cuts))
+            if starts[-1] < self.size:
+                bounds.append((starts[-1], self.size))
+            cache[newline[0]] = bounds
+        return cache[newline[0]]
+
+    def _overlapping(self, start, end):
+        """The parts that overlap [start, end), clipped: (run value or None, bytes or None, lo, hi, part's offset)."""
+        offsets = self.__dict__.setdefault("_part_offsets", [offset for offset, _, _, _ in self.parts])
+        out, k = [], max(0, bisect.bisect_right(offsets, start) - 1)
+        while k < len(self.parts) and self.parts[k][0] < end:
+            offset, value, data, length = self.parts[k]
+            lo, hi = max(start, offset), min(end, offset + length)
+            if lo < hi:
+                out.append((value, data, lo, hi, offset))
+            k += 1
+        return out
+
+    def holds_run(self, start, end):
+        return any(value is not None for value, _, _, _, _ in self._overlapping(start, end))
+
+    def part(self, start, end, x):
+        """(h, xl) of bytes [start, end) under base x: literals by linehash (the hashes of a literal's prefixes computed
+        once per x), runs in closed form by fieldhash.run_part, joined by linehash.followed_by."""
+        prefixes = self.__dict__.setdefault("_prefixes", {})
+        out = (0, 1)
+        for value, data, lo, hi, offset in self._overlapping(start, min(end, self.size)):
+            if data is None:
+                piece = fieldhash.run_part(value, hi - lo, x)
+            elif hi - lo <= 64:
+                piece = linehash.part(data[lo - offset:hi - offset], x)
+            else:
+                if (data, x) not in prefixes:
+                    prefixes[(data, x)] = linehash.Prefix(data, x)
+                piece = prefixes[(data, x)].part(lo - offset, hi - offset)
+            out = linehash.followed_by(out, piece)
+        return out
+
+    def line_hashes(self, newline=b"\n", seed=0):
+        """The hash of every line, as Python integers; computed once per (newline, seed)."""
+        cache = self.__dict__.setdefault("_line_hashes", {})
+        if (newline[0], seed) not in cache:
+            x = linehash.base(seed)
+            cache[(newline[0], seed)] = [self.part(a, b, x)[0] for a, b in self.line_bounds(newline)]
+        return cache[(newline[0], seed)]
+
+    def first_occurrences(self, newline=b"\n", seed=0):
+        """The numbers of the lines that are the first of their hash, ascending; their number is the distinct count."""
+        seen, numbers = set(), []
+        for k, h in enumerate(self.line_hashes(newline, seed)):
+            if h not in seen:
+                seen.add(h)
+                numbers.append(k)
+        return numbers
+
+    def hash_summary(self, start, size, newline=b"\n", seed=0):
+        """The summary of span [start, start + size) as Decoder.hash_lines returns it, and the hashes of the lines the span
+        closes (the first as if the span were entered at a line start) -> (dict, [hashes])."""
+        x, end = linehash.base(seed), start + size
+        cuts = self._within(self.byte_offsets(newline[0]), start, end)
+        starts = [start] + [c + 1 for c in cuts]
+        summary = {"head": self.part(start, cuts[0] if cuts else end, x), "tail": self.part(cuts[-1] + 1, end, x) if cuts else (0, 1),
+                   "has_delimiter": bool(cuts), "tail_non_empty": size > 0 and (not cuts or cuts[-1] != end - 1), "count": len(cuts)}
+        return summary, [self.part(a, b, x)[0] for a, b in zip(starts, cuts)]
+
+    def _field_of(self, a, b, j, delimiters):
+        """(start, size) of field j of the line whose content is [a, b): fields.direct's rule."""
+        lo = int(np.searchsorted(delimiters, np.uint64(a), "left"))
+        n = int(np.searchsorted(delimiters, np.uint64(b), "left")) - lo
+        if j > n:
+            return (b, -1)
+        first = a if j == 0 else int(delimiters[lo + j - 1]) + 1
+        return (first, (int(delimiters[lo + j]) if j < n else b) - first)
+
+    def field_spans(self, j, delimiter=b"\t", newline=b"\n"):
+        """[(start, size)] of field j of every line: a missing field has size -1 and its start at the end of the content."""
+        assert delimiter != newline
+        delimiters = self.byte_offsets(delimiter[0])
+        return [self._field_of(a, b, j, delimiters) for a, b in self.line_bounds(newline)]
+
+    def field_keys(self, j, delimiter=b"\t", newline=b"\n", seed=0):
+        """The key of field j of every line: its hash, or fieldhash.MISSING."""
+        x = linehash.base(seed)
+        return [fieldhash.MISSING if n < 0 else self.part(s, s + n, x)[0] for s, n in self.field_spans(j, delimiter, newline)]
+
+    def field_groups(self, j, delimiter=b"\t", newline=b"\n", seed=0, first=0, count=None):
+        """Lines [first, first + count) grouped by the key of field j, as count_by_field returns them -> (lines, counts,
+        missing, spans): the number of the first line of every distinct value, ascending; how many lines hold it; the
+        number of lines without the field; (start, size) of the field in those first lines."""
+        keys, spans = self.field_keys(j, delimiter, newline, seed), self.field_spans(j, delimiter, newline)
+        last = len(keys) if count is None else min(len(keys), first + count)
+        order, tally, missing = [], {}, 0
+        for k in range(min(first, last), last):
+            if keys[k] == fieldhash.MISSING:
+                missing += 1
+            elif keys[k] in tally:
+                tally[keys[k]][1] += 1
+            else:
+                tally[keys[k]] = [k, 1]
+                order.append(keys[k])
+        return [tally[key][0] for key in order], [tally[key][1] for key in order], missing, [spans[tally[key][0]] for key in order]
+
+    def value_counts(self, j, limit=None, delimiter=b"\t", newline=b"\n", seed=0, first=0, count=None):
+        """[(value, count)] by descending count, then by first occurrence, at most `limit`: what value_counts returns.
+        The values are materialised, so the caller keeps the filler lines out of the chosen groups."""
+        lines, counts, _, spans = self.field_groups(j, delimiter, newline, seed, first, count)
+        order = sorted(range(len(lines)), key=lambda i: (-counts[i], lines[i]))[:limit]
+        return [(self.slice(spans[i][0], spans[i][0] + spans[i][1]), counts[i]) for i in order]
+
+    def field_summary(self, start, size, j, delimiter=b"\t", newline=b"\n"):
+        """The summary of span [start, start + size) for field j as Decoder.field_spans returns it (positions relative
+        to the span, None where not reached), with "fields": (start, size) of the field in the lines the span closes,
+        offsets in the output, the first as if the span were entered at a line start."""
+        assert delimiter != newline
+        end = start + size
+        delimiters = self.byte_offsets(delimiter[0])
+        cuts = self._within(self.byte_offsets(newline[0]), start, end)
+        starts = [start] + [c + 1 for c in cuts]
+        head = [p - start for p in self._within(delimiters, start, cuts[0] if cuts else end)[:j + 1]]
+        tail_start = cuts[-1] + 1 if cuts else start
+        in_tail = [p - start for p in self._within(delimiters, tail_start, end)[:j + 1]]
+        tail = fields.go_on(fields.line_start(j, tail_start - start), j, in_tail, 0)
+        return {"count": len(cuts), "has_delimiter": bool(cuts), "first_nl": cuts[0] - start if cuts else None,
+                "head_positions": head, "tail_start": tail_start - start, "tail_delims": tail[0], "tail_field_start": tail[1],
+                "tail_field_end": tail[2], "tail_non_empty": size > 0 and (not cuts or cuts[-1] != end - 1),
+                "fields": [self._field_of(a, b, j, delimiters) for a, b in zip(starts, cuts)]}
+
+    def field_hash_summary(self, start, size, j, delimiter=b"\t", newline=b"\n", seed=0):
+        """field_summary with what Decoder.field_hashes adds: head and tail as (h, xl), head_hashes, tail_start_hash and
+        tail_end_hash (fieldhash.Text.summary's rule), and "keys" beside "fields"."""
+        x, end = linehash.base(seed), start + size
+        s = self.field_summary(start, size, j, delimiter, newline)
+        s["head"] = self.part(start, start + s["first_nl"] if s["has_delimiter"] else end, x)
+        s["tail"] = self.part(start + s["tail_start"], end, x) if s["has_delimiter"] else (0, 1)
+        s["head_hashes"] = [self.part(start, start + p, x)[0] for p in s["head_positions"]]
+        for name, position in (("tail_start_hash", s["tail_field_start"]), ("tail_end_hash", s["tail_field_end"])):
+            s[name] = None if position is None else self.part(start + s["tail_start"], start + position, x)[0]
+        s["keys"] = [fieldhash.MISSING if n < 0 else self.part(a, a + n, x)[0] for a, n in s["fields"]]
+        return s
+
+    RUN_SHRINK = 4096
+
+    def line_content(self, a, b):
+        """The bytes of [a, b) with every run cut to min(length, RUN_SHRINK) bytes: a line without a run is itself."""
+        out = bytearray()
+        for value, data, lo, hi, offset in self._overlapping(a, b):
+            out += bytes([value]) * min(hi - lo, self.RUN_SHRINK) if data is None else data[lo - offset:hi - offset]
+        assert len(out) <= self.MATERIALISE_MAX
+        return bytes(out)
+
+    def regex_lines(self, pattern, newline=b"\n", ignore_case=False):
+        """The numbers of the lines in whose content re.search(pattern, content, re.DOTALL) finds a match.  A line that
+        holds runs is searched on line_content's copy, every run cut to RUN_SHRINK = 4096 bytes.  That is exact only for
+        patterns in which a filler byte (0x80 and above) is matched by
+
+          * nothing, or
+          * `.` or a negated class that stands unrepeated, under `*` or `+`, or under `{m,n}` with n <= 255
+            (REGEX_MAX_COUNT): such an atom cannot tell 4096 equal bytes from 45 MB of them, 4096 being more than 255
+            plus the length of any pattern used.
+
+        An unbounded group of two or more such atoms, such as `(..)*`, counts the run's length modulo its own and is
+        outside the rule.  FAR_PATTERNS keeps to it; test_bigfiles.py runs every one of them against whole and shrunken
+        runs alike."""
+        cache = self.__dict__.setdefault("_regex_lines", {})
+        key = (bytes(pattern), newline[0], bool(ignore_case))
+        if key not in cache:
+            compiled = re.compile(bytes(pattern), re.DOTALL | (re.IGNORECASE if ignore_case else 0))
+            cache[key] = [k for k, (a, b) in enumerate(self.line_bounds(newline)) if compiled.search(self.line_content(a, b))]
+        return cache[key]
 
 
 # ------------------------------------------------------------------------------------------------------------------ texts
@@ -387,6 +590,38 @@ def far_file(cut=CUT, filler=FULL_BLOCK, text_size=1_000_000, tail_fillers=2):
     for (_, _, _, a), (_, _, _, b) in zip(far.blocks, far.blocks[1:]):
         assert a is None or a != b, "neighbouring fillers differ"
     return far
+
+
+# The regular expressions of the far-file tests, all inside the rule of VirtualRaw.regex_lines: a filler byte is matched
+# by nothing, or by a `.` that stands alone or under `*`.  What each is for (checked by test_bigfiles.py at full scale):
+FAR_PATTERNS = {
+    "caret": rb"^dkb dqtlnhgz dqt",                    # anchored at the start of the line that straddles 2^32
+    "dollar": rb"tmid apktzeld$",                      # ... and at its end
+    "across": rb"pnSQ.*kQzm.*OG4 mb",                  # a literal below 2^32, `.*`, the bytes around it, `.*`, one above
+    "t2-only": rb".N3eDLe#16-MiXed\. pek",             # T2's first line: a filler byte in front of T0's first bytes
+    "ascii-tail": rb"MiXed\. qtlnhgz cnrntjvxu pmb",   # the line that holds the 94 fillers, through T1's first bytes
+    "short": rb"n3EdlE#17-m[iI]xEd\.!",                # every matching line is short (grep_regex returns lines)
+    "class": rb"^[a-z]+ [a-z ]+$",                # many lines, none with a filler
+    "behind-fillers": rb"^.+N3eDLe#16-MiXed\. [a-z]",  # the first lines of T1 and T2, `.+` over every filler in front
+    "nowhere": rb"never[0-9]there",
+}
+FAR_CARRIED = (rb"jdk \.N3e.*nipf lguogvy", b"_")     # under newline b"_": X in T0, the 94 fillers, Y in T1, one line
+
+
+def long_field_batch(far):
+    """(blocks, VirtualRaw) of a batch over far_file()'s blocks in another order: T0, then all fillers (the 94 and the two
+    tail ones, back to back), then T2.  In far_file() itself no byte value is absent from T0 and from T1's first 450 kB,
+    so no closed line or field there reaches 2^32 bytes (the fillers between T0 and T1 are 1.45 MB short of it); in this
+    batch's output the bytes between T0's last byte and T2's first are more than 2^32 of one line.  No second file."""
+    texts = [block for block in far.blocks if block[3] is None]
+    t0 = [block for block in texts if block[1] < len(far.t0)]
+    t2 = [block for block in texts if block[1] >= far.t2_at]
+    fillers = [block for block in far.blocks if block[3] is not None]
+    assert all(a[3] != b[3] for a, b in zip(fillers, fillers[1:])), "neighbouring fillers differ"
+    blocks = t0 + fillers + t2
+    raw = VirtualRaw([far.raw.slice(at, at + size) if value is None else (value, size) for _, at, size, value in blocks])
+    assert raw.size == 2 * len(far.t0) + sum(size for _, _, size, _ in fillers) and raw.size - 2 * len(far.t0) > far.cut
+    return blocks, raw
 
 
 @functools.lru_cache(maxsize=None)

@@ -11,6 +11,10 @@
  * must be strictly ascending, exactly one per matching line -- matching decided by running the table over that line
  * alone --, each inside its line.  Texts with and without a final delimiter, empty lines at cuts, a text that is one
  * delimiter, an empty text, and patterns that match the empty string, ^ and $.
+ *
+ * The stitch beyond 2^32: the same cases once more behind a front stretch of 2^32 - k bytes (k = 0, 1, 300) whose summary
+ * is written down and whose bytes are never held, closed by a delimiter or open: fileOffset and witnesses above 2^32, a
+ * seam exactly at 2^32, a line across it; the expected lines are the unshifted ones plus the shift, and the front's own.
  * Prints "regex ok". */
 #include <cstdio>
 #include <cstdlib>
@@ -258,6 +262,131 @@ checkCuts( const Regex& regex, const std::string& text, char nl, const std::vect
     }
 }
 
+/* ---- the same cases behind a front stretch of 2^32 - k bytes that is never held in memory ----
+ *
+ * The front is FRONT_BYTE over and over -- closed by one delimiter (the text then starts a line at 2^32 - k) or open (the
+ * text's first line then begins at offset 0 and is more than 4 GB long).  Its summary is written down, not computed from
+ * bytes: the map of one FRONT_BYTE is applied until one more application changes nothing (checked; no pattern here counts
+ * FRONT_BYTEs), which is then the head map of any longer run of it. */
+constexpr uint8_t FRONT_BYTE = 'q';
+constexpr uint64_t TWO_32 = uint64_t( 1 ) << 32;
+
+StretchSummary
+frontSummary( const Regex& regex, bool closed )
+{
+    StretchSummary s;
+    for ( uint32_t q = 0; q < regex.n; ++q ) s.headMap[q] = (uint8_t)q;
+    bool stable = false;
+    for ( int round = 0; round < 64 && !stable; ++round ) {
+        stable = true;
+        for ( uint32_t q = 0; q < regex.n; ++q ) {
+            const uint8_t next = regex.transitions[(size_t)s.headMap[q] * 256 + FRONT_BYTE];
+            stable = stable && next == s.headMap[q];
+            s.headMap[q] = next;
+        }
+    }
+    CHECK( stable );
+    s.hasDelimiter = closed;      /* closed: the delimiter is the front's last byte, nothing follows it: exit 0, no body */
+    return s;
+}
+
+/** The lines of front + text and which of them match: the table walked over the text from the state the front leaves. */
+std::vector<size_t>
+matchingLinesBehind( const Regex& regex, const StretchSummary& front, uint64_t frontSize, bool closed, const std::string& text,
+                     char nl, std::vector<std::pair<uint64_t, uint64_t> >* extents )
+{
+    std::vector<size_t> lines;
+    extents->clear();
+    uint8_t state = front.headMap[REGEX_START];
+    uint64_t lineStart = 0;
+    const auto close = [&] ( uint64_t end ) {
+        if ( state == REGEX_MATCHED || regex.acceptsAtEnd[state] != 0 ) lines.push_back( extents->size() );
+        extents->push_back( { lineStart, end } );
+        lineStart = end;
+        state = REGEX_START;
+    };
+    if ( closed ) close( frontSize );
+    for ( size_t i = 0; i < text.size(); ++i ) {
+        if ( text[i] == nl ) {
+            close( frontSize + i + 1 );
+        } else if ( state != REGEX_MATCHED ) {
+            state = regex.transitions[(size_t)state * 256 + (uint8_t)text[i]];
+        }
+    }
+    if ( lineStart < frontSize + text.size() ) close( frontSize + text.size() );
+    return lines;
+}
+
+void
+checkCutsBehind( const Regex& regex, const std::string& text, char nl, const std::vector<size_t>& cuts, size_t chunk,
+                 uint64_t frontSize, bool closed )
+{
+    std::vector<Stretch> stretches( 1 );
+    stretches[0].size = frontSize;
+    stretches[0].summary = frontSummary( regex, closed );
+    std::vector<std::pair<uint64_t, uint64_t> > extents;
+    const auto expected = matchingLinesBehind( regex, stretches[0].summary, frontSize, closed, text, nl, &extents );
+    size_t from = 0;
+    for ( size_t k = 0; k <= cuts.size(); ++k ) {
+        const size_t to = k < cuts.size() ? cuts[k] : text.size();
+        Stretch stretch;
+        stretch.fileOffset = frontSize + from;
+        stretch.size = to - from;
+        stretch.summary = summarise( regex, reinterpret_cast<const uint8_t*>( text.data() ) + from, to - from, (uint8_t)nl,
+                                     chunk == 0 ? text.size() + 1 : chunk, frontSize + from );
+        stretches.push_back( std::move( stretch ) );
+        from = to;
+    }
+    std::vector<uint64_t> witnesses;
+    const auto count = stitchSummaries( regex, stretches, &witnesses );
+    CHECK( count == expected.size() && witnesses.size() == expected.size() );
+    CHECK( stitchSummaries( regex, stretches, nullptr ) == expected.size() );
+    for ( size_t i = 0; i < witnesses.size() && i < expected.size(); ++i ) {
+        const auto& line = extents[expected[i]];
+        CHECK( witnesses[i] >= line.first && witnesses[i] < line.second );
+        CHECK( i == 0 || witnesses[i] > witnesses[i - 1] );
+        /* a line that starts in the text has its witness in the text: beyond what 32 bits hold where the line is */
+        if ( line.first >= frontSize ) CHECK( witnesses[i] >= frontSize && ( line.first < TWO_32 || witnesses[i] >= TWO_32 ) );
+    }
+}
+
+void
+testSummariesBeyondFourGiB( const char* const* patterns, size_t nPatterns, const char* const* texts, size_t nTexts )
+{
+    for ( size_t p = 0; p < nPatterns; ++p ) {
+        for ( const bool fold : { false, true } ) {
+            const auto regex = compiled( patterns[p], fold );
+            for ( const bool closed : { true, false } ) {
+                /* k = 0: the seam between front and text lies at 2^32; k = 1: the text's first line straddles it */
+                for ( const uint64_t k : { uint64_t( 0 ), uint64_t( 1 ) } ) {
+                    for ( size_t t = 0; t < nTexts; ++t ) {
+                        const std::string text( texts[t] );
+                        for ( const size_t chunk : { size_t( 0 ), size_t( 1 ), size_t( 3 ) } ) {
+                            currentCase = std::string( patterns[p] ) + " behind 2^32 - " + std::to_string( k ) + ( closed ? " closed" : " open" )
+                                          + " bytes, a text of " + std::to_string( text.size() ) + " bytes, chunk " + std::to_string( chunk );
+                            checkCutsBehind( regex, text, '\n', {}, chunk, TWO_32 - k, closed );
+                            for ( size_t a = 0; a <= text.size(); ++a ) {
+                                checkCutsBehind( regex, text, '\n', { a }, chunk, TWO_32 - k, closed );
+                                for ( size_t b = a; b <= text.size(); ++b ) checkCutsBehind( regex, text, '\n', { a, b }, chunk, TWO_32 - k, closed );
+                            }
+                        }
+                    }
+                }
+                /* k = 300 under a text of 600 bytes: every single cut, the one at 2^32 exactly among them, lines on both
+                 * sides of it and one across it */
+                std::string text;
+                while ( text.size() < 600 ) text += "aab\n\nb\nxay\nx,y\n,x\nabababab\n";
+                text.resize( 600 );
+                for ( const size_t chunk : { size_t( 0 ), size_t( 5 ) } ) {
+                    currentCase = std::string( patterns[p] ) + " behind 2^32 - 300 bytes, chunk " + std::to_string( chunk );
+                    for ( size_t a = 0; a <= text.size(); ++a ) checkCutsBehind( regex, text, '\n', { a }, chunk, TWO_32 - 300, closed );
+                    checkCutsBehind( regex, text, '\n', { 299, 300, 301 }, chunk, TWO_32 - 300, closed );
+                }
+            }
+        }
+    }
+}
+
 void
 testSummaries()
 {
@@ -283,6 +412,7 @@ testSummaries()
             }
         }
     }
+    testSummariesBeyondFourGiB( patterns, sizeof( patterns ) / sizeof( patterns[0] ), texts, sizeof( texts ) / sizeof( texts[0] ) );
     currentCase = "another delimiter";
     {
         const auto regex = compiled( "^a+$" );

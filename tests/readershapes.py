@@ -28,6 +28,7 @@ import re
 import numpy as np
 
 import datagen
+import fieldhash as FH
 import fields as F
 import grepgen
 import linehash as H
@@ -251,6 +252,25 @@ def first_occurrences_of(lines):
     return numbers
 
 
+def groups_of(values, first=0, count=None):
+    """Lines [first, first + count) of `values` (one field per line, None where it is missing) grouped by value, as
+    count_by_field and value_counts return them -> (lines, counts, missing, ranked): the number of the first line of every
+    distinct value in first-occurrence order, how many lines of the range hold it, the number of lines without the field,
+    and [(value, count)] by descending count, then by first occurrence."""
+    last = len(values) if count is None else min(len(values), first + count)
+    firsts, tally, missing = {}, {}, 0
+    for k in range(min(first, last), last):
+        value = values[k]
+        if value is None:
+            missing += 1
+        else:
+            firsts.setdefault(value, k)
+            tally[value] = tally.get(value, 0) + 1
+    order = sorted(firsts, key=firsts.get)
+    ranked = sorted(((value, tally[value]) for value in order), key=lambda item: (-item[1], firsts[item[0]]))
+    return [firsts[value] for value in order], [tally[value] for value in order], missing, ranked
+
+
 @functools.lru_cache(maxsize=None)
 def expected(variant="tail"):
     """What the reader must answer for a variant, from the models and the standard library alone; computed once per
@@ -268,5 +288,8 @@ def expected(variant="tail"):
         "first_occurrences": first_occurrences_of(lines),
         "spans": {(j, dl): F.direct(raw, NL, dl, j) for j, dl in FIELDS},
         "field3": F.fields_of(raw, NL, TAB, 3),
+        "values": {(j, dl): F.fields_of(raw, NL, dl, j) for j, dl in FIELDS},
+        "keys": {(j, dl, seed): FH.keys_of(raw, NL, dl, j, seed) for j, dl in FIELDS for seed in SEEDS},
+        "groups": {(j, dl): groups_of(F.fields_of(raw, NL, dl, j)) for j, dl in FIELDS},
         "regex": {(pattern, fold): reference_regex(raw, pattern, fold) for pattern in REGEX_PATTERNS for fold in (False, True)},
     }

@@ -1,6 +1,10 @@
 """tests/bigfiles.py on the CPU: VirtualRaw against the same parts held in memory, crc_concat against the oracle's CRC, and
 the two builders against CPython's bz2 decoder and the oracle's block map -- at full scale where that takes seconds
-(far_file's promises, the streams around 2^32), at a shrunken scale where it would not (the whole block map)."""
+(far_file's promises, the streams around 2^32), at a shrunken scale where it would not (the whole block map).
+
+VirtualRaw's answers for the line queries (line hashes, field spans and keys, groups, span summaries, regular expressions)
+are checked on shrunken layouts whose bytes fit in memory, against linehash.py, fields.py, fieldhash.py, regexgen.py and
+re; what the GPU tests rely on at full scale is asserted at full scale."""
 import bz2
 import time
 
@@ -172,6 +176,169 @@ def test_far_file_block_map_on_a_shrunken_layout(oracle):
     assert oracle.find_magic(far.enc, bigfiles.MAGIC_EOS) == far.eos
     for bit, at, size, value in far.blocks:
         assert decoded[at:at + size] == (bytes([value]) * size if value is not None else far.raw.slice(at, at + size))
+
+
+QUERY_LAYOUTS = ({"cut": 1 << 18, "filler": 3_000, "text_size": 60_000}, {"cut": 1 << 18, "filler": 5_000, "text_size": 60_000})
+
+
+def materialised(layout):
+    far = bigfiles.far_file(**layout)
+    data = far.raw.slice(0, far.raw.size)
+    assert len(data) == far.raw.size and (layout["filler"] > bigfiles.VirtualRaw.RUN_SHRINK) == (layout["filler"] == 5_000)
+    return far, data
+
+
+def query_spans(far):
+    """Spans of the shrunken layouts: whole, empty, around the cut, from and into fillers, from a filler to the end."""
+    size, cut = far.raw.size, far.cut
+    first_filler = len(far.t0)
+    return [(0, size), (cut, 0), (cut - 131, 308), (cut - 1, 2), (0, len(far.t0)), (first_filler, size - first_filler),
+            (first_filler - 500, 4_000), (first_filler + 7, far.t1_at + 90 - first_filler - 7), (far.t2_at - 6_000, 9_000), (far.t2_at + 11, 3_000)]
+
+
+def test_virtual_raw_line_hashes_on_shrunken_layouts():
+    import fields as F
+    import linehash as LH
+    import readershapes
+    for layout in QUERY_LAYOUTS:
+        far, data = materialised(layout)
+        raw = far.raw
+        for newline in (b"\n", b"_", b"\0"):
+            lines = F.lines_of(data, newline[0])
+            assert [data[a:b] for a, b in raw.line_bounds(newline)] == lines
+            assert raw.first_occurrences(newline) == readershapes.first_occurrences_of(lines)
+            for seed in (0, 1):
+                assert raw.line_hashes(newline, seed) == LH.direct(data, newline[0], seed), (layout, newline, seed)
+                x = LH.base(seed)
+                for start, n in query_spans(far):
+                    model = LH.summarise_chunk(data[start:start + n], newline[0], x)
+                    summary, hashes = raw.hash_summary(start, n, newline, seed)
+                    assert hashes == model["hashes"] and summary["count"] == len(hashes), (start, n)
+                    assert summary == {key: model[key] for key in ("head", "tail", "has_delimiter", "tail_non_empty")} | {"count": len(hashes)}
+        assert len(raw.first_occurrences()) < len(raw.line_bounds())          # T2 repeats T0
+        for a, b, x in ((0, raw.size, LH.base(0)), (len(far.t0) - 3, far.t1_at + 3, LH.base(1)), (far.cut, far.cut, 300)):
+            assert raw.part(a, b, x) == LH.part(data[a:b], x)
+
+
+def test_virtual_raw_fields_on_shrunken_layouts():
+    import collections
+    import fieldhash as FH
+    import fields as F
+    import linehash as LH
+    for layout in QUERY_LAYOUTS:
+        far, data = materialised(layout)
+        raw = far.raw
+        for delimiter, newline in ((b" ", b"\n"), (b"e", b"\n"), (b"\n", b" "), (b"\t", b"\0"), (b" ", b"_")):
+            dl, nl = delimiter[0], newline[0]
+            for j in (0, 1, 3, 8, 9, 1023):
+                spans = F.direct(data, nl, dl, j)
+                assert raw.field_spans(j, delimiter, newline) == spans, (layout, delimiter, newline, j)
+                if (j, delimiter) not in ((0, b" "), (3, b" "), (1, b"\n"), (0, b"\t")):
+                    continue
+                for seed in (0, 1):
+                    keys = FH.keys_of(data, nl, dl, j, seed)
+                    assert raw.field_keys(j, delimiter, newline, seed) == keys
+                    # groups: the first line, the count and the missing ones, from the values themselves
+                    values = F.fields_of(data, nl, dl, j)
+                    tally = collections.Counter(v for v in values if v is not None)
+                    firsts = {}
+                    for k, v in enumerate(values):
+                        if v is not None:
+                            firsts.setdefault(v, k)
+                    lines, counts, missing, where = raw.field_groups(j, delimiter, newline, seed)
+                    assert lines == sorted(firsts.values()) and missing == sum(1 for v in values if v is None)
+                    assert counts == [tally[values[k]] for k in lines] and where == [spans[k] for k in lines]
+                    lines, counts, missing, _ = raw.field_groups(j, delimiter, newline, seed, 5, 40)
+                    part = values[5:45]
+                    assert missing == sum(1 for v in part if v is None) and sum(counts) + missing == len(part)
+                    assert lines == sorted({5 + part.index(v) for v in part if v is not None})
+                    if newline == b"\n" and delimiter == b" " and j == 3:
+                        first = len(F.lines_of(data[:far.t1_at], nl))                # behind the line that holds the fillers
+                        ordered = sorted(collections.Counter(v for v in values[first:first + 200] if v is not None).items(),
+                                         key=lambda item: (-item[1], values.index(item[0], first)))
+                        assert raw.value_counts(j, 7, delimiter, newline, seed, first, 200) == ordered[:7]
+                    x = LH.base(seed)
+                    for start, n in query_spans(far):
+                        model = FH.Text(data[start:start + n], x, prefixes=False).summary(0, n, nl, dl, j)
+                        got = raw.field_hash_summary(start, n, j, delimiter, newline, seed)
+                        assert {key: got[key] for key in FH.FIELD_KEYS + FH.HASH_KEYS} == {key: model[key] for key in FH.FIELD_KEYS + FH.HASH_KEYS}, (start, n, j)
+                        assert got["keys"] == model["keys"] and got["fields"] == [(start + a, size) for a, size in model["fields"]]
+                        plain = raw.field_summary(start, n, j, delimiter, newline)
+                        assert plain == {key: got[key] for key in FH.FIELD_KEYS + ("fields",)}
+
+
+def test_virtual_raw_regex_on_shrunken_layouts():
+    """Every pattern of the GPU tests, and the same patterns over the shrunken layouts' own first words, against re on the
+    materialised bytes: with fillers of 3 000 bytes regex_lines sees the runs whole, with 5 000 it sees them cut."""
+    import regexgen as G
+    import readershapes
+    for layout in QUERY_LAYOUTS:
+        far, data = materialised(layout)
+        raw = far.raw
+        own = [b"^.+N3eDLe#16-MiXed\\. [a-z]", b"." + far.t0[:22].replace(b".", b"\\."), b"MiXed\\.$", b"^[^ ]* [^ ]*$",
+               far.t0[-30:-24] + b".*" + far.t1[20:26], b"^.{0,255}N3eDLe", b".{200,255}N3eDLe", b"[^a]*N3eDLe#16-MiXed\\. [a-z]"]
+        for pattern in list(bigfiles.FAR_PATTERNS.values()) + [bigfiles.FAR_CARRIED[0]] + own:
+            for ignore_case in (False, True):
+                assert raw.regex_lines(pattern, b"\n", ignore_case) == readershapes.reference_regex(data, pattern, ignore_case)[0], pattern
+                for newline in (b"_", b"\0", bigfiles.FAR_CARRIED[1]):
+                    assert raw.regex_lines(pattern, newline, ignore_case) == G.expected_lines(pattern, data, newline, ignore_case), pattern
+        # the lines that hold fillers do match some of them: the rule is exercised, not vacuous
+        filler_lines = {k for k, (a, b) in enumerate(raw.line_bounds()) if raw.holds_run(a, b)}
+        assert len(filler_lines) == 2 and filler_lines <= set(raw.regex_lines(own[0])) and filler_lines <= set(raw.regex_lines(own[7]))
+        assert set(raw.regex_lines(own[1])) & filler_lines and set(raw.regex_lines(own[4], b"\0")) == {0}
+
+
+def test_far_file_placement_for_the_line_queries():
+    """At full scale, what the GPU tests of the line queries rely on."""
+    import fieldhash as FH
+    far = bigfiles.far_file()
+    raw, cut = far.raw, 1 << 32
+    bounds = raw.line_bounds()
+    assert len(raw.byte_offsets(10)) == len(bounds) == 39_214
+    assert far.t0.count(b"\n") == 13_085 and far.t1.count(b"\n") == 13_044 and far.t0[-1:] == far.t1[-1:] == b"\n"
+    # the line that straddles 2^32: 308 bytes, 8 spaces; its field 4 is the 256-byte needle with the '.' in front of it
+    k = raw.line_of(cut)
+    assert bounds[k] == (cut - 131, cut + 177)
+    line = raw.slice(*bounds[k])
+    assert line.count(b" ") == 8 and line.split(b" ")[4] == b"." + bigfiles.needles()["n256"]
+    spans = {j: raw.field_spans(j, b" ")[k] for j in (0, 3, 4, 8, 9, 1023)}
+    assert spans[4] == (cut - 101, 257) and spans[3][0] + spans[3][1] < cut < spans[8][0]
+    assert spans[8][0] + spans[8][1] == cut + 177 and spans[9] == spans[1023] == (cut + 177, -1)
+    # the first line of T1 begins with all 94 fillers; it and its field 0 are the largest of the file, 1.45 MB short of 2^32
+    # (T0 and the fillers together are 2^32 - 449 924 bytes, and T0 ends in a newline)
+    first = raw.line_of(far.t1_at)
+    assert first == 13_085 and bounds[first][0] == len(far.t0) and bounds[first][1] - bounds[first][0] == 4_293_517_451 < cut
+    assert raw.field_spans(0, b" ")[first] == (len(far.t0), 4_293_517_388)
+    assert max(b - a for a, b in bounds) == 4_293_517_451
+    # ... and no byte value is absent from both T0 and T1's bytes below 2^32, so no other delimiter gives a longer closed line
+    assert set(far.t0) & set(far.t1[:cut - far.t1_at]) == set(far.t0) == set(far.t1)
+    # under a byte that is in no text the whole file is one unterminated line of more than 2^32 bytes
+    assert raw.line_bounds(b"\0") == [(0, raw.size)] and raw.field_spans(0, b"\t", b"\0") == [(0, raw.size)] and raw.size > cut
+    # the first line of T2 begins with the two tail fillers; every other line of T2 is a duplicate of T0's
+    second = raw.line_of(far.t2_at)
+    assert bounds[second] == (far.t2_at - 2 * bigfiles.FULL_BLOCK, far.t2_at + far.t0.index(b"\n"))
+    for seed in (0, 1):
+        hashes = raw.line_hashes(b"\n", seed)
+        assert hashes[second + 1:] == hashes[1:13_085] and hashes[second] not in hashes[:second]
+        firsts = raw.first_occurrences(b"\n", seed)
+        assert [n for n in firsts if n >= second] == [second] and first in firsts
+    assert far.shift == cut + 92_348_546
+    # the patterns are what their names say
+    lines = {name: raw.regex_lines(pattern) for name, pattern in bigfiles.FAR_PATTERNS.items()}
+    assert k in lines["caret"] and k in lines["dollar"] and lines["across"] == [k]
+    assert lines["t2-only"] == [second] and lines["ascii-tail"] == [first] and {first, second} <= set(lines["behind-fillers"])
+    assert lines["nowhere"] == [] and len(lines["class"]) > 100
+    assert lines["short"] and all(b - a < 1000 for a, b in (bounds[n] for n in lines["short"]))
+    assert any(bounds[n][0] > cut for n in lines["short"]) and any(bounds[n][0] < cut for n in lines["short"])
+    pattern, newline = bigfiles.FAR_CARRIED
+    carried = raw.line_bounds(newline)
+    assert raw.regex_lines(pattern, newline) == [3] and carried[3][0] < len(far.t0) and far.t1_at < carried[3][1] < cut
+    # the batch in another order: one field of more than 2^32 bytes in a closed line, not the line's first
+    blocks, other = bigfiles.long_field_batch(far)
+    at = other.line_of(len(far.t0), b" ")
+    start, size = other.field_spans(1, b"\n", b" ")[at]
+    assert size > cut and start == len(far.t0) and other.line_bounds(b" ")[at][0] < start
+    assert other.field_keys(1, b"\n", b" ")[at] not in (0, FH.MISSING)
 
 
 def test_deep_file_on_a_shrunken_layout(oracle):

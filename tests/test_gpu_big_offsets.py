@@ -6,6 +6,12 @@ the stitching, the CRC of a concatenation in plain integers.  A block written to
 (k_rle and k_crc take the offset from one record) and fillers of one value look alike, so the content is checked where the
 CRC cannot tell: every filler is counted, neighbouring fillers differ, and no filler above 2^32 has its own value 2^32 below.
 
+The four line queries -- regular expressions, line hashes, field spans and field hashes -- meet the same offsets: their
+kernels on spans of the batch around, across and above 2^32 and on the whole output as one span (A2), the reader's
+stitching on far_file() with one line of 4.29 GB that runs through 94 launches (B), and, because no closed line of
+far_file() reaches 2^32 bytes, the same blocks decoded in another order, where one field of one closed line does
+(test_field_of_more_than_4_gib).
+
 One module-scoped fixture per file does the decode; the tests ask what is resident.  No test copies more than a few MB to
 the host.
 
@@ -310,6 +316,319 @@ def test_batch_with_kept_stages(native, far):
         dec.close()
 
 
+# ------------------------------------------------- A2. the line queries on the batch: regex, line hashes, field spans, keys
+#
+# Decoder.match_lines, hash_lines, field_spans and field_hashes over spans of the resident batch.  Every expected value is
+# VirtualRaw's (tests/bigfiles.py): summaries, hashes, keys, starts and sizes exactly.  For the regular expressions the
+# matching lines are Python's re (VirtualRaw.regex_lines); the head map and the exit state are the compiled table walked
+# over the span's first and last line alone (regexgen.chunk_summary), as test_gpu_regex.py walks it over whole spans; a
+# witness may be any byte of its line, so the witnesses are compared as the numbers of the lines they lie in.
+
+QUERY_SIZES = (1, 255, 256, 257, 65_535, 65_536, 65_537, 140_000)
+ONES, UNTOUCHED = 2**64 - 1, -1 - 2**62
+FIELD_KEYS = ("count", "has_delimiter", "first_nl", "head_positions", "tail_start", "tail_delims", "tail_field_start",
+              "tail_field_end", "tail_non_empty")
+HASH_KEYS = ("head", "tail", "head_hashes", "tail_start_hash", "tail_end_hash")
+WANTED = {}                      # the reference of a span, computed once, shared by the tests, never changed
+
+
+def wanted(raw, kind, *arguments):
+    key = (id(raw), kind) + arguments
+    if key not in WANTED:
+        WANTED[key] = getattr(raw, kind)(*arguments)
+    return WANTED[key]
+
+
+def query_spans(far):
+    """(aligned, fixed): every size at all 16 start misalignments, ending below 2^32, across it and starting at or above
+    it; and the fixed ones: from and to 2^32 exactly, empty at 2^32, in T2, and 2^32 on a tile edge, on a chunk edge that is
+    no tile edge and inside a chunk of the span (tiles and chunks are counted from the span's start)."""
+    aligned = []
+    for sm in range(16):
+        for size in QUERY_SIZES:
+            aligned.append((((CUT - size - 32) & ~15) + sm, size))
+            across = ((CUT - size // 2 - 16) & ~15) + sm
+            if across < CUT < across + size:
+                aligned.append((across, size))
+            aligned.append((CUT + sm, size))
+    fixed = [(CUT, 70_000), (CUT - 70_000, 70_000), (CUT, 0), (far.t2_at + 5_000, 70_001), (CUT - 65_536, 140_000),
+             (CUT - 3 * 256, 65_537), (CUT - 2 * 65_536 - 100, 140_000)]
+    return aligned, fixed
+
+
+def test_query_spans_cover_what_they_claim(native, far):
+    aligned, fixed = query_spans(far)
+    below = [(a, n) for a, n in aligned if a + n < CUT]
+    across = [(a, n) for a, n in aligned if a < CUT < a + n]
+    above = [(a, n) for a, n in aligned if a >= CUT]
+    assert len(below) + len(across) + len(above) == len(aligned)
+    for group, sizes in ((below, QUERY_SIZES), (across, QUERY_SIZES[1:]), (above, QUERY_SIZES)):
+        assert {(a % 16, n) for a, n in group} == {(sm, n) for sm in range(16) for n in sizes}
+    N = native._native
+    assert N.regex_chunk_bytes() == N.line_hash_chunk_bytes() == N.field_chunk_bytes() == 256
+    edge = lambda span, unit: span[0] < CUT < span[0] + span[1] and (CUT - span[0]) % unit == 0
+    assert edge(fixed[4], 65_536) and edge(fixed[5], 256) and not edge(fixed[5], 65_536) and not edge(fixed[6], 256)
+    assert fixed[6][0] < CUT < fixed[6][0] + fixed[6][1]
+    assert all(a + n <= far.t1_at + len(far.t1) and a >= far.t1_at for a, n in aligned + fixed[:3] + fixed[4:])
+
+
+def check_hash_lines(dec, raw, spans, newline=b"\n", seed=0, capacity=None, room=None):
+    want = [wanted(raw, "hash_summary", a, n, newline, seed) for a, n in spans]
+    summaries, hashes = dec.hash_lines(spans, newline, seed, capacity, room)
+    assert hashes.dtype == np.uint64
+    for span, got, (summary, _) in zip(spans, summaries, want):
+        assert got == summary, (span, newline, seed)
+    flat = [h for _, closed in want for h in closed]
+    written = len(flat) if capacity is None else min(capacity, len(flat))
+    assert hashes[:written].tolist() == flat[:written], (spans[:3], newline, seed)
+    assert (hashes[written:] == ONES).all(), "written at or beyond the capacity"
+    return want
+
+
+def check_fields(dec, raw, spans, field, delimiter=b" ", newline=b"\n", seed=None, capacity=None, room=None):
+    """Decoder.field_spans (seed None) or Decoder.field_hashes against VirtualRaw, exactly."""
+    if seed is None:
+        want = [wanted(raw, "field_summary", a, n, field, delimiter, newline) for a, n in spans]
+        summaries, starts, sizes = dec.field_spans(spans, field, delimiter, newline, capacity, room)
+        keys, names = None, FIELD_KEYS
+    else:
+        want = [wanted(raw, "field_hash_summary", a, n, field, delimiter, newline, seed) for a, n in spans]
+        summaries, keys, starts, sizes = dec.field_hashes(spans, field, delimiter, newline, seed, capacity, room)
+        names = FIELD_KEYS + HASH_KEYS
+    assert starts.dtype == np.uint64 and sizes.dtype == np.int64
+    for span, got, model in zip(spans, summaries, want):
+        assert got == {name: model[name] for name in names}, (span, field, delimiter, newline, seed)
+    flat = [pair for model in want for pair in model["fields"]]
+    written = len(flat) if capacity is None else min(capacity, len(flat))
+    assert starts[:written].tolist() == [s for s, _ in flat[:written]], (spans[:3], field)
+    assert sizes[:written].tolist() == [n for _, n in flat[:written]], (spans[:3], field)
+    assert (starts[written:] == ONES).all() and (sizes[written:] == UNTOUCHED).all(), "written at or beyond the capacity"
+    if keys is not None:
+        assert keys.dtype == np.uint64
+        assert keys[:written].tolist() == [k for model in want for k in model["keys"]][:written], (spans[:3], field, seed)
+        assert (keys[written:] == ONES).all()
+    return want, flat
+
+
+def check_match_lines(native, dec, raw, spans, pattern, newline=b"\n", ignore_case=False, capacity=None):
+    """The spans begin and end in lines without a filler; the lines in between may hold any."""
+    import regexgen as G
+    compiled = native.compile_regex(pattern, ignore_case)
+    transitions, accepts = compiled.transitions.tolist(), compiled.accepts_at_end.tolist()
+    cuts = raw.byte_offsets(newline[0])
+    bounds = raw.line_bounds(newline)
+    matching = raw.regex_lines(pattern, newline, ignore_case)
+    head_maps, has_delimiter, exits, positions, counts = dec.match_lines(spans, compiled, newline, capacity)
+    want_lines = []
+    for i, (a, n) in enumerate(spans):
+        inside = raw._within(cuts, a, a + n)
+        # the head map: every entry state walked over the span's first line (regexgen.chunk_summary's rule, all states at once)
+        states = np.arange(compiled.states)
+        for byte in raw.slice(a, inside[0] if inside else a + n):
+            states = compiled.transitions[states, byte]
+        assert head_maps[i].tolist() == states.tolist() + [0] * (64 - compiled.states) and has_delimiter[i] == bool(inside), (pattern, a, n)
+        lines = []
+        if inside:
+            first, last = raw.line_of(inside[0] + 1, newline), raw.line_of(inside[-1] + 1, newline)
+            lines = [k for k in matching[np.searchsorted(matching, first):np.searchsorted(matching, last)]]
+            tail = G.chunk_summary(transitions, accepts, newline + raw.slice(inside[-1] + 1, a + n), newline[0])
+            assert exits[i] == tail.exit, (pattern, a, n)
+            lines += [last] if tail.witnesses else []
+            assert all(bounds[k][0] > a for k in lines)
+        else:
+            assert exits[i] == 0
+        assert counts[i] == len(lines), (pattern, a, n)
+        want_lines += lines
+    written = len(want_lines) if capacity is None else min(capacity, len(want_lines))
+    assert len(positions) == written
+    got_lines = np.searchsorted(cuts, np.array(positions, dtype=np.uint64), "left").tolist()
+    assert got_lines == want_lines[:written], (pattern, spans[:3])
+    # one witness per line, inside the span that lists it, ascending within it
+    at = 0
+    for (a, n), count in zip(spans, counts):
+        mine = positions[at:at + count]
+        assert all(a <= p < a + n for p in mine) and mine == sorted(set(mine))
+        at += count
+    return positions, want_lines
+
+
+def test_hash_lines_around_2_32(far, far_batch):
+    dec, _, total = far_batch
+    aligned, fixed = query_spans(far)
+    check_hash_lines(dec, far.raw, aligned)
+    check_hash_lines(dec, far.raw, fixed + aligned[::5], seed=1)
+    check_hash_lines(dec, far.raw, fixed + aligned[3::7], newline=b" ")
+    # a capacity that is reached above 2^32
+    span = [(far.t1_at + 100, len(far.t1) - 100)]
+    lower = far.raw.line_of(CUT) - far.raw.line_of(span[0][0])
+    want = check_hash_lines(dec, far.raw, span, capacity=lower + 2, room=lower + 50)
+    assert len(want[0][1]) > lower + 50
+
+
+def test_hash_lines_of_the_whole_output(far, far_batch):
+    dec, _, total = far_batch
+    raw = far.raw
+    t1_line = raw.line_of(far.t1_at)
+    for seed in (0, 1):
+        (summary, hashes), = check_hash_lines(dec, raw, [(0, total)], seed=seed)
+        assert hashes == raw.line_hashes(b"\n", seed) and summary["count"] == len(hashes) == 39_214
+        assert hashes[t1_line] == raw.part(len(far.t0), raw.line_bounds()[t1_line][1], bigfiles.linehash.base(seed))[0]
+        # no delimiter from the first filler's first byte to the end: the head is (h, x^len) of more than 2^32 bytes
+        span = (len(far.t0), total - len(far.t0))
+        (summary, hashes), = check_hash_lines(dec, raw, [span], newline=b"\0", seed=seed)
+        x = bigfiles.linehash.base(seed)
+        assert span[1] > CUT and hashes == [] and summary["count"] == 0 and not summary["has_delimiter"]
+        assert summary["head"][1] == pow(x, span[1], bigfiles.linehash.P) and summary["tail"] == (0, 1)
+    print(f"\ndevice memory after the whole-output span: {dec.device_memory()}")
+
+
+@pytest.mark.parametrize("seed", [None, 0, 1], ids=["spans", "keys-seed0", "keys-seed1"])
+def test_fields_around_2_32(far, far_batch, seed):
+    dec, _, total = far_batch
+    raw = far.raw
+    aligned, fixed = query_spans(far)
+    if seed != 1:
+        check_fields(dec, raw, aligned, 3, seed=seed)
+    for field in (0, 3, 4, 8, 9, 1023):
+        check_fields(dec, raw, fixed + aligned[field % 5::5 if seed is None else 11], field, seed=seed)
+    check_fields(dec, raw, fixed + aligned[2::9], 1, delimiter=b"e", seed=seed)
+    check_fields(dec, raw, fixed + aligned[4::9], 2, delimiter=b"\n", newline=b" ", seed=seed)
+    # the line across 2^32 closed by a span that starts in front of it: its field 4 starts below 2^32 and ends above
+    k = raw.line_of(CUT)
+    a, b = raw.line_bounds()[k]
+    for field, pair in ((4, (CUT - 101, 257)), (8, (CUT + 169, 8)), (9, (CUT + 177, -1))):
+        want, flat = check_fields(dec, raw, [(a - 1, b - a + 2)], field, seed=seed)
+        assert flat[1:] == [pair]
+    # a capacity that is reached above 2^32
+    span = [(far.t1_at + 100, len(far.t1) - 100)]
+    lower = k - raw.line_of(span[0][0])
+    want, flat = check_fields(dec, raw, span, 4, seed=seed, capacity=lower + 2, room=lower + 50)
+    assert len(flat) > lower + 50 and flat[lower - 1][0] < CUT < flat[lower + 1][0]
+
+
+@pytest.mark.parametrize("seed", [None, 0, 1], ids=["spans", "keys-seed0", "keys-seed1"])
+def test_fields_of_the_whole_output(far, far_batch, seed):
+    dec, _, total = far_batch
+    raw = far.raw
+    t1_line, k = raw.line_of(far.t1_at), raw.line_of(CUT)
+    for field in (0, 3) if seed is None else (0, 4):
+        (summary,), flat = check_fields(dec, raw, [(0, total)], field, seed=seed)
+        assert flat == raw.field_spans(field, b" ") and len(flat) == 39_214
+        assert sum(1 for start, _ in flat if start > CUT) > 13_000
+        if seed is not None:
+            assert summary["keys"] == raw.field_keys(field, b" ", b"\n", seed)
+        if field == 0:
+            assert flat[t1_line] == (len(far.t0), 4_293_517_388)           # the largest field of the file
+        if field == 4:
+            assert flat[k] == (CUT - 101, 257)
+    # no newline from the first filler's first byte to the end: nothing is closed, the tail is the span, all above 2^31
+    span = (len(far.t0), total - len(far.t0))
+    (summary,), flat = check_fields(dec, raw, [span], 0, delimiter=b"\t", newline=b"\0", seed=seed)
+    assert flat == [] and summary["count"] == 0 and summary["tail_field_start"] == 0 and summary["tail_field_end"] is None
+    # ... and with the spaces as delimiters: field 1 starts behind the 94 fillers, above 2^32 - 2^21 of the span
+    (summary,), flat = check_fields(dec, raw, [span], 1, newline=b"\0", seed=seed)
+    assert summary["tail_field_start"] == far.t1_at + 17 - span[0] and summary["tail_field_end"] > summary["tail_field_start"]
+    # the last line of the whole output is closed: the tail starts at the end, above 2^32
+    (summary,), _ = check_fields(dec, raw, [(5, total - 5)], 0, seed=seed)
+    assert summary["tail_start"] == total - 5 > CUT and summary["tail_field_start"] == total - 5
+    # a span that ends inside the line across 2^32, behind its field 4: the tail's positions are above 2^32 of the span
+    (summary,), _ = check_fields(dec, raw, [(0, CUT + 170)], 4, seed=seed)
+    assert summary["tail_start"] == CUT - 131 and summary["tail_field_start"] == CUT - 101 and summary["tail_field_end"] == CUT + 156
+    (summary,), _ = check_fields(dec, raw, [(7, CUT + 170)], 8, seed=seed)
+    assert summary["tail_field_start"] == CUT + 169 - 7 > CUT and summary["tail_field_end"] is None
+    print(f"\ndevice memory after the whole-output span: {dec.device_memory()}")
+
+
+@pytest.mark.parametrize("ignore_case", [False, True], ids=["exact", "ignore-case"])
+def test_match_lines_around_2_32(native, far, far_batch, ignore_case):
+    dec, _, total = far_batch
+    raw = far.raw
+    aligned, fixed = query_spans(far)
+    k = raw.line_of(CUT)
+    check_match_lines(native, dec, raw, aligned, bigfiles.FAR_PATTERNS["class"], ignore_case=ignore_case)
+    for name in ("caret", "dollar", "across", "short", "nowhere"):
+        check_match_lines(native, dec, raw, fixed + aligned[len(name)::7], bigfiles.FAR_PATTERNS[name], ignore_case=ignore_case)
+    # the line across 2^32 as a body line, and entered in its middle (then the head map carries it)
+    a, b = raw.line_bounds()[k]
+    for name in ("caret", "dollar", "across"):
+        positions, lines = check_match_lines(native, dec, raw, [(a - 1, b - a + 2), (CUT, b - CUT + 1)], bigfiles.FAR_PATTERNS[name],
+                                             ignore_case=ignore_case)
+        assert lines == [k] and a <= positions[0] <= b
+    # a capacity that is reached above 2^32
+    span = [(far.t1_at + 100, len(far.t1) - 100)]
+    _, lines = check_match_lines(native, dec, raw, span, bigfiles.FAR_PATTERNS["class"], ignore_case=ignore_case)
+    lower = sum(1 for n in lines if n < k)
+    positions, _ = check_match_lines(native, dec, raw, span, bigfiles.FAR_PATTERNS["class"], ignore_case=ignore_case, capacity=lower + 2)
+    assert len(lines) > lower + 5 and positions[-1] > CUT > positions[lower - 1]
+
+
+def test_match_lines_of_the_whole_output(native, far, far_batch):
+    import regexgen as G
+    dec, _, total = far_batch
+    raw = far.raw
+    k, t1_line = raw.line_of(CUT), raw.line_of(far.t1_at)
+    # (a pass over the 4.39 GB takes about a second -- every chunk of a filler is all head, walked for every state -- so
+    # the patterns that need no filler are left to test_match_lines_around_2_32)
+    for name in ("across", "t2-only", "ascii-tail"):
+        pattern = bigfiles.FAR_PATTERNS[name]
+        positions, lines = check_match_lines(native, dec, raw, [(0, total)], pattern)
+        assert lines == [n for n in raw.regex_lines(pattern) if n > 0] and len(lines) == 1
+        if name == "across":
+            assert lines == [k] and CUT - 131 <= positions[0] <= CUT + 177
+        if name in ("across", "t2-only"):
+            assert positions[0] >= CUT                                      # the witness does not fit 32 bits
+        if name == "ascii-tail":
+            assert lines == [t1_line] and far.t1_at - 256 < positions[0] < far.t1_at + 100       # (a chunk's first byte may stand for it)
+    # X in T0, every filler, Y in T1, one line under another delimiter: the state behind X survives 66 000 tiles
+    pattern, newline = bigfiles.FAR_CARRIED
+    positions, lines = check_match_lines(native, dec, raw, [(0, total)], pattern, newline)
+    assert lines == [3] and far.t1_at - 256 < positions[0] < CUT
+    # no delimiter from the first filler's first byte to the end
+    span = (len(far.t0), total - len(far.t0))
+    for pattern, matched in ((rb"N3eDLe#16-MiXed\. qtl", True), (bigfiles.FAR_PATTERNS["nowhere"], False)):
+        head_maps, has_delimiter, exits, positions, counts = dec.match_lines([span], pattern, b"\0")
+        assert (head_maps[0][G.START] == G.MATCHED) == matched and has_delimiter == [False] and positions == [] and counts == [0]
+    print(f"\ndevice memory after the whole-output span: {dec.device_memory()}")
+
+
+def test_field_of_more_than_4_gib(native, far, far_batch):
+    """The same blocks in another order (bigfiles.long_field_batch): between T0's last byte and T2's first lie all 96 fillers,
+    more than 2^32 bytes of one line, closed inside the span.  Under newline b" " and delimiter b"\\n" its field 1 is larger
+    than 2^32 and does not start the line: k_fieldhash_finish raises x to a size with bits above 31 and multiplies a P(start)
+    that is not 0 by it; k_field_sizes subtracts across 2^32; the line's hash is carried over 66 000 tiles."""
+    blocks, raw = bigfiles.long_field_batch(far)
+    dec = native.Decoder(device=0, max_batch_blocks=1)
+    try:
+        dec.share_input(far_batch[0])
+        results, total = dec.decode_batch([bit for bit, _, _, _ in blocks])
+        assert total == raw.size and [r["status"] for r in results] == [0] * len(blocks)
+        span = (len(far.t0) - 3_000, total - 2 * len(far.t0) + 6_000)
+        at = raw.line_of(len(far.t0), b" ") - raw.line_of(span[0], b" ") - 1           # of the long line among the closed ones
+        for seed in (0, 1):
+            x = bigfiles.linehash.base(seed)
+            (summary, hashes), = check_hash_lines(dec, raw, [span], newline=b" ", seed=seed)
+            a, b = raw.line_bounds(b" ")[raw.line_of(len(far.t0), b" ")]
+            assert b - a > CUT and hashes[at + 1] == raw.part(a, b, x)[0]
+            for field in (0, 1, 2):
+                (summary,), flat = check_fields(dec, raw, [span], field, delimiter=b"\n", newline=b" ", seed=seed)
+                if field == 1:
+                    assert flat[at + 1] == (len(far.t0), b - len(far.t0)) and flat[at + 1][1] > CUT
+                    assert summary["keys"][at + 1] == raw.part(len(far.t0), b, x)[0] not in (0, bigfiles.fieldhash.MISSING)
+        (summary,), flat = check_fields(dec, raw, [span], 1, delimiter=b"\n", newline=b" ")
+        assert flat[at + 1][1] > CUT
+        memory = dec.device_memory()
+        print(f"\nthe batch with one field of {flat[at + 1][1]} bytes: device memory {memory}")
+        assert memory["scratch_bytes"] + memory["output_bytes"] < 32 << 30
+    finally:
+        dec.close()
+
+
+def test_device_memory_after_the_line_queries(far_batch):
+    memory = far_batch[0].device_memory()
+    print(f"\nfar batch after the line queries: device memory {memory}")
+    assert memory["scratch_bytes"] + memory["output_bytes"] < 32 << 30
+
+
 # ----------------------------------------------------------------------------------------- B. the reader on far_file()
 
 @pytest.fixture(scope="module")
@@ -566,6 +885,170 @@ def test_reader_grep(far, reader, ignore_case):
     assert k in f.grep(n["n256"], first, t1_end, ignore_case=ignore_case)[0]
 
 
+# The line queries of the reader.  A whole-file call is one pass over all 129 blocks (at parallelization 1 one launch per
+# block: about 2 s); every test makes at most two of them per reader and addresses line ranges otherwise.
+
+REGEX_CASES = ("caret", "dollar", "across", "t2-only", "ascii-tail", "carried")
+
+
+@pytest.mark.parametrize("name", REGEX_CASES)
+def test_reader_regex(far, reader, name):
+    """count_matching_lines_regex, exact and folded: two passes.  `carried` has X in T0 and Y in T1 of one line under
+    another delimiter: "X was seen" must survive every launch in between."""
+    f, mode = reader
+    pattern, newline = bigfiles.FAR_CARRIED if name == "carried" else (bigfiles.FAR_PATTERNS[name], b"\n")
+    for ignore_case in (False, True):
+        want = far.raw.regex_lines(pattern, newline, ignore_case)
+        assert len(want) >= 1
+        assert f.count_matching_lines_regex(pattern, newline, ignore_case=ignore_case) == len(want), (name, ignore_case)
+
+
+def test_reader_grep_regex(far, reader):
+    """grep_regex returns lines, so the pattern is one whose matching lines are all short: once with a limit that is
+    reached above 2^32, once folded and without one -- the last lines then lie in T2, whose launches start above 2^32, so the
+    witnesses of those launches are moved to file offsets that do not fit 32 bits before they are ranked."""
+    f, mode = reader
+    raw = far.raw
+    bounds = raw.line_bounds()
+    pattern = bigfiles.FAR_PATTERNS["short"]
+    for ignore_case in (False, True):
+        want = raw.regex_lines(pattern, b"\n", ignore_case)
+        assert all(bounds[k][1] - bounds[k][0] < 1000 for k in want)
+        lower = sum(1 for k in want if bounds[k][1] < CUT)
+        in_t2 = sum(1 for k in want if bounds[k][0] > far.t2_at)
+        assert lower >= 3 and in_t2 >= 3 and len(want) > lower + 2 + in_t2
+        limit = None if ignore_case else lower + 2
+        numbers, lines = f.grep_regex(pattern, limit, ignore_case=ignore_case)
+        assert numbers.dtype == np.uint64 and numbers.tolist() == want[:limit]
+        assert lines == [raw.slice(bounds[k][0], bounds[k][1] + 1) for k in want[:limit]]
+        assert bounds[int(numbers[-1])][1] > (far.t2_at if ignore_case else CUT)
+
+
+def line_windows(far):
+    """(first, count) around the line across 2^32, in T2 and clipped at the end; none holds a line with a filler."""
+    raw = far.raw
+    n, k, t2_line = len(raw.line_bounds()), raw.line_of(CUT), raw.line_of(far.t2_at)
+    windows = [(k - 2, 5), (k, 1), (k + 1, 300), (t2_line + 1, 40), (t2_line + 3_000, 2_000), (n - 3, 10), (n, 4), (k - 700, 701)]
+    t1_line = raw.line_of(far.t1_at)
+    assert all(not first <= line < first + count for first, count in windows for line in (t1_line, t2_line))
+    return windows
+
+
+def test_reader_line_hashes(far, reader):
+    f, mode = reader
+    raw = far.raw
+    for seed in (0, 1):
+        want = raw.line_hashes(b"\n", seed)
+        got = f.line_hashes(seed=seed)                       # the one whole-file pass of this seed
+        assert got.dtype == np.uint64 and got.tolist() == want
+        for first, count in line_windows(far):
+            assert f.line_hashes(first, count, seed=seed).tolist() == want[first:first + count], (first, count, seed)
+    t1_line = raw.line_of(far.t1_at)
+    a, b = raw.line_bounds()[t1_line]
+    assert b - a > CUT - (1 << 21) and int(got[t1_line]) == raw.part(a, b, bigfiles.linehash.base(1))[0]      # the closed form
+
+
+def test_reader_distinct_lines(far, reader):
+    f, mode = reader
+    raw = far.raw
+    assert f.count_distinct_lines() == len(raw.first_occurrences(b"\n", 0)) == 26_130
+    got = f.first_occurrences(seed=1)
+    want = raw.first_occurrences(b"\n", 1)
+    assert got.dtype == np.uint64 and got.tolist() == want
+    t2_line = raw.line_of(far.t2_at)
+    assert [k for k in want if k >= t2_line] == [t2_line]            # T2 repeats T0: only its first line is new
+
+
+def test_reader_fields(far, reader):
+    f, mode = reader
+    raw = far.raw
+    k, t1_line = raw.line_of(CUT), raw.line_of(far.t1_at)
+    for field in (0, 3):                                             # the two whole-file passes
+        want = raw.field_spans(field, b" ")
+        starts, sizes = f.field_spans(field, delimiter=b" ")
+        assert starts.dtype == np.uint64 and sizes.dtype == np.int64
+        assert list(zip(starts.tolist(), sizes.tolist())) == want, field
+    assert far.t1_at < want[t1_line][0] < CUT                        # field 3 of the line with the 94 fillers lies in T1
+    want = raw.field_spans(0, b" ")
+    starts, sizes = f.field_spans(0, t1_line, 1, delimiter=b" ")
+    assert (int(starts[0]), int(sizes[0])) == want[t1_line] == (len(far.t0), 4_293_517_388)
+    # field 0 starts where its line starts
+    asked = [0, 1, k - 1, k, k + 1, len(want) - 1]
+    starts, _ = f.field_spans(0, k - 1, 3, delimiter=b" ")
+    assert starts.tolist() == f.line_starts([k - 1, k, k + 1]).tolist() == [raw.line_bounds()[i][0] for i in (k - 1, k, k + 1)]
+    assert f.line_starts(asked).tolist() == [want[i][0] for i in asked]
+    for field in (3, 4, 8, 9, 1023):
+        want = raw.field_spans(field, b" ")
+        for first, count in line_windows(far):
+            starts, sizes = f.field_spans(field, first, count, delimiter=b" ")
+            assert list(zip(starts.tolist(), sizes.tolist())) == want[first:first + count], (field, first, count)
+            if field in (3, 4, 9) and count <= 300:
+                values = [None if n < 0 else raw.slice(s, s + n) for s, n in want[first:first + count]]
+                assert f.read_fields(field, first, count, delimiter=b" ") == values, (field, first, count)
+    assert f.read_fields(4, k, 1, delimiter=b" ") == [b"." + bigfiles.needles()["n256"]]            # across 2^32
+    want = raw.field_spans(1, b"e")
+    for first, count in line_windows(far)[:4]:
+        starts, sizes = f.field_spans(1, first, count, delimiter=b"e")
+        assert list(zip(starts.tolist(), sizes.tolist())) == want[first:first + count], (first, count)
+
+
+@pytest.mark.parametrize("seed", [0, 1])
+def test_reader_field_hashes(far, reader, seed):
+    f, mode = reader
+    raw = far.raw
+    for field in (0, 3):                                             # the two whole-file passes
+        want = raw.field_keys(field, b" ", b"\n", seed)
+        got = f.field_hashes(field, delimiter=b" ", seed=seed)
+        assert got.dtype == np.uint64 and got.tolist() == want, (field, seed)
+    for field in (4, 8, 9, 1023):
+        want = raw.field_keys(field, b" ", b"\n", seed)
+        for first, count in line_windows(far):
+            assert f.field_hashes(field, first, count, delimiter=b" ", seed=seed).tolist() == want[first:first + count], (field, first)
+    k = raw.line_of(CUT)
+    assert int(f.field_hashes(4, k, 1, delimiter=b" ", seed=seed)[0]) == bigfiles.linehash.line_hash(b"." + bigfiles.needles()["n256"], seed)
+    assert int(f.field_hashes(9, k, 1, delimiter=b" ", seed=seed)[0]) == bigfiles.fieldhash.MISSING
+
+
+def test_reader_field_groups(far, reader):
+    f, mode = reader
+    raw = far.raw
+    k, t2_line = raw.line_of(CUT), raw.line_of(far.t2_at)
+    lines, counts, missing, spans = raw.field_groups(3, b" ")
+    got = f.count_by_field(3, delimiter=b" ")                        # one whole-file pass
+    assert got[0].dtype == got[1].dtype == np.uint64
+    assert (got[0].tolist(), got[1].tolist(), got[2]) == (lines, counts, missing)
+    assert any(start > CUT for start, _ in spans) and sum(counts) + missing == 39_214
+    for field, first, count, seed in ((4, k - 700, 1_400, 0), (0, t2_line + 1, 5_000, 1), (9, k - 5, 10, 0), (3, 39_000, 1_000, 1)):
+        lines, counts, missing, spans = raw.field_groups(field, b" ", b"\n", seed, first, count)
+        got = f.count_by_field(field, first, count, delimiter=b" ", seed=seed)
+        assert (got[0].tolist(), got[1].tolist(), got[2]) == (lines, counts, missing), (field, first, count)
+        # value_counts fetches the chosen groups' values: none of them is the field of 4.3 GB
+        assert all(size < 1000 for _, size in spans)
+        ranked = raw.value_counts(field, None, b" ", b"\n", seed, first, count)
+        assert f.value_counts(field, 7, first, count, delimiter=b" ", seed=seed) == ranked[:7], (field, first, count)
+        assert f.value_counts(field, None, first, count, delimiter=b" ", seed=seed) == ranked
+    ranked = raw.value_counts(4, 3, b" ", b"\n", 0, k - 700, 1_400)
+    assert len(ranked) == 3 and (b"." + bigfiles.needles()["n256"], 1) in raw.value_counts(4, None, b" ", b"\n", 0, k - 700, 1_400)
+
+
+def test_reader_one_line_of_more_than_4_gib(native, far, far_path):
+    """Under a delimiter that is in no text the whole file is one unterminated line of more than 2^32 bytes: its hash is
+    composed on the host from every launch's (h, x^len), its field 0 has a size above 2^32 and the same key."""
+    raw = far.raw
+    with native.open(far_path, parallelization=4) as f:
+        f.set_block_offsets(far.map)
+        for seed in (0, 1):
+            whole = raw.part(0, raw.size, bigfiles.linehash.base(seed))[0]
+            assert f.line_hashes(newline=b"\0", seed=seed).tolist() == [whole] == raw.line_hashes(b"\0", seed)
+            assert f.field_hashes(0, delimiter=b"\t", newline=b"\0", seed=seed).tolist() == [whole]
+        starts, sizes = f.field_spans(0, delimiter=b"\t", newline=b"\0")
+        assert (starts.tolist(), sizes.tolist()) == ([0], [raw.size]) and raw.size > CUT
+        starts, sizes = f.field_spans(1, delimiter=b" ", newline=b"\0")
+        assert list(zip(starts.tolist(), sizes.tolist())) == raw.field_spans(1, b" ", b"\0")
+        assert f.count_matching_lines_regex(bigfiles.FAR_PATTERNS["t2-only"], b"\0") == 1
+        assert f.count_matching_lines_regex(bigfiles.FAR_PATTERNS["nowhere"], b"\0") == 0
+
+
 DEVICE_CHILD = r"""
 import pickle, sys
 import torch                      # first: one HIP runtime in the process, as bench.py does
@@ -624,6 +1107,87 @@ def test_device_destinations(far, far_path, tmp_path):
     print("\n" + run.stdout.strip())
 
 
+QUERY_CHILD = r"""
+import pickle, sys
+import torch                      # first: one HIP runtime in the process, as bench.py does
+sys.path.insert(0, sys.argv[1])
+import indexed_bzip2_amd as m
+
+with open(sys.argv[3], "rb") as f:
+    case = pickle.load(f)
+with m.open(sys.argv[2], parallelization=4) as f:
+    f.set_block_offsets(case["map"])
+    pattern, limit, numbers, lines = case["grep_regex"]
+    got_numbers, data, bounds = f.grep_regex_to_tensor(pattern, limit)
+    assert got_numbers.tolist() == numbers and data.is_cuda and data.dtype == torch.uint8
+    host = bytes(data.cpu().numpy())
+    assert [host[int(bounds[i]):int(bounds[i + 1])] for i in range(len(numbers))] == lines
+    for first, count, seed, want in case["line_hashes"]:
+        got = f.line_hashes_to_tensor(first, count, seed=seed)
+        assert got.is_cuda and got.dtype == torch.int64 and got.tolist() == want, (first, count, seed)
+    for field, first, count, seed, spans, keys, values in case["fields"]:
+        starts, sizes = f.field_spans_to_tensor(field, first, count, delimiter=b" ")
+        assert starts.is_cuda and sizes.is_cuda and starts.dtype == sizes.dtype == torch.int64
+        assert list(zip(starts.tolist(), sizes.tolist())) == spans, (field, first, count)
+        got = f.field_hashes_to_tensor(field, first, count, delimiter=b" ", seed=seed)
+        assert got.is_cuda and got.dtype == torch.int64 and got.tolist() == keys, (field, first, count, seed)
+        if values is not None:
+            data, bounds = f.read_fields_to_tensor(field, first, count, delimiter=b" ")
+            host = bytes(data.cpu().numpy())
+            assert data.is_cuda and [host[int(bounds[i]):int(bounds[i + 1])] for i in range(len(values))] == values, (field, first)
+print("query destinations ok")
+"""
+
+
+def test_query_device_destinations(far, far_path, tmp_path):
+    """grep_regex_to_tensor, line_hashes_to_tensor, field_spans_to_tensor, read_fields_to_tensor and
+    field_hashes_to_tensor at parallelization 4 with the imported map, in a process that starts torch first; the
+    expected values are computed here, from VirtualRaw."""
+    import pickle
+    import sys
+    raw = far.raw
+    bounds = raw.line_bounds()
+    k = raw.line_of(CUT)
+    pattern = bigfiles.FAR_PATTERNS["short"]
+    matching = raw.regex_lines(pattern)
+    limit = sum(1 for n in matching if bounds[n][1] < CUT) + 2
+    assert len(matching) > limit and all(bounds[n][1] - bounds[n][0] < 1000 for n in matching)
+    case = {"map": far.map,
+            "grep_regex": (pattern, limit, matching[:limit], [raw.slice(bounds[n][0], bounds[n][1] + 1) for n in matching[:limit]]),
+            "line_hashes": [(0, None, 1, raw.line_hashes(b"\n", 1))], "fields": []}
+    for first, count in line_windows(far):
+        case["line_hashes"].append((first, count, 0, raw.line_hashes(b"\n", 0)[first:first + count]))
+    for field, first, count, seed in ((0, 0, None, 0), (3, 0, None, 1), (4, k - 2, 5, 1), (9, k - 2, 5, 0), (4, k + 1, 300, 0)):
+        spans, keys = raw.field_spans(field, b" "), raw.field_keys(field, b" ", b"\n", seed)
+        last = len(spans) if count is None else first + count
+        values = None if count is None else [b"" if n < 0 else raw.slice(s, s + n) for s, n in spans[first:last]]     # a missing field has size 0
+        case["fields"].append((field, first, count, seed, spans[first:last], keys[first:last], values))
+    (tmp_path / "case.pickle").write_bytes(pickle.dumps(case))
+    run = subprocess.run([sys.executable, "-c", QUERY_CHILD, ROOT, far_path, str(tmp_path / "case.pickle")],
+                         capture_output=True, text=True, timeout=600)
+    assert run.returncode == 0, (run.stdout[-2000:], run.stderr[-4000:])
+    assert "query destinations ok" in run.stdout
+
+
+def tool_queries_on_far(far, far_path):
+    """--grep-regex, --count-distinct-lines and --count-by-field: one pass over the file each."""
+    raw = far.raw
+    bounds = raw.line_bounds()
+    pattern = bigfiles.FAR_PATTERNS["short"]
+    matching = raw.regex_lines(pattern)
+    assert all(bounds[n][1] - bounds[n][0] < 1000 for n in matching) and bounds[matching[-1]][0] > CUT
+    run = subprocess.run([CLI, "-P", "4", "--grep-regex", pattern.decode(), "--line-number", far_path], capture_output=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert run.stdout == b"".join(b"%d:" % (n + 1) + raw.slice(bounds[n][0], bounds[n][1] + 1) for n in matching)
+    run = subprocess.run([CLI, "-P", "4", "--count-distinct-lines", far_path], capture_output=True, timeout=600)
+    assert run.returncode == 0 and run.stdout == b"%d\n" % len(raw.first_occurrences()), run.stderr[-2000:]
+    lines, counts, missing, spans = raw.field_groups(3, b" ")
+    assert all(size < 1000 for _, size in spans)                     # the tool prints the values
+    run = subprocess.run([CLI, "-P", "4", "--count-by-field", "3", "--field-delimiter", " ", far_path], capture_output=True, timeout=600)
+    assert run.returncode == 0, run.stderr[-2000:]
+    assert run.stdout == b"".join(b"%d\t%s\n" % (count, value) for value, count in raw.value_counts(3, None, b" "))
+
+
 def test_tool_on_far(far, far_path, tmp_path):
     raw, n = far.raw, bigfiles.needles()
     newlines = raw.newline_offsets()
@@ -652,6 +1216,7 @@ def test_tool_on_far(far, far_path, tmp_path):
     run = subprocess.run([CLI, "-P", "4", "-t", "-L", str(tmp_path / "damaged.txt"), "--", str(tmp_path / "damaged.bz2")],
                          capture_output=True, timeout=600)
     assert run.returncode != 0
+    tool_queries_on_far(far, far_path)
 
 
 # ------------------------------------------------------------------- C. deep_file(): bit offsets of 2^32 and more

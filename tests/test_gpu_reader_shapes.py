@@ -228,13 +228,54 @@ def check_fields(f, e, shape):
     assert f.field_spans(0)[0].tolist() == f.line_starts(range(e["n"])).tolist(), "field_spans(0) against line_starts"
 
 
+def groups_of(e, j, dl, first=0, count=None):
+    return e["groups"][(j, dl)] if (first, count) == (0, None) else R.groups_of(e["values"][(j, dl)], first, count)
+
+
+def grouped(got):
+    lines, counts, missing = got
+    assert lines.dtype == counts.dtype == np.uint64 and isinstance(missing, int)
+    return lines.tolist(), counts.tolist(), missing
+
+
+def check_field_hashes(f, e, shape):
+    windows = windows_of(e, shape)
+    for j, dl in R.FIELDS:
+        delimiter = bytes([dl])
+        for seed in R.SEEDS:
+            got = f.field_hashes(j, delimiter=delimiter, seed=seed)
+            assert got.dtype == np.uint64 and got.tolist() == e["keys"][(j, dl, seed)], "field_hashes(%d, delimiter=%r, seed=%d)" % (j, delimiter, seed)
+        for first, count in windows:
+            assert f.field_hashes(j, first, count, delimiter).tolist() == e["keys"][(j, dl, 0)][first:first + count], \
+                "field_hashes(%d, %d, %d, %r)" % (j, first, count, delimiter)
+        lines, counts, missing, ranked = groups_of(e, j, dl)
+        # (a whole-file call is one pass, hundreds of launches at parallelization 1: the second seed and the unlimited
+        # value_counts go to two of the six fields)
+        for seed in R.SEEDS if j in (1, 3) else R.SEEDS[:1]:
+            assert grouped(f.count_by_field(j, delimiter=delimiter, seed=seed)) == (lines, counts, missing), \
+                "count_by_field(%d, delimiter=%r, seed=%d)" % (j, delimiter, seed)
+        if j in (1, 3):
+            assert f.value_counts(j, delimiter=delimiter) == ranked, "value_counts(%d, delimiter=%r)" % (j, delimiter)
+        assert f.value_counts(j, 5, delimiter=delimiter, seed=1) == ranked[:5], "value_counts(%d, 5, delimiter=%r, seed=1)" % (j, delimiter)
+    first, count = windows[1]
+    assert f.field_hashes(3, first, count, seed=1).tolist() == e["keys"][(3, TAB, 1)][first:first + count], "field_hashes(3, %d, %d, seed=1)" % (first, count)
+    for first, count in windows[:9] + windows[-3:]:
+        for j, dl in ((3, TAB), (1, ord(","))):
+            lines, counts, missing, ranked = groups_of(e, j, dl, first, count)
+            label = "(%d, %d, %d, %r)" % (j, first, count, bytes([dl]))
+            assert grouped(f.count_by_field(j, first, count, bytes([dl]))) == (lines, counts, missing), "count_by_field" + label
+            assert f.value_counts(j, 3, first, count, bytes([dl])) == ranked[:3], "value_counts limit 3 " + label
+
+
 def launches_by_call(f, e):
     """{call: launches it made}, from statistics()["batches"] before and after: whole-file calls of one pass each."""
     counts = {}
     for name, call in (("count_matches", lambda: f.count_matches(NEEDLE)),
                        ("count_matching_lines_regex", lambda: f.count_matching_lines_regex(R.FIELD_REGEX)),
                        ("line_hashes", lambda: f.line_hashes()), ("field_spans", lambda: f.field_spans(3)),
-                       ("grep_regex", lambda: f.grep_regex(R.REGEX_PATTERNS[0])), ("read_fields", lambda: f.read_fields(3))):
+                       ("field_hashes", lambda: f.field_hashes(3)), ("count_by_field", lambda: f.count_by_field(3)),
+                       ("grep_regex", lambda: f.grep_regex(R.REGEX_PATTERNS[0])), ("read_fields", lambda: f.read_fields(3)),
+                       ("value_counts", lambda: f.value_counts(3))):
         before = f.statistics()["batches"]
         call()
         counts[name] = f.statistics()["batches"] - before
@@ -245,7 +286,9 @@ def launches_by_call(f, e):
 @pytest.mark.parametrize("shape", SHAPES, ids=shape_id)
 def test_every_call(native, world, monkeypatch, shape, variant):
     """The time follows the launches: about 47 000 of one block each at parallelization 1 (34 s on an MI355X, 0.7 ms per
-    launch on one context), 16 000 at 3 (7.5 s), 9 400 at 5 on four contexts (3.5 s), under 1 000 from 64 on (1 s)."""
+    launch on one context), 16 000 at 3 (7.5 s), 9 400 at 5 on four contexts (3.5 s), under 1 000 from 64 on (1 s).
+    With field_hashes, count_by_field and value_counts -- about 30 more whole-file calls -- the measured times are 50 s, 12 to
+    15 s, 6 s and 1 s."""
     e = world[variant]
     with open_shape(native, monkeypatch, e["path"], shape) as f:
         check_lines_and_ranges(f, e, shape)
@@ -253,9 +296,9 @@ def test_every_call(native, world, monkeypatch, shape, variant):
         counts = launches_by_call(f, e)
         print("launches %s %s: %r" % (shape_id(shape), variant, counts))
         launches = len(R.launches_of(e["block_starts"], e["size"], cap_of(shape)))
-        for name in ("count_matches", "count_matching_lines_regex", "line_hashes", "field_spans"):
+        for name in ("count_matches", "count_matching_lines_regex", "line_hashes", "field_spans", "field_hashes", "count_by_field"):
             assert counts[name] == launches, (name, counts, launches)
-        assert counts["grep_regex"] > launches and counts["read_fields"] > launches
+        assert counts["grep_regex"] > launches and counts["read_fields"] > launches and counts["value_counts"] > launches
         statistics = f.statistics()
         if shape[2]:
             assert statistics["input_resident"] == 0 and statistics["input_bytes_uploaded"] > 0
@@ -266,6 +309,7 @@ def test_every_call(native, world, monkeypatch, shape, variant):
         check_regex(f, e, shape)
         check_hashes(f, e, shape)
         check_fields(f, e, shape)
+        check_field_hashes(f, e, shape)
         assert f.tell() == 0, "a query moved the position"
         assert f.read() == e["raw"], "read()"
         assert f.block_offsets() == e["block_map"], "block_offsets()"
@@ -309,6 +353,18 @@ def query_operations(f, e, shape, rng):
         ("field_spans(%d, %d, %d, %r)" % (j, first, count, bytes([dl])), lambda: pairs(f.field_spans(j, first, count, bytes([dl]))),
          e["spans"][(j, dl)][first:first + count]),
         ("read_fields(3, %d, %d)" % (first, count), lambda: f.read_fields(3, first, count), e["field3"][first:first + count]),
+        ("field_hashes(%d, %d, %d, %r, seed=%d)" % (j, first, count, bytes([dl]), seed),
+         lambda: f.field_hashes(j, first, count, bytes([dl]), seed=seed).tolist(), e["keys"][(j, dl, seed)][first:first + count]),
+        ("field_hashes(%d, delimiter=%r, seed=%d)" % (j, bytes([dl]), seed),
+         lambda: f.field_hashes(j, delimiter=bytes([dl]), seed=seed).tolist(), e["keys"][(j, dl, seed)]),
+        ("count_by_field(%d, %d, %d, %r, seed=%d)" % (j, first, count, bytes([dl]), seed),
+         lambda: grouped(f.count_by_field(j, first, count, bytes([dl]), seed=seed)), groups_of(e, j, dl, first, count)[:3]),
+        ("count_by_field(%d, delimiter=%r, seed=%d)" % (j, bytes([dl]), seed),
+         lambda: grouped(f.count_by_field(j, delimiter=bytes([dl]), seed=seed)), groups_of(e, j, dl)[:3]),
+        ("value_counts(%d, %r, %d, %d, %r)" % (j, regex_limit, first, count, bytes([dl])),
+         lambda: f.value_counts(j, regex_limit, first, count, bytes([dl])), groups_of(e, j, dl, first, count)[3][:regex_limit]),
+        ("value_counts(%d, %r, delimiter=%r, seed=%d)" % (j, regex_limit, bytes([dl]), seed),
+         lambda: f.value_counts(j, regex_limit, delimiter=bytes([dl]), seed=seed), groups_of(e, j, dl)[3][:regex_limit]),
         ("grep_regex(%r, limit=%r, ignore_case=%r)" % (pattern, regex_limit, fold),
          lambda: (lambda got: (got[0].tolist(), got[1]))(f.grep_regex(pattern, limit=regex_limit, ignore_case=fold)),
          (want_regex[0][:regex_limit], want_regex[1][:regex_limit])),
@@ -409,8 +465,8 @@ FAILURE_SHAPES = [(1, None, False), (3, None, False), (64, None, False)]
 @pytest.mark.parametrize("shape", FAILURE_SHAPES, ids=shape_id)
 def test_damaged_block(native, world, monkeypatch, tmp_path, shape):
     """One byte flipped in the middle of a block, both true indexes imported: grep_regex, line_hashes, the distinct lines,
-    field_spans and read_fields serve what keeps clear of the block and fail, with the status and the bit offset of a plain
-    read, for what needs it -- and go on serving afterwards."""
+    field_spans, read_fields, field_hashes, count_by_field and value_counts serve what keeps clear of the block and fail,
+    with the status and the bit offset of a plain read, for what needs it -- and go on serving afterwards."""
     e = world["tail"]
     blocks = data_blocks_of(e)
     bits, next_bits, start, stop, _ = blocks[block_for_damage(e)]
@@ -425,17 +481,19 @@ def test_damaged_block(native, world, monkeypatch, tmp_path, shape):
         assert status != 0
     in_front, behind = line_of(e, start) - 15, line_of(e, stop) + 2          # windows of 10 lines clear of the block
     inside = line_of(e, start) + 2
-    hashes, spans, field3 = e["hashes"][0], e["spans"][(3, TAB)], e["field3"]
+    hashes, spans, field3, keys = e["hashes"][0], e["spans"][(3, TAB)], e["field3"], e["keys"][(3, TAB, 0)]
 
     def served(f):
-        return [(f.line_hashes(first, 10).tolist(), pairs(f.field_spans(3, first, 10)), f.read_fields(3, first, 10))
+        return [(f.line_hashes(first, 10).tolist(), pairs(f.field_spans(3, first, 10)), f.read_fields(3, first, 10),
+                 f.field_hashes(3, first, 10).tolist(), grouped(f.count_by_field(3, first, 10)), f.value_counts(3, None, first, 10))
                 for first in (in_front, behind)]
 
     with open_shape(native, monkeypatch, str(bad), shape) as f:
         f.set_block_offsets(e["block_map"])
         f.set_line_offsets(e["line_index"])
         before = served(f)
-        assert before == [(hashes[k:k + 10], spans[k:k + 10], field3[k:k + 10]) for k in (in_front, behind)]
+        assert before == [(hashes[k:k + 10], spans[k:k + 10], field3[k:k + 10], keys[k:k + 10], groups_of(e, 3, TAB, k, 10)[:3],
+                           groups_of(e, 3, TAB, k, 10)[3]) for k in (in_front, behind)]
         failing = [("grep_regex", lambda: f.grep_regex(R.REGEX_PATTERNS[0])),
                    ("count_matching_lines_regex", lambda: f.count_matching_lines_regex(R.FIELD_REGEX)),
                    ("line_hashes()", lambda: f.line_hashes()), ("line_hashes(seed=1)", lambda: f.line_hashes(seed=1)),
@@ -446,7 +504,15 @@ def test_damaged_block(native, world, monkeypatch, tmp_path, shape):
                    ("field_spans(3, inside, 2)", lambda: f.field_spans(3, inside, 2)),
                    ("read_fields(3, inside, 2)", lambda: f.read_fields(3, inside, 2)),
                    ("line_hashes(across)", lambda: f.line_hashes(in_front, behind - in_front)),
-                   ("field_spans(across)", lambda: f.field_spans(0, in_front, behind - in_front))]
+                   ("field_spans(across)", lambda: f.field_spans(0, in_front, behind - in_front)),
+                   ("field_hashes(3)", lambda: f.field_hashes(3)), ("field_hashes(1, ',', seed=1)", lambda: f.field_hashes(1, delimiter=b",", seed=1)),
+                   ("count_by_field(3)", lambda: f.count_by_field(3)), ("value_counts(3)", lambda: f.value_counts(3)),
+                   ("value_counts(3, 2)", lambda: f.value_counts(3, 2)),
+                   ("field_hashes(3, inside, 2)", lambda: f.field_hashes(3, inside, 2)),
+                   ("count_by_field(3, inside, 2)", lambda: f.count_by_field(3, inside, 2)),
+                   ("value_counts(3, inside, 2)", lambda: f.value_counts(3, None, inside, 2)),
+                   ("field_hashes(across)", lambda: f.field_hashes(0, in_front, behind - in_front)),
+                   ("count_by_field(across)", lambda: f.count_by_field(0, in_front, behind - in_front))]
         for k, (name, call) in enumerate(failing):
             with pytest.raises(native.Bz2Error) as failure:
                 call()
@@ -456,6 +522,7 @@ def test_damaged_block(native, world, monkeypatch, tmp_path, shape):
             first = (in_front, behind)[k % 2]
             assert f.line_hashes(first, 10).tolist() == hashes[first:first + 10], "line_hashes behind the failure of " + name
             assert pairs(f.field_spans(3, first, 10)) == spans[first:first + 10], "field_spans behind the failure of " + name
+            assert f.field_hashes(3, first, 10).tolist() == keys[first:first + 10], "field_hashes behind the failure of " + name
         assert served(f) == before
         # (a read() fills a buffer of 1 MiB, more than the file: it would ask for the damaged block)
         assert f.tell() == 0 and f.read_ranges([(0, 1000), (stop, 700)]) == [e["raw"][:1000], e["raw"][stop:stop + 700]]
@@ -470,7 +537,8 @@ def block_for_lie(e):
 
 @pytest.mark.parametrize("shape", FAILURE_SHAPES, ids=shape_id)
 def test_lying_line_index(native, world, monkeypatch, shape):
-    """The imported line index gives block b one delimiter more and block b + 1 one fewer: line_hashes and field_spans of a
+    """The imported line index gives block b one delimiter more and block b + 1 one fewer: line_hashes, field_spans,
+    read_fields, field_hashes, count_by_field and value_counts of a
     window that needs block b fail with status 106 and say which block, what was promised and what was counted; a window
     clear of both blocks is served, and so is everything once the true index is back."""
     e = world["tail"]
@@ -483,21 +551,28 @@ def test_lying_line_index(native, world, monkeypatch, shape):
     failing = (true_index[start] + 3, 4)                                       # lines that lie inside block b
     clear = (true_index[blocks[b - 1][2]] + 2, 3)                              # ... inside block b - 1
     assert true_index[following] - true_index[start] == held and failing[0] + failing[1] < true_index[following] - 2
-    hashes, spans = e["hashes"][0], e["spans"][(3, TAB)]
+    hashes, spans, keys = e["hashes"][0], e["spans"][(3, TAB)], e["keys"][(3, TAB, 0)]
     message = "decoded offset %d %d delimiters, it holds %d" % (start, held + 1, held)
     with open_shape(native, monkeypatch, e["path"], shape) as f:
         f.set_block_offsets(e["block_map"])
         f.set_line_offsets(lying)
         for name, call in (("line_hashes", lambda: f.line_hashes(*failing)), ("field_spans", lambda: f.field_spans(3, *failing)),
-                           ("read_fields", lambda: f.read_fields(3, *failing))):
+                           ("read_fields", lambda: f.read_fields(3, *failing)), ("field_hashes", lambda: f.field_hashes(3, *failing)),
+                           ("count_by_field", lambda: f.count_by_field(3, *failing)),
+                           ("value_counts", lambda: f.value_counts(3, None, *failing))):
             with pytest.raises(native.Bz2Error) as failure:
                 call()
             assert failure.value.status == 106 and "line index" in str(failure.value), name
             assert message in str(failure.value), (name, str(failure.value))
             assert f.line_hashes(*clear).tolist() == hashes[clear[0]:clear[0] + clear[1]], "line_hashes clear of the lie"
             assert pairs(f.field_spans(3, *clear)) == spans[clear[0]:clear[0] + clear[1]], "field_spans clear of the lie"
+            assert f.field_hashes(3, *clear).tolist() == keys[clear[0]:clear[0] + clear[1]], "field_hashes clear of the lie"
+            assert grouped(f.count_by_field(3, *clear)) == groups_of(e, 3, TAB, *clear)[:3], "count_by_field clear of the lie"
         f.set_line_offsets(true_index)
         assert f.line_hashes(*failing).tolist() == hashes[failing[0]:failing[0] + failing[1]]
         assert pairs(f.field_spans(3, *failing)) == spans[failing[0]:failing[0] + failing[1]]
         assert f.read_fields(3, *failing) == e["field3"][failing[0]:failing[0] + failing[1]]
+        assert f.field_hashes(3, *failing).tolist() == keys[failing[0]:failing[0] + failing[1]]
+        assert grouped(f.count_by_field(3, *failing)) == groups_of(e, 3, TAB, *failing)[:3]
+        assert f.value_counts(3, None, *failing) == groups_of(e, 3, TAB, *failing)[3]
         assert f.tell() == 0 and f.read(1000) == e["raw"][:1000]

@@ -115,6 +115,42 @@ def test_launch_boundaries(c, cap):
     assert later >= 1, "no match wholly in a later launch than its line's start"
 
 
+@pytest.mark.parametrize("cap", R.CAPS)
+def test_field_3_across_a_launch_boundary(c, cap):
+    """field_hashes patches the one line per seam on the host from P(end) - P(start) * x^(end - start): for every cap at
+    least one line has its field 3 start in one launch and end in a later one, so P(start) and P(end) come from different
+    launches."""
+    boundaries = R.boundaries_of(c["block_starts"], cap)
+    for j in (3,):
+        across = [(start, size) for start, size in c["spans"][(j, TAB)] if size > 0 and any(start < b < start + size for b in boundaries)]
+        assert len(across) >= 1, "no field %d across a launch boundary at cap %d" % (j, cap)
+    # ... and, but for the few launches of cap 64, one whose line starts in a launch of its own: three launches in one key
+    launches = R.launches_of(c["block_starts"], len(c["raw"]), cap)
+    three = 0
+    for (start, size), line_start in zip(c["spans"][(3, TAB)], c["line_starts"].tolist()):
+        if size > 0:
+            three += launch_of(launches, line_start) < launch_of(launches, start) < launch_of(launches, start + size - 1)
+    assert three >= 1 or cap == 64, "no line whose start, field 3's start and field 3's end lie in three launches at cap %d" % cap
+
+
+def test_field_keys_do_not_collide(c):
+    """Distinct values have distinct keys under every seed, none is MISSING's: grouping by key is grouping by value."""
+    import fieldhash as FH
+    for (j, dl), values in c["values"].items():
+        distinct = {value for value in values if value is not None}
+        for seed in R.SEEDS:
+            keys = c["keys"][(j, dl, seed)]
+            assert len(keys) == len(values) == len(c["lines"])
+            assert [key == FH.MISSING for key in keys] == [value is None for value in values]
+            assert len({key for key in keys if key != FH.MISSING}) == len(distinct), (j, dl, seed)
+        lines, counts, missing, ranked = c["groups"][(j, dl)]
+        assert lines == sorted(lines) and len(lines) == len(distinct) and sum(counts) + missing == len(values)
+        assert [count for _, count in ranked] == sorted(counts, reverse=True)
+    lines, counts, missing, ranked = c["groups"][(1, TAB)]
+    assert len(lines) > 100 and max(counts) > 20 and missing > 100                      # not trivial
+    assert c["groups"][(1023, TAB)] == ([], [], len(c["lines"]), [])
+
+
 def test_hashes_do_not_collide(c):
     """Distinct contents have distinct model hashes under every seed the GPU tests use, so a collision can neither hide a
     failure nor cause one."""
