@@ -16,7 +16,11 @@ VirtualRaw asserts both for every question it answers, so everything is computed
 The same holds for the four line queries (regex, line hashes, field spans, field hashes): newlines and delimiters come from
 the literals alone, a hash over a run comes in closed form (fieldhash.run_part), and a regular expression sees a line that
 holds runs with every run cut to RUN_SHRINK bytes.  That last step is exact only under the rule written at
-VirtualRaw.regex_lines; FAR_PATTERNS is the list of patterns the tests use, all inside it."""
+VirtualRaw.regex_lines; FAR_PATTERNS is the list of patterns the tests use, all inside it.
+
+For the encoder (at the end): far_pieces(), far_file()'s decoded bytes as buffers whose level-9 blocks are ONE launch with
+more than 2^32 bytes of input, deep_input(), incompressible bytes whose stream passes 2^32 bits, and the launch planner of
+csrc/bz2_compress.hpp restated in Python (plan_blocks, block_bytes, plan_launches)."""
 import bisect
 import bz2
 import functools
@@ -667,3 +671,89 @@ def deep_slice(deep, start, end):
     if end > deep.prefix_decoded:
         out += deep.tail.slice(max(start, deep.prefix_decoded) - deep.prefix_decoded, end - deep.prefix_decoded)
     return bytes(out)
+
+
+# ------------------------------------------------------------------------------------------------ inputs of the encoder
+# The same offsets the other way round: far_pieces() is far_file()'s decoded bytes as buffers to compress (one launch whose
+# input passes 2^32 bytes), deep_input() is incompressible bytes whose stream passes 2^32 bits.  The launch planner of
+# csrc/bz2_compress.hpp is restated below in plain Python; test_bigfiles.py compares its constants with the header.
+
+LAUNCH_BLOCKS = 512
+LAUNCH_BYTES = 12 << 30
+BYTES_PER_POSITION = 45
+GROUP_SIZE = 50
+
+
+@functools.lru_cache(maxsize=None)
+def _filler_array(value, length):
+    a = np.full(length, value, dtype=np.uint8)
+    a.setflags(write=False)
+    return a
+
+
+@functools.lru_cache(maxsize=None)
+def far_pieces():
+    """The decoded pieces of far_file(), in order, as buffers: the texts as bytes, every filler a read-only numpy uint8
+    array of one value.  Fillers of equal value and length are the SAME object: nine arrays, about 0.4 GB, stand for 4.4 GB."""
+    far = far_file()
+    pieces = tuple(data if value is None else _filler_array(value, length) for _, value, data, length in far.raw.parts)
+    assert sum(len(p) for p in pieces) == far.raw.size
+    return pieces
+
+
+def plan_blocks(part, level=9):
+    """[(start, size, rle)] of the blocks libbz2 cuts `part` into -- bytes, or a (value, length) run: RLE1 pieces are runs
+    of one value cut every 255 bytes, a piece of L < 4 bytes takes L RLE1 bytes, a longer one 5; a block ends with the first
+    piece that brings its RLE1 bytes to 100 000 level - 19."""
+    if isinstance(part, tuple):
+        runs = np.array([part[1]], dtype=np.int64)
+    else:
+        a = np.frombuffer(bytes(part), dtype=np.uint8)
+        edges = np.concatenate([[0], np.flatnonzero(a[1:] != a[:-1]) + 1, [len(a)]])
+        runs = np.diff(edges).astype(np.int64)
+    whole, rest = runs // 255, runs % 255
+    counts = whole + (rest > 0)
+    lengths = np.full(int(counts.sum()), 255, dtype=np.int64)
+    last = np.cumsum(counts) - 1
+    lengths[last[rest > 0]] = rest[rest > 0]
+    ends = np.cumsum(lengths)                                # input bytes up to and with each piece
+    rle = np.cumsum(np.where(lengths < 4, lengths, 5))       # RLE1 bytes likewise
+    limit = 100_000 * level - 19
+    blocks, first, start, base = [], 0, 0, 0
+    while first < len(lengths):
+        k = int(np.searchsorted(rle, base + limit, "left"))  # the first piece that fills the block
+        k = min(k, len(lengths) - 1)
+        blocks.append((start, int(ends[k]) - start, int(rle[k]) - base))
+        first, start, base = k + 1, int(ends[k]), int(rle[k])
+    return blocks
+
+
+def block_bytes(size, rle):
+    """blockBytes of bz2_compress.hpp: what a block costs of a launch's device budget."""
+    return rle * BYTES_PER_POSITION + size + -(-(rle + 1) // GROUP_SIZE) * 8
+
+
+def plan_launches(blocks, cap=0, budget=0):
+    """[(first, count, input start, input bytes, device bytes)]: planLaunches of bz2_compress.hpp over [(size, rle)]."""
+    cap, budget = cap or LAUNCH_BLOCKS, budget or LAUNCH_BYTES
+    launches, at = [], 0
+    for i, (size, rle) in enumerate(blocks):
+        need = block_bytes(size, rle)
+        if not launches or launches[-1][1] == cap or launches[-1][4] + need > budget:
+            launches.append([i, 0, at, 0, 0])
+        launches[-1][1] += 1
+        launches[-1][3] += size
+        launches[-1][4] += need
+        at += size
+    return [tuple(l) for l in launches]
+
+
+DEEP_INPUT_SIZE = 550_000_000
+DEEP_INPUT_SEED = 0xDEE9
+
+
+@functools.lru_cache(maxsize=None)
+def deep_input():
+    """550 000 000 seeded incompressible bytes: at level 9 about 611 blocks and a stream of more than 2^32 + 2^26 bits
+    (libbz2's ratio on such bytes is above 1: test_bigfiles.py)."""
+    return datagen.random_bytes(DEEP_INPUT_SIZE, DEEP_INPUT_SEED)

@@ -3,7 +3,10 @@
  * closed before the next byte, and after the last one, once the flushed RLE1 bytes reach the limit) on runs, random bytes and run edges at a cut.
  * Launches: caps of 1, 2, 3, 7 and 512 blocks and several memory budgets (including one below a single block), checked
  * for every block in exactly one launch, in order, counts and budgets kept, and the launch sums (positions, symbol and
- * selector slots, input span).  Map layout: one entry per block plus two, or one for an empty buffer.  Prints
+ * selector slots, input span).  Beyond 2^32: 200 blocks of one repeated byte (45 899 235 input bytes in 899 985 RLE1
+ * positions each) are cut by the budget at 148, so the first launch holds 6.8 GB of input, block offsets in it (inOff, the
+ * prefix sums runCall forms) pass 2^32 at block 94 and the second launch's inputStart lies above 2^32; the same blocks as
+ * one buffer whose Block::start values pass 2^32; caps of 1 and 0.  Map layout: one entry per block plus two, or one for an empty buffer.  Prints
  * "compress plan ok". */
 #include <cstdio>
 #include <random>
@@ -103,6 +106,10 @@ checkLaunches( const std::vector<Block>& blocks, uint32_t cap, uint64_t budget )
         }
         CHECK( l.positions == positions && l.symbols == symbols && l.selectors == selectors && l.bytes == bytes );
         CHECK( l.inputStart == input && l.inputBytes == span );
+        /* the launch's input span, the last of the inOff prefix sums runCall forms, against a 128-bit sum */
+        unsigned __int128 wide = 0;
+        for ( uint32_t k = l.first; k < l.first + l.count; ++k ) wide += blocks[k].size;
+        CHECK( (unsigned __int128)l.inputBytes == wide );
         CHECK( l.count == 1 || l.bytes <= maxBytes );
         CHECK( positions < ( uint64_t( 1 ) << 32 ) );
         next += l.count;
@@ -160,6 +167,47 @@ main()
         }
     }
     CHECK( planLaunches( {}, 0, 0 ).empty() );
+
+    currentCase = "launches beyond 2^32";
+    {
+        constexpr uint64_t FILLER = 45'899'235, CUT = uint64_t( 1 ) << 32;   /* 179 997 pieces of 255 equal bytes */
+        constexpr uint32_t FILLER_RLE = 899'985;
+        std::vector<Block> fillers;   /* 200 buffers of one block each: every start is 0 */
+        for ( int i = 0; i < 200; ++i ) fillers.push_back( { 0, FILLER, FILLER_RLE } );
+        CHECK( blockBytes( fillers[0] ) == 86'542'560 );
+        const auto byBudget = planLaunches( fillers, 0, 0 );
+        CHECK( byBudget.size() == 2 && byBudget[0].count == 148 && byBudget[1].count == 52 );
+        CHECK( byBudget.size() == 2 && byBudget[0].bytes <= DEFAULT_LAUNCH_BYTES
+               && byBudget[0].bytes + blockBytes( fillers[0] ) > DEFAULT_LAUNCH_BYTES );
+        CHECK( byBudget.size() == 2 && byBudget[0].inputBytes == 148 * FILLER && byBudget[0].inputBytes > CUT );
+        CHECK( byBudget.size() == 2 && byBudget[1].inputStart == 148 * FILLER && byBudget[1].inputStart > CUT
+               && byBudget[1].inputBytes == 52 * FILLER );
+        CHECK( 93 * FILLER < CUT && 94 * FILLER >= CUT );   /* inOff of block 94 is the first at or above 2^32 */
+        std::vector<Block> oneBuffer;   /* the same bytes as ONE buffer: Block::start passes 2^32 */
+        for ( uint64_t i = 0; i < 200; ++i ) oneBuffer.push_back( { i * FILLER, FILLER, FILLER_RLE } );
+        CHECK( oneBuffer[94].start >= CUT && oneBuffer[93].start < CUT );
+        const auto again = planLaunches( oneBuffer, 0, 0 );
+        CHECK( again.size() == byBudget.size() );
+        for ( size_t i = 0; i < again.size() && i < byBudget.size(); ++i ) {
+            CHECK( again[i].first == byBudget[i].first && again[i].count == byBudget[i].count
+                   && again[i].inputStart == byBudget[i].inputStart && again[i].inputBytes == byBudget[i].inputBytes );
+            CHECK( again[i].inputStart == oneBuffer[again[i].first].start );
+        }
+        const auto single = planLaunches( oneBuffer, 1, 0 );
+        CHECK( single.size() == 200 );
+        for ( size_t i = 0; i < single.size(); ++i ) {
+            CHECK( single[i].inputStart == i * FILLER && single[i].inputBytes == FILLER && single[i].count == 1 );
+        }
+        for ( const uint32_t cap : { 0u, 1u, 93u, 94u, 95u, 512u } ) {
+            for ( const uint64_t budget : { uint64_t( 0 ), uint64_t( 1 ) << 20, uint64_t( 9 ) << 30, uint64_t( 64 ) << 30 } ) {
+                checkLaunches( fillers, cap, budget );
+                checkLaunches( oneBuffer, cap, budget );
+            }
+        }
+        /* a budget that does not bind: the cap of 512 does, and one launch holds all 200 (9.2 GB of input) */
+        const auto wide = planLaunches( fillers, 0, uint64_t( 64 ) << 30 );
+        CHECK( wide.size() == 1 && wide[0].inputBytes == 200 * FILLER && wide[0].positions == 200ull * FILLER_RLE );
+    }
 
     currentCase = "map layout";
     for ( const uint32_t c : counts ) CHECK( mapEntries( c ) == ( c == 0 ? 1u : c + 2u ) );

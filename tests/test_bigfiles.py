@@ -372,3 +372,100 @@ def test_deep_file_keeps_its_promises():
         for i in range(per_copy):
             assert deep.blocks[k * per_copy + i][0] == deep.blocks[i][0] + 8 * k * len(deep.body_stream)
     assert bz2.BZ2Decompressor().decompress(deep.body_stream) == deep.body
+
+
+# ------------------------------------------------------------------------------------------------ inputs of the encoder
+
+def header_constants():
+    """The planner's constants, read from csrc/bz2_compress.hpp."""
+    import os
+    import re
+    from conftest import ROOT
+    with open(os.path.join(ROOT, "indexed_bzip2_amd", "csrc", "bz2_compress.hpp")) as f:
+        text = f.read()
+    blocks = int(re.search(r"DEFAULT_LAUNCH_BLOCKS = (\d+);", text).group(1))
+    gib = int(re.search(r"DEFAULT_LAUNCH_BYTES = uint64_t\( (\d+) \) << 30;", text).group(1))
+    terms = re.search(r"BYTES_PER_POSITION = ([0-9 +]+);", text).group(1)
+    group = int(re.search(r"GROUP_SIZE = (\d+);", text).group(1))
+    assert "(uint64_t)b.rle * BYTES_PER_POSITION + b.size + selectorSlots( b.rle ) * 8" in text
+    assert "( symbolSlots( rle ) + GROUP_SIZE - 1 ) / GROUP_SIZE" in text and "return (uint64_t)rle + 1;" in text
+    assert "return 100000 * (uint64_t)level - 19;" in text
+    return blocks, gib << 30, sum(int(t) for t in terms.split("+")), group
+
+
+def far_blocks():
+    """[(piece, input offset in the launch, size, rle)] of far_pieces() at level 9, by bigfiles.plan_blocks."""
+    far = bigfiles.far_file()
+    cuts = {}
+    out, at = [], 0
+    for index, (_, value, data, length) in enumerate(far.raw.parts):
+        key = data if value is None else (value, length)
+        if key not in cuts:
+            cuts[key] = bigfiles.plan_blocks(key, 9)
+        for start, size, rle in cuts[key]:
+            assert size > 0 and start + size <= length
+            out.append((index, at + start, size, rle))
+        at += length
+    return out
+
+
+def test_far_pieces_are_one_launch_beyond_4_gib(native):
+    assert header_constants() == (bigfiles.LAUNCH_BLOCKS, bigfiles.LAUNCH_BYTES, bigfiles.BYTES_PER_POSITION, bigfiles.GROUP_SIZE)
+    assert (bigfiles.LAUNCH_BLOCKS, bigfiles.LAUNCH_BYTES, bigfiles.BYTES_PER_POSITION) == (512, 12 << 30, 45)
+    far, pieces, cut = bigfiles.far_file(), bigfiles.far_pieces(), 1 << 32
+    # T0, 93 full fillers, the partial one, T1, two fillers, T2: 99 buffers, nine distinct filler arrays and texts
+    full = [p for p in pieces if isinstance(p, np.ndarray) and len(p) == bigfiles.FULL_BLOCK]
+    assert len(pieces) == 99 and len(full) == 95 and len({id(p) for p in full}) == 7
+    assert [isinstance(p, bytes) for p in pieces] == [True] + [False] * 94 + [True] + [False] * 2 + [True]
+    assert pieces[0] == far.t0 == pieces[98] and pieces[95] == far.t1 and 0 < len(pieces[94]) < bigfiles.FULL_BLOCK
+    assert sum(len(p) for p in pieces) == far.raw.size == 4_388_315_842
+    assert all(int(p[0]) == int(p[-1]) == value and len(p) == length
+               for p, (_, value, _, length) in zip(pieces, far.raw.parts) if value is not None)
+    assert sum(p.nbytes for p in {id(p): p for p in pieces if isinstance(p, np.ndarray)}.values()) < 420 << 20
+    # the cuts: the product's planner on each distinct piece agrees with the restatement; a full filler is ONE block of
+    # exactly 899 985 RLE1 bytes, a text two blocks
+    for piece in {id(p): p for p in pieces}.values():
+        key = piece if isinstance(piece, bytes) else (int(piece[0]), len(piece))
+        assert native.plan_compress_blocks(piece, 9) == [size for _, size, _ in bigfiles.plan_blocks(key, 9)]
+    assert bigfiles.plan_blocks((0x81, bigfiles.FULL_BLOCK), 9) == [(0, bigfiles.FULL_BLOCK, 899_985)]
+    assert len(bigfiles.plan_blocks((0x81, bigfiles.FULL_BLOCK + 1), 9)) == 2
+    assert bigfiles.block_bytes(bigfiles.FULL_BLOCK, 899_985) == 86_542_560
+    blocks = far_blocks()
+    assert len(blocks) == 102 and [index for index, _, _, _ in blocks[:3]] == [0, 0, 1]
+    # inOff: the running sum of the sizes, every block inside its piece
+    at = 0
+    for index, offset, size, rle in blocks:
+        assert offset == at and rle <= 899_985
+        at += size
+    assert at == far.raw.size
+    # one launch: 102 blocks, 8.4 GB of the 12 GiB budget -- the budget is by blockBytes, not by input bytes
+    launches = bigfiles.plan_launches([(size, rle) for _, _, size, rle in blocks])
+    assert launches == [(0, 102, 0, far.raw.size, sum(bigfiles.block_bytes(size, rle) for _, _, size, rle in blocks))]
+    assert launches[0][4] == 8_406_950_504 < bigfiles.LAUNCH_BYTES and launches[0][3] > cut
+    # the first inOff at or above 2^32 is block 97's: T1's second block, 450 057 bytes above; five blocks start above
+    above = [k for k, (_, offset, _, _) in enumerate(blocks) if offset >= cut]
+    assert above == [97, 98, 99, 100, 101] and blocks[97][1] == cut + 450_057 and blocks[96][1] == far.t1_at < cut
+    # a block read at inOff - 2^32 would read other bytes: the fillers another value (assert_no_alias), the texts other text
+    bigfiles.assert_no_alias(far.raw, cut)
+    for k in above:
+        index, offset, size, _ = blocks[k]
+        n = min(size, 4096)
+        assert far.raw.slice(offset, offset + n) != far.raw.slice(offset - cut, offset - cut + n), k
+        assert far.raw.slice(offset + size - n, offset + size) != far.raw.slice(offset + size - n - cut, offset + size - cut), k
+        if isinstance(pieces[index], np.ndarray):
+            low = far.raw.slice(offset - cut, offset - cut + 1) + far.raw.slice(offset + size - 1 - cut, offset + size - cut)
+            assert int(pieces[index][0]) not in low
+    # 148 fillers fit one launch by the budget, 6.8 GB of input; the 149th does not
+    filler = (bigfiles.FULL_BLOCK, 899_985)
+    assert [l[1] for l in bigfiles.plan_launches([filler] * 200)] == [148, 52]
+    assert bigfiles.plan_launches([filler] * 200)[1][2] == 148 * bigfiles.FULL_BLOCK > cut
+
+
+def test_deep_input_is_incompressible():
+    """libbz2's ratio on 4.5 MB of deep_input()'s generator is at least 1, so the stream of the 550 000 000 bytes has more
+    than 2^32 + 2^26 bits whatever the encoder (deep_file relies on the same)."""
+    sample = datagen.random_bytes(4_500_000, bigfiles.DEEP_INPUT_SEED)
+    assert len(bz2.compress(sample, 9)) >= len(sample)
+    assert 8 * bigfiles.DEEP_INPUT_SIZE >= 2**32 + 2**26
+    blocks = -(-bigfiles.DEEP_INPUT_SIZE // 899_981)
+    assert 611 <= blocks <= 613 and blocks * bigfiles.block_bytes(899_981, 899_981) > bigfiles.LAUNCH_BYTES      # two launches
