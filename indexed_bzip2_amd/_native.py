@@ -482,6 +482,57 @@ class _KeptInputs(tuple):
     """(previous, current) host buffers of set_input_host_async."""
 
 
+def _with_device_copies(what, hosts, call):
+    """call(*pointers) with one device array per numpy array of `hosts`, all in one device allocation: filled from the host
+    arrays before the call, copied back to them behind it, and freed whatever happens."""
+    # device memory from the HIP runtime the library itself is linked to (it is loaded already)
+    hip = ctypes.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
+    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    hip.hipFree.argtypes = [ctypes.c_void_p]
+    total = sum(host.nbytes for host in hosts)
+    device = ctypes.c_void_p()
+    if hip.hipMalloc(ctypes.byref(device), total) != 0:
+        raise Bz2Error(101, f"{what}: no device memory for {total} bytes")
+    try:
+        pointers = [ctypes.c_void_p(device.value + sum(host.nbytes for host in hosts[:k])) for k in range(len(hosts))]
+        for host, pointer in zip(hosts, pointers):
+            if hip.hipMemcpy(pointer, host.ctypes.data, host.nbytes, 1) != 0:           # hipMemcpyHostToDevice
+                raise Bz2Error(101, f"{what}: the copy to the device failed")
+        call(*pointers)
+        for host, pointer in zip(hosts, pointers):
+            if hip.hipMemcpy(host.ctypes.data, pointer, host.nbytes, 2) != 0:           # hipMemcpyDeviceToHost
+                raise Bz2Error(101, f"{what}: the copy from the device failed")
+    finally:
+        hip.hipFree(device)
+
+
+def _field_query_arguments(newline, delimiter, field):
+    """(newline byte, delimiter byte, field) of a field query on the last batch's output, checked."""
+    nl, dl = bytes(newline), bytes(delimiter)
+    if len(nl) != 1 or len(dl) != 1:
+        raise ValueError("newline and delimiter must be exactly one byte each")
+    field = int(field)
+    if field < 0 or field > 1023:
+        raise ValueError("field must be between 0 and 1023")
+    if nl == dl:
+        raise ValueError("delimiter and newline must differ")
+    return nl[0], dl[0], field
+
+
+def _field_summary_dict(s, heads):
+    """The field members of a span's summary (FieldSummary, or FieldHashSummary, which repeats them); `heads` starts at the
+    span's head positions.  None for a position the span does not reach."""
+    none = 2**64 - 1
+    return {"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
+            "first_nl": None if s.first_nl == none else int(s.first_nl),
+            "head_positions": [int(v) for v in heads[:s.head_delims]],
+            "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
+            "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
+            "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
+            "tail_non_empty": bool(s.tail_non_empty)}
+
+
 class Decoder:
     """One decoder context = one GPU + one HIP stream (mi355x_bz2_ctx)."""
 
@@ -804,22 +855,7 @@ class Decoder:
             capacity = sum(s.count for s in summaries[:len(spans)])
         room = capacity if room is None else max(int(room), capacity)
         hashes = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
-        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        hip.hipFree.argtypes = [ctypes.c_void_p]
-        device = ctypes.c_void_p()
-        if hip.hipMalloc(ctypes.byref(device), hashes.nbytes) != 0:
-            raise Bz2Error(101, f"hash_lines: no device memory for {hashes.nbytes} bytes")
-        try:
-            if hip.hipMemcpy(device, hashes.ctypes.data, hashes.nbytes, 1) != 0:         # hipMemcpyHostToDevice
-                raise Bz2Error(101, "hash_lines: the copy to the device failed")
-            call(device, capacity)
-            if hip.hipMemcpy(hashes.ctypes.data, device, hashes.nbytes, 2) != 0:         # hipMemcpyDeviceToHost
-                raise Bz2Error(101, "hash_lines: the copy from the device failed")
-        finally:
-            hip.hipFree(device)
+        _with_device_copies("hash_lines", [hashes], lambda device: call(device, capacity))
         out = [{"head": (s.head_hash, s.head_xl), "tail": (s.tail_hash, s.tail_xl), "has_delimiter": bool(s.has_delimiter),
                 "tail_non_empty": bool(s.tail_non_empty), "count": int(s.count)} for s in summaries[:len(spans)]]
         return out, hashes[:room]
@@ -833,21 +869,14 @@ class Decoder:
         values (default: capacity) that were all ones before the call and of which the call may write the first
         `capacity` (None: as many as there are closed lines).  A start is an offset in the output."""
         import numpy as np
-        nl, dl = bytes(newline), bytes(delimiter)
-        if len(nl) != 1 or len(dl) != 1:
-            raise ValueError("newline and delimiter must be exactly one byte each")
-        field = int(field)
-        if field < 0 or field > 1023:
-            raise ValueError("field must be between 0 and 1023")
-        if nl == dl:
-            raise ValueError("delimiter and newline must differ")
+        nl, dl, field = _field_query_arguments(newline, delimiter, field)
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
         summaries = (FieldSummary * max(1, len(spans)))()
         heads = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
 
         def call(starts, sizes, capacity):
-            self._check(lib().mi355x_bz2_field_spans(self._h, arr, len(spans), nl[0], dl[0], field, summaries, heads.ctypes.data,
+            self._check(lib().mi355x_bz2_field_spans(self._h, arr, len(spans), nl, dl, field, summaries, heads.ctypes.data,
                                                      starts, sizes, capacity))
         if capacity is None:
             call(None, None, 0)
@@ -855,35 +884,8 @@ class Decoder:
         room = capacity if room is None else max(int(room), capacity)
         starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
         sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
-        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        hip.hipFree.argtypes = [ctypes.c_void_p]
-        device = ctypes.c_void_p()
-        if hip.hipMalloc(ctypes.byref(device), 2 * starts.nbytes) != 0:
-            raise Bz2Error(101, f"field_spans: no device memory for {2 * starts.nbytes} bytes")
-        try:
-            second = ctypes.c_void_p(device.value + starts.nbytes)
-            if (hip.hipMemcpy(device, starts.ctypes.data, starts.nbytes, 1) != 0            # hipMemcpyHostToDevice
-                    or hip.hipMemcpy(second, sizes.ctypes.data, sizes.nbytes, 1) != 0):
-                raise Bz2Error(101, "field_spans: the copy to the device failed")
-            call(device, second, capacity)
-            if (hip.hipMemcpy(starts.ctypes.data, device, starts.nbytes, 2) != 0            # hipMemcpyDeviceToHost
-                    or hip.hipMemcpy(sizes.ctypes.data, second, sizes.nbytes, 2) != 0):
-                raise Bz2Error(101, "field_spans: the copy from the device failed")
-        finally:
-            hip.hipFree(device)
-        none = 2**64 - 1
-        out = []
-        for i, s in enumerate(summaries[:len(spans)]):
-            out.append({"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
-                        "first_nl": None if s.first_nl == none else int(s.first_nl),
-                        "head_positions": [int(v) for v in heads[i * (field + 1):i * (field + 1) + s.head_delims]],
-                        "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
-                        "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
-                        "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
-                        "tail_non_empty": bool(s.tail_non_empty)})
+        _with_device_copies("field_spans", [starts, sizes], lambda *device: call(*device, capacity))
+        out = [_field_summary_dict(s, heads[i * (field + 1):]) for i, s in enumerate(summaries[:len(spans)])]
         return out, starts[:room], sizes[:room]
 
     def field_hashes(self, spans, field, delimiter=b"\t", newline=b"\n", seed=0, capacity=None, room=None):
@@ -894,14 +896,7 @@ class Decoder:
         reach them).  keys is a numpy uint64 array shaped and filled like starts and sizes: `room` values that were all
         ones before the call, of which the call may write the first `capacity`."""
         import numpy as np
-        nl, dl = bytes(newline), bytes(delimiter)
-        if len(nl) != 1 or len(dl) != 1:
-            raise ValueError("newline and delimiter must be exactly one byte each")
-        field = int(field)
-        if field < 0 or field > 1023:
-            raise ValueError("field must be between 0 and 1023")
-        if nl == dl:
-            raise ValueError("delimiter and newline must differ")
+        nl, dl, field = _field_query_arguments(newline, delimiter, field)
         seed = int(seed)
         if seed < 0 or seed >= 2**64:
             raise ValueError("seed must not be negative and must fit 64 bits")
@@ -912,7 +907,7 @@ class Decoder:
         head_hashes = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
 
         def call(keys, starts, sizes, capacity):
-            self._check(lib().mi355x_bz2_field_hashes(self._h, arr, len(spans), nl[0], dl[0], field, seed, summaries,
+            self._check(lib().mi355x_bz2_field_hashes(self._h, arr, len(spans), nl, dl, field, seed, summaries,
                                                       heads.ctypes.data, head_hashes.ctypes.data, keys, starts, sizes, capacity))
         if capacity is None:
             call(None, None, None, 0)
@@ -921,41 +916,16 @@ class Decoder:
         keys = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
         starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
         sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
-        # device memory from the HIP runtime the library itself is linked to (it is loaded already)
-        hip = ctypes.CDLL("libamdhip64.so")
-        hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        hip.hipFree.argtypes = [ctypes.c_void_p]
-        device = ctypes.c_void_p()
-        if hip.hipMalloc(ctypes.byref(device), 3 * keys.nbytes) != 0:
-            raise Bz2Error(101, f"field_hashes: no device memory for {3 * keys.nbytes} bytes")
-        try:
-            columns = [(keys, device), (starts, ctypes.c_void_p(device.value + keys.nbytes)),
-                       (sizes, ctypes.c_void_p(device.value + 2 * keys.nbytes))]
-            for host, pointer in columns:
-                if hip.hipMemcpy(pointer, host.ctypes.data, host.nbytes, 1) != 0:       # hipMemcpyHostToDevice
-                    raise Bz2Error(101, "field_hashes: the copy to the device failed")
-            call(columns[0][1], columns[1][1], columns[2][1], capacity)
-            for host, pointer in columns:
-                if hip.hipMemcpy(host.ctypes.data, pointer, host.nbytes, 2) != 0:       # hipMemcpyDeviceToHost
-                    raise Bz2Error(101, "field_hashes: the copy from the device failed")
-        finally:
-            hip.hipFree(device)
+        _with_device_copies("field_hashes", [keys, starts, sizes], lambda *device: call(*device, capacity))
         none = 2**64 - 1
         out = []
         for i, s in enumerate(summaries[:len(spans)]):
             at = i * (field + 1)
-            out.append({"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
-                        "first_nl": None if s.first_nl == none else int(s.first_nl),
-                        "head_positions": [int(v) for v in heads[at:at + s.head_delims]],
+            out.append({**_field_summary_dict(s, heads[at:]),
                         "head_hashes": [int(v) for v in head_hashes[at:at + s.head_delims]],
-                        "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
-                        "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
-                        "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
                         "tail_start_hash": None if s.tail_field_start == none else int(s.tail_start_hash),
                         "tail_end_hash": None if s.tail_field_end == none else int(s.tail_end_hash),
-                        "head": (int(s.head_hash), int(s.head_xl)), "tail": (int(s.tail_hash), int(s.tail_xl)),
-                        "tail_non_empty": bool(s.tail_non_empty)})
+                        "head": (int(s.head_hash), int(s.head_xl)), "tail": (int(s.tail_hash), int(s.tail_xl))})
         return out, keys[:room], starts[:room], sizes[:room]
 
     def output_device_ptr(self) -> int:

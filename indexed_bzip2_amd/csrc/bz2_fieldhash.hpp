@@ -3,7 +3,7 @@
  * _field_groups): the definition, the summary of a stretch of bytes, and the rule that stitches the summaries of
  * stretches that lie back to back.  Host code only, no HIP: the reader and the context call it, and
  * tests/native/fieldhash_cases.cpp pins it on the CPU.  The fields are those of bz2_fields.hpp, the hash is that of
- * bz2_linehash.hpp, and the block plan is planFields as it is.
+ * bz2_linehash.hpp, and the block plan is planLineHashes as it is (the reader calls it for all three column queries).
  *
  * The definition.  The KEY of a line is lineHash( content.split( dl )[j], seed ); a line with fewer than j + 1 fields has
  * the key FIELD_MISSING = 2^61 - 1 = p, which no hash takes; an empty field is present and hashes to 0.

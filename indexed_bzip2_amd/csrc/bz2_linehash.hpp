@@ -274,6 +274,9 @@ struct LineHashPlan
     uint64_t firstClosed{ 0 }, N{ 0 };
     uint64_t first{ 0 }, count{ 0 };     /* the range, count clipped to N + 1 - first (the tail may turn out empty) */
     bool reachesEnd{ false };
+
+    /** The lines of the range that a delimiter closes: all of them but the unterminated tail. */
+    [[nodiscard]] uint64_t wantedClosed() const { return reachesEnd ? N - first : count; }
 };
 
 inline LineHashPlan
@@ -302,5 +305,37 @@ planLineHashes( const std::vector<std::pair<uint64_t, uint64_t> >& map, const ui
         at += segment.size;
     }
     return plan;
+}
+
+/** A stretch's place in a column with one entry per line of the range: the stretch closes `closed` lines, the index says;
+ * of those, `take` lines behind the first `skip` are wanted, and they are entries [at, at + take) of the column. */
+struct ColumnPlace
+{
+    uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 };
+};
+
+/**
+ * The place of every stretch of `plan`, from the line index the plan was made with: every launch knows where its lines go
+ * before any has run.  The closed lines of the stretches are numbered from plan.firstClosed on, the wanted ones are
+ * [first, first + wantedClosed()), and a stretch that closes none of them has take == 0.  The places tile the column
+ * [0, wantedClosed()) in the order of the stretches; the unterminated tail, if the range reaches it, comes behind them.
+ */
+[[nodiscard]] inline std::vector<ColumnPlace>
+placeLineColumn( const LineHashPlan& plan, const uint64_t* lineBytes, const uint64_t* lineLines, size_t nIndex )
+{
+    std::vector<ColumnPlace> places( plan.stretches.size() );
+    const uint64_t first = plan.first, wantedClosed = plan.wantedClosed();
+    uint64_t closedBefore = plan.firstClosed;
+    for ( size_t k = 0; k < places.size(); ++k ) {
+        const auto& piece = plan.stretches[k];
+        const auto from = std::upper_bound( lineBytes, lineBytes + nIndex, piece.fileOffset ) - lineBytes - 1;
+        const auto to = std::lower_bound( lineBytes, lineBytes + nIndex, piece.fileOffset + piece.size ) - lineBytes;
+        auto& place = places[k];
+        place.closed = lineLines[to] - lineLines[from];
+        const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + place.closed, first + wantedClosed );
+        if ( end > begin ) place = { begin - closedBefore, end - begin, begin - first, place.closed };
+        closedBefore += place.closed;
+    }
+    return places;
 }
 }  // namespace bz2gpu

@@ -872,6 +872,25 @@ takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uin
     *set = makePatternSet( patterns, sizes, n, ( flags & SEARCH_IGNORE_CASE ) != 0 );
     return true;
 }
+
+/** The field members of a span's C summary -- mi355x_bz2_field_summary, or mi355x_bz2_field_hash_summary, which repeats
+ * them -- as the FieldSummary of a stretch of `size` bytes; `heads` has room for field + 1 head positions. */
+template<typename CSummary>
+void
+setFieldSummary( bz2gpu::FieldSummary& f, const CSummary& s, uint64_t size, std::vector<uint64_t> heads )
+{
+    f.size = size;
+    f.hasDelimiter = s.has_delimiter != 0;
+    f.tailNonEmpty = s.tail_non_empty != 0;
+    f.count = s.count;
+    f.firstNl = s.first_nl;
+    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
+    f.headPositions = std::move( heads );
+    f.tailStart = s.tail_start;
+    f.tailDelims = s.tail_delims;
+    f.tailFieldStart = s.tail_field_start;
+    f.tailFieldEnd = s.tail_field_end;
+}
 }  // namespace
 
 int
@@ -939,17 +958,7 @@ mi355x::fieldSpansOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent,
     const int status = fieldSpans( c, "field_spans", &extent, &fileOffset, 1, nl, dl, field, &s, heads.data(), skip, take, dStarts, dSizes );
     *summary = bz2gpu::emptyFieldSummary( field );
     if ( status != MI355X_BZ2_OK ) return status;
-    summary->size = extent.size;
-    summary->hasDelimiter = s.has_delimiter != 0;
-    summary->tailNonEmpty = s.tail_non_empty != 0;
-    summary->count = s.count;
-    summary->firstNl = s.first_nl;
-    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
-    summary->headPositions = std::move( heads );
-    summary->tailStart = s.tail_start;
-    summary->tailDelims = s.tail_delims;
-    summary->tailFieldStart = s.tail_field_start;
-    summary->tailFieldEnd = s.tail_field_end;
+    setFieldSummary( *summary, s, extent.size, std::move( heads ) );
     return status;
 }
 
@@ -968,19 +977,8 @@ mi355x::fieldHashesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent
                                     skip, take, dKeys, dStarts, dSizes );
     *summary = bz2gpu::emptyFieldHashSummary( field );
     if ( status != MI355X_BZ2_OK ) return status;
-    auto& f = summary->fields;
-    f.size = extent.size;
-    f.hasDelimiter = s.has_delimiter != 0;
-    f.tailNonEmpty = s.tail_non_empty != 0;
-    f.count = s.count;
-    f.firstNl = s.first_nl;
-    heads.resize( std::min<size_t>( s.head_delims, heads.size() ) );
-    headHashes.resize( heads.size() );
-    f.headPositions = std::move( heads );
-    f.tailStart = s.tail_start;
-    f.tailDelims = s.tail_delims;
-    f.tailFieldStart = s.tail_field_start;
-    f.tailFieldEnd = s.tail_field_end;
+    setFieldSummary( summary->fields, s, extent.size, std::move( heads ) );
+    headHashes.resize( summary->fields.headPositions.size() );
     summary->headHashes = std::move( headHashes );
     summary->head = { s.head_hash, s.head_xl };
     summary->tail = { s.tail_hash, s.tail_xl };

@@ -19,6 +19,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cerrno>
 #include <chrono>
@@ -1114,21 +1115,56 @@ runRankWork( mi355x_bz2_ctx* const ctx, const RankWork& work )
     }
 }
 
+/** How far a search with a limit has come: what the launches at the front of the range that are through have found.
+ * Once that reaches the limit, `stop` cancels the launches that have not been started. */
+struct SearchProgress
+{
+    std::mutex mutex;
+    std::vector<uint8_t> finished;              /* per launch */
+    std::vector<uint64_t> values;               /* per launch: what it adds to `found` */
+    size_t through{ 0 };                        /* launches [0, through) are finished ... */
+    uint64_t found{ 0 };                        /* ... and have found this many */
+    std::atomic<bool> stop{ false };
+
+    explicit SearchProgress( size_t launches ) : finished( launches, 0 ), values( launches, 0 ) {}
+
+    /** Launch `index` is through and adds `value`. */
+    void
+    finish( size_t index, uint64_t value, uint64_t limit )
+    {
+        const std::scoped_lock lock( mutex );
+        finished[index] = 1;
+        values[index] = value;
+        while ( through < finished.size() && finished[through] != 0 ) found += values[through++];
+        if ( found >= limit ) stop.store( true, std::memory_order_release );
+    }
+};
+
+/** The seams of the first `usable` works of a search for patterns of at most m bytes: the first and the last
+ * seamLength( m, size ) bytes of every extent, which its launch left in the work's `seam`. */
+template<typename Work>
+static std::vector<bz2gpu::ExtentSeam>
+extentSeams( const std::vector<Work>& works, size_t usable, uint32_t m )
+{
+    std::vector<bz2gpu::ExtentSeam> seams( usable );
+    for ( size_t l = 0; l < usable; ++l ) {
+        const auto& extent = works[l].extent;
+        const auto* const head = works[l].seam;
+        const auto* const tail = head + bz2gpu::SEARCH_PATTERN_MAX;
+        const auto k = bz2gpu::seamLength( m, extent.size );
+        seams[l] = { extent.fileOffset, extent.size, { head, head + k }, { tail, tail + k } };
+    }
+    return seams;
+}
+
 /** What the launches of one search share: the pattern (folded once here if the flags ask for it; the context folds what
- * it uploads all the same), the flags, and -- with a limit -- how many matches the launches at the front of the range
- * that are through have found.  Once these reach the limit, `stop` cancels the launches that have
- * not been started. */
+ * it uploads all the same), the flags, and -- with a limit -- the progress, which counts every match of a launch. */
 struct SearchCall
 {
     std::vector<uint8_t> pattern;
     uint32_t flags{ 0 };                        /* MI355X_BZ2_SEARCH_* */
     uint64_t limit{ 0 };                        /* 0: count only */
-    std::mutex mutex;
-    std::vector<uint8_t> finished;              /* per launch */
-    std::vector<uint64_t> counts;
-    size_t through{ 0 };                        /* launches [0, through) are finished ... */
-    uint64_t found{ 0 };                        /* ... and have found this many */
-    std::atomic<bool> stop{ false };
+    SearchProgress progress;
 };
 
 /** What a launch of a search does with its decoded blocks: mi355x::searchOutput over its extent. */
@@ -1148,29 +1184,16 @@ runSearchWork( mi355x_bz2_ctx* const ctx, SearchWork& work )
     auto& call = *work.call;
     checkDevice( ctx, searchOutput( ctx, { work.extent.src, work.extent.size }, call.pattern.data(), (uint32_t)call.pattern.size(),
                                     call.flags, call.limit, call.limit > 0 ? &work.positions : nullptr, &work.count, work.seam ) );
-    if ( call.limit > 0 ) {
-        const std::scoped_lock lock( call.mutex );
-        call.finished[work.index] = 1;
-        call.counts[work.index] = work.count;
-        while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
-            call.found += call.counts[call.through++];
-        }
-        if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
-    }
+    if ( call.limit > 0 ) call.progress.finish( work.index, work.count, call.limit );
 }
 
-/** SearchCall for a set of patterns; the set holds the flag and the patterns folded once.  `found` counts, of the pairs of the launches at the front that are through, only
- * those that end m_max bytes in front of their extent's end (bz2_search.hpp: the limit of a set). */
+/** SearchCall for a set of patterns; the set holds the flag and the patterns folded once.  The progress counts, of the
+ * pairs of a launch, only those that end m_max bytes in front of its extent's end (bz2_search.hpp: the limit of a set). */
 struct SetSearchCall
 {
     const bz2gpu::PatternSet* set{ nullptr };
     uint64_t limit{ 0 };                        /* 0: count only */
-    std::mutex mutex;
-    std::vector<uint8_t> finished;              /* per launch */
-    std::vector<uint64_t> safe;
-    size_t through{ 0 };
-    uint64_t found{ 0 };
-    std::atomic<bool> stop{ false };
+    SearchProgress progress;
 };
 
 struct SetSearchWork
@@ -1196,16 +1219,101 @@ runSetSearchWork( mi355x_bz2_ctx* const ctx, SetSearchWork& work )
                                        pairs ? nullptr : work.perPattern.data(), work.seam ) );
     if ( pairs ) {
         for ( auto& position : work.positions ) position = work.extent.fileOffset + ( position - work.extent.src );
-        const std::scoped_lock lock( call.mutex );
-        call.finished[work.index] = 1;
-        call.safe[work.index] = bz2gpu::safePairs( work.positions.data(), work.positions.size(),
-                                                   work.extent.fileOffset + work.extent.size, call.set->mMax );
-        while ( call.through < call.finished.size() && call.finished[call.through] != 0 ) {
-            call.found += call.safe[call.through++];
-        }
-        if ( call.found >= call.limit ) call.stop.store( true, std::memory_order_release );
+        call.progress.finish( work.index, bz2gpu::safePairs( work.positions.data(), work.positions.size(),
+                                                             work.extent.fileOffset + work.extent.size, call.set->mMax ), call.limit );
     }
 }
+
+/* The per-line column queries, as StreamReader::lineColumns takes them: COLUMNS device columns of one 8-byte word per
+ * line; the stretch type of the stitcher and where a stretch's size goes; pass() does one stretch on the context that
+ * decoded it, writing the lines of `place` at to[c] (the column's pointer at place.at), and returns the number of lines it
+ * found the stretch to close; stitch() is the stitcher; words() is a stitched value as its line's word in every column,
+ * and tail() the unterminated tail of what the stitcher returned. */
+using ColumnPiece = bz2gpu::LineHashPlan::Piece;
+
+struct LineHashQuery
+{
+    static constexpr size_t COLUMNS = 1;        /* hashes */
+    using Stretch = bz2gpu::HashStretch;
+    uint8_t nl;
+    uint64_t x;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, hashLinesOutput( ctx, { piece.src, piece.size }, nl, x, place.skip, place.take, to[0], &stretch.summary ) );
+        return stretch.summary.count;
+    }
+
+    template<typename Patch>
+    auto stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const { return bz2gpu::stitchSummaries( stretches, patch ); }
+
+    static std::array<uint64_t, COLUMNS> words( uint64_t hash ) { return { hash }; }
+    static uint64_t tail( const bz2gpu::StitchedHashes& stitched ) { return stitched.tailHash; }
+};
+
+struct FieldSpanQuery
+{
+    static constexpr size_t COLUMNS = 2;        /* starts, sizes (int64) */
+    using Stretch = bz2gpu::FieldStretch;
+    uint8_t nl, dl;
+    uint32_t field;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, place.skip, place.take,
+                                            to[0], reinterpret_cast<int64_t*>( to[1] ), &stretch.summary ) );
+        return stretch.summary.count;
+    }
+
+    template<typename Patch>
+    auto stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const { return bz2gpu::stitchFields( stretches, field, patch ); }
+
+    static std::array<uint64_t, COLUMNS> words( const bz2gpu::FieldSpan& span ) { return { span.start, (uint64_t)span.size }; }
+    static const bz2gpu::FieldSpan& tail( const bz2gpu::StitchedFields& stitched ) { return stitched.tail; }
+};
+
+struct FieldHashQuery
+{
+    static constexpr size_t COLUMNS = 3;        /* keys, starts, sizes (int64) */
+    using Stretch = bz2gpu::FieldHashStretch;
+    uint8_t nl, dl;
+    uint32_t field;
+    uint64_t x;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.fields.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldHashesOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, x, place.skip, place.take,
+                                             to[0], to[1], reinterpret_cast<int64_t*>( to[2] ), &stretch.summary ) );
+        return stretch.summary.fields.count;
+    }
+
+    template<typename Patch>
+    auto
+    stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const
+    {
+        return bz2gpu::stitchFieldHashes( stretches, x, dl, field, patch );
+    }
+
+    static std::array<uint64_t, COLUMNS>
+    words( const bz2gpu::FieldKey& key )
+    {
+        return { key.key, key.field.start, (uint64_t)key.field.size };
+    }
+
+    static const bz2gpu::FieldKey& tail( const bz2gpu::StitchedFieldHashes& stitched ) { return stitched.tail; }
+};
 
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
@@ -1431,12 +1539,7 @@ public:
             return bz2gpu::planSearch( map, start, end, m, m_batch, packed, m_source->size() );
         } );
         const size_t n = plan.launches.size();
-        SearchCall call;
-        call.pattern = bz2gpu::foldedBytes( pattern, m, fold );
-        call.flags = flags;
-        call.limit = limit;
-        call.finished.assign( n, 0 );
-        call.counts.assign( n, 0 );
+        SearchCall call{ bz2gpu::foldedBytes( pattern, m, fold ), flags, limit, SearchProgress( n ) };
         std::vector<SearchWork> searches( n );
         for ( size_t l = 0; l < n; ++l ) {
             searches[l].call = &call;
@@ -1447,15 +1550,8 @@ public:
          * and every match that needs a byte behind them starts behind all of those (bz2_search.hpp) */
         const size_t usable = runJobs( plan.launches, [&] ( size_t l ) {
             return [work = &searches[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) { runSearchWork( ctx, *work ); };
-        }, &call.stop );
-        std::vector<bz2gpu::ExtentSeam> seams( usable );
-        for ( size_t l = 0; l < usable; ++l ) {
-            const auto& extent = searches[l].extent;
-            const auto k = bz2gpu::seamLength( m, extent.size );
-            seams[l] = { extent.fileOffset, extent.size, { searches[l].seam, searches[l].seam + k },
-                         { searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX, searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX + k } };
-        }
-        const auto between = bz2gpu::seamMatches( call.pattern.data(), m, seams, fold );
+        }, &call.progress.stop );
+        const auto between = bz2gpu::seamMatches( call.pattern.data(), m, extentSeams( searches, usable, m ), fold );
         if ( limit == 0 ) {
             uint64_t total = between.size();
             for ( const auto& work : searches ) total += work.count;
@@ -1495,11 +1591,7 @@ public:
             return bz2gpu::planSearchSet( map, start, end, set, m_batch, packed, m_source->size() );
         } );
         const size_t n = plan.launches.size();
-        SetSearchCall call;
-        call.set = &set;
-        call.limit = limit;
-        call.finished.assign( n, 0 );
-        call.safe.assign( n, 0 );
+        SetSearchCall call{ &set, limit, SearchProgress( n ) };
         std::vector<SetSearchWork> searches( n );
         for ( size_t l = 0; l < n; ++l ) {
             searches[l].call = &call;
@@ -1510,15 +1602,8 @@ public:
          * sort in front of every pair that needs a byte behind them (bz2_search.hpp) */
         const size_t usable = runJobs( plan.launches, [&] ( size_t l ) {
             return [work = &searches[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) { runSetSearchWork( ctx, *work ); };
-        }, &call.stop );
-        std::vector<bz2gpu::ExtentSeam> seams( usable );
-        for ( size_t l = 0; l < usable; ++l ) {
-            const auto& extent = searches[l].extent;
-            const auto length = bz2gpu::seamLength( set.mMax, extent.size );
-            seams[l] = { extent.fileOffset, extent.size, { searches[l].seam, searches[l].seam + length },
-                         { searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX, searches[l].seam + bz2gpu::SEARCH_PATTERN_MAX + length } };
-        }
-        const auto between = bz2gpu::seamMatchesSet( set, seams );
+        }, &call.progress.stop );
+        const auto between = bz2gpu::seamMatchesSet( set, extentSeams( searches, usable, set.mMax ) );
         if ( limit == 0 ) {
             uint64_t total = between.size();
             for ( const auto& work : searches ) total += work.count;
@@ -1828,75 +1913,27 @@ public:
         }
     }
 
-    /** mi355x_bz2_reader_line_hashes: the launches of planLineHashes, each hashing its stretch (hashLinesOutput) on the
-     * context that decoded it, straight into the reader's device buffer (runLineColumn); then stitchSummaries, and one
-     * 8-byte copy for every line that crosses a seam and for the unterminated tail. */
+    /** mi355x_bz2_reader_line_hashes: lineColumns with the hashing pass (hashLinesOutput) and stitchSummaries, one column. */
     void
     lineHashes( uint8_t nl, uint64_t seed, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
     {
         const auto& index = lineIndex( nl );
         dropHeldLines();
         dropHeldHashes();
-        const auto plan = planLaunches( [&] ( bool packed ) {
-            return bz2gpu::planLineHashes( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
-                                           count, m_batch, packed, m_source->size() );
-        } );
-        *nLines = 0;
-        HeldHashes held;
-        held.onDevice = keepOnDevice;
-        if ( plan.count == 0 ) {
-            m_hashes = std::move( held );
-            return;
-        }
-        std::vector<bz2gpu::HashStretch> stretches( plan.stretches.size() );
-        for ( size_t k = 0; k < stretches.size(); ++k ) {
-            stretches[k].fileOffset = plan.stretches[k].fileOffset;
-            stretches[k].size = plan.stretches[k].size;
-        }
-        std::string why;
-        held.device = m_device;
-        held.capacity = plan.count;
-        held.dHashes = static_cast<uint64_t*>( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
-        if ( held.dHashes == nullptr ) fail( MI355X_BZ2_ERR_DEVICE, "line_hashes: " + why );
-        const uint64_t x = bz2gpu::lineHashBase( seed );
-        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, x, to = held.dHashes]
-                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
-            checkDevice( ctx, hashLinesOutput( ctx, { piece.src, piece.size }, nl, x, work.skip, work.take, to + work.at, &stretches[k].summary ) );
-            return stretches[k].summary.count;
-        } );
-        /* the first closed line of a stretch is line firstClosed + k of the file */
-        std::vector<std::pair<uint64_t, uint64_t> > patches;
-        const auto stitched = bz2gpu::stitchSummaries( stretches, [&] ( uint64_t k, uint64_t hash ) {
-            const uint64_t line = plan.firstClosed + k;
-            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, hash );
-        } );
-        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
-        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tailHash );
-        for ( const auto& [at, hash] : patches ) {
-            if ( !hostToDevice( m_device, held.dHashes + at, &hash, sizeof( hash ), &why ) ) fail( MI355X_BZ2_ERR_DEVICE, "line_hashes: " + why );
-        }
-        held.n = n;
-        *nLines = n;
-        m_hashes = std::move( held );
+        m_hashes = lineColumns( LineHashQuery{ nl, bz2gpu::lineHashBase( seed ) }, "line_hashes", index, first, count, keepOnDevice, nLines );
     }
 
     /** mi355x_bz2_reader_take_line_hashes. */
     void
     takeLineHashes( void* hashes, uint64_t capacity, bool dstIsDevice )
     {
-        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_line_hashes on a closed reader" );
-        if ( !m_hashes ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_line_hashes: no hashes are held (line_hashes first)" );
-        std::string why;
-        if ( !deviceToHost( m_hashes->device, hashes, m_hashes->dHashes, std::min( capacity, m_hashes->n ) * sizeof( uint64_t ),
-                            dstIsDevice, &why ) ) {
-            fail( MI355X_BZ2_ERR_DEVICE, "take_line_hashes: " + why );
-        }
+        takeColumns( "take_line_hashes", "no hashes are held (line_hashes first)", m_hashes, { hashes }, capacity, dstIsDevice );
     }
 
     [[nodiscard]] const uint64_t*
     lineHashesDevice() const
     {
-        return m_hashes && m_hashes->onDevice && m_hashes->n > 0 ? m_hashes->dHashes : nullptr;
+        return m_hashes && m_hashes->onDevice && m_hashes->n > 0 ? m_hashes->column<const uint64_t>( 0 ) : nullptr;
     }
 
     /** mi355x_bz2_reader_distinct_lines: lineHashes over the whole file, then bz2_distinct.hip. */
@@ -1907,7 +1944,7 @@ public:
         lineHashes( nl, seed, 0, std::numeric_limits<uint64_t>::max(), false, &n );
         std::vector<uint64_t> numbers;
         std::string why;
-        const bool done = distinctHashes( m_device, m_hashes->dHashes, n, nDistinct, wantNumbers ? &numbers : nullptr, &why );
+        const bool done = distinctHashes( m_device, m_hashes->column<const uint64_t>( 0 ), n, nDistinct, wantNumbers ? &numbers : nullptr, &why );
         dropHeldHashes();
         if ( !done ) fail( MI355X_BZ2_ERR_DEVICE, why );
         if ( wantNumbers ) m_distinct = std::move( numbers );
@@ -1924,9 +1961,7 @@ public:
         std::copy_n( m_distinct->begin(), (size_t)std::min<uint64_t>( capacity, m_distinct->size() ), lineNumbers );
     }
 
-    /** mi355x_bz2_reader_field_spans: lineHashes' launches and places with fieldSpansOutput in place of the hashing pass;
-     * then stitchFields, and one start and one size copied for every line that crosses a seam and for the unterminated
-     * tail. */
+    /** mi355x_bz2_reader_field_spans: lineColumns with fieldSpansOutput and stitchFields, a column of starts and one of sizes. */
     void
     fieldSpans( uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
     {
@@ -1935,71 +1970,18 @@ public:
         const auto& index = lineIndex( nl );
         dropHeldLines();
         m_fields.reset();
-        const auto plan = planLaunches( [&] ( bool packed ) {
-            return bz2gpu::planFields( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
-                                       count, m_batch, packed, m_source->size() );
-        } );
-        *nLines = 0;
-        HeldFields held;
-        held.onDevice = keepOnDevice;
-        if ( plan.count == 0 ) {
-            m_fields = std::move( held );
-            return;
-        }
-        std::vector<bz2gpu::FieldStretch> stretches( plan.stretches.size() );
-        for ( size_t k = 0; k < stretches.size(); ++k ) {
-            stretches[k].fileOffset = plan.stretches[k].fileOffset;
-            stretches[k].summary.size = plan.stretches[k].size;
-        }
-        std::string why;
-        held.device = m_device;
-        held.starts.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
-        if ( held.starts ) held.sizes.reset( deviceAllocate( m_device, plan.count * sizeof( int64_t ), &why ) );
-        if ( !held.starts || !held.sizes ) fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
-        auto* const dStarts = static_cast<uint64_t*>( held.starts.get() );
-        auto* const dSizes = static_cast<int64_t*>( held.sizes.get() );
-        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, dl, field, dStarts, dSizes]
-                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
-            checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, work.skip, work.take,
-                                                dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
-            return stretches[k].summary.count;
-        } );
-        /* the first closed line of a stretch is line firstClosed + k of the file */
-        std::vector<std::pair<uint64_t, bz2gpu::FieldSpan> > patches;
-        const auto stitched = bz2gpu::stitchFields( stretches, field, [&] ( uint64_t k, const bz2gpu::FieldSpan& span ) {
-            const uint64_t line = plan.firstClosed + k;
-            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, span );
-        } );
-        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
-        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tail );
-        for ( const auto& [at, span] : patches ) {
-            if ( !hostToDevice( m_device, dStarts + at, &span.start, sizeof( span.start ), &why )
-                 || !hostToDevice( m_device, dSizes + at, &span.size, sizeof( span.size ), &why ) ) {
-                fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
-            }
-        }
-        held.n = n;
-        *nLines = n;
-        m_fields = std::move( held );
+        m_fields = lineColumns( FieldSpanQuery{ nl, dl, field }, "field_spans", index, first, count, keepOnDevice, nLines );
     }
 
     /** mi355x_bz2_reader_take_field_spans. */
     void
     takeFieldSpans( void* starts, void* sizes, uint64_t capacity, bool dstIsDevice )
     {
-        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_spans on a closed reader" );
-        if ( !m_fields ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_spans: no field spans are held (field_spans first)" );
-        std::string why;
-        const uint64_t bytes = std::min( capacity, m_fields->n ) * sizeof( uint64_t );
-        if ( !deviceToHost( m_fields->device, starts, m_fields->starts.get(), bytes, dstIsDevice, &why )
-             || !deviceToHost( m_fields->device, sizes, m_fields->sizes.get(), bytes, dstIsDevice, &why ) ) {
-            fail( MI355X_BZ2_ERR_DEVICE, "take_field_spans: " + why );
-        }
+        takeColumns( "take_field_spans", "no field spans are held (field_spans first)", m_fields, { starts, sizes }, capacity, dstIsDevice );
     }
 
-    /** mi355x_bz2_reader_field_hashes: fieldSpans' launches and places with fieldHashesOutput in place of its pass, a
-     * column of keys beside the two of the spans; then stitchFieldHashes, and one key and one span copied for every line
-     * that crosses a seam and for the unterminated tail. */
+    /** mi355x_bz2_reader_field_hashes: lineColumns with fieldHashesOutput and stitchFieldHashes, a column of keys in front of
+     * the two of the spans.  `what` names the call in its messages: field_groups goes through here. */
     void
     fieldHashes( uint8_t nl, uint8_t dl, uint32_t field, uint64_t seed, uint64_t first, uint64_t count, bool keepOnDevice,
                  uint64_t* nLines, const char* what = "field_hashes" )
@@ -2009,70 +1991,15 @@ public:
         const auto& index = lineIndex( nl );
         dropHeldLines();
         dropHeldFieldHashes();
-        const auto plan = planLaunches( [&] ( bool packed ) {
-            return bz2gpu::planFields( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
-                                       count, m_batch, packed, m_source->size() );
-        } );
-        *nLines = 0;
-        HeldFieldHashes held;
-        held.first = first;
-        held.spans.onDevice = keepOnDevice;
-        if ( plan.count == 0 ) {
-            m_fieldHashes = std::move( held );
-            return;
-        }
-        std::vector<bz2gpu::FieldHashStretch> stretches( plan.stretches.size() );
-        for ( size_t k = 0; k < stretches.size(); ++k ) {
-            stretches[k].fileOffset = plan.stretches[k].fileOffset;
-            stretches[k].summary.fields.size = plan.stretches[k].size;
-        }
-        std::string why;
-        held.spans.device = m_device;
-        held.keys.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
-        if ( held.keys ) held.spans.starts.reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
-        if ( held.spans.starts ) held.spans.sizes.reset( deviceAllocate( m_device, plan.count * sizeof( int64_t ), &why ) );
-        if ( !held.keys || !held.spans.starts || !held.spans.sizes ) fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
-        auto* const dKeys = static_cast<uint64_t*>( held.keys.get() );
-        auto* const dStarts = static_cast<uint64_t*>( held.spans.starts.get() );
-        auto* const dSizes = static_cast<int64_t*>( held.spans.sizes.get() );
-        const uint64_t x = bz2gpu::lineHashBase( seed );
-        const uint64_t wantedClosed = runLineColumn( index, plan, [&stretches, nl, dl, field, x, dKeys, dStarts, dSizes]
-                                                     ( mi355x_bz2_ctx* ctx, size_t k, const auto& piece, const ColumnWork& work ) {
-            checkDevice( ctx, fieldHashesOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, x, work.skip, work.take,
-                                                 dKeys + work.at, dStarts + work.at, dSizes + work.at, &stretches[k].summary ) );
-            return stretches[k].summary.fields.count;
-        } );
-        /* the first closed line of a stretch is line firstClosed + k of the file */
-        std::vector<std::pair<uint64_t, bz2gpu::FieldKey> > patches;
-        const auto stitched = bz2gpu::stitchFieldHashes( stretches, x, dl, field, [&] ( uint64_t k, const bz2gpu::FieldKey& key ) {
-            const uint64_t line = plan.firstClosed + k;
-            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, key );
-        } );
-        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
-        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, stitched.tail );
-        for ( const auto& [at, key] : patches ) {
-            if ( !hostToDevice( m_device, dKeys + at, &key.key, sizeof( key.key ), &why )
-                 || !hostToDevice( m_device, dStarts + at, &key.field.start, sizeof( key.field.start ), &why )
-                 || !hostToDevice( m_device, dSizes + at, &key.field.size, sizeof( key.field.size ), &why ) ) {
-                fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
-            }
-        }
-        held.spans.n = n;
-        *nLines = n;
-        m_fieldHashes = std::move( held );
+        m_fieldHashes = lineColumns( FieldHashQuery{ nl, dl, field, bz2gpu::lineHashBase( seed ) }, what, index, first, count,
+                                     keepOnDevice, nLines );
     }
 
-    /** mi355x_bz2_reader_take_field_hashes. */
+    /** mi355x_bz2_reader_take_field_hashes: the keys; the spans beside them are field_groups'. */
     void
     takeFieldHashes( void* keys, uint64_t capacity, bool dstIsDevice )
     {
-        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_hashes on a closed reader" );
-        if ( !m_fieldHashes ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_hashes: no field hashes are held (field_hashes first)" );
-        std::string why;
-        const uint64_t bytes = std::min( capacity, m_fieldHashes->spans.n ) * sizeof( uint64_t );
-        if ( !deviceToHost( m_fieldHashes->spans.device, keys, m_fieldHashes->keys.get(), bytes, dstIsDevice, &why ) ) {
-            fail( MI355X_BZ2_ERR_DEVICE, "take_field_hashes: " + why );
-        }
+        takeColumns( "take_field_hashes", "no field hashes are held (field_hashes first)", m_fieldHashes, { keys }, capacity, dstIsDevice );
     }
 
     /** mi355x_bz2_reader_field_groups: fieldHashes over the range, then bz2_distinct.hip's groupHashes. */
@@ -2085,10 +2012,8 @@ public:
         std::vector<FieldGroup> groups;
         std::string why;
         const auto& held = *m_fieldHashes;
-        const bool done = groupHashes( m_device, static_cast<const uint64_t*>( held.keys.get() ),
-                                       static_cast<const uint64_t*>( held.spans.starts.get() ),
-                                       static_cast<const int64_t*>( held.spans.sizes.get() ), n, bz2gpu::FIELD_MISSING, &groups,
-                                       nMissing, &why );
+        const bool done = groupHashes( m_device, held.column<const uint64_t>( 0 ), held.column<const uint64_t>( 1 ),
+                                       held.column<const int64_t>( 2 ), n, bz2gpu::FIELD_MISSING, &groups, nMissing, &why );
         dropHeldFieldHashes();
         if ( !done ) fail( MI355X_BZ2_ERR_DEVICE, why );
         for ( auto& group : groups ) group.line += first;
@@ -2190,50 +2115,18 @@ private:
         std::vector<uint64_t> numbers, sizes;              /* per matching line; the bytes are m_held's */
     };
 
-    /** The hashes of line_hashes, in device memory of the reader's own. */
-    struct HeldHashes
-    {
-        uint64_t* dHashes{ nullptr };
-        uint64_t n{ 0 }, capacity{ 0 };
-        int device{ -1 };
-        bool onDevice{ false };
-
-        HeldHashes() = default;
-        HeldHashes( const HeldHashes& ) = delete;
-        HeldHashes& operator=( const HeldHashes& ) = delete;
-        HeldHashes( HeldHashes&& other ) noexcept { *this = std::move( other ); }
-        HeldHashes&
-        operator=( HeldHashes&& other ) noexcept
-        {
-            if ( this != &other ) {
-                deviceRelease( dHashes );
-                dHashes = std::exchange( other.dHashes, nullptr );
-                n = other.n;
-                capacity = other.capacity;
-                device = other.device;
-                onDevice = other.onDevice;
-            }
-            return *this;
-        }
-        ~HeldHashes() { deviceRelease( dHashes ); }
-    };
-
-    /** The starts and sizes of field_spans, in device memory of the reader's own. */
-    struct HeldFields
+    /** The result of a per-line column query, in device memory of the reader's own: up to three columns of n 8-byte words
+     * -- hashes; starts and sizes; keys, starts and sizes.  An empty result has no memory. */
+    struct HeldColumns
     {
         struct Release { void operator()( void* pointer ) const { deviceRelease( pointer ); } };
-        std::unique_ptr<void, Release> starts, sizes;
+        std::array<std::unique_ptr<void, Release>, 3> columns;
         uint64_t n{ 0 };
         int device{ -1 };
         bool onDevice{ false };
-    };
 
-    /** The keys of field_hashes beside their spans, in device memory of the reader's own; `first` is the line of keys[0]. */
-    struct HeldFieldHashes
-    {
-        std::unique_ptr<void, HeldFields::Release> keys;
-        HeldFields spans;
-        uint64_t first{ 0 };
+        template<typename T>
+        [[nodiscard]] T* column( size_t c ) const { return static_cast<T*>( columns[c].get() ); }
     };
 
     void
@@ -2367,42 +2260,98 @@ private:
         } );
     }
 
-    /** What lineHashes and fieldSpans share, columns with one entry per line: per stretch of `plan` the lines it closes --
-     * the line index says how many, so every launch knows its place before any has run --, which of them are wanted
-     * (skip, take) and where they go (at); then the launches, in which perStretch( ctx, k, stretch, work ) does stretch k on
-     * the context that decoded it and returns the number of lines it found the stretch to close, which has to be the
-     * index's.  Returns the number of wanted lines but for the tail. */
-    struct ColumnWork { uint64_t skip{ 0 }, take{ 0 }, at{ 0 }, closed{ 0 }; };
-
+    /** The launches of `plan`, in which perStretch( ctx, k, stretch, place ) does stretch k on the context that decoded it
+     * and returns the number of lines it found the stretch to close, which has to be the index's (places[k].closed). */
     template<typename PerStretch>
-    uint64_t
-    runLineColumn( const LineIndex& index, const bz2gpu::LineHashPlan& plan, const PerStretch& perStretch )
+    void
+    runLineColumn( const bz2gpu::LineHashPlan& plan, const std::vector<bz2gpu::ColumnPlace>& places, const PerStretch& perStretch )
     {
-        std::vector<ColumnWork> works( plan.stretches.size() );
         std::vector<std::vector<size_t> > ofLaunch( plan.launches.size() );
-        const uint64_t first = plan.first, wantedClosed = plan.reachesEnd ? plan.N - first : plan.count;
-        uint64_t closedBefore = plan.firstClosed;
-        for ( size_t k = 0; k < works.size(); ++k ) {
-            const auto& piece = plan.stretches[k];
-            const auto from = std::upper_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset ) - index.bytes.begin() - 1;
-            const auto to = std::lower_bound( index.bytes.begin(), index.bytes.end(), piece.fileOffset + piece.size ) - index.bytes.begin();
-            auto& work = works[k];
-            work.closed = index.lines[to] - index.lines[from];
-            const uint64_t begin = std::max( closedBefore, first ), end = std::min( closedBefore + work.closed, first + wantedClosed );
-            if ( end > begin ) work = { begin - closedBefore, end - begin, begin - first, work.closed };
-            closedBefore += work.closed;
-            ofLaunch[piece.launch].push_back( k );
-        }
+        for ( size_t k = 0; k < plan.stretches.size(); ++k ) ofLaunch[plan.stretches[k].launch].push_back( k );
         runJobs( plan.launches, [&] ( size_t l ) {
-            return [&plan, &works, &perStretch, mine = &ofLaunch[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
+            return [&plan, &places, &perStretch, mine = &ofLaunch[l]] ( mi355x_bz2_ctx* ctx, const bz2gpu::RangeLaunch& ) {
                 for ( const auto k : *mine ) {
                     const auto& piece = plan.stretches[k];
-                    const uint64_t counted = perStretch( ctx, k, piece, works[k] );
-                    if ( counted != works[k].closed ) failLyingLineIndex( piece.fileOffset, works[k].closed, counted );
+                    const uint64_t counted = perStretch( ctx, k, piece, places[k] );
+                    if ( counted != places[k].closed ) failLyingLineIndex( piece.fileOffset, places[k].closed, counted );
                 }
             };
         } );
-        return wantedClosed;
+    }
+
+    /** What line_hashes, field_spans and field_hashes do, given the `query` (the three structs in front of the reader):
+     * the launches of planLineHashes for lines [first, first + count), each doing its stretches on the context that
+     * decoded them, straight into device columns that are allocated before anything is launched and in which every
+     * stretch knows its place (placeLineColumn); then the query's stitcher over the stretches' summaries, and one 8-byte
+     * copy per column for every line that crosses a seam and for the unterminated tail.  *nLines = the lines of the
+     * result, which the caller holds.  A range without lines gives a result without memory.  `what` starts the messages. */
+    template<typename Query>
+    [[nodiscard]] HeldColumns
+    lineColumns( const Query& query, const std::string& what, const LineIndex& index, uint64_t first, uint64_t count,
+                 bool keepOnDevice, uint64_t* nLines )
+    {
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLineHashes( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
+                                           count, m_batch, packed, m_source->size() );
+        } );
+        *nLines = 0;
+        HeldColumns held;
+        held.onDevice = keepOnDevice;
+        if ( plan.count == 0 ) return held;
+        std::vector<typename Query::Stretch> stretches( plan.stretches.size() );
+        for ( size_t k = 0; k < stretches.size(); ++k ) {
+            stretches[k].fileOffset = plan.stretches[k].fileOffset;
+            Query::size( stretches[k] ) = plan.stretches[k].size;
+        }
+        std::string why;
+        held.device = m_device;
+        std::array<uint64_t*, Query::COLUMNS> columns{};
+        for ( size_t c = 0; c < columns.size(); ++c ) {
+            held.columns[c].reset( deviceAllocate( m_device, plan.count * sizeof( uint64_t ), &why ) );
+            if ( !held.columns[c] ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            columns[c] = held.column<uint64_t>( c );
+        }
+        const auto places = bz2gpu::placeLineColumn( plan, index.bytes.data(), index.lines.data(), index.bytes.size() );
+        runLineColumn( plan, places, [&] ( mi355x_bz2_ctx* ctx, size_t k, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place ) {
+            auto to = columns;
+            for ( auto& column : to ) column += place.at;
+            return query.pass( ctx, piece, place, to, stretches[k] );
+        } );
+        /* the first closed line of a stretch is line firstClosed + k of the file */
+        const uint64_t wantedClosed = plan.wantedClosed();
+        std::vector<std::pair<uint64_t, std::array<uint64_t, Query::COLUMNS> > > patches;
+        const auto stitched = query.stitch( stretches, [&] ( uint64_t k, const auto& value ) {
+            const uint64_t line = plan.firstClosed + k;
+            if ( line >= first && line - first < wantedClosed ) patches.emplace_back( line - first, Query::words( value ) );
+        } );
+        uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
+        if ( plan.reachesEnd && stitched.hasTail ) patches.emplace_back( n++, Query::words( Query::tail( stitched ) ) );
+        for ( const auto& [at, words] : patches ) {
+            for ( size_t c = 0; c < columns.size(); ++c ) {
+                if ( !hostToDevice( m_device, columns[c] + at, &words[c], sizeof( words[c] ), &why ) ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            }
+        }
+        held.n = n;
+        *nLines = n;
+        return held;
+    }
+
+    /** What the takes of the column queries do: the first min( capacity, n ) words of the first columns of `held` to the
+     * destinations `to`, one per column; the result stays held. */
+    void
+    takeColumns( const std::string& what, const char* nothingHeld, const std::optional<HeldColumns>& held,
+                 std::initializer_list<void*> to, uint64_t capacity, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, what + " on a closed reader" );
+        if ( !held ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": " + nothingHeld );
+        std::string why;
+        size_t c = 0;
+        for ( void* const destination : to ) {
+            if ( !deviceToHost( held->device, destination, held->columns[c++].get(), std::min( capacity, held->n ) * sizeof( uint64_t ),
+                                dstIsDevice, &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            }
+        }
     }
 
     /** The line index for `nl`: the one the reader holds, or a new one.  The block map is completed first if it has to
@@ -2574,9 +2523,9 @@ private:
     std::optional<HeldSetMatches> m_setMatches;        /* between search_set (with a limit) and take_set_matches */
     std::optional<HeldGrep> m_grep;       /* between grep and take_line_ranges, beside m_held */
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
-    std::optional<HeldHashes> m_hashes;   /* between line_hashes and the next line_hashes / distinct_lines */
-    std::optional<HeldFields> m_fields;   /* between field_spans and the next field_spans */
-    std::optional<HeldFieldHashes> m_fieldHashes;             /* between field_hashes and the next call of its family */
+    std::optional<HeldColumns> m_hashes;  /* between line_hashes and the next line_hashes / distinct_lines */
+    std::optional<HeldColumns> m_fields;  /* between field_spans and the next field_spans */
+    std::optional<HeldColumns> m_fieldHashes;                 /* between field_hashes and the next call of its family */
     std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };

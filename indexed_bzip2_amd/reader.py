@@ -77,6 +77,34 @@ class _IndexedBzip2FileParallel:
         if not self._h:
             raise Exception("Invalid file object!")
 
+    def _device_index(self):
+        """The reader's device index for torch: the one it was opened with, or torch's current device."""
+        import torch
+        torch.cuda.init()
+        return self._device if self._device >= 0 else torch.cuda.current_device()
+
+    def _columns(self, query, take, dtypes, tensors):
+        """Step 1 of a per-line query, then its take -> one array per column.  query(keep_on_device, n) is the native call
+        that holds the columns and sets n, the number of lines; take(*destinations, n, on_device) copies their first n
+        values.  The arrays are numpy arrays of `dtypes`, or with `tensors` torch.int64 tensors on the reader's device,
+        which nothing reaches through the host."""
+        n = ctypes.c_uint64()
+        if not tensors:
+            import numpy as np
+            self._check(query(0, ctypes.byref(n)))
+            out = [np.empty(n.value, dtype=dtype) for dtype in dtypes]
+            self._check(take(*[column.ctypes.data if n.value else None for column in out], n.value, 0))
+            return out
+        import torch
+        dev = self._device_index()
+        self._check(query(1, ctypes.byref(n)))
+        out = [torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}") for _ in dtypes]
+        if n.value:
+            # the new tensors' memory may still be in use by work queued on torch's stream: the copy comes after it
+            torch.cuda.current_stream(out[0].device).synchronize()
+            self._check(take(*[ctypes.c_void_p(column.data_ptr()) for column in out], n.value, 1))
+        return out
+
     def __del__(self):
         try:
             self.close()
@@ -313,8 +341,7 @@ class _IndexedBzip2FileParallel:
         ``data[offsets[i]:offsets[i + 1]]``; `offsets` is an int64 CPU tensor of n + 1 boundaries.  The bytes never pass
         through the host."""
         import torch
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        dev = self._device_index()
         sizes, total = self._read_line_ranges(ranges, newline, True)
         data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
         if total:
@@ -486,8 +513,7 @@ class _IndexedBzip2FileParallel:
         limit = self._line_limit(limit)
         self._require()
         self._grep_arguments(pattern, start, end, newline, any_of)
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        dev = self._device_index()
         if limit == 0:
             numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
         else:
@@ -567,8 +593,7 @@ class _IndexedBzip2FileParallel:
         limit = self._line_limit(limit)
         self._require()
         regex, nl = self._regex(pattern, ignore_case), self._newline(newline)
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        dev = self._device_index()
         if limit == 0:
             numbers, sizes, total = np.empty(0, dtype=np.uint64), [], 0
         else:
@@ -594,34 +619,23 @@ class _IndexedBzip2FileParallel:
         (count,), _ = self._u64([2**64 - 1 if count is None else count], "count")
         return nl, first, count, seed
 
+    def _line_hashes(self, first, count, newline, seed, tensors):
+        nl, first, count, seed = self._line_hash_arguments(first, count, newline, seed)
+        L = N.lib()
+        return self._columns(lambda keep, n: L.mi355x_bz2_reader_line_hashes(self._h, nl, seed, first, count, keep, n),
+                             lambda *to: L.mi355x_bz2_reader_take_line_hashes(self._h, *to), ("uint64",), tensors)[0]
+
     def line_hashes(self, first=0, count=None, newline=b"\n", seed=0):
         """The hashes of lines [first, first + count) (count None: to the last line; clipped there) -> numpy uint64, one
         value below 2^61 per line, equal to line_hash(content, seed).  Only the blocks that hold those lines are decoded,
         each once; the hashes are computed on the GPU and 8 bytes per line come back.  Builds the line index first if
         the reader does not hold one for `newline`.  Positionless."""
-        import numpy as np
-        nl, first, count, seed = self._line_hash_arguments(first, count, newline, seed)
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_line_hashes(self._h, nl, seed, first, count, 0, ctypes.byref(n)))
-        out = np.empty(n.value, dtype=np.uint64)
-        self._check(N.lib().mi355x_bz2_reader_take_line_hashes(self._h, out.ctypes.data if n.value else None, n.value, 0))
-        return out
+        return self._line_hashes(first, count, newline, seed, False)
 
     def line_hashes_to_tensor(self, first=0, count=None, newline=b"\n", seed=0):
         """line_hashes as a torch.int64 tensor on the reader's device; the hashes never pass through the host.  A hash
         is below 2^61, so torch.unique, sort and isin order and compare it as the unsigned value."""
-        import torch
-        nl, first, count, seed = self._line_hash_arguments(first, count, newline, seed)
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_line_hashes(self._h, nl, seed, first, count, 1, ctypes.byref(n)))
-        out = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
-        if n.value:
-            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
-            torch.cuda.current_stream(out.device).synchronize()
-            self._check(N.lib().mi355x_bz2_reader_take_line_hashes(self._h, ctypes.c_void_p(out.data_ptr()), n.value, 1))
-        return out
+        return self._line_hashes(first, count, newline, seed, True)
 
     def _distinct_lines(self, newline, seed, want_numbers):
         nl, _, _, seed = self._line_hash_arguments(0, None, newline, seed)
@@ -662,6 +676,12 @@ class _IndexedBzip2FileParallel:
         (count,), _ = self._u64([2**64 - 1 if count is None else count], "count")
         return nl, delimiter[0], field, first, count
 
+    def _field_spans(self, field, first, count, delimiter, newline, tensors):
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        L = N.lib()
+        return tuple(self._columns(lambda keep, n: L.mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, keep, n),
+                                   lambda *to: L.mi355x_bz2_reader_take_field_spans(self._h, *to), ("uint64", "int64"), tensors))
+
     def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """Where field `field` (0-based, at most 1023) lies in lines [first, first + count) (count None: to the last
         line; clipped there) -> (starts numpy uint64, sizes numpy int64), one pair per line: data[start:start + size] ==
@@ -669,32 +689,12 @@ class _IndexedBzip2FileParallel:
         content ends.  No quoting, no escaping: `cut -f`, not a CSV parser.  Only the blocks that hold those lines are
         decoded, each once; the spans are computed on the GPU and 16 bytes per line come back.  Builds the line index
         first if the reader does not hold one for `newline`.  Positionless."""
-        import numpy as np
-        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, 0, ctypes.byref(n)))
-        starts, sizes = np.empty(n.value, dtype=np.uint64), np.empty(n.value, dtype=np.int64)
-        self._check(N.lib().mi355x_bz2_reader_take_field_spans(self._h, starts.ctypes.data if n.value else None,
-                                                                sizes.ctypes.data if n.value else None, n.value, 0))
-        return starts, sizes
+        return self._field_spans(field, first, count, delimiter, newline, False)
 
     def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """field_spans as two torch.int64 tensors (starts, sizes) on the reader's device; nothing passes through the
         host.  A start is below 2^63, so int64 holds it as it is."""
-        import torch
-        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, 1, ctypes.byref(n)))
-        starts = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
-        sizes = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
-        if n.value:
-            # the new tensors' memory may still be in use by work queued on torch's stream: the copy comes after it
-            torch.cuda.current_stream(starts.device).synchronize()
-            self._check(N.lib().mi355x_bz2_reader_take_field_spans(self._h, ctypes.c_void_p(starts.data_ptr()),
-                                                                    ctypes.c_void_p(sizes.data_ptr()), n.value, 1))
-        return starts, sizes
+        return self._field_spans(field, first, count, delimiter, newline, True)
 
     def _read_fields(self, field, first, count, delimiter, newline, make):
         """field_spans, then the existing read_ranges over the present fields; make(total) -> (destination, pointer,
@@ -732,8 +732,7 @@ class _IndexedBzip2FileParallel:
         fields' bytes never pass through the host."""
         import torch
         self._field_arguments(field, first, count, delimiter, newline)      # refused before the GPU is touched
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
+        dev = self._device_index()
 
         def make(total):
             data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
@@ -753,36 +752,25 @@ class _IndexedBzip2FileParallel:
         (seed,), _ = self._u64([seed], "seed")
         return nl, dl, field, first, count, seed
 
+    def _field_hashes(self, field, first, count, delimiter, newline, seed, tensors):
+        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
+        L = N.lib()
+        return self._columns(lambda keep, n: L.mi355x_bz2_reader_field_hashes(self._h, nl, dl, field, seed, first, count, keep, n),
+                             lambda *to: L.mi355x_bz2_reader_take_field_hashes(self._h, *to), ("uint64",), tensors)[0]
+
     def field_hashes(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """The keys of lines [first, first + count) (count None: to the last line; clipped there) -> numpy uint64, one
         per line: line_hash(content.split(delimiter)[field], seed), or FIELD_MISSING where the line has no such field.
         Only the blocks that hold those lines are decoded, each once; field and hash are found on the GPU in shared
         passes and 8 bytes per line come back.  Builds the line index first if the reader does not hold one for
         `newline`.  Not a CSV parser.  Positionless."""
-        import numpy as np
-        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_field_hashes(self._h, nl, dl, field, seed, first, count, 0, ctypes.byref(n)))
-        out = np.empty(n.value, dtype=np.uint64)
-        self._check(N.lib().mi355x_bz2_reader_take_field_hashes(self._h, out.ctypes.data if n.value else None, n.value, 0))
-        return out
+        return self._field_hashes(field, first, count, delimiter, newline, seed, False)
 
     def field_hashes_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """field_hashes as a torch.int64 tensor on the reader's device; the keys never pass through the host.  A key is
         below 2^61 and FIELD_MISSING is 2^61 - 1, so torch.unique, sort and isin order and compare them as they are:
         join keys for torch.isin."""
-        import torch
-        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
-        torch.cuda.init()
-        dev = self._device if self._device >= 0 else torch.cuda.current_device()
-        n = ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_field_hashes(self._h, nl, dl, field, seed, first, count, 1, ctypes.byref(n)))
-        out = torch.empty(n.value, dtype=torch.int64, device=f"cuda:{dev}")
-        if n.value:
-            # the new tensor's memory may still be in use by work queued on torch's stream: the copy comes after it
-            torch.cuda.current_stream(out.device).synchronize()
-            self._check(N.lib().mi355x_bz2_reader_take_field_hashes(self._h, ctypes.c_void_p(out.data_ptr()), n.value, 1))
-        return out
+        return self._field_hashes(field, first, count, delimiter, newline, seed, True)
 
     def _field_groups(self, field, first, count, delimiter, newline, seed):
         """mi355x_bz2_reader_field_groups and its take -> (lines, counts, starts, sizes, missing)."""

@@ -2,8 +2,11 @@
  * linehash_cases.cpp -- indexed_bzip2_amd/csrc/bz2_linehash.hpp on the CPU, as a program of its own that the test suite
  * builds with -fsanitize=address,undefined: the known answers, mulmod against 128-bit arithmetic, the composition's
  * associativity, summarise against the direct definition and independent of the chunk size, stitchSummaries over random
- * cuts, its refusals, spans beyond 2^32 (synthetic summaries, no bytes) and the plan of a range of lines.
+ * cuts, its refusals, spans beyond 2^32 (synthetic summaries, no bytes), the plan of a range of lines and the places of
+ * its stretches in a column (placeLineColumn) against a direct count of the delimiters.
  */
+#include <algorithm>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -247,6 +250,94 @@ plans()
     for ( const auto& launch : p.launches ) blocks += launch.bits.size();
     CHECK( blocks == 4 );
 }
+
+/** placeLineColumn against a direct count of the delimiters in the bytes: a text in blocks of 150 to 400 bytes, a long line
+ * through three of them, with and without an unterminated tail, planned with caps that give one to many launches. */
+void
+places( std::mt19937_64& rng )
+{
+    const uint8_t nl = '\n';
+    for ( const bool tail : { true, false } ) {
+        Bytes text;
+        std::vector<uint64_t> lineBytes{ 0 }, lineLines{ 0 };
+        std::vector<std::pair<uint64_t, uint64_t> > map{ { 32, 0 } };
+        for ( size_t block = 0; block < 12; ++block ) {
+            const size_t size = 150 + rng() % 251;
+            for ( size_t i = 0; i < size; ++i ) {
+                const bool inLongLine = block >= 4 && block <= 6;       /* blocks 4 to 6 close no line */
+                text.push_back( !inLongLine && rng() % 40 == 0 ? nl : uint8_t( 'a' + rng() % 3 ) );
+            }
+            if ( block == 11 ) text.back() = tail ? 'x' : nl;
+            lineBytes.push_back( text.size() );
+            lineLines.push_back( (uint64_t)std::count( text.begin(), text.end(), nl ) );
+            map.emplace_back( 32 + 1000 * ( block + 1 ), text.size() );
+        }
+        const uint64_t N = lineLines.back();
+        const auto delimitersIn = [&] ( uint64_t from, uint64_t to ) {
+            return (uint64_t)std::count( text.begin() + (ptrdiff_t)from, text.begin() + (ptrdiff_t)to, nl );
+        };
+        CHECK( N > 20 && delimitersIn( lineBytes[4], lineBytes[7] ) == 0 );
+        /* the line that runs through blocks 4 to 6, and a block that closes at least three lines */
+        const uint64_t longLine = lineLines[4];
+        size_t busy = 0;
+        while ( lineLines[busy + 1] - lineLines[busy] < 3 ) ++busy;
+        const std::vector<std::pair<uint64_t, uint64_t> > ranges{
+            { 0, ~uint64_t( 0 ) }, { 0, N }, { 0, N + 1 }, { 0, 1 }, { lineLines[busy] + 1, 1 }, { lineLines[busy] + 1, 2 },
+            { longLine, 1 }, { longLine + 1, 3 }, { longLine - 1, 4 }, { lineLines[8] + 1, 5 }, { 3, N - 5 }, { N - 2, 2 },
+            { N - 2, 3 }, { N - 2, 1000 }, { N - 1, ~uint64_t( 0 ) }, { N, 1 }, { N, 0 }, { N + 1, 1 }, { N + 7, ~uint64_t( 0 ) }, { 5, 0 } };
+        bool sawInsideOneStretch = false, sawEarlierBlock = false, sawNoLine = false, sawLaunches = false, sawTail = false;
+        for ( const size_t cap : { size_t( 1 ), size_t( 2 ), size_t( 3 ), size_t( 5 ), size_t( 64 ) } ) {
+            for ( const auto& [first, count] : ranges ) {
+                const auto plan = planLineHashes( map, lineBytes.data(), lineLines.data(), lineBytes.size(), first, count, cap, false,
+                                                  ( 32 + 1000 * 12 ) / 8 + 100 );
+                const auto placed = placeLineColumn( plan, lineBytes.data(), lineLines.data(), lineBytes.size() );
+                /* count clipped at N + 1 - first, nothing for first > N; the tail is wanted where the range goes past line N - 1 */
+                CHECK( plan.N == N && plan.first == first );
+                CHECK( plan.count == ( first > N ? 0 : std::min( count, N + 1 - first ) ) );
+                CHECK( plan.reachesEnd == ( plan.count > 0 && plan.count > N - first ) );
+                const uint64_t wanted = plan.count - ( plan.reachesEnd ? 1 : 0 );
+                CHECK( plan.wantedClosed() == wanted );
+                CHECK( placed.size() == plan.stretches.size() && ( plan.count > 0 ) == !placed.empty() );
+                if ( placed.empty() ) continue;
+                CHECK( plan.firstClosed == delimitersIn( 0, plan.stretches.front().fileOffset ) && plan.firstClosed <= first );
+                uint64_t closedBefore = plan.firstClosed, next = 0, taking = 0;
+                for ( size_t k = 0; k < placed.size(); ++k ) {
+                    const auto& piece = plan.stretches[k];
+                    const uint64_t closed = delimitersIn( piece.fileOffset, piece.fileOffset + piece.size );
+                    CHECK( placed[k].closed == closed );
+                    /* from the delimiters themselves: the one at text[p] closes line number( p ) = the delimiters in front
+                     * of it; of those inside the stretch, the wanted ones are lines [first, first + wanted) */
+                    uint64_t skip = 0, take = 0, at = 0;
+                    for ( uint64_t p = piece.fileOffset; p < piece.fileOffset + piece.size; ++p ) {
+                        if ( text[p] != nl ) continue;
+                        const uint64_t line = delimitersIn( 0, p );
+                        if ( line < first ) ++skip;
+                        if ( line >= first && line - first < wanted && take++ == 0 ) at = line - first;
+                    }
+                    if ( take > 0 ) {
+                        CHECK( placed[k].skip == skip && placed[k].take == take && placed[k].at == at );
+                        CHECK( placed[k].at == next );         /* the places tile the column without gap or overlap */
+                        next += placed[k].take;
+                        ++taking;
+                        if ( placed[k].skip > 0 && placed[k].skip + placed[k].take < closed && placed[k].take == wanted ) sawInsideOneStretch = true;
+                    } else {
+                        CHECK( placed[k].take == 0 );
+                    }
+                    if ( closed == 0 ) sawNoLine = true;
+                    closedBefore += closed;
+                }
+                CHECK( next == wanted );
+                /* the last stretch reaches the delimiter that closes the last wanted line, or the end of the file */
+                CHECK( closedBefore >= first + wanted );
+                if ( plan.reachesEnd ) CHECK( plan.stretches.back().fileOffset + plan.stretches.back().size == text.size() );
+                if ( first > plan.firstClosed && first == longLine + 1 ) sawEarlierBlock = true;
+                if ( plan.launches.size() > 2 && taking > 2 ) sawLaunches = true;
+                if ( plan.reachesEnd && wanted > 0 ) sawTail = true;
+            }
+        }
+        CHECK( sawInsideOneStretch && sawEarlierBlock && sawNoLine && sawLaunches && sawTail );
+    }
+}
 }  // namespace
 
 int
@@ -259,6 +350,7 @@ main()
     refusals();
     beyondFourGiB();
     plans();
+    places( rng );
     std::puts( "linehash cases ok" );
     return 0;
 }
