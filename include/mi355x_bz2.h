@@ -478,6 +478,42 @@ int mi355x_bz2_field_hashes( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* sp
                              uint64_t* head_hashes, uint64_t* hashes_device, uint64_t* starts_device, int64_t* sizes_device,
                              uint64_t capacity );
 
+/* Field `field` of every line as a number.  The bytes b of a field are a NUMBER iff they match [+-]?[0-9]{1,18} from end
+ * to end, and the value is the decimal integer they spell: no whitespace, no '_', no hex, no floats; leading zeros count
+ * towards the 18 digits; "-0" is 0; the empty field, "+", "-" and 19 or more digits are no numbers.  This is not awk's
+ * strtod and not Python's int(), which both accept more.  18 digits always fit int64: nothing overflows, and a number has
+ * at most 19 bytes.  Per line one int64 word: the value; MI355X_BZ2_FIELD_NOT_A_NUMBER = -2^63 where the field is present
+ * and no number; MI355X_BZ2_FIELD_NUMBER_MISSING = -2^63 + 1 where the line has fewer fields.  No value takes either.
+ * Fields and line numbering are those of mi355x_bz2_field_spans.
+ *   _parse_field_number  the definition on the CPU: the value of bytes[0, size), or MI355X_BZ2_FIELD_NOT_A_NUMBER.
+ *   _field_numbers    over spans as for _field_spans, with the same refusals before anything is launched and the same
+ *                     summaries and head_positions.  A mi355x_bz2_field_text is the first 19 bytes of a byte string and
+ *                     its size, saturated at 20.  head_texts[i * ( field + 1 ) + k], k <= head_delims and k <= field, is
+ *                     that of span i's bytes between head position k - 1 (or the span's start) and head position k (or
+ *                     first_nl, or the span's end); tail_texts[i] that of the field of the line that begins at
+ *                     tail_start, from tail_field_start to tail_field_end or the span's end, empty where
+ *                     tail_field_start is not reached (host memory, room for n * ( field + 1 ) and for n; each may be
+ *                     NULL).  numbers_device[] (int64, DEVICE memory, room for `capacity`) receives the words of the
+ *                     closed lines in _field_spans' order, the first `capacity` of them; starts_device[] and
+ *                     sizes_device[] receive what _field_spans writes, or are both NULL.  Nothing is written at or
+ *                     beyond `capacity`.  The first closed line of a span is computed as if the span were entered at a
+ *                     line start: the caller that knows the field's bytes in front of the span replaces it
+ *                     (bz2_fieldnum.hpp: stitchFieldNumbers).  The call returns when everything is written.
+ *                     k_field_chunks, k_field_link, k_scan_tiles, k_field_emit, k_field_sizes, k_field_numbers,
+ *                     k_field_texts. */
+#define MI355X_BZ2_FIELD_NOT_A_NUMBER ( -0x7FFFFFFFFFFFFFFFll - 1 )
+#define MI355X_BZ2_FIELD_NUMBER_MISSING ( -0x7FFFFFFFFFFFFFFFll )
+typedef struct mi355x_bz2_field_text
+{
+    uint8_t size;
+    uint8_t bytes[19];
+} mi355x_bz2_field_text;
+int64_t mi355x_bz2_parse_field_number( const uint8_t* bytes, uint64_t size );
+int mi355x_bz2_field_numbers( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl,
+                              uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* head_positions,
+                              mi355x_bz2_field_text* head_texts, mi355x_bz2_field_text* tail_texts, int64_t* numbers_device,
+                              uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
+
 /* Many independent bzip2 buffers (each a complete .bz2 byte string: ZIP members, Avro / Hadoop blocks, one blob per
  * sample) in shared GPU batches.  Buffer i decodes to exactly what mi355x_bz2_reader_open_memory( buffers[i], sizes[i],
  * 1, ... ) and a read to the end produce, stream-CRC check included; when that read would fail, results[i].status is
@@ -846,6 +882,42 @@ int mi355x_bz2_reader_field_groups( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl
                                     uint64_t count, uint64_t* n_groups, uint64_t* n_missing );
 int mi355x_bz2_reader_take_field_groups( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts,
                                          int64_t* sizes, uint64_t capacity );
+
+/* ---- field numbers and sums (mi355x_bz2_field_numbers says what the number of a field is: not awk's strtod).
+ *   _field_numbers    the int64 words of lines [first, first + count), count clipped at the last line; *n_lines = their
+ *                     number.  Refusals, line index, launches, residency and failure rules are _field_spans': every needed
+ *                     block is decoded once per call, each launch runs mi355x_bz2_field_numbers' kernels on the context
+ *                     that decoded its blocks, straight into three device buffers of the reader's (numbers, starts,
+ *                     sizes) allocated before anything is launched, and the host stitches the launches' summaries and
+ *                     patches one number and one span per seam and for the tail.  They are held until the next
+ *                     _field_numbers or _field_sums or the close.  Positionless; releases line ranges held by earlier
+ *                     calls.
+ *   _take_field_numbers  the first min( capacity, n_lines ) held words (int64 each) to `dst`, host memory or, with
+ *                     dst_is_device, device memory; they stay held.
+ *   _field_sums       the lines [first, first + count) grouped by the key of key_field (mi355x_bz2_field_hashes' key
+ *                     under `seed`), with the numbers of value_field summed per group: every needed block is decoded
+ *                     ONCE, each launch runs the field-hash kernels for key_field and the field-number kernels for
+ *                     value_field over the same resident bytes; then on the GPU a stable radix sort (rocPRIM) of (key,
+ *                     line) over 61 bits and one reduce-by-key over the values in that order -- a 128-bit sum, min, max,
+ *                     the count of numbers, the count of lines and the first line --, so that one key shared by every
+ *                     line costs what all-distinct keys cost.  The run of MI355X_BZ2_FIELD_MISSING is dropped and its
+ *                     length is *n_missing; the others, *n_groups of them, are sorted by first line.  72 bytes per group
+ *                     come to the host and nothing per line.  key_field == value_field is allowed.  Nothing per line
+ *                     stays held; the groups are held until the next call of this family or the close.
+ *   _take_field_sums  of the first min( capacity, n_groups ) held groups, ascending by first line: lines[] = the first
+ *                     line (numbered in the file), counts[] = the lines with that key, starts[] / sizes[] = the key
+ *                     field in that first line, numbers[] = those of the lines whose value field is a number, sums_lo[]
+ *                     (uint64) and sums_hi[] (int64) their exact sum = hi * 2^64 + lo, mins[] / maxs[] the least and the
+ *                     largest of them, MI355X_BZ2_FIELD_NOT_A_NUMBER where numbers[] is 0.  Any of the nine may be
+ *                     NULL. */
+int mi355x_bz2_reader_field_numbers( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
+                                     int keep_on_device, uint64_t* n_lines );
+int mi355x_bz2_reader_take_field_numbers( mi355x_bz2_reader* r, void* dst, uint64_t capacity, int dst_is_device );
+int mi355x_bz2_reader_field_sums( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t key_field, uint32_t value_field,
+                                  uint64_t seed, uint64_t first, uint64_t count, uint64_t* n_groups, uint64_t* n_missing );
+int mi355x_bz2_reader_take_field_sums( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes,
+                                       uint64_t* numbers, uint64_t* sums_lo, int64_t* sums_hi, int64_t* mins, int64_t* maxs,
+                                       uint64_t capacity );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

@@ -23,7 +23,10 @@ a delimiter byte exactly as bytes.split splits it (size -1 where a line has fewe
 read_fields_to_tensor bring those bytes and nothing else (`cut -f`, `awk -F`); there is no quoting or escaping, this is not
 a CSV parser.  And how often each value of a column occurs: field_hashes and field_hashes_to_tensor give the hash of
 field j of every line (FIELD_MISSING, 2^61 - 1, where a line has no such field), count_by_field groups the lines by it on
-the GPU and value_counts adds the values (`cut -f3 | sort | uniq -c | sort -rn`).
+the GPU and value_counts adds the values (`cut -f3 | sort | uniq -c | sort -rn`).  And how much: field_ints and
+field_ints_to_tensor give field j of every line as an int64 (parse_field_number says which bytes are a number:
+[+-]?[0-9]{1,18}, not awk's strtod; FIELD_NOT_A_NUMBER and FIELD_NUMBER_MISSING otherwise), sum_by_field sums one column
+per value of another on the GPU from one decode, exactly, and value_sums adds the keys (`awk '{s[$1]+=$3}'`).
 """
 __version__ = "0.1.0"
 
@@ -36,8 +39,8 @@ import os as _os
 # existing setting wins
 _os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 
-from ._native import (FIELD_MISSING, Bz2Error, CompiledRegex, Decoder, compile_regex, find_magic, lib,  # noqa: F401
-                      line_hash, plan_compress_blocks, status_string, warmup)
+from ._native import (FIELD_MISSING, FIELD_NOT_A_NUMBER, FIELD_NUMBER_MISSING, Bz2Error, CompiledRegex, Decoder,  # noqa: F401
+                      compile_regex, find_magic, lib, line_hash, parse_field_number, plan_compress_blocks, status_string, warmup)
 from .buffers import (compress, compress_many, decompress, decompress_many,  # noqa: F401
                       decompress_many_to_tensor)
 from .reader import (IndexedBzip2File, IndexedBzip2FileRaw, open, read_block_offsets,  # noqa: F401

@@ -207,6 +207,15 @@ SYMBOLS = [
     ("mi355x_bz2_reader_field_groups", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
                                                        ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
     ("mi355x_bz2_reader_take_field_groups", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_parse_field_number", ctypes.c_int64, [ctypes.c_char_p, ctypes.c_uint64]),
+    ("mi355x_bz2_field_numbers", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
+                                                 ctypes.c_uint32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_field_numbers", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                                                        ctypes.c_uint64, ctypes.c_int, _u64p]),
+    ("mi355x_bz2_reader_take_field_numbers", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_reader_field_sums", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint32,
+                                                     ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_field_sums", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -452,6 +461,31 @@ class FieldHashSummary(ctypes.Structure):
                 ("head_xl", ctypes.c_uint64), ("tail_hash", ctypes.c_uint64), ("tail_xl", ctypes.c_uint64),
                 ("tail_start_hash", ctypes.c_uint64), ("tail_end_hash", ctypes.c_uint64), ("head_delims", ctypes.c_uint32),
                 ("tail_delims", ctypes.c_uint32), ("has_delimiter", ctypes.c_uint32), ("tail_non_empty", ctypes.c_uint32)]
+
+
+FIELD_NOT_A_NUMBER = -2**63          # MI355X_BZ2_FIELD_NOT_A_NUMBER: the field is present and is no number
+FIELD_NUMBER_MISSING = -2**63 + 1    # MI355X_BZ2_FIELD_NUMBER_MISSING: the line has no such field
+
+
+class FieldText(ctypes.Structure):
+    """mi355x_bz2_field_text: the first 19 bytes of a byte string and its size, saturated at 20"""
+    _fields_ = [("size", ctypes.c_uint8), ("bytes", ctypes.c_uint8 * 19)]
+
+    def as_tuple(self):
+        """(size, the bytes that are kept)"""
+        return int(self.size), bytes(self.bytes[:min(self.size, 19)])
+
+
+def parse_field_number(content):
+    """The number field_ints gives a field with these bytes, on the CPU: int(content) if the bytes match
+    [+-]?[0-9]{1,18} from end to end, else None.  No whitespace, no '_', no hex, no floats; leading zeros count towards
+    the 18 digits; b"-0" is 0; b"", b"+", b"-" and 19 or more digits are no numbers.  This is not awk's strtod and not
+    Python's int(), which accept more.  Needs no GPU."""
+    if isinstance(content, str):
+        raise TypeError("the content must be a bytes-like object, not str")
+    data = bytes(_byte_view(content))
+    value = int(lib().mi355x_bz2_parse_field_number(data, len(data)))
+    return None if value == FIELD_NOT_A_NUMBER else value
 
 
 def pattern_set(patterns, check=True):
@@ -927,6 +961,43 @@ class Decoder:
                         "tail_end_hash": None if s.tail_field_end == none else int(s.tail_end_hash),
                         "head": (int(s.head_hash), int(s.head_xl)), "tail": (int(s.tail_hash), int(s.tail_xl))})
         return out, keys[:room], starts[:room], sizes[:room]
+
+    def field_numbers(self, spans, field, delimiter=b"\t", newline=b"\n", capacity=None, room=None):
+        """k_field_chunks, k_field_link, k_scan_tiles, k_field_emit, k_field_sizes, k_field_numbers, k_field_texts:
+        field_spans with the number of the field beside its span -> (summaries, numbers, starts, sizes).  A summary is
+        field_spans' dict with head_texts (one (size, bytes) per head segment: the span's bytes between two head
+        positions, at most field + 1 of them, the size saturated at 20 and at most 19 bytes kept) and tail_text (that of
+        the tail line's field as far as the span reaches).  numbers is a numpy int64 array shaped and filled like starts
+        and sizes: `room` values that were FIELD_NOT_A_NUMBER + 2 before the call, of which the call may write the first
+        `capacity`: parse_field_number's value, FIELD_NOT_A_NUMBER, or FIELD_NUMBER_MISSING (not awk's strtod)."""
+        import numpy as np
+        nl, dl, field = _field_query_arguments(newline, delimiter, field)
+        spans = [(int(o), int(n)) for o, n in spans]
+        arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
+        summaries = (FieldSummary * max(1, len(spans)))()
+        heads = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
+        head_texts = (FieldText * max(1, len(spans) * (field + 1)))()
+        tail_texts = (FieldText * max(1, len(spans)))()
+
+        def call(numbers, starts, sizes, capacity):
+            self._check(lib().mi355x_bz2_field_numbers(self._h, arr, len(spans), nl, dl, field, summaries, heads.ctypes.data,
+                                                       head_texts, tail_texts, numbers, starts, sizes, capacity))
+        if capacity is None:
+            call(None, None, None, 0)
+            capacity = sum(s.count for s in summaries[:len(spans)])
+        room = capacity if room is None else max(int(room), capacity)
+        numbers = np.full(max(1, room), FIELD_NOT_A_NUMBER + 2, dtype=np.int64)
+        starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
+        _with_device_copies("field_numbers", [numbers, starts, sizes], lambda *device: call(*device, capacity))
+        out = []
+        for i, s in enumerate(summaries[:len(spans)]):
+            at = i * (field + 1)
+            listed = min(s.head_delims + 1, field + 1)
+            out.append({**_field_summary_dict(s, heads[at:]),
+                        "head_texts": [text.as_tuple() for text in head_texts[at:at + listed]],
+                        "tail_text": tail_texts[i].as_tuple()})
+        return out, numbers[:room], starts[:room], sizes[:room]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

@@ -12,6 +12,7 @@
 
 #include "../../include/mi355x_bz2.h"
 #include "bz2_fieldhash.hpp"
+#include "bz2_fieldnum.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_regex.hpp"
@@ -82,6 +83,15 @@ int fieldHashesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, 
                        uint32_t field, uint64_t x, uint64_t skip, uint64_t take, uint64_t* dKeys, uint64_t* dStarts, int64_t* dSizes,
                        bz2gpu::FieldHashSummary* summary );
 
+/** The reader's field-number pass in one launch: mi355x_bz2_field_numbers with `extent` as its one span, whose first byte
+ * is offset `fileOffset` of the decoded file.  *summary receives the extent's summary with its texts and the count of the
+ * lines it closes, none of them listed; the number of the field in its closed lines [skip, skip + take) goes to
+ * dNumbers[0, ...), device memory, and start and size to dStarts[0, ...) and dSizes[0, ...), the starts as offsets in the
+ * file, unless both are null. */
+int fieldNumbersOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                        uint32_t field, uint64_t skip, uint64_t take, int64_t* dNumbers, uint64_t* dStarts, int64_t* dSizes,
+                        bz2gpu::FieldNumberSummary* summary );
+
 /** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
  * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies
  * to device memory instead. */
@@ -109,6 +119,22 @@ struct FieldGroup
  * fills it. */
 bool groupHashes( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t missing,
                   std::vector<FieldGroup>* groups, uint64_t* nMissing, std::string* error );
+
+/** One group of lines with the same key and the numbers among their values: the FieldGroup, how many of the values are
+ * numbers, their exact sum = sumHi * 2^64 + sumLo, and the least and the largest of them (FIELD_NOT_A_NUMBER without
+ * one). */
+struct FieldSumGroup
+{
+    uint64_t line{ 0 }, count{ 0 }, start{ 0 };
+    int64_t size{ 0 };
+    uint64_t numbers{ 0 }, sumLo{ 0 };
+    int64_t sumHi{ 0 }, min{ 0 }, max{ 0 };
+};
+
+/** groupHashes with dValues[0, n), the lines' field-number words, reduced per group in one reduce-by-key behind the
+ * sort: a key that every line shares costs what all-distinct keys cost. */
+bool groupSums( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, const int64_t* dValues, uint64_t n,
+                uint64_t missing, std::vector<FieldSumGroup>* groups, uint64_t* nMissing, std::string* error );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

@@ -34,6 +34,7 @@
 #include "bz2_linehash.hip.h"
 #include "bz2_fields.hip.h"
 #include "bz2_fieldhash.hip.h"
+#include "bz2_fieldnum.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
 #include "bz2_walk.hip.h"
@@ -45,6 +46,7 @@
 #include "bz2_linehash.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_fieldhash.hpp"
+#include "bz2_fieldnum.hpp"
 
 using namespace bz2gpu;
 

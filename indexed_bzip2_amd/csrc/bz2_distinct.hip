@@ -17,14 +17,28 @@
  *   rocPRIM           sort ( first line, run ) ascending
  *   k_group_order     the groups in that order, 32 bytes each, for the one D2H
  *
+ * and those groups with the numbers of a second field summed per group (mi355x_bz2_reader_field_sums):
+ *
+ *   rocPRIM           the stable sort of ( key, line ) and k_flag_runs as above, for the number of runs; then ONE
+ *                     reduce-by-key over the sorted line numbers, each
+ *                     read as the SumPart of its line's value: a 128-bit sum ( uint64 lo, int64 hi, with carry ), min, max,
+ *                     the count of numbers, the count of lines and the least line.  Its cost does not depend on the
+ *                     lengths of the runs: one key shared by every line costs what all-distinct keys cost
+ *   k_sum_runs        per run: the group from its SumPart and its first line's key span; the last run's length goes
+ *                     aside if its key stands for a missing field
+ *   rocPRIM           sort ( first line, run ) ascending
+ *   k_sum_order       the groups in that order, 72 bytes each, for the one D2H
+ *
  * The null stream and buffers of the call's own: it comes when the reader's launches are through.  Every buffer is
  * allocated before the pass that fills it, so that a failed allocation loses no result.
  */
 #include <hip/hip_runtime.h>
 
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_reduce_by_key.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
+#include <rocprim/iterator/transform_iterator.hpp>
 
 #include <algorithm>
 #include <cstdint>
@@ -81,6 +95,69 @@ k_group_runs( const uint64_t* __restrict__ runStarts, uint64_t nRuns, uint64_t n
 __global__ __launch_bounds__( DISTINCT_THREADS ) void
 k_group_order( const mi355x::FieldGroup* __restrict__ groups, const uint64_t* __restrict__ order, uint64_t nGroups,
                mi355x::FieldGroup* __restrict__ ordered )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( i < nGroups ) ordered[i] = groups[order[i]];
+}
+
+/** What reduce-by-key carries per run of equal keys in groupSums: the exact sum of the numbers as 128 bits, their least,
+ * their largest and their count, the count of lines and the first line. */
+struct SumPart
+{
+    uint64_t lo;
+    int64_t hi, min, max;
+    uint64_t numbers, count, line;
+};
+
+constexpr int64_t SUM_NOT_A_NUMBER = bz2gpu::FIELD_NOT_A_NUMBER, SUM_MISSING = bz2gpu::FIELD_NUMBER_MISSING;
+
+/** The SumPart of one sorted element: line number -> that line's value. */
+struct SumOfLine
+{
+    const int64_t* values;
+
+    __device__ SumPart
+    operator()( uint64_t line ) const
+    {
+        const int64_t value = values[line];
+        if ( value == SUM_NOT_A_NUMBER || value == SUM_MISSING ) return { 0, 0, INT64_MAX, INT64_MIN, 0, 1, line };
+        return { (uint64_t)value, value < 0 ? -1 : 0, value, value, 1, 1, line };
+    }
+};
+
+/** Two SumParts as one: associative and commutative. */
+struct SumJoin
+{
+    __device__ SumPart
+    operator()( const SumPart& a, const SumPart& b ) const
+    {
+        const uint64_t lo = a.lo + b.lo;
+        return { lo, a.hi + b.hi + ( lo < a.lo ? 1 : 0 ), a.min < b.min ? a.min : b.min, a.max > b.max ? a.max : b.max,
+                 a.numbers + b.numbers, a.count + b.count, a.line < b.line ? a.line : b.line };
+    }
+};
+
+/** One lane per run of equal keys: keys[r] ascend and parts[r] is the run's reduction. */
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_sum_runs( const uint64_t* __restrict__ keys, const SumPart* __restrict__ parts, uint64_t nRuns, const uint64_t* __restrict__ starts,
+            const int64_t* __restrict__ sizes, uint64_t missing, mi355x::FieldSumGroup* __restrict__ groups,
+            uint64_t* __restrict__ firstLines, uint64_t* __restrict__ runs, unsigned long long* __restrict__ nMissing )
+{
+    const uint64_t r = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( r >= nRuns ) return;
+    const SumPart part = parts[r];
+    const bool none = part.numbers == 0;
+    groups[r] = { part.line, part.count, starts[part.line], sizes[part.line], part.numbers, part.lo, part.hi,
+                  none ? SUM_NOT_A_NUMBER : part.min, none ? SUM_NOT_A_NUMBER : part.max };
+    firstLines[r] = part.line;
+    runs[r] = r;
+    /* the keys ascend and `missing` is the largest there is */
+    if ( r + 1 == nRuns && keys[r] == missing ) *nMissing = part.count;
+}
+
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_sum_order( const mi355x::FieldSumGroup* __restrict__ groups, const uint64_t* __restrict__ order, uint64_t nGroups,
+             mi355x::FieldSumGroup* __restrict__ ordered )
 {
     const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
     if ( i < nGroups ) ordered[i] = groups[order[i]];
@@ -307,6 +384,101 @@ mi355x::groupHashes( int device, const uint64_t* dKeys, const uint64_t* dStarts,
                         0, stream, dGroups, dOrder, nGroups, dOrdered );
     DISTINCT_TRY( hipGetLastError() );
     DISTINCT_TRY( hipMemcpyAsync( groups->data(), dOrdered, nGroups * sizeof( FieldGroup ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    return true;
+}
+
+bool
+mi355x::groupSums( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, const int64_t* dValues, uint64_t n,
+                   uint64_t missing, std::vector<FieldSumGroup>* groups, uint64_t* nMissing, std::string* error )
+{
+    static_assert( sizeof( FieldSumGroup ) == 72, "72 bytes per group come to the host" );
+    groups->clear();
+    *nMissing = 0;
+    if ( n == 0 ) return true;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    const hipStream_t stream = nullptr;
+    const uint32_t blocks = (uint32_t)( ( n + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS );
+    if ( (uint64_t)blocks * DISTINCT_THREADS < n ) {
+        *error = "field_sums: too many lines";
+        return false;
+    }
+
+    Buffers buffers;
+    buffers.who = "field_sums";
+    uint64_t *dNumbers = nullptr, *dSortedKeys = nullptr, *dSortedNumbers = nullptr, *dRunKeys = nullptr;
+    uint8_t* dFlags = nullptr;
+    SumPart* dParts = nullptr;
+    unsigned long long* dCount = nullptr;     /* runs, lines with a missing key field, the reduction's runs */
+    void* dTemp = nullptr;
+    size_t sortBytes = 0, reduceBytes = 0;
+    DISTINCT_TRY( rocprim::radix_sort_pairs( nullptr, sortBytes, dKeys, dSortedKeys, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+    if ( !buffers.get( &dNumbers, n * 8, "the line numbers", error ) || !buffers.get( &dSortedKeys, n * 8, "the sorted keys", error )
+         || !buffers.get( &dSortedNumbers, n * 8, "the sorted line numbers", error ) || !buffers.get( &dFlags, n, "the flags", error )
+         || !buffers.get( &dCount, 3 * sizeof( unsigned long long ), "the counts", error )
+         || !buffers.get( &dTemp, sortBytes, "the sort", error ) ) {
+        return false;
+    }
+    DISTINCT_TRY( hipMemsetAsync( dCount, 0, 3 * sizeof( unsigned long long ), stream ) );
+    hipLaunchKernelGGL( k_iota, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dNumbers, n );
+    DISTINCT_TRY( hipGetLastError() );
+    DISTINCT_TRY( rocprim::radix_sort_pairs( dTemp, sortBytes, dKeys, dSortedKeys, dNumbers, dSortedNumbers, (size_t)n, 0, 61, stream ) );
+
+    /* the runs are counted first, so that the reduction's output takes 56 bytes per run and not per line */
+    hipLaunchKernelGGL( k_flag_runs, dim3( blocks ), dim3( DISTINCT_THREADS ), 0, stream, dSortedKeys, n, dFlags, dCount );
+    DISTINCT_TRY( hipGetLastError() );
+    unsigned long long nRuns = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &nRuns, dCount, sizeof( nRuns ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+
+    /* one reduction over the values in sorted order, whatever the lengths of the runs; the runs' keys go where the
+     * unsorted numbers were */
+    dRunKeys = dNumbers;
+    const auto values = rocprim::make_transform_iterator( dSortedNumbers, SumOfLine{ dValues } );
+    DISTINCT_TRY( rocprim::reduce_by_key( nullptr, reduceBytes, dSortedKeys, values, (size_t)n, dRunKeys, dParts, dCount + 2, SumJoin{},
+                                          rocprim::equal_to<uint64_t>{}, stream ) );
+    void* dTempReduce = dTemp;
+    if ( !buffers.get( &dParts, nRuns * sizeof( SumPart ), "the sums", error )
+         || ( reduceBytes > sortBytes && !buffers.get( &dTempReduce, reduceBytes, "the reduction", error ) ) ) {
+        return false;
+    }
+    DISTINCT_TRY( rocprim::reduce_by_key( dTempReduce, reduceBytes, dSortedKeys, values, (size_t)n, dRunKeys, dParts, dCount + 2, SumJoin{},
+                                          rocprim::equal_to<uint64_t>{}, stream ) );
+
+    FieldSumGroup *dGroups = nullptr, *dOrdered = nullptr;
+    uint64_t *dFirstLines = nullptr, *dRuns = nullptr, *dSortedLines = nullptr, *dOrder = nullptr;
+    void* dTemp2 = nullptr;
+    size_t orderBytes = 0;
+    DISTINCT_TRY( rocprim::radix_sort_pairs( nullptr, orderBytes, dFirstLines, dSortedLines, dRuns, dOrder, (size_t)nRuns, 0, 64, stream ) );
+    if ( !buffers.get( &dGroups, nRuns * sizeof( FieldSumGroup ), "the groups", error )
+         || !buffers.get( &dOrdered, nRuns * sizeof( FieldSumGroup ), "the ordered groups", error )
+         || !buffers.get( &dFirstLines, nRuns * 8, "the first lines", error ) || !buffers.get( &dRuns, nRuns * 8, "the runs", error )
+         || !buffers.get( &dSortedLines, nRuns * 8, "the sorted first lines", error )
+         || !buffers.get( &dOrder, nRuns * 8, "the order", error ) || !buffers.get( &dTemp2, orderBytes, "the second sort", error ) ) {
+        return false;
+    }
+    const uint32_t runBlocks = (uint32_t)( ( nRuns + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS );
+    hipLaunchKernelGGL( k_sum_runs, dim3( runBlocks ), dim3( DISTINCT_THREADS ), 0, stream, dRunKeys, dParts, (uint64_t)nRuns, dStarts,
+                        dSizes, missing, dGroups, dFirstLines, dRuns, dCount + 1 );
+    DISTINCT_TRY( hipGetLastError() );
+    unsigned long long missingLines = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &missingLines, dCount + 1, sizeof( missingLines ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    *nMissing = missingLines;
+    /* the run of the missing key is the last one: the groups are the runs in front of it */
+    const uint64_t nGroups = nRuns - ( missingLines != 0 ? 1 : 0 );
+    if ( nGroups == 0 ) return true;
+    try {
+        groups->resize( (size_t)nGroups );
+    } catch ( const std::exception& ) {
+        *error = "field_sums: no host memory for " + std::to_string( nGroups ) + " groups";
+        return false;
+    }
+    DISTINCT_TRY( rocprim::radix_sort_pairs( dTemp2, orderBytes, dFirstLines, dSortedLines, dRuns, dOrder, (size_t)nGroups, 0, 64, stream ) );
+    hipLaunchKernelGGL( k_sum_order, dim3( (uint32_t)( ( nGroups + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS ) ), dim3( DISTINCT_THREADS ),
+                        0, stream, dGroups, dOrder, nGroups, dOrdered );
+    DISTINCT_TRY( hipGetLastError() );
+    DISTINCT_TRY( hipMemcpyAsync( groups->data(), dOrdered, nGroups * sizeof( FieldSumGroup ), hipMemcpyDeviceToHost, stream ) );
     DISTINCT_TRY( hipStreamSynchronize( stream ) );
     return true;
 }

@@ -857,6 +857,114 @@ fieldHashes( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* sp
     return MI355X_BZ2_OK;
 }
 
+static_assert( sizeof( FieldNumberSpan ) == 16 && sizeof( FieldText ) == FIELDNUM_TEXT_BYTES && sizeof( mi355x_bz2_field_text ) == 20,
+               "the layout's extents and texts" );
+static_assert( FIELDNUM_NOT_A_NUMBER == FIELD_NOT_A_NUMBER && FIELDNUM_MISSING == FIELD_NUMBER_MISSING
+               && FIELDNUM_BYTES == FIELD_NUMBER_BYTES && FIELDNUM_TEXT_BYTES == FIELD_TEXT_LONG, "the kernels' constants are the host's" );
+static_assert( FIELD_NOT_A_NUMBER == MI355X_BZ2_FIELD_NOT_A_NUMBER && FIELD_NUMBER_MISSING == MI355X_BZ2_FIELD_NUMBER_MISSING,
+               "the C ABI's constants" );
+
+/**
+ * mi355x_bz2_field_numbers and the reader's launches.  fieldSpans' passes as they are, with its lists; behind k_field_sizes
+ * k_field_numbers parses the field of the closed lines [skip, skip + capacity) into dNumbers, device memory of the
+ * caller's (dStarts and dSizes may both be null: they then lie in dSearchPositions), and behind k_field_emit
+ * k_field_texts writes the texts of every span's head and tail, which come back with the summaries in one D2H.  The
+ * first byte of span 0 counts as offset *fileOffset (nullptr: every span's first byte as its offset in the output), which
+ * takes n == 1: k_field_numbers finds a field in the output from its start alone.
+ */
+int
+fieldNumbers( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, const uint64_t* fileOffset, uint32_t n,
+              uint8_t nl, uint8_t dl, uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* headPositions,
+              mi355x_bz2_field_text* headTexts, mi355x_bz2_field_text* tailTexts, uint64_t skip, uint64_t capacity,
+              int64_t* dNumbers, uint64_t* dStarts, int64_t* dSizes )
+{
+    const std::scoped_lock lock( c->mutex );
+    const auto why = fieldArgumentsError( nl, dl, field );
+    if ( !why.empty() ) return refuse( c, what, why );
+    if ( const int status = refuseQuery( c, what, spans, n ) ) return status;
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    if ( fileOffset != nullptr && n != 1 ) return refuse( c, what, "a file offset takes one span" );
+    const auto firstTile = firstTiles( spans, n, COUNT_TILE, 1 );
+    const uint64_t nTiles = firstTile.back(), slots = nTiles * FIELD_THREADS, cap = (uint64_t)field + 1;
+    if ( slots > 0x7FFFFFFFu ) return refuse( c, what, "too many spans" );
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    const FieldNumberLayout l = layFieldNumbers( QUERY_SIZES, nTiles, n, field );
+    if ( const int status = growLineStaging( c, l.tileSummariesAt, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    writeCountTiles( at<CountTile>( h, l.tilesAt ), spans, n, COUNT_TILE, 1 );
+    uint64_t bytesInSpans = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        const uint64_t base = fileOffset != nullptr ? *fileOffset : spans[s].offset;
+        at<FieldSpanTiles>( h, l.spansAt )[s] = { firstTile[s], firstTile[s + 1] - firstTile[s], base };
+        at<FieldNumberSpan>( h, l.extentsAt )[s] = { spans[s].offset, spans[s].size };
+        bytesInSpans += spans[s].size;
+    }
+    /* a start less this is the field's offset in the output */
+    const uint64_t delta = fileOffset != nullptr ? *fileOffset - spans[0].offset : 0;
+    const auto* const dTiles = at<const CountTile>( d, l.tilesAt );
+    const auto* const dSpans = at<const FieldSpanTiles>( d, l.spansAt );
+    auto* const dSummaries = at<FieldSpanSummary>( d, l.resultsAt );
+    auto* const dHeads = at<uint64_t>( d, l.headsAt );
+    auto* const dTileSummaries = at<FieldTile>( d, l.tileSummariesAt );
+    auto* const dPlaces = at<uint64_t>( d, l.placesAt );
+    auto* const dPrefixes = at<uint32_t>( d, l.prefixesAt );
+    auto* const dCounts = at<uint32_t>( d, l.countsAt );
+    /* a span closes at most one line per byte */
+    const uint64_t most = std::min( capacity, bytesInSpans );
+    if ( most > 0 && ( dStarts == nullptr || dSizes == nullptr ) ) {
+        const uint64_t need = most * 2 * sizeof( uint64_t );
+        HIP_TRY( c, c->dSearchPositions.grow( c, need, need + need / 4, need ) );
+        dStarts = at<uint64_t>( c->dSearchPositions.bytes, 0 );
+        dSizes = reinterpret_cast<int64_t*>( dStarts + most );
+    }
+    HIP_TRY( c, hipMemcpyAsync( d, h, l.resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_field_chunks, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, (uint32_t)cap, dPrefixes, dCounts, dTileSummaries );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_field_link, dim3( n ), dim3( FIELD_THREADS ), 0, c->stream, dSpans, dTileSummaries, dSummaries, field );
+    HIP_TRY( c, hipGetLastError() );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+        HIP_TRY( c, hipGetLastError() );
+        hipLaunchKernelGGL( k_field_emit, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, field, dSpans, dPrefixes, dTileSummaries, dPlaces, dSummaries, dHeads, skip,
+                            most, dStarts, dSizes );
+        HIP_TRY( c, hipGetLastError() );
+        if ( most > 0 ) {
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( most + FIELD_SIZES_THREADS - 1 ) / FIELD_SIZES_THREADS, FIELD_SIZES_BLOCKS );
+            hipLaunchKernelGGL( k_field_sizes, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
+                                skip, most, dStarts, dSizes );
+            HIP_TRY( c, hipGetLastError() );
+            hipLaunchKernelGGL( k_field_numbers, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
+                                skip, most, c->dOut, delta, dStarts, dSizes, reinterpret_cast<long long*>( dNumbers ) );
+            HIP_TRY( c, hipGetLastError() );
+        }
+    }
+    hipLaunchKernelGGL( k_field_texts, dim3( n ), dim3( FIELDNUM_TEXT_THREADS ), 0, c->stream, at<const FieldNumberSpan>( d, l.extentsAt ),
+                        dSummaries, dHeads, c->dOut, field, d + l.headTextsAt, d + l.tailTextsAt );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( h + l.resultsAt, d + l.resultsAt, l.tileSummariesAt - l.resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& from = at<const FieldSpanSummary>( h, l.resultsAt )[i];
+        summaries[i] = { from.count, from.firstNl, from.tailStart, from.tailFieldStart, from.tailFieldEnd, from.headDelims,
+                         from.tailDelims, ( from.info & FIELD_HAS_DELIMITER ) != 0 ? 1u : 0u,
+                         ( from.info & FIELD_TAIL_NON_EMPTY ) != 0 ? 1u : 0u };
+        const uint64_t listed = std::min<uint64_t>( from.headDelims, cap );
+        if ( headPositions != nullptr ) std::copy_n( at<const uint64_t>( h, l.headsAt ) + i * cap, listed, headPositions + i * cap );
+        if ( headTexts != nullptr ) {
+            std::memcpy( headTexts + i * cap, h + l.headTextsAt + i * cap * FIELDNUM_TEXT_BYTES,
+                         std::min( listed + 1, cap ) * FIELDNUM_TEXT_BYTES );
+        }
+        if ( tailTexts != nullptr ) std::memcpy( tailTexts + i, h + l.tailTextsAt + (uint64_t)i * FIELDNUM_TEXT_BYTES, FIELDNUM_TEXT_BYTES );
+    }
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -984,6 +1092,30 @@ mi355x::fieldHashesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent
     summary->tail = { s.tail_hash, s.tail_xl };
     summary->tailStartHash = s.tail_start_hash;
     summary->tailEndHash = s.tail_end_hash;
+    return status;
+}
+
+int
+mi355x::fieldNumbersOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                            uint32_t field, uint64_t skip, uint64_t take, int64_t* dNumbers, uint64_t* dStarts, int64_t* dSizes,
+                            bz2gpu::FieldNumberSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr || field > FIELD_MAX || ( take > 0 && dNumbers == nullptr )
+         || ( dStarts == nullptr ) != ( dSizes == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    mi355x_bz2_field_summary s{};
+    std::vector<uint64_t> heads( (size_t)field + 1 );
+    std::vector<mi355x_bz2_field_text> headTexts( (size_t)field + 1 );
+    mi355x_bz2_field_text tailText{};
+    const int status = fieldNumbers( c, "field_numbers", &extent, &fileOffset, 1, nl, dl, field, &s, heads.data(), headTexts.data(),
+                                     &tailText, skip, take, dNumbers, dStarts, dSizes );
+    *summary = bz2gpu::emptyFieldNumberSummary( field );
+    if ( status != MI355X_BZ2_OK ) return status;
+    setFieldSummary( summary->fields, s, extent.size, std::move( heads ) );
+    summary->headTexts.resize( bz2gpu::headTextCount( summary->fields.headDelims(), field ) );
+    std::memcpy( summary->headTexts.data(), headTexts.data(), summary->headTexts.size() * sizeof( FieldText ) );
+    std::memcpy( &summary->tailText, &tailText, sizeof( FieldText ) );
     return status;
 }
 
@@ -1119,6 +1251,20 @@ mi355x_bz2_field_hashes( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, u
     }
     return fieldHashes( c, "field_hashes", spans, nullptr, n, nl, dl, field, lineHashBase( seed ), summaries, headPositions, headHashes,
                         0, capacity, hashesDevice, startsDevice, sizesDevice );
+}
+
+int
+mi355x_bz2_field_numbers( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl, uint32_t field,
+                          mi355x_bz2_field_summary* summaries, uint64_t* headPositions, mi355x_bz2_field_text* headTexts,
+                          mi355x_bz2_field_text* tailTexts, int64_t* numbersDevice, uint64_t* startsDevice, int64_t* sizesDevice,
+                          uint64_t capacity )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) ) || ( capacity > 0 && numbersDevice == nullptr )
+         || ( startsDevice == nullptr ) != ( sizesDevice == nullptr ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return fieldNumbers( c, "field_numbers", spans, nullptr, n, nl, dl, field, summaries, headPositions, headTexts, tailTexts, 0,
+                         capacity, numbersDevice, startsDevice, sizesDevice );
 }
 
 int

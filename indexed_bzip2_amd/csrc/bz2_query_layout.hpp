@@ -157,6 +157,25 @@ layFields( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field )
              r.add( slots * 4 ), r.size() };
 }
 
+/* field_numbers for field `field`: field_spans' lists, and for k_field_texts where every span lies in the output and the
+ * texts of 20 bytes it writes: [tiles][spans][extents, 16 bytes per span] up, [span summaries][head positions, field + 1 per
+ * span][head texts, field + 1 per span][tail texts, one per span] down;
+ * [tile summaries][chunk places][chunk prefixes][chunk counts] */
+struct FieldNumberLayout
+{
+    uint64_t tilesAt, spansAt, extentsAt, resultsAt, headsAt, headTextsAt, tailTextsAt, tileSummariesAt, placesAt, prefixesAt,
+             countsAt, bytes;
+};
+inline FieldNumberLayout
+layFieldNumbers( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field )
+{
+    const uint64_t slots = nTiles * s.chunksPerTile;
+    Regions r;
+    return { r.add( nTiles * s.countTile ), r.add( n * s.fieldSpan, 16 ), r.add( n * 16, 16 ), r.add( n * s.fieldSummary, 16 ),
+             r.add( n * ( field + 1 ) * 8, 16 ), r.add( n * ( field + 1 ) * 20, 16 ), r.add( n * 20, 16 ),
+             r.add( nTiles * s.fieldTile, 16 ), r.add( slots * 8, 16 ), r.add( slots * 4 ), r.add( slots * 4 ), r.size() };
+}
+
 /* field_hashes for field `field`: field_spans' and hash_lines' lists side by side, since both first passes run as they
  * are: [tiles][field spans][hash spans] up, [field summaries][hash summaries][tail hashes, 16 bytes per span]
  * [head positions][head hashes, field + 1 per span each] down; [field tile summaries][hash tile summaries][chunk places]

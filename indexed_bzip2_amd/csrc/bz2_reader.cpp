@@ -1315,6 +1315,131 @@ struct FieldHashQuery
     static const bz2gpu::FieldKey& tail( const bz2gpu::StitchedFieldHashes& stitched ) { return stitched.tail; }
 };
 
+struct FieldNumberQuery
+{
+    static constexpr size_t COLUMNS = 3;        /* numbers (int64), starts, sizes (int64) */
+    using Stretch = bz2gpu::FieldNumberStretch;
+    uint8_t nl, dl;
+    uint32_t field;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.fields.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldNumbersOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, place.skip, place.take,
+                                              reinterpret_cast<int64_t*>( to[0] ), to[1], reinterpret_cast<int64_t*>( to[2] ),
+                                              &stretch.summary ) );
+        return stretch.summary.fields.count;
+    }
+
+    /** stitchFieldNumbers with a line's number and field as one value, as lineColumns patches them. */
+    struct Stitched
+    {
+        uint64_t closed{ 0 };
+        bool hasTail{ false };
+        bz2gpu::FieldNumber tail;
+    };
+
+    template<typename Patch>
+    Stitched
+    stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const
+    {
+        const auto stitched = bz2gpu::stitchFieldNumbers( stretches, field, [&patch] ( uint64_t k, int64_t number, const bz2gpu::FieldSpan& span ) {
+            patch( k, bz2gpu::FieldNumber{ number, span } );
+        } );
+        return { stitched.closed, stitched.hasTail, { stitched.tailNumber, stitched.tail } };
+    }
+
+    static std::array<uint64_t, COLUMNS>
+    words( const bz2gpu::FieldNumber& number )
+    {
+        return { (uint64_t)number.number, number.field.start, (uint64_t)number.field.size };
+    }
+
+    static const bz2gpu::FieldNumber& tail( const Stitched& stitched ) { return stitched.tail; }
+};
+
+/* field_sums: the key of one field and the number of another per line, from ONE decode: both passes run over the stretch
+ * while it is resident, and both stitchers over the summaries; their patches name the same lines. */
+struct FieldSumQuery
+{
+    static constexpr size_t COLUMNS = 4;        /* keys, the key field's starts and sizes (int64), values (int64) */
+    struct Stretch
+    {
+        uint64_t fileOffset{ 0 }, size{ 0 };
+        bz2gpu::FieldHashSummary keys;
+        bz2gpu::FieldNumberSummary values;
+    };
+    struct Value
+    {
+        bz2gpu::FieldKey key;
+        int64_t number{ bz2gpu::FIELD_NUMBER_MISSING };
+    };
+    struct Stitched
+    {
+        uint64_t closed{ 0 };
+        bool hasTail{ false };
+        Value tail;
+    };
+    uint8_t nl, dl;
+    uint32_t keyField, valueField;
+    uint64_t x;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldHashesOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, keyField, x, place.skip, place.take,
+                                             to[0], to[1], reinterpret_cast<int64_t*>( to[2] ), &stretch.keys ) );
+        checkDevice( ctx, fieldNumbersOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, valueField, place.skip, place.take,
+                                              reinterpret_cast<int64_t*>( to[3] ), nullptr, nullptr, &stretch.values ) );
+        if ( stretch.keys.fields.count != stretch.values.fields.count ) {
+            fail( MI355X_BZ2_ERR_LOGIC, "field_sums: the two passes over one stretch count different lines" );
+        }
+        return stretch.keys.fields.count;
+    }
+
+    template<typename Patch>
+    Stitched
+    stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const
+    {
+        std::vector<bz2gpu::FieldHashStretch> keys( stretches.size() );
+        std::vector<bz2gpu::FieldNumberStretch> values( stretches.size() );
+        for ( size_t i = 0; i < stretches.size(); ++i ) {
+            keys[i] = { stretches[i].fileOffset, stretches[i].keys };
+            values[i] = { stretches[i].fileOffset, stretches[i].values };
+            keys[i].summary.fields.size = values[i].summary.fields.size = stretches[i].size;
+        }
+        std::vector<std::pair<uint64_t, bz2gpu::FieldKey> > keyPatches;
+        const auto stitchedKeys = bz2gpu::stitchFieldHashes( keys, x, dl, keyField, [&] ( uint64_t k, const bz2gpu::FieldKey& key ) {
+            keyPatches.emplace_back( k, key );
+        } );
+        size_t next = 0;
+        const auto stitchedValues = bz2gpu::stitchFieldNumbers( values, valueField, [&] ( uint64_t k, int64_t number, const bz2gpu::FieldSpan& ) {
+            if ( next >= keyPatches.size() || keyPatches[next].first != k ) {
+                fail( MI355X_BZ2_ERR_LOGIC, "field_sums: the two stitchers patch different lines" );
+            }
+            patch( k, Value{ keyPatches[next++].second, number } );
+        } );
+        if ( next != keyPatches.size() || stitchedKeys.closed != stitchedValues.closed || stitchedKeys.hasTail != stitchedValues.hasTail ) {
+            fail( MI355X_BZ2_ERR_LOGIC, "field_sums: the two stitchers disagree about the lines" );
+        }
+        return { stitchedKeys.closed, stitchedKeys.hasTail, { stitchedKeys.tail, stitchedValues.tailNumber } };
+    }
+
+    static std::array<uint64_t, COLUMNS>
+    words( const Value& value )
+    {
+        return { value.key.key, value.key.field.start, (uint64_t)value.key.field.size, (uint64_t)value.number };
+    }
+
+    static const Value& tail( const Stitched& stitched ) { return stitched.tail; }
+};
+
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
 {
@@ -1343,6 +1468,7 @@ public:
         dropHeldHashes();
         m_fields.reset();
         dropHeldFieldHashes();
+        dropHeldFieldNumbers();
         m_matches.reset();
         m_setMatches.reset();
         m_scheduler.reset();
@@ -2037,6 +2163,76 @@ public:
         }
     }
 
+    /** mi355x_bz2_reader_field_numbers: lineColumns with fieldNumbersOutput and stitchFieldNumbers, a column of numbers in
+     * front of the two of the spans. */
+    void
+    fieldNumbers( uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "field_numbers: " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        dropHeldFieldNumbers();
+        m_fieldNumbers = lineColumns( FieldNumberQuery{ nl, dl, field }, "field_numbers", index, first, count, keepOnDevice, nLines );
+    }
+
+    /** mi355x_bz2_reader_take_field_numbers: the numbers. */
+    void
+    takeFieldNumbers( void* numbers, uint64_t capacity, bool dstIsDevice )
+    {
+        takeColumns( "take_field_numbers", "no field numbers are held (field_numbers first)", m_fieldNumbers, { numbers }, capacity,
+                     dstIsDevice );
+    }
+
+    /** mi355x_bz2_reader_field_sums: lineColumns with both passes per stretch (FieldSumQuery), then bz2_distinct.hip's
+     * groupSums over the four columns. */
+    void
+    fieldSums( uint8_t nl, uint8_t dl, uint32_t keyField, uint32_t valueField, uint64_t seed, uint64_t first, uint64_t count,
+               uint64_t* nGroups, uint64_t* nMissing )
+    {
+        for ( const auto field : { keyField, valueField } ) {
+            const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+            if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "field_sums: " + refused );
+        }
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        dropHeldFieldNumbers();
+        uint64_t n = 0;
+        const auto held = lineColumns( FieldSumQuery{ nl, dl, keyField, valueField, bz2gpu::lineHashBase( seed ) }, "field_sums", index,
+                                       first, count, false, &n );
+        std::vector<FieldSumGroup> groups;
+        std::string why;
+        if ( !groupSums( m_device, held.column<const uint64_t>( 0 ), held.column<const uint64_t>( 1 ), held.column<const int64_t>( 2 ),
+                         held.column<const int64_t>( 3 ), n, bz2gpu::FIELD_MISSING, &groups, nMissing, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, why );
+        }
+        for ( auto& group : groups ) group.line += first;
+        *nGroups = groups.size();
+        m_fieldSums = std::move( groups );
+    }
+
+    /** mi355x_bz2_reader_take_field_sums. */
+    void
+    takeFieldSums( uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes, uint64_t* numbers, uint64_t* sumsLo,
+                   int64_t* sumsHi, int64_t* mins, int64_t* maxs, uint64_t capacity )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_sums on a closed reader" );
+        if ( !m_fieldSums ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_sums: no sums are held (field_sums first)" );
+        const size_t n = (size_t)std::min<uint64_t>( capacity, m_fieldSums->size() );
+        for ( size_t i = 0; i < n; ++i ) {
+            const auto& group = ( *m_fieldSums )[i];
+            if ( lines != nullptr ) lines[i] = group.line;
+            if ( counts != nullptr ) counts[i] = group.count;
+            if ( starts != nullptr ) starts[i] = group.start;
+            if ( sizes != nullptr ) sizes[i] = group.size;
+            if ( numbers != nullptr ) numbers[i] = group.numbers;
+            if ( sumsLo != nullptr ) sumsLo[i] = group.sumLo;
+            if ( sumsHi != nullptr ) sumsHi[i] = group.sumHi;
+            if ( mins != nullptr ) mins[i] = group.min;
+            if ( maxs != nullptr ) maxs[i] = group.max;
+        }
+    }
+
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
 
     [[nodiscard]] OffsetMap
@@ -2115,12 +2311,13 @@ private:
         std::vector<uint64_t> numbers, sizes;              /* per matching line; the bytes are m_held's */
     };
 
-    /** The result of a per-line column query, in device memory of the reader's own: up to three columns of n 8-byte words
-     * -- hashes; starts and sizes; keys, starts and sizes.  An empty result has no memory. */
+    /** The result of a per-line column query, in device memory of the reader's own: up to four columns of n 8-byte words
+     * -- hashes; starts and sizes; keys, starts and sizes; numbers, starts and sizes; keys, starts, sizes and values.  An
+     * empty result has no memory. */
     struct HeldColumns
     {
         struct Release { void operator()( void* pointer ) const { deviceRelease( pointer ); } };
-        std::array<std::unique_ptr<void, Release>, 3> columns;
+        std::array<std::unique_ptr<void, Release>, 4> columns;
         uint64_t n{ 0 };
         int device{ -1 };
         bool onDevice{ false };
@@ -2134,6 +2331,13 @@ private:
     {
         m_fieldHashes.reset();
         m_fieldGroups.reset();
+    }
+
+    void
+    dropHeldFieldNumbers()
+    {
+        m_fieldNumbers.reset();
+        m_fieldSums.reset();
     }
 
     void
@@ -2279,7 +2483,8 @@ private:
         } );
     }
 
-    /** What line_hashes, field_spans and field_hashes do, given the `query` (the three structs in front of the reader):
+    /** What line_hashes, field_spans, field_hashes, field_numbers and field_sums do, given the `query` (the structs in front
+     * of the reader):
      * the launches of planLineHashes for lines [first, first + count), each doing its stretches on the context that
      * decoded them, straight into device columns that are allocated before anything is launched and in which every
      * stretch knows its place (placeLineColumn); then the query's stitcher over the stretches' summaries, and one 8-byte
@@ -2527,6 +2732,8 @@ private:
     std::optional<HeldColumns> m_fields;  /* between field_spans and the next field_spans */
     std::optional<HeldColumns> m_fieldHashes;                 /* between field_hashes and the next call of its family */
     std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
+    std::optional<HeldColumns> m_fieldNumbers;                /* between field_numbers and the next call of its family */
+    std::optional<std::vector<FieldSumGroup> > m_fieldSums;   /* between field_sums and the next call of its family */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
@@ -2986,6 +3193,46 @@ mi355x_bz2_reader_take_field_groups( mi355x_bz2_reader* r, uint64_t* lines, uint
                                      uint64_t capacity )
 {
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldGroups( lines, counts, starts, sizes, capacity ); } );
+}
+
+int
+mi355x_bz2_reader_field_numbers( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
+                                 int keepOnDevice, uint64_t* nLines )
+{
+    if ( nLines == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldNumbers( nl, dl, field, first, count, keepOnDevice != 0, nLines );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_field_numbers( mi355x_bz2_reader* r, void* numbers, uint64_t capacity, int dstIsDevice )
+{
+    if ( capacity > 0 && numbers == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldNumbers( numbers, capacity, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_field_sums( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t keyField, uint32_t valueField, uint64_t seed,
+                              uint64_t first, uint64_t count, uint64_t* nGroups, uint64_t* nMissing )
+{
+    if ( nGroups == nullptr || nMissing == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nGroups = 0;
+    *nMissing = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldSums( nl, dl, keyField, valueField, seed, first, count, nGroups, nMissing );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_field_sums( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes,
+                                   uint64_t* numbers, uint64_t* sumsLo, int64_t* sumsHi, int64_t* mins, int64_t* maxs,
+                                   uint64_t capacity )
+{
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.takeFieldSums( lines, counts, starts, sizes, numbers, sumsLo, sumsHi, mins, maxs, capacity );
+    } );
 }
 
 int

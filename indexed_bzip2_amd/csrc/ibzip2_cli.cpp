@@ -46,7 +46,8 @@ struct Options
     bool lineHashes{ false }, countDistinctLines{ false }, hasSeed{ false };
     uint64_t seed{ 0 };
     bool cutField{ false }, hasFieldDelimiter{ false }, countByField{ false };
-    unsigned field{ 0 };
+    bool sumByField{ false };
+    unsigned field{ 0 }, valueField{ 0 };
     uint8_t fieldDelimiter{ '\t' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
     bool hasOutput{ false };
@@ -131,6 +132,14 @@ printHelp()
         "                                distinct hashes with overwhelming probability, not with certainty. Only the\n"
         "                                values' bytes are copied to the host. --field-delimiter applies; this is not a\n"
         "                                CSV parser.\n"
+        "      --sum-by-field arg        Given KEY,VALUE (two field numbers as for --cut-field): print one line\n"
+        "                                'sum<TAB>numbers<TAB>key' per distinct value of field KEY, in the order of their\n"
+        "                                first occurrence: the exact sum of field VALUE over the lines with that key, and\n"
+        "                                how many of them hold a number there (awk '{s[$1]+=$3}'). A number is\n"
+        "                                [+-]?[0-9]{1,18} from end to end, not awk's strtod: anything else adds nothing.\n"
+        "                                Lines without field KEY are in no group. The data is decoded once; keys\n"
+        "                                (grouped by a hash, --seed chooses its base) and numbers are found and summed\n"
+        "                                on the GPU. --field-delimiter applies; this is not a CSV parser.\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -165,6 +174,8 @@ printHelp()
         "  ibzip2-mi355x --cut-field 2 file.tsv.bz2\n\n"
         "Print how often each value of the third column occurs, the most frequent first:\n"
         "  ibzip2-mi355x --count-by-field 2 file.tsv.bz2\n\n"
+        "Sum the third column per value of the first:\n"
+        "  ibzip2-mi355x --sum-by-field 0,2 file.tsv.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -333,6 +344,19 @@ parseArguments( int argc, char** argv, Options& o )
                 }
                 o.field = (unsigned)field;
                 o.countByField = true;
+            }
+            else if ( name == "sum-by-field" ) {
+                uint64_t key = 0, number = 0;     /* KEY,VALUE: digits only, as --cut-field */
+                const bool given = need( value );
+                const auto comma = value.find( ',' );
+                if ( !given || comma == std::string::npos || !parseSeed( value.substr( 0, comma ).c_str(), key ) || key > 1023
+                     || !parseSeed( value.substr( comma + 1 ).c_str(), number ) || number > 1023 ) {
+                    std::cerr << "Bad value for --sum-by-field\n";
+                    return 1;
+                }
+                o.field = (unsigned)key;
+                o.valueField = (unsigned)number;
+                o.sumByField = true;
             }
             else if ( name == "field-delimiter" ) {
                 if ( !need( value ) || !parseByte( value, o.fieldDelimiter ) || o.fieldDelimiter == '\n' ) {
@@ -563,13 +587,20 @@ main( int argc, char** argv )
                      "'--grep-regex', '--count-matches', '--grep-file' or '--count-matches-file'\n";
         return 1;
     }
+    if ( o.sumByField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
+                           || o.countDistinctLines || o.cutField || o.countByField ) ) {
+        std::cerr << "Option '--sum-by-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
+                     "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines', '--cut-field' or "
+                     "'--count-by-field'\n";
+        return 1;
+    }
     if ( o.countByField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
                              || o.countDistinctLines || o.cutField ) ) {
         std::cerr << "Option '--count-by-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
                      "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines' or '--cut-field'\n";
         return 1;
     }
-    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines && !o.countByField ) {
+    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines && !o.countByField && !o.sumByField ) {
         std::cerr << "Option '--seed' needs '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
@@ -579,7 +610,7 @@ main( int argc, char** argv )
                      "'--grep-file', '--count-matches-file', '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
-    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField ) {
+    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField && !o.sumByField ) {
         std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
         return 1;
     }
@@ -784,6 +815,81 @@ main( int argc, char** argv )
             uint64_t at = 0;
             for ( uint64_t i = 0; i < m; ++i ) {
                 text += std::to_string( counts[order[first + i]] );
+                text.push_back( '\t' );
+                text.append( bytes, at, lengths[i] );
+                text.push_back( '\n' );
+                at += lengths[i];
+            }
+            std::cout << text;
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        return 0;
+    }
+
+    /* likewise an action of its own: the sum of one field per distinct value of another, from the reader's field_sums; the
+     * keys of the groups come by read_ranges, in windows of groups */
+    if ( o.sumByField ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t n = 0, missing = 0;
+        rc = mi355x_bz2_reader_field_sums( reader, '\n', o.fieldDelimiter, o.field, o.valueField, o.seed, 0, ~uint64_t( 0 ), &n, &missing );
+        std::vector<uint64_t> starts( n ), numbers( n ), low( n );
+        std::vector<int64_t> sizes( n ), high( n );
+        if ( rc == MI355X_BZ2_OK ) {
+            rc = mi355x_bz2_reader_take_field_sums( reader, nullptr, nullptr, starts.data(), sizes.data(), numbers.data(), low.data(),
+                                                    high.data(), nullptr, nullptr, n );
+        }
+        /* hi * 2^64 + lo in decimal */
+        const auto decimal = [] ( int64_t hi, uint64_t lo ) {
+            const __int128 value = (__int128)( ( (unsigned __int128)(uint64_t)hi << 64 ) | lo );
+            unsigned __int128 magnitude = value < 0 ? -(unsigned __int128)value : (unsigned __int128)value;
+            std::string digits;
+            do {
+                digits.push_back( (char)( '0' + (int)( magnitude % 10 ) ) );
+                magnitude /= 10;
+            } while ( magnitude != 0 );
+            if ( value < 0 ) digits.push_back( '-' );
+            return std::string( digits.rbegin(), digits.rend() );
+        };
+        constexpr uint64_t WINDOW = uint64_t( 1 ) << 20;
+        std::vector<uint64_t> lengths, got;
+        std::string bytes, text;
+        for ( uint64_t first = 0; rc == MI355X_BZ2_OK && first < n; first += WINDOW ) {
+            const uint64_t m = std::min( WINDOW, n - first );
+            lengths.resize( m );
+            got.resize( m );
+            uint64_t total = 0;
+            for ( uint64_t i = 0; i < m; ++i ) total += lengths[i] = (uint64_t)sizes[first + i];
+            bytes.resize( total );
+            rc = mi355x_bz2_reader_read_ranges( reader, starts.data() + first, lengths.data(), (uint32_t)m, bytes.data(), 0, got.data() );
+            if ( rc != MI355X_BZ2_OK ) break;
+            text.clear();
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < m; ++i ) {
+                text += decimal( high[first + i], low[first + i] );
+                text.push_back( '\t' );
+                text += std::to_string( numbers[first + i] );
                 text.push_back( '\t' );
                 text.append( bytes, at, lengths[i] );
                 text.push_back( '\n' );

@@ -810,6 +810,75 @@ class _IndexedBzip2FileParallel:
         values = self.read_ranges([(int(starts[i]), int(sizes[i])) for i in chosen])
         return [(value, int(counts[i])) for value, i in zip(values, chosen)]
 
+    # -- field numbers and sums: the NUMBER of a line is N.parse_field_number(content.split(delimiter)[field]): the bytes
+    # must match [+-]?[0-9]{1,18} from end to end -- no whitespace, no '_', no hex, no floats, at most 18 digits, which
+    # always fit int64: this is not awk's strtod and not Python's int().  A present field that is no number gives
+    # N.FIELD_NOT_A_NUMBER = -2^63, a line with fewer fields N.FIELD_NUMBER_MISSING = -2^63 + 1; no number takes either.
+    # No quoting, no escaping: `cut -f`, not a CSV parser
+    def _field_ints(self, field, first, count, delimiter, newline, tensors):
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        L = N.lib()
+        return self._columns(lambda keep, n: L.mi355x_bz2_reader_field_numbers(self._h, nl, dl, field, first, count, keep, n),
+                             lambda *to: L.mi355x_bz2_reader_take_field_numbers(self._h, *to), ("int64",), tensors)[0]
+
+    def field_ints(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """Field `field` of lines [first, first + count) (count None: to the last line; clipped there) as numbers ->
+        numpy int64, one per line: parse_field_number(content.split(delimiter)[field]) where that is a number
+        ([+-]?[0-9]{1,18}: not awk's strtod), FIELD_NOT_A_NUMBER where the field is something else, FIELD_NUMBER_MISSING
+        where the line has no such field.  Only the blocks that hold those lines are decoded, each once; the fields are
+        found and parsed on the GPU and 8 bytes per line come back.  Builds the line index first if the reader does not
+        hold one for `newline`.  Not a CSV parser.  Positionless."""
+        return self._field_ints(field, first, count, delimiter, newline, False)
+
+    def field_ints_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """field_ints as a torch.int64 tensor on the reader's device; the numbers never pass through the host.  Mask
+        the two sentinels (both below -2^63 + 2) before arithmetic."""
+        return self._field_ints(field, first, count, delimiter, newline, True)
+
+    def _field_sums(self, key_field, value_field, first, count, delimiter, newline, seed):
+        """mi355x_bz2_reader_field_sums and its take -> (lines, counts, starts, sizes, numbers, sums, mins, maxs, missing)."""
+        import numpy as np
+        nl, dl, key_field, first, count, seed = self._field_hash_arguments(key_field, first, count, delimiter, newline, seed)
+        value_field = self._field_arguments(value_field, first, count, delimiter, newline)[2]
+        n, missing = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_field_sums(self._h, nl, dl, key_field, value_field, seed, first, count,
+                                                          ctypes.byref(n), ctypes.byref(missing)))
+        lines, counts, starts, numbers, lo = (np.empty(n.value, dtype=np.uint64) for _ in range(5))
+        sizes, hi, mins, maxs = (np.empty(n.value, dtype=np.int64) for _ in range(4))
+        if n.value:
+            self._check(N.lib().mi355x_bz2_reader_take_field_sums(
+                self._h, *[a.ctypes.data for a in (lines, counts, starts, sizes, numbers, lo, hi, mins, maxs)], n.value))
+        sums = [(int(h) << 64) + int(l) for h, l in zip(hi, lo)]
+        return lines, counts, starts, sizes, numbers, sums, mins, maxs, missing.value
+
+    def sum_by_field(self, key_field, value_field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """Lines [first, first + count) grouped by field `key_field`, with field `value_field` summed per group
+        (`awk -F'\\t' '{s[$1]+=$3}'`, but exact and with parse_field_number's numbers: not awk's strtod) -> (lines,
+        counts, numbers, sums, mins, maxs, missing).  `lines` (numpy uint64, ascending) holds the file's line number of
+        the first line of every distinct key, `counts` (numpy uint64) how many lines of the range have that key,
+        `numbers` (numpy uint64) how many of those have a number in the value field, `sums` (a list of Python ints) their
+        exact sum, `mins` and `maxs` (numpy int64) the least and the largest of them, FIELD_NOT_A_NUMBER where `numbers`
+        is 0, and `missing` the number of lines without the key field.  Every needed block is decoded once: keys and
+        numbers are found on the GPU over the same resident bytes, sorted and reduced there; 72 bytes per distinct key come
+        back and nothing per line.  key_field == value_field is allowed.  Not a CSV parser.  Positionless."""
+        lines, counts, _, _, numbers, sums, mins, maxs, missing = self._field_sums(key_field, value_field, first, count, delimiter,
+                                                                                   newline, seed)
+        return lines, counts, numbers, sums, mins, maxs, missing
+
+    def value_sums(self, key_field, value_field, limit=None, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """sum_by_field with the keys themselves -> a list of (key bytes, sum, numbers) by descending sum, then by first
+        occurrence, at most `limit` entries (None: all).  The keys are fetched by read_ranges over the chosen groups'
+        spans, so only those bytes leave the GPU.  Lines without the key field are in no entry.  Numbers are
+        parse_field_number's (not awk's strtod).  Not a CSV parser.  Positionless."""
+        limit = self._line_limit(limit)
+        _, _, starts, sizes, numbers, sums, _, _, _ = self._field_sums(key_field, value_field, first, count, delimiter, newline, seed)
+        # the groups ascend by first line: a stable sort by descending sum keeps that order among equal sums
+        chosen = sorted(range(len(sums)), key=lambda i: -sums[i])[:limit]
+        if len(chosen) == 0:
+            return []
+        values = self.read_ranges([(int(starts[i]), int(sizes[i])) for i in chosen])
+        return [(value, sums[i], int(numbers[i])) for value, i in zip(values, chosen)]
+
     # -- a set of patterns: a match is a pair (p, i) with data[p:p + len(patterns[i])] == patterns[i], start <= p and
     # p + len(patterns[i]) <= end; a result is ordered by p, then i.  Every block of the range is decoded once per call.
     # With ignore_case=True both sides are compared under bytes.lower(); patterns that are then equal, or prefixes of one
@@ -1062,6 +1131,22 @@ class IndexedBzip2File(io.BufferedReader):
     def value_counts(self, field, limit=None, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """See _IndexedBzip2FileParallel.value_counts."""
         return self._open_reader().value_counts(field, limit, first, count, delimiter, newline, seed)
+
+    def field_ints(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.field_ints."""
+        return self._open_reader().field_ints(field, first, count, delimiter, newline)
+
+    def field_ints_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.field_ints_to_tensor."""
+        return self._open_reader().field_ints_to_tensor(field, first, count, delimiter, newline)
+
+    def sum_by_field(self, key_field, value_field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.sum_by_field."""
+        return self._open_reader().sum_by_field(key_field, value_field, first, count, delimiter, newline, seed)
+
+    def value_sums(self, key_field, value_field, limit=None, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.value_sums."""
+        return self._open_reader().value_sums(key_field, value_field, limit, first, count, delimiter, newline, seed)
 
     def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """See _IndexedBzip2FileParallel.read_fields."""
