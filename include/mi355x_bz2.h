@@ -450,6 +450,27 @@ int mi355x_bz2_field_spans( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spa
                             uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* head_positions,
                             uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
 
+/* A column of fields as bytes: the fields that _field_spans found, packed back to back in the order of their lines.
+ *   _gather_fields_tile_bytes  the bytes of the destination one GPU workgroup writes: of interest to tests and tuning.
+ *   _gather_fields    starts_device[n] (uint64) and sizes_device[n] (int64; both DEVICE memory) are n spans as
+ *                     _field_spans writes them; `base` is what takes a start back to an offset in the last batch's
+ *                     output: span i is its bytes [starts[i] - base, starts[i] - base + sizes[i]).  A span with a
+ *                     size <= 0 (a missing or an empty field) has no bytes and its start does not matter.  The spans
+ *                     may come in any order and may overlap.  offsets_device[n + 1] (uint64, DEVICE memory) receives
+ *                     the exclusive prefix sums of max( size, 0 ), offsets[n] and *total their sum; the bytes of span
+ *                     i go to dst_device[offsets[i], offsets[i + 1]) iff total <= dst_capacity and dst_device is not
+ *                     NULL -- with NULL, or too little room, the call gives the total and the offsets, and writes
+ *                     nothing to dst_device.  The GPU checks every span with bytes against the output's size before
+ *                     any is read: with one that does not lie inside it the call is MI355X_BZ2_ERR_INVALID_ARGUMENT,
+ *                     its message names the first such span, *total is 0, nothing is written to dst_device and what
+ *                     offsets_device holds is not defined.  No batch may be in flight.  The call never reads outside
+ *                     the batch's output and the slack behind it, and returns when everything is written.
+ *                     k_fieldcol_sums, k_fieldcol_top, k_fieldcol_offsets, k_field_gather. */
+uint32_t mi355x_bz2_gather_fields_tile_bytes( void );
+int mi355x_bz2_gather_fields( mi355x_bz2_ctx* ctx, const uint64_t* starts_device, const int64_t* sizes_device, uint64_t n,
+                              uint64_t base, uint64_t* offsets_device, void* dst_device, uint64_t dst_capacity,
+                              uint64_t* total );
+
 /* The hash of field `field` of every line: the KEY of a line is mi355x_bz2_line_hash's hash (same seed, same base) of
  * content.split( dl )[field], the field mi355x_bz2_field_spans finds; a line with fewer fields has the key
  * MI355X_BZ2_FIELD_MISSING = 2^61 - 1, the hash's modulus, which no hash takes; an empty field is present and hashes
@@ -854,6 +875,32 @@ int mi355x_bz2_reader_take_distinct_lines( mi355x_bz2_reader* r, uint64_t* line_
 int mi355x_bz2_reader_field_spans( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
                                    int keep_on_device, uint64_t* n_lines );
 int mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* sizes, uint64_t capacity, int dst_is_device );
+
+/* ---- field columns: the bytes of several fields of every line, each packed in line order, from one decode.
+ *   _field_columns    for lines [first, first + count), count clipped at the last line, and each of the n_fields (1 to 16)
+ *                     entries of `fields` (each at most 1023; one may be named twice, every entry gets a column of its
+ *                     own): the bytes of that field of every line back to back, the n_lines + 1 offsets of the lines'
+ *                     fields in them and the n_lines sizes, -1 where a line has no such field, which then owns no bytes.
+ *                     *n_lines = the lines, total_bytes[i] = the bytes of column i.  n_fields 0 or above 16, a field
+ *                     above 1023 and dl == nl are MI355X_BZ2_ERR_INVALID_ARGUMENT, before anything is launched.  The
+ *                     launches are _field_spans' for the same range; every launch runs _field_spans' kernels once per
+ *                     field over its resident blocks and mi355x_bz2_gather_fields' into a buffer of its own per field,
+ *                     allocated when its size is known: every needed block is decoded ONCE per call, whatever the number
+ *                     of fields.  The host stitches the summaries per field; the one line per launch that crosses a seam,
+ *                     and the tail, are fetched as byte ranges (_read_ranges' path): the few blocks that hold them are
+ *                     the only ones decoded a second time.  The final offsets are scanned on the device; nothing per
+ *                     line passes through the host.  Peak device memory: the columns' bytes once and 24 bytes per line
+ *                     and field.  A failed allocation is MI355X_BZ2_ERR_DEVICE with a message, and nothing stays held.
+ *                     The columns are held, as the launches' pieces, until the next _field_columns or the close.
+ *                     Positionless; releases line ranges held by earlier calls, and nothing else.
+ *   _take_field_column  held column `column` (an index into `fields`): its bytes assembled straight into `data`
+ *                     (total_bytes[column] bytes), its offsets (uint64, n_lines + 1) and sizes (int64, n_lines), each to
+ *                     host memory or, with dst_is_device, device memory, each skipped if NULL; the column stays held. */
+int mi355x_bz2_reader_field_columns( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t n_fields,
+                                     uint64_t first, uint64_t count, int keep_on_device, uint64_t* n_lines,
+                                     uint64_t* total_bytes );
+int mi355x_bz2_reader_take_field_column( mi355x_bz2_reader* r, uint32_t column, void* data, void* offsets, void* sizes,
+                                         int dst_is_device );
 
 /* ---- field hashes and groups (mi355x_bz2_field_hashes says what the key of a line is).
  *   _field_hashes     the keys of lines [first, first + count), count clipped at the last line; *n_lines = their number.

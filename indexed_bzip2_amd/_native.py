@@ -196,9 +196,14 @@ SYMBOLS = [
     ("mi355x_bz2_field_chunk_bytes", ctypes.c_uint32, []),
     ("mi355x_bz2_field_spans", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
                                                ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_gather_fields_tile_bytes", ctypes.c_uint32, []),
+    ("mi355x_bz2_gather_fields", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_field_spans", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
                                                       ctypes.c_uint64, ctypes.c_int, _u64p]),
     ("mi355x_bz2_reader_take_field_spans", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_reader_field_columns", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, _u32p, ctypes.c_uint32, ctypes.c_uint64,
+                                                        ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_field_column", ctypes.c_int, [_vp, ctypes.c_uint32, _vp, _vp, _vp, ctypes.c_int]),
     ("mi355x_bz2_field_hashes", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
                                                 ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
     ("mi355x_bz2_reader_field_hashes", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
@@ -449,6 +454,11 @@ class FieldSummary(ctypes.Structure):
 def field_chunk_bytes():
     """The bytes of a span that one GPU lane walks in field_spans (mi355x_bz2_field_chunk_bytes)."""
     return int(lib().mi355x_bz2_field_chunk_bytes())
+
+
+def gather_fields_tile_bytes():
+    """The bytes of the destination that one GPU workgroup writes in gather_fields (mi355x_bz2_gather_fields_tile_bytes)."""
+    return int(lib().mi355x_bz2_gather_fields_tile_bytes())
 
 
 FIELD_MISSING = 2**61 - 1      # MI355X_BZ2_FIELD_MISSING: the key of a line that has no such field
@@ -921,6 +931,47 @@ class Decoder:
         _with_device_copies("field_spans", [starts, sizes], lambda *device: call(*device, capacity))
         out = [_field_summary_dict(s, heads[i * (field + 1):]) for i, s in enumerate(summaries[:len(spans)])]
         return out, starts[:room], sizes[:room]
+
+    def gather_fields(self, starts, sizes, base=0, room=None, capacity=None, dst=True, fill=0xA5, misalign=0):
+        """k_fieldcol_sums, k_fieldcol_top, k_fieldcol_offsets, k_field_gather: the spans (starts[i] - base, sizes[i]) of
+        the last batch's output -- field_spans' two arrays -- packed back to back -> (total, offsets, data): the sum of
+        max(size, 0), a numpy uint64 array of their n + 1 exclusive prefix sums, and a numpy uint8 array of `room` bytes
+        (default: the total the sizes give) that all were `fill` before the call and of which the call writes the first
+        `total` if total <= capacity (default: room).  dst=False: no destination (data is None).  The destination begins
+        `misalign` bytes (0 to 15) behind a 16-byte boundary.  A refused call raises Bz2Error, which carries the
+        destination as the call left it in `.destination`."""
+        import numpy as np
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        if starts.ndim != 1 or starts.shape != sizes.shape:
+            raise ValueError("starts and sizes must be one-dimensional and equally long")
+        if not 0 <= int(misalign) <= 15:
+            raise ValueError("misalign must be between 0 and 15")
+        n = int(starts.size)
+        if room is None:
+            room = int(np.maximum(sizes, 0).sum())
+        capacity = int(room) if capacity is None else int(capacity)
+        if capacity > room:
+            raise ValueError("the capacity must not exceed the room")
+        offsets = np.full(n + 1, 2**64 - 1, dtype=np.uint64)
+        hosts = [np.resize(starts, max(1, n)), np.resize(sizes, max(1, n)), offsets]
+        # the device arrays lie back to back from an aligned allocation: pad so that the destination begins as asked
+        before = sum(host.nbytes for host in hosts)
+        hosts.append(np.zeros((-before) % 16 + int(misalign), dtype=np.uint8))
+        data = np.full(max(1, int(room)), fill, dtype=np.uint8)
+        hosts.append(data)
+        total = ctypes.c_uint64(2**64 - 1)
+        status = []
+
+        def call(d_starts, d_sizes, d_offsets, _, d_data):
+            status.append(lib().mi355x_bz2_gather_fields(self._h, d_starts, d_sizes, n, int(base), d_offsets,
+                                                         d_data if dst else None, capacity, ctypes.byref(total)))
+        _with_device_copies("gather_fields", hosts, call)
+        if status[0] != OK:
+            error = Bz2Error(status[0], lib().mi355x_bz2_last_error(self._h).decode())
+            error.destination = data[:int(room)]
+            raise error
+        return total.value, offsets, (data[:int(room)] if dst else None)
 
     def field_hashes(self, spans, field, delimiter=b"\t", newline=b"\n", seed=0, capacity=None, room=None):
         """k_field_chunks, k_field_link, k_linehash_chunks, k_linehash_link, k_scan_tiles, k_fieldhash_emit,

@@ -7,6 +7,7 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -75,6 +76,14 @@ int hashLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, ui
 int fieldSpansOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
                       uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes, bz2gpu::FieldSummary* summary );
 
+/** The reader's gather in one launch: mi355x_bz2_gather_fields over the n spans that fieldSpansOutput wrote for an extent
+ * that begins at `srcOffset` of the last batch's output and at `fileOffset` of the decoded file.  When the total is known,
+ * allocate( total ) names the device memory the bytes go to (not called for a total of 0; nullptr: there is none, and the
+ * call is MI355X_BZ2_ERR_DEVICE with a message).  dOffsets[0, n] receives the offsets, *firstSize the bytes of span 0. */
+int gatherFieldsOutput( mi355x_bz2_ctx* ctx, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t srcOffset,
+                        uint64_t fileOffset, uint64_t* dOffsets, const std::function<uint8_t*( uint64_t )>& allocate,
+                        uint64_t* total, uint64_t* firstSize );
+
 /** The reader's field-hash pass in one launch: mi355x_bz2_field_hashes with `extent` as its one span, whose first byte is
  * offset `fileOffset` of the decoded file, and the base x instead of the seed.  *summary receives the extent's summary
  * and the count of the lines it closes, none of them listed; key, start and size of the field in its closed lines [skip,
@@ -99,6 +108,10 @@ void* deviceAllocate( int device, uint64_t bytes, std::string* error );
 void deviceRelease( void* pointer );
 bool deviceToHost( int device, void* dst, const void* src, uint64_t bytes, bool dstIsDevice, std::string* error );
 bool hostToDevice( int device, void* dst, const void* src, uint64_t bytes, std::string* error );
+
+/** dOffsets[0, n] = the exclusive prefix sums of max( dSizes[i], 0 ) (both device memory; rocPRIM, bz2_distinct.hip) and
+ * *total their sum.  False with *error set if an allocation or a launch fails. */
+bool columnOffsets( int device, const int64_t* dSizes, uint64_t n, uint64_t* dOffsets, uint64_t* total, std::string* error );
 
 /** The distinct values among dHashes[0, n) (device memory, left as it is): *nDistinct = their number and, if `numbers` is
  * given, the index of the first occurrence of each, ascending.  False with *error set if an allocation or a launch

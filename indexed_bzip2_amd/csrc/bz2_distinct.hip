@@ -36,6 +36,7 @@
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/device/device_reduce_by_key.hpp>
+#include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_select.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
 #include <rocprim/iterator/transform_iterator.hpp>
@@ -238,6 +239,43 @@ mi355x::hostToDevice( int device, void* dst, const void* src, uint64_t bytes, st
     if ( bytes == 0 ) return true;
     if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
     DISTINCT_TRY( hipMemcpy( dst, src, bytes, hipMemcpyHostToDevice ) );
+    return true;
+}
+
+namespace
+{
+/** Item i of columnOffsets' scan: the bytes of line i's field, and nothing for the one item behind the lines. */
+struct BytesOfLine
+{
+    const int64_t* sizes;
+    uint64_t n;
+
+    __device__ uint64_t
+    operator()( uint64_t i ) const
+    {
+        const int64_t size = i < n ? sizes[i] : 0;
+        return size > 0 ? (uint64_t)size : 0;
+    }
+};
+}  // namespace
+
+bool
+mi355x::columnOffsets( int device, const int64_t* dSizes, uint64_t n, uint64_t* dOffsets, uint64_t* total, std::string* error )
+{
+    *total = 0;
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    const hipStream_t stream = nullptr;
+    /* n + 1 items, the last one 0: the exclusive scan's last value is the total */
+    const auto bytes = rocprim::make_transform_iterator( rocprim::make_counting_iterator( uint64_t( 0 ) ), BytesOfLine{ dSizes, n } );
+    Buffers buffers;
+    buffers.who = "field_columns";
+    void* dTemp = nullptr;
+    size_t tempBytes = 0;
+    DISTINCT_TRY( rocprim::exclusive_scan( nullptr, tempBytes, bytes, dOffsets, uint64_t( 0 ), (size_t)n + 1, rocprim::plus<uint64_t>(), stream ) );
+    if ( !buffers.get( &dTemp, tempBytes, "the scan", error ) ) return false;
+    DISTINCT_TRY( rocprim::exclusive_scan( dTemp, tempBytes, bytes, dOffsets, uint64_t( 0 ), (size_t)n + 1, rocprim::plus<uint64_t>(), stream ) );
+    DISTINCT_TRY( hipMemcpyAsync( total, dOffsets + n, sizeof( uint64_t ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
     return true;
 }
 

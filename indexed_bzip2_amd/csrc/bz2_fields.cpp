@@ -3,6 +3,7 @@
  */
 #include "../../include/mi355x_bz2.h"
 #include "bz2_fields.hpp"
+#include "bz2_fieldcols.hpp"
 
 extern "C" {
 
@@ -10,6 +11,12 @@ uint32_t
 mi355x_bz2_field_chunk_bytes( void )
 {
     return bz2gpu::FIELD_CHUNK_BYTES;
+}
+
+uint32_t
+mi355x_bz2_gather_fields_tile_bytes( void )
+{
+    return bz2gpu::FIELD_COLUMN_TILE_BYTES;
 }
 
 }  // extern "C"

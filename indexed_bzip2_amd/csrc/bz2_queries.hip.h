@@ -1,8 +1,8 @@
 /**
  * bz2_queries.hip.h -- the host side of the calls that read a finished batch's output: gather, count / find / rank of a
- * byte, search for a string or a set of strings, regular expressions, line hashes, field spans and field hashes, their
- * mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's translation unit
- * (the context's layout names device record types), included below the context's definition and HIP_TRY.
+ * byte, search for a string or a set of strings, regular expressions, line hashes, field spans, field columns and field
+ * hashes, their mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's
+ * translation unit (the context's layout names device record types), included below the context's definition and HIP_TRY.
  *
  * Every launcher but gatherPieces (millions of one-tile pieces, a plain loop) has the same shape: refuseQuery, the tiles
  * of its spans (firstTiles / writeCountTiles), its layout (bz2_query_layout.hpp) and growStaging, one H2D of what goes
@@ -748,6 +748,77 @@ fieldSpans( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spa
     return MI355X_BZ2_OK;
 }
 
+static_assert( sizeof( FieldColumnCheck ) == 24 && FIELDCOL_TILE == FIELD_COLUMN_TILE_BYTES, "the layout's check; the host's constant" );
+
+/**
+ * mi355x_bz2_gather_fields.  The n spans are in device memory already, so nothing goes up and the check that refuseQuery
+ * makes on the host is k_fieldcol_sums': the spans' check and the tile sums, k_fieldcol_top for the tiles' prefixes and the
+ * total, and the 24 bytes of the check come back -- the one wait of the call before its last.  With an offender the call
+ * ends there: no span is read.  Else destination( total, &dst ) names where the bytes go (null: nowhere; false: it found
+ * no memory, MI355X_BZ2_ERR_DEVICE), k_fieldcol_offsets writes dOffsets[0, n] and k_field_gather copies the bytes.  A
+ * span's start counts from `base`, modulo 2^64: start - base is its offset in the output.  *firstSize, if wanted,
+ * receives the bytes of span 0: dOffsets[1].
+ */
+template<typename Destination>
+int
+gatherFields( mi355x_bz2_ctx* c, const char* what, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t base,
+              uint64_t* dOffsets, const Destination& destination, uint64_t* total, uint64_t* firstSize = nullptr )
+{
+    const std::scoped_lock lock( c->mutex );
+    if ( const int status = refuseQuery( c, what, nullptr, 0 ) ) return status;
+    *total = 0;
+    if ( firstSize != nullptr ) *firstSize = 0;
+    const FieldColumnLayout l = layFieldColumn( n, FIELDCOL_SCAN_TILE );
+    if ( l.scanTiles > 0x7FFFFFFFu ) return refuse( c, what, "too many spans" );
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    if ( n == 0 ) {
+        HIP_TRY( c, hipMemsetAsync( dOffsets, 0, sizeof( uint64_t ), c->stream ) );
+        HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+        return MI355X_BZ2_OK;
+    }
+    if ( const int status = growLineStaging( c, l.tileSumsAt, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    auto* const hCheck = at<FieldColumnCheck>( h, l.checkAt );
+    auto* const dCheck = at<FieldColumnCheck>( d, l.checkAt );
+    auto* const dTileSums = at<uint64_t>( d, l.tileSumsAt );
+    auto* const dTilePrefixes = at<uint64_t>( d, l.tilePrefixesAt );
+    *hCheck = { 0, FIELDCOL_NONE, 0 };
+    HIP_TRY( c, hipMemcpyAsync( dCheck, hCheck, sizeof( FieldColumnCheck ), hipMemcpyHostToDevice, c->stream ) );
+    hipLaunchKernelGGL( k_fieldcol_sums, dim3( (uint32_t)l.scanTiles ), dim3( FIELDCOL_THREADS ), 0, c->stream, dStarts, dSizes, n, base,
+                        c->outSize, dTileSums, dCheck );
+    HIP_TRY( c, hipGetLastError() );
+    hipLaunchKernelGGL( k_fieldcol_top, dim3( 1 ), dim3( FIELDCOL_THREADS ), 0, c->stream, dTileSums, l.scanTiles, dTilePrefixes, dCheck );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipMemcpyAsync( hCheck, dCheck, sizeof( FieldColumnCheck ), hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    if ( hCheck->offenders != 0 ) {
+        return refuse( c, what, "span " + std::to_string( hCheck->first ) + " lies outside the last batch's output ("
+                                + std::to_string( hCheck->offenders ) + " of the spans do)" );
+    }
+    *total = hCheck->total;
+    uint8_t* dst = nullptr;
+    if ( !destination( *total, &dst ) ) {
+        c->lastError = std::string( what ) + ": no device memory for the " + std::to_string( *total ) + " bytes of the fields";
+        return MI355X_BZ2_ERR_DEVICE;
+    }
+    const uint64_t gatherTiles = fieldGatherTiles( *total, reinterpret_cast<uintptr_t>( dst ) & 15u, FIELDCOL_TILE );
+    if ( gatherTiles > 0x7FFFFFFFu ) return refuse( c, what, "too many bytes" );
+    hipLaunchKernelGGL( k_fieldcol_offsets, dim3( (uint32_t)l.scanTiles ), dim3( FIELDCOL_THREADS ), 0, c->stream, dSizes, n,
+                        dTilePrefixes, dCheck, dOffsets );
+    HIP_TRY( c, hipGetLastError() );
+    auto* const hFirst = at<uint64_t>( h, sizeof( FieldColumnCheck ) );   /* behind the check, in front of tileSumsAt */
+    if ( firstSize != nullptr ) HIP_TRY( c, hipMemcpyAsync( hFirst, dOffsets + 1, sizeof( uint64_t ), hipMemcpyDeviceToHost, c->stream ) );
+    if ( dst != nullptr && gatherTiles > 0 ) {
+        hipLaunchKernelGGL( k_field_gather, dim3( (uint32_t)gatherTiles ), dim3( FIELDCOL_THREADS ), 0, c->stream, dStarts, dOffsets, n,
+                            base, *total, c->dOut, dst );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    if ( firstSize != nullptr ) *firstSize = *hFirst;
+    return MI355X_BZ2_OK;
+}
+
 static_assert( sizeof( FieldHashTail ) == 16 && FIELDHASH_MISSING == FIELD_MISSING, "the layout's tail hashes; the host's constant" );
 static_assert( FIELD_MISSING == MI355X_BZ2_FIELD_MISSING, "the C ABI's constant" );
 
@@ -1120,6 +1191,21 @@ mi355x::fieldNumbersOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& exten
 }
 
 int
+mi355x::gatherFieldsOutput( mi355x_bz2_ctx* c, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t srcOffset,
+                            uint64_t fileOffset, uint64_t* dOffsets, const std::function<uint8_t*( uint64_t )>& allocate,
+                            uint64_t* total, uint64_t* firstSize )
+{
+    if ( c == nullptr || total == nullptr || dOffsets == nullptr || ( n > 0 && ( dStarts == nullptr || dSizes == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    /* modulo 2^64: start - ( fileOffset - srcOffset ) = srcOffset + ( start - fileOffset ) */
+    return gatherFields( c, "field_columns", dStarts, dSizes, n, fileOffset - srcOffset, dOffsets, [&] ( uint64_t bytes, uint8_t** dst ) {
+        *dst = bytes > 0 ? allocate( bytes ) : nullptr;
+        return bytes == 0 || *dst != nullptr;
+    }, total, firstSize );
+}
+
+int
 mi355x::gatherResult( mi355x_bz2_ctx* c, const mi355x_bz2_gather_piece* pieces, uint32_t nPieces, void* dst, int dstIsDevice )
 {
     if ( c == nullptr || ( nPieces > 0 && pieces == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
@@ -1238,6 +1324,19 @@ mi355x_bz2_field_spans( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, ui
     }
     return fieldSpans( c, "field_spans", spans, nullptr, n, nl, dl, field, summaries, headPositions, 0, capacity, startsDevice,
                        sizesDevice );
+}
+
+int
+mi355x_bz2_gather_fields( mi355x_bz2_ctx* c, const uint64_t* startsDevice, const int64_t* sizesDevice, uint64_t n, uint64_t base,
+                          uint64_t* offsetsDevice, void* dstDevice, uint64_t dstCapacity, uint64_t* total )
+{
+    if ( c == nullptr || total == nullptr || offsetsDevice == nullptr || ( n > 0 && ( startsDevice == nullptr || sizesDevice == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return gatherFields( c, "gather_fields", startsDevice, sizesDevice, n, base, offsetsDevice, [=] ( uint64_t bytes, uint8_t** dst ) {
+        *dst = bytes <= dstCapacity ? static_cast<uint8_t*>( dstDevice ) : nullptr;
+        return true;
+    }, total );
 }
 
 int

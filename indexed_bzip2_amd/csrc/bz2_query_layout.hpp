@@ -196,4 +196,23 @@ layFieldHashes( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field
              r.add( nTiles * s.fieldTile, 16 ), r.add( nTiles * s.lineHashTile, 16 ), r.add( slots * 8, 16 ),
              r.add( slots * s.lineHashPrefix, 16 ), r.add( slots * 4 ), r.add( slots * 4 ), r.add( slots * 4 ), r.size() };
 }
+
+/* gather_fields over n spans that are in device memory already, scanned in tiles of `scanTile` spans: nothing up,
+ * [the check: offenders, first offender, total; 24 bytes] down; [tile sums][tile prefixes] */
+struct FieldColumnLayout { uint64_t checkAt, tileSumsAt, tilePrefixesAt, bytes, scanTiles; };
+inline FieldColumnLayout
+layFieldColumn( uint64_t n, uint64_t scanTile )
+{
+    const uint64_t scanTiles = ( n + scanTile - 1 ) / scanTile;
+    Regions r;
+    return { r.add( 24 ), r.add( scanTiles * 8, 16 ), r.add( scanTiles * 8, 16 ), r.size(), scanTiles };
+}
+
+/** The workgroups of k_field_gather for `total` bytes to a destination whose address is `lead` mod 16: it cuts the
+ * destination at multiples of tileBytes counted from the 16-byte boundary in front of it. */
+inline uint64_t
+fieldGatherTiles( uint64_t total, uint64_t lead, uint64_t tileBytes )
+{
+    return total == 0 ? 0 : ( lead + total + tileBytes - 1 ) / tileBytes;
+}
 }  // namespace bz2gpu

@@ -45,6 +45,7 @@
 #include "bz2_lines.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_fields.hpp"
+#include "bz2_fieldcols.hpp"
 #include "bz2_search.hpp"
 #include "bz2_ranges.hpp"
 
@@ -1467,6 +1468,7 @@ public:
         dropHeldLines();
         dropHeldHashes();
         m_fields.reset();
+        m_fieldColumns.reset();
         dropHeldFieldHashes();
         dropHeldFieldNumbers();
         m_matches.reset();
@@ -2106,6 +2108,186 @@ public:
         takeColumns( "take_field_spans", "no field spans are held (field_spans first)", m_fields, { starts, sizes }, capacity, dstIsDevice );
     }
 
+    /**
+     * mi355x_bz2_reader_field_columns: the launches of lineColumns' plan, in which every stretch runs fieldSpansOutput once
+     * per field while it is resident -- every needed block is decoded once, whatever the number of fields -- and packs each
+     * field's bytes with gatherFieldsOutput into a buffer of that stretch's own, allocated when the stretch's total is
+     * known.  Then per field: stitchFields, its patches into the sizes, the final offsets scanned on the device over the
+     * patched sizes (columnOffsets), planColumnAssembly (bz2_fieldcols.hpp), and the fix-ups -- the patched lines' fields,
+     * one per launch seam and the tail -- fetched by readRanges, the only second decode.  The result is held as pieces:
+     * the stretches' packs and the fix-ups' bytes.  Peak device memory: the columns' bytes once, and per line and field
+     * 24 bytes (start, size, offset), of which the 8 of the start are given back when the call returns.
+     */
+    void
+    fieldColumns( uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t nFields, uint64_t first, uint64_t count, bool keepOnDevice,
+                  uint64_t* nLines, uint64_t* totals )
+    {
+        const std::string what = "field_columns";
+        if ( nFields == 0 || nFields > bz2gpu::FIELD_COLUMNS_MAX ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": the number of fields must be 1 to " + std::to_string( bz2gpu::FIELD_COLUMNS_MAX )
+                                                   + ", not " + std::to_string( nFields ) );
+        }
+        for ( uint32_t f = 0; f < nFields; ++f ) {
+            const auto refused = bz2gpu::fieldArgumentsError( nl, dl, fields[f] );
+            if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": " + refused );
+        }
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        m_fieldColumns.reset();
+        const auto plan = planLaunches( [&] ( bool packed ) {
+            return bz2gpu::planLineHashes( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
+                                           count, m_batch, packed, m_source->size() );
+        } );
+        HeldFieldColumns held;
+        held.device = m_device;
+        held.onDevice = keepOnDevice;
+        held.columns.resize( nFields );
+        if ( plan.count == 0 ) {
+            m_fieldColumns = std::move( held );
+            return;
+        }
+        using Memory = HeldFieldColumn::Memory;
+        const auto allocate = [&] ( uint64_t bytes ) {
+            std::string why;
+            Memory memory( deviceAllocate( m_device, bytes, &why ) );
+            if ( !memory ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            return memory;
+        };
+        const size_t nStretches = plan.stretches.size();
+        /* a stretch's offsets are local to it and have one more entry than it has lines: stretch k's lie k entries further
+         * on than its lines, so that no two stretches share one; the final offsets overwrite them */
+        std::vector<Memory> starts( nFields );
+        std::vector<std::vector<bz2gpu::FieldStretch> > stretches( nFields, std::vector<bz2gpu::FieldStretch>( nStretches ) );
+        std::vector<std::vector<bz2gpu::ColumnStretch> > packed( nFields, std::vector<bz2gpu::ColumnStretch>( nStretches ) );
+        for ( uint32_t f = 0; f < nFields; ++f ) {
+            starts[f] = allocate( plan.count * sizeof( uint64_t ) );
+            held.columns[f].sizes = allocate( plan.count * sizeof( int64_t ) );
+            held.columns[f].offsets = allocate( ( plan.count + nStretches + 1 ) * sizeof( uint64_t ) );
+            held.columns[f].packs.resize( nStretches );
+            for ( size_t k = 0; k < nStretches; ++k ) {
+                stretches[f][k].fileOffset = plan.stretches[k].fileOffset;
+                stretches[f][k].summary.size = plan.stretches[k].size;
+            }
+        }
+        const auto places = bz2gpu::placeLineColumn( plan, index.bytes.data(), index.lines.data(), index.bytes.size() );
+        runLineColumn( plan, places, [&] ( mi355x_bz2_ctx* ctx, size_t k, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place ) {
+            for ( uint32_t f = 0; f < nFields; ++f ) {
+                auto& column = held.columns[f];
+                auto* const dStarts = static_cast<uint64_t*>( starts[f].get() ) + place.at;
+                auto* const dSizes = static_cast<int64_t*>( column.sizes.get() ) + place.at;
+                auto& summary = stretches[f][k].summary;
+                checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, fields[f], place.skip, place.take,
+                                                    dStarts, dSizes, &summary ) );
+                if ( summary.count != stretches[0][k].summary.count ) {
+                    fail( MI355X_BZ2_ERR_LOGIC, what + ": the passes over one stretch count different lines" );
+                }
+                if ( place.take == 0 ) continue;
+                auto& pack = packed[f][k];
+                pack.at = place.at;
+                pack.take = place.take;
+                std::string why;
+                checkDevice( ctx, gatherFieldsOutput( ctx, dStarts, dSizes, place.take, piece.src, piece.fileOffset,
+                                                      static_cast<uint64_t*>( column.offsets.get() ) + place.at + k, [&] ( uint64_t bytes ) {
+                    column.packs[k].reset( deviceAllocate( m_device, bytes, &why ) );
+                    return static_cast<uint8_t*>( column.packs[k].get() );
+                }, &pack.total, &pack.firstSize ) );
+            }
+            return stretches[0][k].summary.count;
+        } );
+
+        const uint64_t wantedClosed = plan.wantedClosed();
+        uint64_t lines = 0;
+        std::string why;
+        for ( uint32_t f = 0; f < nFields; ++f ) {
+            auto& column = held.columns[f];
+            std::vector<bz2gpu::ColumnPatch> patches;
+            const auto stitched = bz2gpu::stitchFields( stretches[f], fields[f], [&] ( uint64_t k, const bz2gpu::FieldSpan& field ) {
+                const uint64_t line = plan.firstClosed + k;
+                if ( line >= first && line - first < wantedClosed ) patches.push_back( { line - first, field.start, field.size } );
+            } );
+            uint64_t n = std::min( wantedClosed, plan.firstClosed + stitched.closed - first );
+            if ( plan.reachesEnd && stitched.hasTail ) patches.push_back( { n++, stitched.tail.start, stitched.tail.size } );
+            if ( f > 0 && n != lines ) fail( MI355X_BZ2_ERR_LOGIC, what + ": the stitchers disagree about the lines" );
+            lines = n;
+            auto* const dSizes = static_cast<int64_t*>( column.sizes.get() );
+            for ( const auto& patch : patches ) {
+                if ( !hostToDevice( m_device, dSizes + patch.line, &patch.size, sizeof( patch.size ), &why ) ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            }
+            uint64_t total = 0;
+            if ( !columnOffsets( m_device, dSizes, n, static_cast<uint64_t*>( column.offsets.get() ), &total, &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            }
+            try {
+                column.plan = bz2gpu::planColumnAssembly( packed[f], patches );
+            } catch ( const std::invalid_argument& e ) {
+                fail( MI355X_BZ2_ERR_LOGIC, what + ": " + e.what() );
+            }
+            if ( column.plan.size != total ) fail( MI355X_BZ2_ERR_LOGIC, what + ": the assembled column and its offsets disagree about its size" );
+            totals[f] = total;
+        }
+        /* the fix-ups of all fields in ONE call of the reader's ranges path, back to back into one buffer: a block that
+         * holds patched fields of several columns is decoded once more, not once per column */
+        std::vector<uint64_t> fixOffsets, fixSizes;
+        uint64_t fixed = 0;
+        for ( auto& column : held.columns ) {
+            column.fixedAt = fixed;
+            for ( const auto& fixup : column.plan.fixups ) {
+                if ( fixup.size == 0 ) continue;
+                fixOffsets.push_back( fixup.fileOffset );
+                fixSizes.push_back( fixup.size );
+                fixed += fixup.size;
+            }
+        }
+        if ( fixed > 0 ) {
+            held.fixed = allocate( fixed );
+            std::vector<uint64_t> nRead( fixSizes.size() );
+            readRanges( fixOffsets.data(), fixSizes.data(), fixSizes.size(), held.fixed.get(), true, nRead.data() );
+            if ( nRead != fixSizes ) fail( MI355X_BZ2_ERR_LOGIC, what + ": a patched field lies behind the end of the file" );
+        }
+        held.n = lines;
+        *nLines = lines;
+        m_fieldColumns = std::move( held );
+    }
+
+    /** mi355x_bz2_reader_take_field_column: sizes and offsets of held column `column` as they are, and its bytes assembled
+     * straight into `data`, piece by piece: the library holds no second copy of a column.  Each may be null. */
+    void
+    takeFieldColumn( uint32_t column, void* data, void* offsets, void* sizes, bool dstIsDevice )
+    {
+        const std::string what = "take_field_column";
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, what + " on a closed reader" );
+        if ( !m_fieldColumns ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": no field columns are held (field_columns first)" );
+        const auto& held = *m_fieldColumns;
+        if ( column >= held.columns.size() ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": column " + std::to_string( column ) + " of " + std::to_string( held.columns.size() ) );
+        }
+        const auto& from = held.columns[column];
+        std::string why;
+        const auto copy = [&] ( void* dst, const void* src, uint64_t bytes ) {
+            if ( !deviceToHost( held.device, dst, src, bytes, dstIsDevice, &why ) ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+        };
+        if ( sizes != nullptr ) copy( sizes, from.sizes.get(), held.n * sizeof( int64_t ) );
+        if ( offsets != nullptr && held.n > 0 ) copy( offsets, from.offsets.get(), ( held.n + 1 ) * sizeof( uint64_t ) );
+        if ( offsets != nullptr && held.n == 0 ) {
+            const uint64_t zero = 0;
+            if ( !dstIsDevice ) {
+                std::memcpy( offsets, &zero, sizeof( zero ) );
+            } else if ( !hostToDevice( held.device, offsets, &zero, sizeof( zero ), &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
+            }
+        }
+        if ( data == nullptr ) return;
+        auto* const to = static_cast<uint8_t*>( data );
+        for ( const auto& piece : from.plan.copies ) {
+            copy( to + piece.dst, static_cast<const uint8_t*>( from.packs[piece.stretch].get() ) + piece.src, piece.size );
+        }
+        uint64_t at = from.fixedAt;
+        for ( const auto& fixup : from.plan.fixups ) {
+            copy( to + fixup.dst, static_cast<const uint8_t*>( held.fixed.get() ) + at, fixup.size );
+            at += fixup.size;
+        }
+    }
+
     /** mi355x_bz2_reader_field_hashes: lineColumns with fieldHashesOutput and stitchFieldHashes, a column of keys in front of
      * the two of the spans.  `what` names the call in its messages: field_groups goes through here. */
     void
@@ -2324,6 +2506,27 @@ private:
 
         template<typename T>
         [[nodiscard]] T* column( size_t c ) const { return static_cast<T*>( columns[c].get() ); }
+    };
+
+    /** One column of field_columns, held as pieces: sizes (n int64) and offsets (n + 1 uint64) as they are, the bytes as
+     * the packs of the plan's stretches (null where a stretch packed nothing) and the fix-ups' bytes, back to back in the
+     * assembly's order in the buffer all columns share; `plan` says where each piece goes. */
+    struct HeldFieldColumn
+    {
+        using Memory = std::unique_ptr<void, HeldColumns::Release>;
+        Memory sizes, offsets;
+        std::vector<Memory> packs;
+        bz2gpu::ColumnAssembly plan;
+        uint64_t fixedAt{ 0 };                  /* where its fix-ups begin in HeldFieldColumns::fixed */
+    };
+
+    struct HeldFieldColumns
+    {
+        std::vector<HeldFieldColumn> columns;
+        HeldFieldColumn::Memory fixed;          /* the fix-ups' bytes of all columns, column by column */
+        uint64_t n{ 0 };
+        int device{ -1 };
+        bool onDevice{ false };
     };
 
     void
@@ -2730,6 +2933,7 @@ private:
     HeldBytes m_heldBytes;                /* of m_held's pieces, per context; written by the line jobs */
     std::optional<HeldColumns> m_hashes;  /* between line_hashes and the next line_hashes / distinct_lines */
     std::optional<HeldColumns> m_fields;  /* between field_spans and the next field_spans */
+    std::optional<HeldFieldColumns> m_fieldColumns;           /* between field_columns and the next field_columns */
     std::optional<HeldColumns> m_fieldHashes;                 /* between field_hashes and the next call of its family */
     std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
     std::optional<HeldColumns> m_fieldNumbers;                /* between field_numbers and the next call of its family */
@@ -3158,6 +3362,24 @@ mi355x_bz2_reader_take_field_spans( mi355x_bz2_reader* r, void* starts, void* si
 {
     if ( capacity > 0 && ( starts == nullptr || sizes == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
     return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldSpans( starts, sizes, capacity, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_field_columns( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t nFields, uint64_t first,
+                                 uint64_t count, int keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+{
+    if ( nLines == nullptr || totalBytes == nullptr || ( nFields > 0 && fields == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    std::fill_n( totalBytes, std::min<uint32_t>( nFields, bz2gpu::FIELD_COLUMNS_MAX ), uint64_t( 0 ) );
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldColumns( nl, dl, fields, nFields, first, count, keepOnDevice != 0, nLines, totalBytes );
+    } );
+}
+
+int
+mi355x_bz2_reader_take_field_column( mi355x_bz2_reader* r, uint32_t column, void* data, void* offsets, void* sizes, int dstIsDevice )
+{
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldColumn( column, data, offsets, sizes, dstIsDevice != 0 ); } );
 }
 
 int

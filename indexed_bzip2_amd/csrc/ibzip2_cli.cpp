@@ -46,6 +46,7 @@ struct Options
     bool lineHashes{ false }, countDistinctLines{ false }, hasSeed{ false };
     uint64_t seed{ 0 };
     bool cutField{ false }, hasFieldDelimiter{ false }, countByField{ false };
+    std::vector<uint32_t> cutFields;            /* --cut-fields: not empty iff given */
     bool sumByField{ false };
     unsigned field{ 0 }, valueField{ 0 };
     uint8_t fieldDelimiter{ '\t' };
@@ -122,6 +123,11 @@ printHelp()
         "                                awk -F): a line is split at every --field-delimiter byte; there is no quoting\n"
         "                                and no escaping, this is not a CSV parser. The fields are found on the GPU and\n"
         "                                only their bytes are copied to the host.\n"
+        "      --cut-fields arg          Given N[,N...] (1 to 16 field numbers as for --cut-field, in any order, one may\n"
+        "                                repeat): print those fields of every line in the order given, joined by the\n"
+        "                                --field-delimiter byte, one line per line (cut -f1,4,6); a field a line does\n"
+        "                                not have prints as empty. The data is decoded once, whatever the number of\n"
+        "                                fields, and the GPU packs each field's bytes. This is not a CSV parser.\n"
         "      --field-delimiter arg     With --cut-field: the byte between fields, as itself (',') or as \\t, \\0 or\n"
         "                                \\xHH; not the newline. (default: \\t)\n"
         "      --count-by-field arg      Print how often every value of field N (as for --cut-field) occurs, one line\n"
@@ -172,6 +178,8 @@ printHelp()
         "  ibzip2-mi355x --count-distinct-lines file.bz2\n\n"
         "Print the third column of a tab-separated file:\n"
         "  ibzip2-mi355x --cut-field 2 file.tsv.bz2\n\n"
+        "Print the first, fourth and sixth column of a tab-separated file:\n"
+        "  ibzip2-mi355x --cut-fields 0,3,5 file.tsv.bz2\n\n"
         "Print how often each value of the third column occurs, the most frequent first:\n"
         "  ibzip2-mi355x --count-by-field 2 file.tsv.bz2\n\n"
         "Sum the third column per value of the first:\n"
@@ -335,6 +343,21 @@ parseArguments( int argc, char** argv, Options& o )
                 }
                 o.field = (unsigned)field;
                 o.cutField = true;
+            }
+            else if ( name == "cut-fields" ) {
+                /* N[,N...]: digits only, as --cut-field; no empty list, no empty entry, at most 16 */
+                bool good = need( value ) && !value.empty();
+                for ( size_t from = 0; good && from <= value.size(); ) {
+                    const auto comma = std::min( value.find( ',', from ), value.size() );
+                    uint64_t field = 0;
+                    good = parseSeed( value.substr( from, comma - from ).c_str(), field ) && field <= 1023 && o.cutFields.size() < 16;
+                    if ( good ) o.cutFields.push_back( (uint32_t)field );
+                    from = comma + 1;
+                }
+                if ( !good ) {
+                    std::cerr << "Bad value for --cut-fields\n";
+                    return 1;
+                }
             }
             else if ( name == "count-by-field" ) {
                 uint64_t field = 0;     /* digits only, as --cut-field */
@@ -587,6 +610,13 @@ main( int argc, char** argv )
                      "'--grep-regex', '--count-matches', '--grep-file' or '--count-matches-file'\n";
         return 1;
     }
+    if ( !o.cutFields.empty() && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
+                                   || o.countDistinctLines || o.cutField || o.countByField || o.sumByField ) ) {
+        std::cerr << "Option '--cut-fields' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
+                     "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines', '--cut-field', "
+                     "'--count-by-field' or '--sum-by-field'\n";
+        return 1;
+    }
     if ( o.sumByField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
                            || o.countDistinctLines || o.cutField || o.countByField ) ) {
         std::cerr << "Option '--sum-by-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
@@ -610,7 +640,7 @@ main( int argc, char** argv )
                      "'--grep-file', '--count-matches-file', '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
-    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField && !o.sumByField ) {
+    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField && !o.sumByField && o.cutFields.empty() ) {
         std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
         return 1;
     }
@@ -752,6 +782,66 @@ main( int argc, char** argv )
                 text.append( bytes, at, lengths[i] );
                 text.push_back( '\n' );
                 at += lengths[i];
+            }
+            std::cout << text;
+            if ( n < WINDOW ) break;
+        }
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        return 0;
+    }
+
+    /* likewise an action of its own: several fields of every line from the reader's field_columns -- one decode, each
+     * field packed on the GPU --, in windows of lines so that the memory is bounded whatever the file */
+    if ( !o.cutFields.empty() ) {
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        constexpr uint64_t WINDOW = uint64_t( 1 ) << 20;
+        const size_t nFields = o.cutFields.size();
+        std::vector<uint64_t> totals( nFields );
+        std::vector<std::string> bytes( nFields );
+        std::vector<std::vector<uint64_t> > offsets( nFields );
+        std::string text;
+        for ( uint64_t first = 0; rc == MI355X_BZ2_OK; first += WINDOW ) {
+            uint64_t n = 0;
+            rc = mi355x_bz2_reader_field_columns( reader, '\n', o.fieldDelimiter, o.cutFields.data(), (uint32_t)nFields, first, WINDOW, 0, &n,
+                                                  totals.data() );
+            if ( rc != MI355X_BZ2_OK || n == 0 ) break;
+            uint64_t total = 0;
+            for ( size_t f = 0; f < nFields && rc == MI355X_BZ2_OK; ++f ) {
+                bytes[f].resize( totals[f] );
+                offsets[f].resize( n + 1 );
+                rc = mi355x_bz2_reader_take_field_column( reader, (uint32_t)f, bytes[f].data(), offsets[f].data(), nullptr, 0 );
+                total += totals[f];
+            }
+            if ( rc != MI355X_BZ2_OK ) break;
+            text.clear();
+            text.reserve( total + n * nFields );
+            for ( uint64_t i = 0; i < n; ++i ) {
+                for ( size_t f = 0; f < nFields; ++f ) {
+                    text.append( bytes[f], offsets[f][i], offsets[f][i + 1] - offsets[f][i] );
+                    text.push_back( f + 1 < nFields ? (char)o.fieldDelimiter : '\n' );
+                }
             }
             std::cout << text;
             if ( n < WINDOW ) break;

@@ -717,7 +717,8 @@ class _IndexedBzip2FileParallel:
         """Field `field` of lines [first, first + count) -> a list with one bytes object per line, content.split(
         delimiter)[field], and None where the line has no such field.  No quoting, no escaping: `cut -f`, not a CSV
         parser.  field_spans finds the fields on the GPU; then the blocks that hold them are decoded a second time and
-        only the fields' bytes are copied out.  Positionless."""
+        only the fields' bytes are copied out.  Positionless.  read_columns gives the same, for several fields, from one
+        decode."""
         def make(total):
             out = bytearray(total)
             return out, ((ctypes.c_char * total).from_buffer(out) if total else None), 0
@@ -729,7 +730,8 @@ class _IndexedBzip2FileParallel:
         """read_fields into ONE contiguous torch.uint8 tensor on the reader's device -> (data, offsets) as
         read_line_ranges_to_tensor shapes them: line i's field is ``data[offsets[i]:offsets[i + 1]]``, `offsets` an
         int64 CPU tensor of n + 1 boundaries; a missing field has size 0 (field_spans tells it from an empty one).  The
-        fields' bytes never pass through the host."""
+        fields' bytes never pass through the host.  read_columns_to_tensor gives the bytes from one decode, with offsets
+        and sizes on the device."""
         import torch
         self._field_arguments(field, first, count, delimiter, newline)      # refused before the GPU is touched
         dev = self._device_index()
@@ -742,6 +744,74 @@ class _IndexedBzip2FileParallel:
             return data, (ctypes.c_void_p(data.data_ptr()) if total else None), 1
         _, bounds, data = self._read_fields(field, first, count, delimiter, newline, make)
         return data, torch.from_numpy(bounds)
+
+    # -- field columns: the bytes of several fields of every line from ONE decode, each column packed on the GPU
+    def _column_arguments(self, fields, first, count, delimiter, newline):
+        if isinstance(fields, (str, bytes, bytearray)):
+            raise TypeError("fields must be a sequence of field numbers")
+        fields = list(fields)
+        if not 1 <= len(fields) <= 16:
+            raise ValueError("fields must name 1 to 16 fields")
+        nl = dl = first_ = count_ = None
+        checked = []
+        for field in fields:
+            nl, dl, field, first_, count_ = self._field_arguments(field, first, count, delimiter, newline)
+            checked.append(field)
+        return nl, dl, checked, first_, count_
+
+    def _field_columns(self, fields, first, count, delimiter, newline):
+        """mi355x_bz2_reader_field_columns -> (the number of lines, the bytes of every column); the columns are held."""
+        nl, dl, fields, first, count = self._column_arguments(fields, first, count, delimiter, newline)
+        numbers = (ctypes.c_uint32 * len(fields))(*fields)
+        n = ctypes.c_uint64()
+        totals = (ctypes.c_uint64 * len(fields))()
+        self._check(N.lib().mi355x_bz2_reader_field_columns(self._h, nl, dl, numbers, len(fields), first, count, 1, ctypes.byref(n),
+                                                            totals))
+        return n.value, list(totals)
+
+    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """The fields `fields` (1 to 16 field numbers, each at most 1023; one may be named twice) of lines [first, first +
+        count) -> a list with one (data, offsets, sizes) per entry of `fields`, all on the reader's device: `data` a
+        torch.uint8 tensor of the field's bytes packed in line order, `offsets` torch.int64 of n + 1 boundaries and `sizes`
+        torch.int64 of n: ``data[offsets[i]:offsets[i + 1]] == content.split(delimiter)[field]``, and sizes[i] == -1 with
+        an empty slice where line i has fewer fields.  Every needed block is decoded once, whatever the number of fields
+        -- but for the few blocks that hold a line crossing a launch seam --, the GPU copies the fields out of the launch
+        that found them, and nothing per line passes through the host.  No quoting, no escaping: `cut -f1,4,6`, not a
+        CSV parser.  Positionless."""
+        import torch
+        self._column_arguments(fields, first, count, delimiter, newline)    # refused before the GPU is touched
+        dev = self._device_index()
+        n, totals = self._field_columns(fields, first, count, delimiter, newline)
+        out = []
+        for column, total in enumerate(totals):
+            data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+            offsets = torch.empty(n + 1, dtype=torch.int64, device=f"cuda:{dev}")
+            sizes = torch.empty(n, dtype=torch.int64, device=f"cuda:{dev}")
+            # the new tensors' memory may still be in use by work queued on torch's stream: the copies come after it
+            torch.cuda.current_stream(data.device).synchronize()
+            self._check(N.lib().mi355x_bz2_reader_take_field_column(
+                self._h, column, ctypes.c_void_p(data.data_ptr()) if total else None, ctypes.c_void_p(offsets.data_ptr()),
+                ctypes.c_void_p(sizes.data_ptr()) if n else None, 1))
+            out.append((data, offsets, sizes))
+        return out
+
+    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """read_columns_to_tensor on the host -> a list with, per entry of `fields`, a list with one bytes object per line
+        and None where the line has no such field: [read_fields(j, ...) for j in fields], from one decode."""
+        import numpy as np
+        n, totals = self._field_columns(fields, first, count, delimiter, newline)
+        out = []
+        for column, total in enumerate(totals):
+            data = bytearray(total)
+            offsets = np.empty(n + 1, dtype=np.uint64)
+            sizes = np.empty(n, dtype=np.int64)
+            self._check(N.lib().mi355x_bz2_reader_take_field_column(
+                self._h, column, (ctypes.c_char * total).from_buffer(data) if total else None, ctypes.c_void_p(offsets.ctypes.data),
+                ctypes.c_void_p(sizes.ctypes.data) if n else None, 0))
+            data = bytes(data)
+            bounds = offsets.tolist()
+            out.append([data[bounds[i]:bounds[i + 1]] if size >= 0 else None for i, size in enumerate(sizes.tolist())])
+        return out
 
     # -- field hashes and groups: the KEY of a line is N.line_hash(content.split(delimiter)[field], seed), computed where the
     # decoded bytes lie; a line with fewer fields has the key N.FIELD_MISSING = 2^61 - 1, which no hash takes, and an
@@ -1155,6 +1225,14 @@ class IndexedBzip2File(io.BufferedReader):
     def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """See _IndexedBzip2FileParallel.read_fields_to_tensor."""
         return self._open_reader().read_fields_to_tensor(field, first, count, delimiter, newline)
+
+    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_columns."""
+        return self._open_reader().read_columns(fields, first, count, delimiter, newline)
+
+    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        """See _IndexedBzip2FileParallel.read_columns_to_tensor."""
+        return self._open_reader().read_columns_to_tensor(fields, first, count, delimiter, newline)
 
     def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
