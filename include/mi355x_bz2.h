@@ -471,6 +471,25 @@ int mi355x_bz2_gather_fields( mi355x_bz2_ctx* ctx, const uint64_t* starts_device
                               uint64_t base, uint64_t* offsets_device, void* dst_device, uint64_t dst_capacity,
                               uint64_t* total );
 
+/* Is a field one of a set of values: the predicate of mi355x_bz2_reader_field_matches over columns that are in device
+ * memory already.  A line MATCHES iff it has the field and the field's bytes are byte for byte one of the values; the
+ * empty value matches an empty field that is present, never a missing one; equal values count once.  The key is only a
+ * filter in front of the comparison of the bytes: the flags do not depend on `seed`, as long as the keys were made with it.
+ *   _match_fields     `values` holds the n_values values one behind the other, value i with value_sizes[i] bytes: 1 to
+ *                     1024 values of 0 to 256 bytes each and at most 16384 bytes in total.  keys_device[n] (uint64),
+ *                     starts_device[n] (uint64) and sizes_device[n] (int64; all DEVICE memory) are what _field_hashes wrote
+ *                     under `seed` for n lines of the last batch's output; `base` is what takes a start back to an offset
+ *                     in that output, as for _gather_fields.  flags_device[n] (uint64, DEVICE memory) receives 1 for a
+ *                     line that matches and 0 for every other; nothing is written at or beyond n.  A line with a size
+ *                     < 0 (no such field) gives 0; so does one whose span does not lie inside the output, which is never
+ *                     read.  The refusals come before anything is launched: a set outside the limits above, and two
+ *                     DIFFERENT values with the same key under `seed` -- the message names both and says to pass another
+ *                     seed --, MI355X_BZ2_ERR_INVALID_ARGUMENT; no batch may be in flight.  The call returns when
+ *                     everything is written.  k_field_match. */
+int mi355x_bz2_match_fields( mi355x_bz2_ctx* ctx, const uint8_t* values, const uint32_t* value_sizes, uint32_t n_values,
+                             uint64_t seed, const uint64_t* keys_device, const uint64_t* starts_device,
+                             const int64_t* sizes_device, uint64_t n, uint64_t base, uint64_t* flags_device );
+
 /* The hash of field `field` of every line: the KEY of a line is mi355x_bz2_line_hash's hash (same seed, same base) of
  * content.split( dl )[field], the field mi355x_bz2_field_spans finds; a line with fewer fields has the key
  * MI355X_BZ2_FIELD_MISSING = 2^61 - 1, the hash's modulus, which no hash takes; an empty field is present and hashes
@@ -965,6 +984,45 @@ int mi355x_bz2_reader_field_sums( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, 
 int mi355x_bz2_reader_take_field_sums( mi355x_bz2_reader* r, uint64_t* lines, uint64_t* counts, uint64_t* starts, int64_t* sizes,
                                        uint64_t* numbers, uint64_t* sums_lo, int64_t* sums_hi, int64_t* mins, int64_t* maxs,
                                        uint64_t capacity );
+
+/* ---- lines selected by a field (mi355x_bz2_match_fields says when a field is one of a set of values;
+ * mi355x_bz2_field_numbers what the number of a field is).  A predicate on field `field` is a set of VALUES or a RANGE
+ * lo <= n <= hi over the field's number: a field that is no number and a line without the field are in no range.  A side
+ * without has_lo / has_hi is open; bounds are clipped to [-(10^18 - 1), 10^18 - 1], the numbers there are, and lo > hi
+ * afterwards is the empty range, not an error.  With `invert` the complement within the line range is selected (grep -v):
+ * then also the lines without the field and, for a range, the fields that are no numbers.  Lines, fields, first / count
+ * and line numbers are _field_spans'; there is no quoting, this is not a CSV parser.
+ *   _field_matches    the lines of [first, first + count), count clipped at the last line, whose field is one of the
+ *                     values (limits and refusals of mi355x_bz2_match_fields, which come before anything is decoded).
+ *                     *n_matching (may be NULL) = their number, *n_selected = min( limit, *n_matching ): the first
+ *                     n_selected line numbers, ascending and numbered in the file, are held in device memory until the
+ *                     next _field_matches / _field_in_range / _select_lines or the close.  limit 0 counts: nothing per
+ *                     line leaves the GPU, 8 bytes come to the host.  Every needed block is decoded ONCE: each launch runs
+ *                     mi355x_bz2_field_hashes' kernels and k_field_match over its resident blocks, then one rocPRIM select
+ *                     over the flags.  A line that crosses a launch seam and the unterminated tail are known by key, start
+ *                     and size only: where key and size hit a value, the field's bytes are fetched by one
+ *                     _read_ranges-like call -- at most launches + 1 fields, the only second decode -- and compared on
+ *                     the host.  The answer does not depend on `seed`.  Line index, launches, residency and failure rules
+ *                     are _field_spans'.  Positionless; releases line ranges held by earlier calls.
+ *   _field_in_range   the same for a range: mi355x_bz2_reader_field_numbers' launches, then the select over the numbers.
+ *   _take_field_matches  the first min( capacity, n_selected ) held line numbers (uint64 each) to `dst`, host memory or,
+ *                     with dst_is_device, device memory; they stay held.
+ *   _select_lines     the selected lines themselves: values (n_values > 0) or a range (n_values == 0), not both; then
+ *                     _read_line_ranges with one range per selected line, as _grep does it.  max_lines is grep's: 0 gives
+ *                     *n_lines = the number of selected lines and holds nothing; otherwise the first max_lines lines are
+ *                     held as grep's: _take_grep gives their numbers and sizes, _take_line_ranges their bytes. */
+int mi355x_bz2_reader_field_matches( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const uint8_t* values,
+                                     const uint32_t* value_sizes, uint32_t n_values, uint64_t seed, int invert, uint64_t first,
+                                     uint64_t count, uint64_t limit, int keep_on_device, uint64_t* n_selected,
+                                     uint64_t* n_matching );
+int mi355x_bz2_reader_field_in_range( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, int has_lo, int64_t lo,
+                                      int has_hi, int64_t hi, int invert, uint64_t first, uint64_t count, uint64_t limit,
+                                      int keep_on_device, uint64_t* n_selected, uint64_t* n_matching );
+int mi355x_bz2_reader_take_field_matches( mi355x_bz2_reader* r, void* dst, uint64_t capacity, int dst_is_device );
+int mi355x_bz2_reader_select_lines( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const uint8_t* values,
+                                    const uint32_t* value_sizes, uint32_t n_values, uint64_t seed, int has_lo, int64_t lo,
+                                    int has_hi, int64_t hi, int invert, uint64_t first, uint64_t count, uint64_t max_lines,
+                                    int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

@@ -26,7 +26,10 @@ field j of every line (FIELD_MISSING, 2^61 - 1, where a line has no such field),
 the GPU and value_counts adds the values (`cut -f3 | sort | uniq -c | sort -rn`).  And how much: field_ints and
 field_ints_to_tensor give field j of every line as an int64 (parse_field_number says which bytes are a number:
 [+-]?[0-9]{1,18}, not awk's strtod; FIELD_NOT_A_NUMBER and FIELD_NUMBER_MISSING otherwise), sum_by_field sums one column
-per value of another on the GPU from one decode, exactly, and value_sums adds the keys (`awk '{s[$1]+=$3}'`).
+per value of another on the GPU from one decode, exactly, and value_sums adds the keys (`awk '{s[$1]+=$3}'`).  And which
+rows: where_field, where_field_to_tensor and count_where_field select the lines whose field j is byte for byte one of a set
+of values, or whose number lies in a range (`awk -F'\t' '$3 == "GET"'`, `awk '$5 >= 500'`, a semi-join), invert=True the
+others; select_lines and select_lines_to_tensor bring those lines as grep brings its own.
 """
 __version__ = "0.1.0"
 

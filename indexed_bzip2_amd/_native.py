@@ -221,6 +221,19 @@ SYMBOLS = [
     ("mi355x_bz2_reader_field_sums", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint32,
                                                      ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, _u64p, _u64p]),
     ("mi355x_bz2_reader_take_field_sums", ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_match_fields", ctypes.c_int, [_vp, ctypes.c_char_p, _vp, ctypes.c_uint32, ctypes.c_uint64, _vp, _vp, _vp,
+                                                ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    ("mi355x_bz2_reader_field_matches", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_char_p, _vp,
+                                                        ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64,
+                                                        ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_reader_field_in_range", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_int,
+                                                         ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_uint64,
+                                                         ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_reader_take_field_matches", ctypes.c_int, [_vp, _vp, ctypes.c_uint64, ctypes.c_int]),
+    ("mi355x_bz2_reader_select_lines", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_char_p, _vp,
+                                                       ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                                                       ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
+                                                       ctypes.c_int, _u64p, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -520,6 +533,55 @@ def pattern_set(patterns, check=True):
             raise ValueError(f"the patterns must have at most {SET_MAX_BYTES} bytes in total, not {sum(map(len, items))}")
     sizes = (ctypes.c_uint32 * max(1, len(items)))(*[len(pattern) for pattern in items])
     return b"".join(items), sizes, len(items)
+
+
+FIELD_VALUES_MAX = 1024          # of a where_field predicate: values, bytes per value, bytes in total
+FIELD_VALUE_BYTES_MAX = 256
+FIELD_VALUES_BYTES_MAX = 16384
+FIELD_NUMBER_MAX = 10**18 - 1    # the largest number a field can be; the least is its negative
+
+
+def value_set(values, check=True):
+    """The values of a where_field predicate: (the values concatenated, their sizes as a uint32 array, their number).
+    `values` is any sequence of bytes-like objects; a str element, or a bare bytes-like object in place of the sequence,
+    is a TypeError.  With `check`, a set outside the limits -- 1 to 1 024 values of 0 to 256 bytes, at most 16 384 bytes
+    in total -- is a ValueError (without it, the native call refuses the set).  The empty value is allowed."""
+    if isinstance(values, (str, bytes, bytearray, memoryview)):
+        raise TypeError("values must be a sequence of bytes-like objects, not one " + type(values).__name__)
+    items = []
+    for value in values:
+        if isinstance(value, str):
+            raise TypeError("a value must be bytes-like, not str")
+        items.append(bytes(memoryview(value)))      # TypeError for what is not bytes-like
+    if check:
+        if not 1 <= len(items) <= FIELD_VALUES_MAX:
+            raise ValueError(f"the set must have 1 to {FIELD_VALUES_MAX} values, not {len(items)}")
+        for i, value in enumerate(items):
+            if len(value) > FIELD_VALUE_BYTES_MAX:
+                raise ValueError(f"value {i} has {len(value)} bytes, more than {FIELD_VALUE_BYTES_MAX}")
+        if sum(map(len, items)) > FIELD_VALUES_BYTES_MAX:
+            raise ValueError(f"the values must have at most {FIELD_VALUES_BYTES_MAX} bytes in total, not {sum(map(len, items))}")
+    sizes = (ctypes.c_uint32 * max(1, len(items)))(*[len(value) for value in items])
+    return b"".join(items), sizes, len(items)
+
+
+def number_range(between):
+    """The bounds of a where_field range as the native calls take them: (has_lo, lo, has_hi, hi).  `between` is (lo, hi),
+    each a Python int or None for an open side; a bound is clipped to [-(10**18 - 1), 10**18 - 1], the numbers a field
+    can be."""
+    try:
+        lo, hi = between
+    except (TypeError, ValueError):
+        raise ValueError("between must be a pair (lo, hi), each an int or None") from None
+    out = []
+    for bound in (lo, hi):
+        if bound is None:
+            out += [0, 0]
+            continue
+        if isinstance(bound, bool) or not isinstance(bound, int):
+            raise TypeError("a bound must be an int or None, not " + type(bound).__name__)
+        out += [1, max(-FIELD_NUMBER_MAX, min(FIELD_NUMBER_MAX, bound))]
+    return tuple(out)
 
 
 class _KeptInputs(tuple):
@@ -1049,6 +1111,33 @@ class Decoder:
                         "head_texts": [text.as_tuple() for text in head_texts[at:at + listed]],
                         "tail_text": tail_texts[i].as_tuple()})
         return out, numbers[:room], starts[:room], sizes[:room]
+
+    def match_fields(self, values, keys, starts, sizes, base=0, seed=0, room=None, check=True):
+        """k_field_match: is the field of every line one of `values`, byte for byte?  keys, starts and sizes are
+        field_hashes' three arrays for n lines of the last batch's output (made under `seed`); start - base is a field's
+        offset in that output -> flags: a numpy uint64 array of `room` words (default: n) that were all ones before the
+        call, of which the call writes the first n: 1 where the line matches, 0 elsewhere.  The key only filters: a line
+        whose key is a value's but whose bytes are not gives 0."""
+        import numpy as np
+        data, value_sizes, n_values = value_set(values, check=check)
+        seed = int(seed)
+        if seed < 0 or seed >= 2**64:
+            raise ValueError("seed must not be negative and must fit 64 bits")
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        if keys.ndim != 1 or keys.shape != starts.shape or keys.shape != sizes.shape:
+            raise ValueError("keys, starts and sizes must be one-dimensional and equally long")
+        n = int(keys.size)
+        room = n if room is None else max(int(room), n)
+        flags = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        hosts = [np.resize(keys, max(1, n)), np.resize(starts, max(1, n)), np.resize(sizes, max(1, n)), flags]
+
+        def call(d_keys, d_starts, d_sizes, d_flags):
+            self._check(lib().mi355x_bz2_match_fields(self._h, data, value_sizes, n_values, seed, d_keys, d_starts, d_sizes, n,
+                                                      int(base) % 2**64, d_flags))
+        _with_device_copies("match_fields", hosts, call)
+        return flags[:room]
 
     def output_device_ptr(self) -> int:
         return lib().mi355x_bz2_output_device(self._h) or 0

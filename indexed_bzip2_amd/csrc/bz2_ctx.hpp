@@ -13,6 +13,7 @@
 
 #include "../../include/mi355x_bz2.h"
 #include "bz2_fieldhash.hpp"
+#include "bz2_fieldmatch.hpp"
 #include "bz2_fieldnum.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
@@ -101,6 +102,13 @@ int fieldNumbersOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent,
                         uint32_t field, uint64_t skip, uint64_t take, int64_t* dNumbers, uint64_t* dStarts, int64_t* dSizes,
                         bz2gpu::FieldNumberSummary* summary );
 
+/** The reader's value match in one launch: mi355x_bz2_match_fields with a finished table, over the n lines whose keys,
+ * starts and sizes fieldHashesOutput wrote for an extent that begins at `srcOffset` of the last batch's output and at
+ * `fileOffset` of the decoded file.  dFlags[0, n), device memory, receives 1 where the field's bytes are one of the table's
+ * values and 0 elsewhere. */
+int matchFieldsOutput( mi355x_bz2_ctx* ctx, const bz2gpu::ValueTable& table, const uint64_t* dKeys, const uint64_t* dStarts,
+                       const int64_t* dSizes, uint64_t n, uint64_t srcOffset, uint64_t fileOffset, uint64_t* dFlags );
+
 /** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
  * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies
  * to device memory instead. */
@@ -148,6 +156,23 @@ struct FieldSumGroup
  * sort: a key that every line shares costs what all-distinct keys cost. */
 bool groupSums( int device, const uint64_t* dKeys, const uint64_t* dStarts, const int64_t* dSizes, const int64_t* dValues, uint64_t n,
                 uint64_t missing, std::vector<FieldSumGroup>* groups, uint64_t* nMissing, std::string* error );
+
+/** What selectLines selects by: dFlags[i] != 0 (one word per line), or, with dFlags null, lo <= dNumbers[i] <= hi over
+ * field-number words, whose two sentinels lie below every lo there is.  `invert` selects the others. */
+struct LinePredicate
+{
+    const uint64_t* dFlags{ nullptr };
+    const int64_t* dNumbers{ nullptr };
+    int64_t lo{ 0 }, hi{ 0 };
+    bool invert{ false };
+};
+
+/** The numbers base + i, ascending, of the i < n for which the predicate holds (device memory, left as it is; rocPRIM
+ * select over a counting iterator): *nMatching = how many there are, which takes 8 bytes to the host, and *selected = new
+ * device memory (deviceRelease) with the first min( limit, *nMatching ) of them, null where that is none.  False with
+ * *error set if an allocation or a launch fails. */
+bool selectLines( int device, const LinePredicate& predicate, uint64_t n, uint64_t base, uint64_t limit, uint64_t** selected,
+                  uint64_t* nMatching, std::string* error );
 
 /** From now until the next batch begins, mi355x_bz2_output_device / _copy_output / _gather_output address the first
  * `size` bytes of the result buffer. */

@@ -29,6 +29,13 @@
  *   rocPRIM           sort ( first line, run ) ascending
  *   k_sum_order       the groups in that order, 72 bytes each, for the one D2H
  *
+ * and the numbers of the lines that a predicate selects (mi355x_bz2_reader_field_matches, _field_in_range):
+ *
+ *   rocPRIM           ONE select over a counting iterator, the predicate reading the line's flag word (k_field_match wrote
+ *                     it) or its field-number word against lo and hi, inverted or not: the selected numbers ascend, their
+ *                     count takes 8 bytes to the host
+ *   k_number_lines    + the number of the range's first line, over the numbers that are kept (the first `limit`)
+ *
  * The null stream and buffers of the call's own: it comes when the reader's launches are through.  Every buffer is
  * allocated before the pass that fills it, so that a failed allocation loses no result.
  */
@@ -518,5 +525,79 @@ mi355x::groupSums( int device, const uint64_t* dKeys, const uint64_t* dStarts, c
     DISTINCT_TRY( hipGetLastError() );
     DISTINCT_TRY( hipMemcpyAsync( groups->data(), dOrdered, nGroups * sizeof( FieldSumGroup ), hipMemcpyDeviceToHost, stream ) );
     DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    return true;
+}
+
+namespace
+{
+/** Is line i selected: its flag word, or its field-number word against the range; inverted or not. */
+struct LineSelected
+{
+    mi355x::LinePredicate by;
+
+    __device__ bool
+    operator()( uint64_t i ) const
+    {
+        const bool holds = by.dFlags != nullptr ? by.dFlags[i] != 0 : ( by.dNumbers[i] >= by.lo && by.dNumbers[i] <= by.hi );
+        return holds != by.invert;
+    }
+};
+
+/** numbers[i] += base for the first n. */
+__global__ __launch_bounds__( DISTINCT_THREADS ) void
+k_number_lines( uint64_t* __restrict__ numbers, uint64_t n, uint64_t base )
+{
+    const uint64_t i = (uint64_t)blockIdx.x * DISTINCT_THREADS + threadIdx.x;
+    if ( i < n ) numbers[i] += base;
+}
+}  // namespace
+
+bool
+mi355x::selectLines( int device, const LinePredicate& predicate, uint64_t n, uint64_t base, uint64_t limit, uint64_t** selected,
+                     uint64_t* nMatching, std::string* error )
+{
+    *selected = nullptr;
+    *nMatching = 0;
+    if ( n == 0 ) return true;
+    if ( predicate.dFlags == nullptr && predicate.dNumbers == nullptr ) {
+        *error = "select_lines: neither flags nor numbers";
+        return false;
+    }
+    if ( device >= 0 ) DISTINCT_TRY( hipSetDevice( device ) );
+    const hipStream_t stream = nullptr;
+    Buffers buffers;
+    buffers.who = "select_lines";
+    uint64_t* dNumbers = nullptr;
+    unsigned long long* dCount = nullptr;
+    void* dTemp = nullptr;
+    size_t selectBytes = 0;
+    const rocprim::counting_iterator<uint64_t> lines( 0 );
+    const LineSelected isSelected{ predicate };
+    DISTINCT_TRY( rocprim::select( nullptr, selectBytes, lines, dNumbers, dCount, (size_t)n, isSelected, stream ) );
+    if ( !buffers.get( &dNumbers, n * 8, "the line numbers", error ) || !buffers.get( &dCount, sizeof( unsigned long long ), "the count", error )
+         || !buffers.get( &dTemp, selectBytes, "the selection", error ) ) {
+        return false;
+    }
+    DISTINCT_TRY( hipMemsetAsync( dCount, 0, sizeof( unsigned long long ), stream ) );
+    DISTINCT_TRY( rocprim::select( dTemp, selectBytes, lines, dNumbers, dCount, (size_t)n, isSelected, stream ) );
+    unsigned long long count = 0;
+    DISTINCT_TRY( hipMemcpyAsync( &count, dCount, sizeof( count ), hipMemcpyDeviceToHost, stream ) );
+    DISTINCT_TRY( hipStreamSynchronize( stream ) );
+    *nMatching = count;
+    const uint64_t kept = std::min<uint64_t>( count, limit );
+    if ( kept == 0 ) return true;
+    if ( base != 0 ) {
+        hipLaunchKernelGGL( k_number_lines, dim3( (uint32_t)( ( kept + DISTINCT_THREADS - 1 ) / DISTINCT_THREADS ) ), dim3( DISTINCT_THREADS ),
+                            0, stream, dNumbers, kept, base );
+        DISTINCT_TRY( hipGetLastError() );
+    }
+    auto* const held = static_cast<uint64_t*>( deviceAllocate( -1, kept * 8, error ) );
+    if ( held == nullptr ) return false;
+    if ( !tried( hipMemcpyAsync( held, dNumbers, kept * 8, hipMemcpyDeviceToDevice, stream ), "hipMemcpyAsync", error )
+         || !tried( hipStreamSynchronize( stream ), "hipStreamSynchronize", error ) ) {
+        deviceRelease( held );
+        return false;
+    }
+    *selected = held;
     return true;
 }

@@ -1,7 +1,7 @@
 /**
  * bz2_queries.hip.h -- the host side of the calls that read a finished batch's output: gather, count / find / rank of a
- * byte, search for a string or a set of strings, regular expressions, line hashes, field spans, field columns and field
- * hashes, their mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's
+ * byte, search for a string or a set of strings, regular expressions, line hashes, field spans, field columns, field
+ * hashes, field numbers and field matches, their mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's
  * translation unit (the context's layout names device record types), included below the context's definition and HIP_TRY.
  *
  * Every launcher but gatherPieces (millions of one-tile pieces, a plain loop) has the same shape: refuseQuery, the tiles
@@ -1036,6 +1036,44 @@ fieldNumbers( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* s
     return MI355X_BZ2_OK;
 }
 
+static_assert( FIELDMATCH_VALUES == FIELDMATCH_MAX_VALUES && FIELDMATCH_VALUE_BYTES == FIELDMATCH_MAX_VALUE_BYTES
+               && FIELDMATCH_BYTES == FIELDMATCH_MAX_BYTES && FIELDMATCH_IMAGE_WORDS * 4 == FIELDMATCH_IMAGE_MAX
+               && FIELDMATCH_MAX_VALUES == SET_MAX_PATTERNS && FIELDMATCH_MAX_BYTES == SET_MAX_BYTES
+               && ( 1u << FIELDMATCH_STEPS ) == FIELDMATCH_VALUES, "the kernel's constants are the host's, the caps the search set's" );
+
+/**
+ * mi355x_bz2_match_fields and the reader's launches.  The n lines' keys, starts and sizes are in device memory already --
+ * the field-hash passes wrote them --, so only the table's image goes up; k_field_match writes dFlags[0, n), one word per
+ * line.  A start counts from `base`, modulo 2^64: start - base is the field's offset in the output, and the kernel reads no
+ * span that does not lie inside it.
+ */
+int
+matchFields( mi355x_bz2_ctx* c, const char* what, const ValueTable& table, const uint64_t* dKeys, const uint64_t* dStarts,
+             const int64_t* dSizes, uint64_t n, uint64_t base, uint64_t* dFlags )
+{
+    const std::scoped_lock lock( c->mutex );
+    std::string why;
+    if ( table.count() == 0 || table.count() > FIELDMATCH_MAX_VALUES || table.image.size() > FIELDMATCH_IMAGE_MAX
+         || table.image.size() % 4 != 0 || table.image.size() < (uint64_t)table.count() * 12 + 4 ) {
+        why = "the value table is not one of buildValueTable's";
+    }
+    if ( const int status = refuseQuery( c, what, nullptr, 0, why ) ) return status;
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    const FieldMatchLayout l = layFieldMatch( table.image.size() );
+    if ( const int status = growLineStaging( c, l.bytes, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    std::memcpy( h + l.imageAt, table.image.data(), table.image.size() );
+    HIP_TRY( c, hipMemcpyAsync( d + l.imageAt, h + l.imageAt, table.image.size(), hipMemcpyHostToDevice, c->stream ) );
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( n + FIELDMATCH_THREADS - 1 ) / FIELDMATCH_THREADS, FIELDMATCH_BLOCKS );
+    hipLaunchKernelGGL( k_field_match, dim3( blocks ), dim3( FIELDMATCH_THREADS ), 0, c->stream, at<const uint32_t>( d, l.imageAt ),
+                        (uint32_t)( table.image.size() / 4 ), table.count(), dKeys, dStarts, dSizes, n, c->dOut, c->outSize, base, dFlags );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -1191,6 +1229,17 @@ mi355x::fieldNumbersOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& exten
 }
 
 int
+mi355x::matchFieldsOutput( mi355x_bz2_ctx* c, const bz2gpu::ValueTable& table, const uint64_t* dKeys, const uint64_t* dStarts,
+                           const int64_t* dSizes, uint64_t n, uint64_t srcOffset, uint64_t fileOffset, uint64_t* dFlags )
+{
+    if ( c == nullptr || ( n > 0 && ( dKeys == nullptr || dStarts == nullptr || dSizes == nullptr || dFlags == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    /* modulo 2^64, as gatherFieldsOutput has it */
+    return matchFields( c, "field_matches", table, dKeys, dStarts, dSizes, n, fileOffset - srcOffset, dFlags );
+}
+
+int
 mi355x::gatherFieldsOutput( mi355x_bz2_ctx* c, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n, uint64_t srcOffset,
                             uint64_t fileOffset, uint64_t* dOffsets, const std::function<uint8_t*( uint64_t )>& allocate,
                             uint64_t* total, uint64_t* firstSize )
@@ -1337,6 +1386,33 @@ mi355x_bz2_gather_fields( mi355x_bz2_ctx* c, const uint64_t* startsDevice, const
         *dst = bytes <= dstCapacity ? static_cast<uint8_t*>( dstDevice ) : nullptr;
         return true;
     }, total );
+}
+
+int
+mi355x_bz2_match_fields( mi355x_bz2_ctx* c, const uint8_t* values, const uint32_t* valueSizes, uint32_t nValues, uint64_t seed,
+                         const uint64_t* keysDevice, const uint64_t* startsDevice, const int64_t* sizesDevice, uint64_t n, uint64_t base,
+                         uint64_t* flagsDevice )
+{
+    if ( c == nullptr || ( nValues > 0 && valueSizes == nullptr )
+         || ( n > 0 && ( keysDevice == nullptr || startsDevice == nullptr || sizesDevice == nullptr || flagsDevice == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    ValueTable table;
+    try {
+        const auto why = valueSetError( valueSizes, nValues );
+        if ( why.empty() && values == nullptr && std::any_of( valueSizes, valueSizes + nValues, [] ( uint32_t size ) { return size > 0; } ) ) {
+            return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+        }
+        table = valueTableOf( values, valueSizes, nValues, seed );
+    } catch ( const std::invalid_argument& refused ) {
+        const std::scoped_lock lock( c->mutex );
+        return refuse( c, "match_fields", refused.what() );
+    } catch ( const std::exception& failed ) {
+        const std::scoped_lock lock( c->mutex );
+        c->lastError = std::string( "match_fields: " ) + failed.what();
+        return MI355X_BZ2_ERR_DEVICE;
+    }
+    return matchFields( c, "match_fields", table, keysDevice, startsDevice, sizesDevice, n, base, flagsDevice );
 }
 
 int

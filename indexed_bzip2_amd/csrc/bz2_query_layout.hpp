@@ -176,6 +176,19 @@ layFieldNumbers( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t fiel
              r.add( nTiles * s.fieldTile, 16 ), r.add( slots * 8, 16 ), r.add( slots * 4 ), r.add( slots * 4 ), r.size() };
 }
 
+/* match_fields over lines whose columns are in device memory already, against a value table whose image has `imageBytes`
+ * bytes, a multiple of 4 (bz2_fieldmatch.hpp): [image] up, nothing down; nothing for the kernel alone */
+struct FieldMatchLayout
+{
+    uint64_t imageAt, bytes;
+};
+inline FieldMatchLayout
+layFieldMatch( uint64_t imageBytes )
+{
+    Regions r;
+    return { r.add( imageBytes, 16 ), r.size() };
+}
+
 /* field_hashes for field `field`: field_spans' and hash_lines' lists side by side, since both first passes run as they
  * are: [tiles][field spans][hash spans] up, [field summaries][hash summaries][tail hashes, 16 bytes per span]
  * [head positions][head hashes, field + 1 per span each] down; [field tile summaries][hash tile summaries][chunk places]

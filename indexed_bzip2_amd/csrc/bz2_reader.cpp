@@ -1441,6 +1441,50 @@ struct FieldSumQuery
     static const Value& tail( const Stitched& stitched ) { return stitched.tail; }
 };
 
+/* field_matches: field_hashes' three columns and a flag per line, from ONE decode: behind the field-hash pass, while the
+ * stretch is resident, k_field_match compares the fields whose key and size hit the value table with the values' bytes
+ * (matchFieldsOutput).  The stitcher is field_hashes': a line that crosses a seam and the tail get the flag 0 here, and
+ * StreamReader::fieldMatches decides them from their bytes. */
+struct FieldMatchQuery
+{
+    static constexpr size_t COLUMNS = 4;        /* keys, starts, sizes (int64), flags */
+    using Stretch = bz2gpu::FieldHashStretch;
+    uint8_t nl, dl;
+    uint32_t field;
+    uint64_t x;
+    const bz2gpu::ValueTable* table;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.fields.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldHashesOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, x, place.skip, place.take,
+                                             to[0], to[1], reinterpret_cast<int64_t*>( to[2] ), &stretch.summary ) );
+        const uint64_t closed = stretch.summary.fields.count;
+        const uint64_t written = closed > place.skip ? std::min( closed - place.skip, place.take ) : 0;
+        checkDevice( ctx, matchFieldsOutput( ctx, *table, to[0], to[1], reinterpret_cast<const int64_t*>( to[2] ), written, piece.src,
+                                             piece.fileOffset, to[3] ) );
+        return closed;
+    }
+
+    template<typename Patch>
+    auto
+    stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const
+    {
+        return bz2gpu::stitchFieldHashes( stretches, x, dl, field, patch );
+    }
+
+    static std::array<uint64_t, COLUMNS>
+    words( const bz2gpu::FieldKey& key )
+    {
+        return { key.key, key.field.start, (uint64_t)key.field.size, 0 };
+    }
+
+    static const bz2gpu::FieldKey& tail( const bz2gpu::StitchedFieldHashes& stitched ) { return stitched.tail; }
+};
+
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
 {
@@ -1471,6 +1515,7 @@ public:
         m_fieldColumns.reset();
         dropHeldFieldHashes();
         dropHeldFieldNumbers();
+        m_fieldMatches.reset();
         m_matches.reset();
         m_setMatches.reset();
         m_scheduler.reset();
@@ -2415,6 +2460,137 @@ public:
         }
     }
 
+    /** mi355x_bz2_reader_field_matches: the lines of [first, first + count) whose field is one of the table's values, or
+     * with `invert` the others.  lineColumns with FieldMatchQuery: every block is decoded once, the field-hash pass and
+     * k_field_match run over each resident stretch.  The lines that cross a launch seam and the unterminated tail come
+     * from the stitcher as ( key, start, size ) without bytes: for those whose key and size hit the table the field's bytes
+     * are fetched by ONE readRanges call -- a second decode of their blocks, at most launches + 1 of them -- and compared
+     * on the host.  Then bz2_distinct.hip's selectLines over the flags; the first `limit` numbers are held. */
+    void
+    fieldMatches( uint8_t nl, uint8_t dl, uint32_t field, const bz2gpu::ValueTable& table, uint64_t seed, bool invert, uint64_t first,
+                  uint64_t count, uint64_t limit, bool keepOnDevice, uint64_t* nSelected, uint64_t* nMatching,
+                  const char* what = "field_matches" )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        m_fieldMatches.reset();
+        uint64_t n = 0;
+        std::vector<std::pair<uint64_t, std::array<uint64_t, FieldMatchQuery::COLUMNS> > > patched;
+        const auto held = lineColumns( FieldMatchQuery{ nl, dl, field, bz2gpu::lineHashBase( seed ), &table }, what, index, first, count,
+                                       false, &n, &patched );
+        /* the seam lines and the tail: an empty field that hits is decided, the others need their bytes */
+        std::vector<uint64_t> hits, at, offsets, sizes;
+        std::vector<uint32_t> values;
+        uint64_t bytes = 0;
+        for ( const auto& [line, words] : patched ) {
+            const uint32_t value = table.candidateValue( words[0], (int64_t)words[2] );
+            if ( value == table.count() ) continue;
+            if ( words[2] == 0 ) {
+                hits.push_back( line );
+                continue;
+            }
+            at.push_back( line );
+            values.push_back( value );
+            offsets.push_back( words[1] );
+            sizes.push_back( words[2] );
+            bytes += words[2];
+        }
+        if ( !at.empty() ) {
+            std::vector<uint8_t> fetched( (size_t)bytes );
+            std::vector<uint64_t> nRead( at.size() );
+            readRanges( offsets.data(), sizes.data(), at.size(), fetched.data(), false, nRead.data() );
+            if ( nRead != sizes ) fail( MI355X_BZ2_ERR_LOGIC, std::string( what ) + ": a patched field lies behind the end of the file" );
+            uint64_t from = 0;
+            for ( size_t i = 0; i < at.size(); ++i ) {
+                if ( std::memcmp( table.values[values[i]].data(), fetched.data() + from, (size_t)sizes[i] ) == 0 ) hits.push_back( at[i] );
+                from += sizes[i];
+            }
+        }
+        std::string why;
+        const uint64_t one = 1;
+        for ( const auto line : hits ) {
+            if ( !hostToDevice( m_device, held.column<uint64_t>( 3 ) + line, &one, sizeof( one ), &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
+            }
+        }
+        LinePredicate predicate;
+        predicate.dFlags = held.column<const uint64_t>( 3 );
+        predicate.invert = invert;
+        holdSelectedLines( what, predicate, n, first, limit, keepOnDevice, nSelected, nMatching );
+    }
+
+    /** mi355x_bz2_reader_field_in_range: the lines whose field is a number n with lo <= n <= hi, or with `invert` the
+     * others.  FieldNumberQuery as field_numbers runs it, then selectLines over its number column: a range needs no
+     * bytes. */
+    void
+    fieldInRange( uint8_t nl, uint8_t dl, uint32_t field, const bz2gpu::NumberRange& range, bool invert, uint64_t first, uint64_t count,
+                  uint64_t limit, bool keepOnDevice, uint64_t* nSelected, uint64_t* nMatching, const char* what = "field_in_range" )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        m_fieldMatches.reset();
+        uint64_t n = 0;
+        const auto held = lineColumns( FieldNumberQuery{ nl, dl, field }, what, index, first, count, false, &n );
+        LinePredicate predicate;
+        predicate.dNumbers = held.column<const int64_t>( 0 );
+        predicate.lo = range.lo;
+        predicate.hi = range.hi;
+        predicate.invert = invert;
+        holdSelectedLines( what, predicate, n, first, limit, keepOnDevice, nSelected, nMatching );
+    }
+
+    /** mi355x_bz2_reader_take_field_matches: the first min( capacity, held ) line numbers; they stay held. */
+    void
+    takeFieldMatches( void* numbers, uint64_t capacity, bool dstIsDevice )
+    {
+        if ( closed() ) fail( MI355X_BZ2_ERR_CLOSED, "take_field_matches on a closed reader" );
+        if ( !m_fieldMatches ) {
+            fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "take_field_matches: no line numbers are held (field_matches or field_in_range first)" );
+        }
+        std::string why;
+        if ( !deviceToHost( m_fieldMatches->device, numbers, m_fieldMatches->numbers.get(), std::min( capacity, m_fieldMatches->n ) * 8,
+                            dstIsDevice, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, "take_field_matches: " + why );
+        }
+    }
+
+    /** mi355x_bz2_reader_select_lines: the selection (select( limit, &nSelected, &nMatching ) is fieldMatches or
+     * fieldInRange with everything else bound), then -- unless only the number of lines is wanted -- readLineRanges with
+     * one range ( line, 1 ) per selected line, exactly as grepPositions hands them over: the result is held as grep's. */
+    template<typename Select>
+    void
+    selectLines( const Select& select, uint8_t nl, uint64_t maxLines, bool keepOnDevice, uint64_t* nLines, uint64_t* totalBytes )
+    {
+        uint64_t nSelected = 0, nMatching = 0;
+        select( maxLines, &nSelected, &nMatching );
+        *totalBytes = 0;
+        *nLines = maxLines == 0 ? nMatching : nSelected;
+        if ( maxLines == 0 ) {
+            m_fieldMatches.reset();
+            return;
+        }
+        std::vector<uint64_t> numbers( (size_t)nSelected );
+        takeFieldMatches( numbers.data(), nSelected, false );
+        m_fieldMatches.reset();
+        if ( numbers.empty() ) {
+            HeldLines held;
+            held.onDevice = keepOnDevice;
+            m_held = std::move( held );
+            m_grep = HeldGrep{};
+            return;
+        }
+        HeldGrep held;
+        held.sizes.assign( numbers.size(), 0 );
+        const std::vector<uint64_t> ones( numbers.size(), 1 );
+        readLineRanges( nl, numbers.data(), ones.data(), numbers.size(), keepOnDevice, held.sizes.data(), totalBytes );
+        held.numbers = std::move( numbers );
+        m_grep = std::move( held );
+    }
+
     [[nodiscard]] bool indexComplete() const { return m_index.sealed(); }
 
     [[nodiscard]] OffsetMap
@@ -2494,8 +2670,8 @@ private:
     };
 
     /** The result of a per-line column query, in device memory of the reader's own: up to four columns of n 8-byte words
-     * -- hashes; starts and sizes; keys, starts and sizes; numbers, starts and sizes; keys, starts, sizes and values.  An
-     * empty result has no memory. */
+     * -- hashes; starts and sizes; keys, starts and sizes; numbers, starts and sizes; keys, starts, sizes and values; keys,
+     * starts, sizes and flags.  An empty result has no memory. */
     struct HeldColumns
     {
         struct Release { void operator()( void* pointer ) const { deviceRelease( pointer ); } };
@@ -2528,6 +2704,34 @@ private:
         int device{ -1 };
         bool onDevice{ false };
     };
+
+    /** The line numbers field_matches and field_in_range select, in device memory of the reader's own. */
+    struct HeldFieldMatches
+    {
+        std::unique_ptr<void, HeldColumns::Release> numbers;
+        uint64_t n{ 0 };
+        int device{ -1 };
+        bool onDevice{ false };
+    };
+
+    /** selectLines over the n lines of a finished column, numbered from `first`: the first `limit` numbers are held. */
+    void
+    holdSelectedLines( const char* what, const LinePredicate& predicate, uint64_t n, uint64_t first, uint64_t limit, bool keepOnDevice,
+                       uint64_t* nSelected, uint64_t* nMatching )
+    {
+        std::string why;
+        uint64_t* selected = nullptr;
+        if ( !mi355x::selectLines( m_device, predicate, n, first, limit, &selected, nMatching, &why ) ) {
+            fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
+        }
+        HeldFieldMatches held;
+        held.numbers.reset( selected );
+        held.n = std::min( *nMatching, limit );
+        held.device = m_device;
+        held.onDevice = keepOnDevice;
+        *nSelected = held.n;
+        m_fieldMatches = std::move( held );
+    }
 
     void
     dropHeldFieldHashes()
@@ -2686,17 +2890,18 @@ private:
         } );
     }
 
-    /** What line_hashes, field_spans, field_hashes, field_numbers and field_sums do, given the `query` (the structs in front
-     * of the reader):
+    /** What line_hashes, field_spans, field_hashes, field_numbers, field_sums and field_matches do, given the `query` (the
+     * structs in front of the reader):
      * the launches of planLineHashes for lines [first, first + count), each doing its stretches on the context that
      * decoded them, straight into device columns that are allocated before anything is launched and in which every
      * stretch knows its place (placeLineColumn); then the query's stitcher over the stretches' summaries, and one 8-byte
-     * copy per column for every line that crosses a seam and for the unterminated tail.  *nLines = the lines of the
-     * result, which the caller holds.  A range without lines gives a result without memory.  `what` starts the messages. */
+     * copy per column for every line that crosses a seam and for the unterminated tail (*patched, if wanted, receives
+     * those lines and their words).  *nLines = the lines of the result, which the caller holds.  A range without lines gives a result without memory.  `what` starts the messages. */
     template<typename Query>
     [[nodiscard]] HeldColumns
     lineColumns( const Query& query, const std::string& what, const LineIndex& index, uint64_t first, uint64_t count,
-                 bool keepOnDevice, uint64_t* nLines )
+                 bool keepOnDevice, uint64_t* nLines,
+                 std::vector<std::pair<uint64_t, std::array<uint64_t, Query::COLUMNS> > >* patched = nullptr )
     {
         const auto plan = planLaunches( [&] ( bool packed ) {
             return bz2gpu::planLineHashes( m_index.snapshot(), index.bytes.data(), index.lines.data(), index.bytes.size(), first,
@@ -2741,6 +2946,7 @@ private:
         }
         held.n = n;
         *nLines = n;
+        if ( patched != nullptr ) *patched = std::move( patches );
         return held;
     }
 
@@ -2938,6 +3144,7 @@ private:
     std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
     std::optional<HeldColumns> m_fieldNumbers;                /* between field_numbers and the next call of its family */
     std::optional<std::vector<FieldSumGroup> > m_fieldSums;   /* between field_sums and the next call of its family */
+    std::optional<HeldFieldMatches> m_fieldMatches;           /* between field_matches / field_in_range and the next of the two */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
@@ -3008,6 +3215,23 @@ copyOffsets( const std::map<size_t, size_t>& offsets, uint64_t* bits, uint64_t* 
         ++i;
     }
     return MI355X_BZ2_OK;
+}
+
+/** The values of a C ABI call as a table, checked before anything touches the GPU; throws std::invalid_argument. */
+bz2gpu::ValueTable
+takeValues( const char* what, const uint8_t* values, const uint32_t* valueSizes, uint32_t nValues, uint64_t seed )
+{
+    try {
+        if ( nValues > 0 && valueSizes == nullptr ) throw std::invalid_argument( "no sizes for the values" );
+        const auto why = bz2gpu::valueSetError( valueSizes, nValues );
+        if ( !why.empty() ) throw std::invalid_argument( why );
+        if ( values == nullptr && std::any_of( valueSizes, valueSizes + nValues, [] ( uint32_t size ) { return size > 0; } ) ) {
+            throw std::invalid_argument( "no bytes for the values" );
+        }
+        return bz2gpu::valueTableOf( values, valueSizes, nValues, seed );
+    } catch ( const std::invalid_argument& refused ) {
+        throw std::invalid_argument( std::string( what ) + ": " + refused.what() );
+    }
 }
 }  // namespace
 
@@ -3454,6 +3678,64 @@ mi355x_bz2_reader_take_field_sums( mi355x_bz2_reader* r, uint64_t* lines, uint64
 {
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
         reader.takeFieldSums( lines, counts, starts, sizes, numbers, sumsLo, sumsHi, mins, maxs, capacity );
+    } );
+}
+
+int
+mi355x_bz2_reader_field_matches( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const uint8_t* values,
+                                 const uint32_t* valueSizes, uint32_t nValues, uint64_t seed, int invert, uint64_t first, uint64_t count,
+                                 uint64_t limit, int keepOnDevice, uint64_t* nSelected, uint64_t* nMatching )
+{
+    if ( nSelected == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        const auto table = takeValues( "field_matches", values, valueSizes, nValues, seed );
+        uint64_t matching = 0;
+        reader.fieldMatches( nl, dl, field, table, seed, invert != 0, first, count, limit, keepOnDevice != 0, nSelected, &matching );
+        if ( nMatching != nullptr ) *nMatching = matching;
+    } );
+}
+
+int
+mi355x_bz2_reader_field_in_range( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, int hasLo, int64_t lo, int hasHi,
+                                  int64_t hi, int invert, uint64_t first, uint64_t count, uint64_t limit, int keepOnDevice,
+                                  uint64_t* nSelected, uint64_t* nMatching )
+{
+    if ( nSelected == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        uint64_t matching = 0;
+        reader.fieldInRange( nl, dl, field, bz2gpu::clipNumberRange( hasLo != 0, lo, hasHi != 0, hi ), invert != 0, first, count, limit,
+                             keepOnDevice != 0, nSelected, &matching );
+        if ( nMatching != nullptr ) *nMatching = matching;
+    } );
+}
+
+int
+mi355x_bz2_reader_take_field_matches( mi355x_bz2_reader* r, void* dst, uint64_t capacity, int dstIsDevice )
+{
+    if ( capacity > 0 && dst == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) { reader.takeFieldMatches( dst, capacity, dstIsDevice != 0 ); } );
+}
+
+int
+mi355x_bz2_reader_select_lines( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const uint8_t* values,
+                                const uint32_t* valueSizes, uint32_t nValues, uint64_t seed, int hasLo, int64_t lo, int hasHi, int64_t hi,
+                                int invert, uint64_t first, uint64_t count, uint64_t maxLines, int keepOnDevice, uint64_t* nLines,
+                                uint64_t* totalBytes )
+{
+    if ( nLines == nullptr || totalBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        if ( nValues > 0 && ( hasLo != 0 || hasHi != 0 ) ) throw std::invalid_argument( "select_lines: values or a range, not both" );
+        if ( nValues > 0 ) {
+            const auto table = takeValues( "select_lines", values, valueSizes, nValues, seed );
+            reader.selectLines( [&] ( uint64_t limit, uint64_t* nSelected, uint64_t* nMatching ) {
+                reader.fieldMatches( nl, dl, field, table, seed, invert != 0, first, count, limit, false, nSelected, nMatching, "select_lines" );
+            }, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
+        } else {
+            const auto range = bz2gpu::clipNumberRange( hasLo != 0, lo, hasHi != 0, hi );
+            reader.selectLines( [&] ( uint64_t limit, uint64_t* nSelected, uint64_t* nMatching ) {
+                reader.fieldInRange( nl, dl, field, range, invert != 0, first, count, limit, false, nSelected, nMatching, "select_lines" );
+            }, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
+        }
     } );
 }
 

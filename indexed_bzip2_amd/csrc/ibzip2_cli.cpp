@@ -48,6 +48,10 @@ struct Options
     bool cutField{ false }, hasFieldDelimiter{ false }, countByField{ false };
     std::vector<uint32_t> cutFields;            /* --cut-fields: not empty iff given */
     bool sumByField{ false };
+    bool whereField{ false }, whereEquals{ false }, whereInFile{ false }, whereBetween{ false }, invertMatch{ false };
+    bool hasLow{ false }, hasHigh{ false };
+    int64_t low{ 0 }, high{ 0 };
+    std::string equals, valueFile;
     unsigned field{ 0 }, valueField{ 0 };
     uint8_t fieldDelimiter{ '\t' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
@@ -146,6 +150,23 @@ printHelp()
         "                                Lines without field KEY are in no group. The data is decoded once; keys\n"
         "                                (grouped by a hash, --seed chooses its base) and numbers are found and summed\n"
         "                                on the GPU. --field-delimiter applies; this is not a CSV parser.\n"
+        "      --where-field arg         Given N (a field number as for --cut-field): print the lines whose field N\n"
+        "                                satisfies ONE of --equals, --in-file or --between, whole and in file order, as\n"
+        "                                --grep prints them (awk -F'\\t' '$3 == \"GET\"'). The field must be equal byte for\n"
+        "                                byte; a line without field N is not selected. The data is decoded once and the\n"
+        "                                rows are chosen on the GPU (a hash, whose base --seed chooses, only filters in\n"
+        "                                front of the comparison of the bytes); the selected lines come in a second\n"
+        "                                pass. The exit status is 0 whether or not a line was selected.\n"
+        "                                --field-delimiter and --line-number apply; this is not a CSV parser.\n"
+        "      --equals arg              With --where-field: the one value the field must be equal to; may be empty.\n"
+        "      --in-file arg             With --where-field: the field must be equal to one line of the given file (a\n"
+        "                                semi-join): 1 to 1024 values of at most 256 bytes, 16384 bytes in total, read\n"
+        "                                as --grep-file reads its file.\n"
+        "      --between arg             With --where-field: given LO,HI (either side may be empty: open), the field\n"
+        "                                must be a number n with LO <= n <= HI (awk '$5 >= 500 && $5 <= 599'). A\n"
+        "                                number is [+-]?[0-9]{1,18} from end to end, not awk's strtod.\n"
+        "      --invert-match            With --where-field: print the lines that are NOT selected (grep -v), those\n"
+        "                                without field N included.\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
         "                                line, in the file's order.\n"
         "      --line-number             With --grep or --grep-file: prefix each line with its 1-based line number\n"
@@ -184,6 +205,8 @@ printHelp()
         "  ibzip2-mi355x --count-by-field 2 file.tsv.bz2\n\n"
         "Sum the third column per value of the first:\n"
         "  ibzip2-mi355x --sum-by-field 0,2 file.tsv.bz2\n\n"
+        "Print the rows whose fifth column is a 5xx status, with their line numbers:\n"
+        "  ibzip2-mi355x --where-field 4 --between 500,599 --line-number file.tsv.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -381,6 +404,38 @@ parseArguments( int argc, char** argv, Options& o )
                 o.valueField = (unsigned)number;
                 o.sumByField = true;
             }
+            else if ( name == "where-field" ) {
+                uint64_t field = 0;     /* digits only, as --cut-field */
+                if ( !need( value ) || !parseSeed( value.c_str(), field ) || field > 1023 ) {
+                    std::cerr << "Bad value for --where-field\n";
+                    return 1;
+                }
+                o.field = (unsigned)field;
+                o.whereField = true;
+            }
+            else if ( name == "equals" ) { if ( !need( o.equals ) ) return 1; o.whereEquals = true; }
+            else if ( name == "in-file" ) { if ( !need( o.valueFile ) ) return 1; o.whereInFile = true; }
+            else if ( name == "between" ) {
+                /* LO,HI: each side empty or [+-]?digits, at most 18 of them */
+                const bool given = need( value );
+                const auto comma = value.find( ',' );
+                const auto bound = [] ( const std::string& text, bool& has, int64_t& number ) {
+                    has = !text.empty();
+                    if ( !has ) return true;
+                    const size_t from = text[0] == '-' || text[0] == '+' ? 1 : 0;
+                    uint64_t magnitude = 0;
+                    if ( text.size() - from > 18 || !parseSeed( text.c_str() + from, magnitude ) ) return false;
+                    number = text[0] == '-' ? -(int64_t)magnitude : (int64_t)magnitude;
+                    return true;
+                };
+                if ( !given || comma == std::string::npos || !bound( value.substr( 0, comma ), o.hasLow, o.low )
+                     || !bound( value.substr( comma + 1 ), o.hasHigh, o.high ) ) {
+                    std::cerr << "Bad value for --between\n";
+                    return 1;
+                }
+                o.whereBetween = true;
+            }
+            else if ( name == "invert-match" ) o.invertMatch = true;
             else if ( name == "field-delimiter" ) {
                 if ( !need( value ) || !parseByte( value, o.fieldDelimiter ) || o.fieldDelimiter == '\n' ) {
                     std::cerr << "Bad value for --field-delimiter\n";
@@ -592,7 +647,22 @@ main( int argc, char** argv )
         std::cerr << "Option '--grep-regex' cannot be combined with '--grep', '--count-matches', '--grep-file' or '--count-matches-file'\n";
         return 1;
     }
-    if ( o.lineNumber && !o.grep && !o.grepFile && !o.grepRegex ) {
+    if ( o.whereField && ( o.grep || o.countMatches || o.grepFile || o.countMatchesFile || o.grepRegex || o.countLines || o.lineHashes
+                           || o.countDistinctLines || o.cutField || o.countByField || o.sumByField || !o.cutFields.empty() ) ) {
+        std::cerr << "Option '--where-field' cannot be combined with '--count-lines', '--grep', '--grep-regex', '--count-matches', "
+                     "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines', '--cut-field', '--cut-fields', "
+                     "'--count-by-field' or '--sum-by-field'\n";
+        return 1;
+    }
+    if ( o.whereField && (int)o.whereEquals + (int)o.whereInFile + (int)o.whereBetween != 1 ) {
+        std::cerr << "Option '--where-field' needs exactly one of '--equals', '--in-file' and '--between'\n";
+        return 1;
+    }
+    if ( !o.whereField && ( o.whereEquals || o.whereInFile || o.whereBetween || o.invertMatch ) ) {
+        std::cerr << "Options '--equals', '--in-file', '--between' and '--invert-match' need '--where-field'\n";
+        return 1;
+    }
+    if ( o.lineNumber && !o.grep && !o.grepFile && !o.grepRegex && !o.whereField ) {
         std::cerr << "Option '--line-number' needs '--grep' or '--grep-file'\n";
         return 1;
     }
@@ -630,7 +700,7 @@ main( int argc, char** argv )
                      "'--grep-file', '--count-matches-file', '--line-hashes', '--count-distinct-lines' or '--cut-field'\n";
         return 1;
     }
-    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines && !o.countByField && !o.sumByField ) {
+    if ( o.hasSeed && !o.lineHashes && !o.countDistinctLines && !o.countByField && !o.sumByField && !o.whereField ) {
         std::cerr << "Option '--seed' needs '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
@@ -640,7 +710,7 @@ main( int argc, char** argv )
                      "'--grep-file', '--count-matches-file', '--line-hashes' or '--count-distinct-lines'\n";
         return 1;
     }
-    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField && !o.sumByField && o.cutFields.empty() ) {
+    if ( o.hasFieldDelimiter && !o.cutField && !o.countByField && !o.sumByField && o.cutFields.empty() && !o.whereField ) {
         std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
         return 1;
     }
@@ -922,6 +992,71 @@ main( int argc, char** argv )
         }
         mi355x_bz2_reader_close( reader );
         return 0;
+    }
+
+    /* likewise an action of its own: the lines that a predicate on one field selects, from the reader's select_lines, printed
+     * as --grep prints its lines */
+    if ( o.whereField ) {
+        std::string values = o.equals;
+        std::vector<uint32_t> valueSizes;
+        if ( o.whereEquals ) {
+            if ( values.size() > 256 ) {
+                std::cerr << "Bad value for --equals: more than 256 bytes\n";
+                return 1;
+            }
+            valueSizes.push_back( (uint32_t)values.size() );
+        } else if ( o.whereInFile ) {
+            values.clear();
+            if ( !readPatternFile( o.valueFile, values, valueSizes ) ) return 1;
+            if ( valueSizes.empty() ) {
+                std::cerr << "The value file '" << o.valueFile << "' holds no value\n";
+                return 1;
+            }
+        }
+        Input in;
+        if ( !in.open( o.input ) ) {
+            std::cerr << "Could not open '" << o.input << "'\n";
+            return 1;
+        }
+        if ( mi355x_bz2_read_stream_header( in.data, in.size, 0 ) == 0 ) {
+            std::cerr << "Decoding failed: " << mi355x_bz2_status_string( MI355X_BZ2_ERR_STREAM_HEADER ) << "\n";
+            return 1;
+        }
+        mi355x_bz2_reader* reader = nullptr;
+        int rc = mi355x_bz2_reader_open_memory( in.data, in.size, o.decoderParallelism, o.device, &reader );
+        if ( rc != MI355X_BZ2_OK ) {
+            std::cerr << "Could not open the bzip2 stream: " << mi355x_bz2_status_string( rc ) << "\n";
+            return 1;
+        }
+        uint64_t nLines = 0, total = 0;
+        rc = mi355x_bz2_reader_select_lines( reader, '\n', o.fieldDelimiter, o.field, reinterpret_cast<const uint8_t*>( values.data() ),
+                                             valueSizes.data(), (uint32_t)std::min<size_t>( valueSizes.size(), 0xFFFFFFFFu ), o.seed,
+                                             o.hasLow ? 1 : 0, o.low, o.hasHigh ? 1 : 0, o.high, o.invertMatch ? 1 : 0, 0, ~uint64_t( 0 ),
+                                             ~uint64_t( 0 ), 0, &nLines, &total );
+        std::vector<uint64_t> numbers( nLines ), sizes( nLines );
+        std::vector<char> bytes( total );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );
+        if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_line_ranges( reader, bytes.data(), 0 );
+        if ( rc != MI355X_BZ2_OK ) {
+            const char* detail = mi355x_bz2_reader_last_error( reader );
+            std::cerr << "Selecting failed: " << mi355x_bz2_status_string( rc );
+            if ( detail != nullptr && detail[0] != '\0' ) std::cerr << " (" << detail << ")";
+            std::cerr << "\n";
+            mi355x_bz2_reader_close( reader );
+            return 1;
+        }
+        mi355x_bz2_reader_close( reader );
+        if ( !o.lineNumber ) {
+            std::cout.write( bytes.data(), (std::streamsize)bytes.size() );
+        } else {
+            uint64_t at = 0;
+            for ( uint64_t i = 0; i < nLines; at += sizes[i], ++i ) {
+                std::cout << numbers[i] + 1 << ':';
+                std::cout.write( bytes.data() + at, (std::streamsize)sizes[i] );
+            }
+        }
+        std::cout.flush();
+        return std::cout.good() ? 0 : 1;
     }
 
     /* likewise an action of its own: the sum of one field per distinct value of another, from the reader's field_sums; the

@@ -905,6 +905,128 @@ class _IndexedBzip2FileParallel:
         the two sentinels (both below -2^63 + 2) before arithmetic."""
         return self._field_ints(field, first, count, delimiter, newline, True)
 
+    # -- rows by a column: the lines whose field `field` is one of a set of values, or whose number lies in a range (`awk
+    # -F'\t' '$3 == "GET"'`, `awk '$5 >= 500 && $5 < 600'`, a semi-join on a key column).  A line matches `values` iff it has
+    # the field and content.split(delimiter)[field] is byte for byte one of them: the empty value matches an empty field
+    # that is present, never a missing one.  It matches between=(lo, hi) iff N.parse_field_number(field) is a number n with
+    # lo <= n <= hi; None is an open side; a field that is no number and a missing one never match.  invert=True selects
+    # the complement within the line range (`grep -v`).  The key under `seed` only filters in front of the comparison of
+    # the bytes: the answer does not depend on it.  No quoting, no escaping: not a CSV parser
+    def _where_arguments(self, field, values, between, invert, first, count, limit, delimiter, newline, seed):
+        if (values is None) == (between is None):
+            raise ValueError("exactly one of values and between must be given")
+        nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
+        predicate = N.value_set(values) if values is not None else N.number_range(between)
+        return nl, dl, field, first, count, seed, predicate, 1 if invert else 0, self._line_limit(limit)
+
+    def _where_field(self, arguments, limit, keep):
+        """mi355x_bz2_reader_field_matches or _field_in_range -> (the numbers held, the lines that match)."""
+        nl, dl, field, first, count, seed, predicate, invert, _ = arguments
+        held, matching = ctypes.c_uint64(), ctypes.c_uint64()
+        if len(predicate) == 3:
+            data, sizes, k = predicate
+            self._check(N.lib().mi355x_bz2_reader_field_matches(self._h, nl, dl, field, data, sizes, k, seed, invert, first, count, limit,
+                                                                 keep, ctypes.byref(held), ctypes.byref(matching)))
+        else:
+            self._check(N.lib().mi355x_bz2_reader_field_in_range(self._h, nl, dl, field, *predicate, invert, first, count, limit, keep,
+                                                                  ctypes.byref(held), ctypes.byref(matching)))
+        return held.value, matching.value
+
+    def where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
+                    newline=b"\n", seed=0):
+        """The numbers of the lines of [first, first + count) whose field `field` is one of `values` (1 to 1 024 bytes
+        objects of 0 to 256 bytes, at most 16 384 bytes in total) or whose number lies in between=(lo, hi) -> numpy uint64,
+        ascending, numbered in the file, at most `limit` of them (None: all).  Exactly one of values and between.  The
+        numbers index the arrays of read_columns, field_ints and field_hashes over the same line range (less `first`).
+        Every needed block is decoded once; the predicate is evaluated and its flags are compacted on the GPU, and 8 bytes
+        per selected line come back.  Two different values with the same key under `seed` are refused: pass another seed.
+        Not a CSV parser.  Positionless."""
+        import numpy as np
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        n, _ = self._where_field(arguments, arguments[-1], 0)
+        out = np.empty(n, dtype=np.uint64)
+        if n:
+            self._check(N.lib().mi355x_bz2_reader_take_field_matches(self._h, out.ctypes.data, n, 0))
+        return out
+
+    def where_field_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                              delimiter=b"\t", newline=b"\n", seed=0):
+        """where_field as a torch.int64 tensor on the reader's device; the numbers never pass through the host.  Less
+        `first`, it indexes the tensors of read_columns_to_tensor, field_ints_to_tensor and field_hashes_to_tensor."""
+        import torch
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        dev = self._device_index()
+        n, _ = self._where_field(arguments, arguments[-1], 1)
+        out = torch.empty(n, dtype=torch.int64, device=f"cuda:{dev}")
+        if n:
+            torch.cuda.current_stream(out.device).synchronize()
+            self._check(N.lib().mi355x_bz2_reader_take_field_matches(self._h, ctypes.c_void_p(out.data_ptr()), n, 1))
+        return out
+
+    def count_where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                          delimiter=b"\t", newline=b"\n", seed=0):
+        """len(where_field(...)) without the numbers: nothing per line leaves the GPU, 8 bytes come back."""
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        _, matching = self._where_field(arguments, 0, 0)
+        return min(matching, arguments[-1])
+
+    def _select_lines(self, arguments, on_device):
+        """mi355x_bz2_reader_select_lines and the numbers and sizes of the held lines (_take_grep), as _grep."""
+        import numpy as np
+        nl, dl, field, first, count, seed, predicate, invert, limit = arguments
+        if limit == 0:
+            return np.empty(0, dtype=np.uint64), [], 0
+        if len(predicate) == 3:
+            data, sizes, k = predicate
+            bounds = (0, 0, 0, 0)
+        else:
+            data, sizes, k, bounds = None, None, 0, predicate
+        n, total = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(N.lib().mi355x_bz2_reader_select_lines(self._h, nl, dl, field, data, sizes, k, seed, *bounds, invert, first, count,
+                                                            limit, 1 if on_device else 0, ctypes.byref(n), ctypes.byref(total)))
+        numbers = (ctypes.c_uint64 * max(1, n.value))()
+        sizes = (ctypes.c_uint64 * max(1, n.value))()
+        self._check(N.lib().mi355x_bz2_reader_take_grep(self._h, numbers, sizes, n.value))
+        return (np.frombuffer(numbers, dtype=np.uint64, count=n.value).copy(), [sizes[i] for i in range(n.value)], total.value)
+
+    def select_lines(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
+                     newline=b"\n", seed=0):
+        """The lines where_field selects -> (numbers, lines) as grep returns them: the line numbers (numpy uint64,
+        ascending) and one bytes object per line, whole and with its delimiter, at most `limit` lines (None: all).  The
+        selection, then the lines themselves in a second pass over the blocks that hold them.  Releases line ranges held
+        by earlier calls.  Positionless."""
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        numbers, sizes, total = self._select_lines(arguments, False)
+        if arguments[-1] == 0:
+            return numbers, []
+        out = bytearray(total)
+        dst = (ctypes.c_char * max(1, total)).from_buffer(out) if total > 0 else None
+        self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, dst, 0))
+        del dst
+        lines, at = [], 0
+        for size in sizes:
+            lines.append(bytes(out[at:at + size]))
+            at += size
+        return numbers, lines
+
+    def select_lines_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                               delimiter=b"\t", newline=b"\n", seed=0):
+        """select_lines into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets) as
+        grep_to_tensor returns them: line i is ``data[offsets[i]:offsets[i + 1]]``."""
+        import torch
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        dev = self._device_index()
+        numbers, sizes, total = self._select_lines(arguments, True)
+        data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
+        if total:
+            torch.cuda.current_stream(data.device).synchronize()
+        if arguments[-1] != 0:
+            self._check(N.lib().mi355x_bz2_reader_take_line_ranges(self._h, ctypes.c_void_p(data.data_ptr()) if total else None, 1))
+        bounds = [0]
+        for size in sizes:
+            bounds.append(bounds[-1] + size)
+        return numbers, data, torch.tensor(bounds, dtype=torch.int64)
+
     def _field_sums(self, key_field, value_field, first, count, delimiter, newline, seed):
         """mi355x_bz2_reader_field_sums and its take -> (lines, counts, starts, sizes, numbers, sums, mins, maxs, missing)."""
         import numpy as np
@@ -1209,6 +1331,31 @@ class IndexedBzip2File(io.BufferedReader):
     def field_ints_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
         """See _IndexedBzip2FileParallel.field_ints_to_tensor."""
         return self._open_reader().field_ints_to_tensor(field, first, count, delimiter, newline)
+
+    def where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
+                    newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.where_field."""
+        return self._open_reader().where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+
+    def where_field_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                              delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.where_field_to_tensor."""
+        return self._open_reader().where_field_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+
+    def count_where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                          delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.count_where_field."""
+        return self._open_reader().count_where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+
+    def select_lines(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
+                     newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.select_lines."""
+        return self._open_reader().select_lines(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+
+    def select_lines_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
+                               delimiter=b"\t", newline=b"\n", seed=0):
+        """See _IndexedBzip2FileParallel.select_lines_to_tensor."""
+        return self._open_reader().select_lines_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed)
 
     def sum_by_field(self, key_field, value_field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """See _IndexedBzip2FileParallel.sum_by_field."""
