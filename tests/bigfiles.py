@@ -307,6 +307,16 @@ class VirtualRaw:
         delimiters = self.byte_offsets(delimiter[0])
         return [self._field_of(a, b, j, delimiters) for a, b in self.line_bounds(newline)]
 
+    def field_values(self, j, delimiter=b"\t", newline=b"\n", first=0, count=None):
+        """Field j of lines [first, first + count) as bytes, None where it is missing: what read_fields and read_columns
+        return, from field_spans (computed once per field) and slice.  For windows whose fields are short."""
+        cache = self.__dict__.setdefault("_field_spans", {})
+        key = (j, delimiter[0], newline[0])
+        if key not in cache:
+            cache[key] = self.field_spans(j, delimiter, newline)
+        spans = cache[key][first:None if count is None else first + count]
+        return [None if size < 0 else self.slice(start, start + size) for start, size in spans]
+
     def field_keys(self, j, delimiter=b"\t", newline=b"\n", seed=0):
         """The key of field j of every line: its hash, or fieldhash.MISSING."""
         x = linehash.base(seed)

@@ -233,6 +233,10 @@ def test_virtual_raw_fields_on_shrunken_layouts():
             for j in (0, 1, 3, 8, 9, 1023):
                 spans = F.direct(data, nl, dl, j)
                 assert raw.field_spans(j, delimiter, newline) == spans, (layout, delimiter, newline, j)
+                if max(size for _, size in spans) < raw.MATERIALISE_MAX:
+                    values = F.fields_of(data, nl, dl, j)
+                    assert raw.field_values(j, delimiter, newline) == values
+                    assert raw.field_values(j, delimiter, newline, 7, 30) == values[7:37] and raw.field_values(j, delimiter, newline, len(values), 3) == []
                 if (j, delimiter) not in ((0, b" "), (3, b" "), (1, b"\n"), (0, b"\t")):
                     continue
                 for seed in (0, 1):

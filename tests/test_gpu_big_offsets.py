@@ -1031,6 +1031,71 @@ def test_reader_field_groups(far, reader):
     assert len(ranked) == 3 and (b"." + bigfiles.needles()["n256"], 1) in raw.value_counts(4, None, b" ", b"\n", 0, k - 700, 1_400)
 
 
+def test_reader_columns_numbers_and_selections(far, reader):
+    """read_columns, field_ints, where_field / select_lines / count_where_field and sum_by_field around 2^32 and in T2, whose
+    file offsets all lie above it, against VirtualRaw.field_values.  The field across 2^32 under b" " is b"." + n256, 257
+    bytes, one more than a value of where_field may have: it comes back from read_columns and is refused as a value, and
+    the selection takes the piece of it that b"k" delimits, 20 bytes from 2^32 - 1 on.  One whole-file pass
+    (count_where_field); 5.2 - 5.9 s at parallelization 1 and 2.0 s at 4 on an MI355X."""
+    import fieldnum
+    f, mode = reader
+    raw = far.raw
+    n256 = bigfiles.needles()["n256"]
+    k, t2_line = raw.line_of(CUT), raw.line_of(far.t2_at)
+    bounds = raw.line_bounds()
+    for first, count in line_windows(far):
+        want = [raw.field_values(j, b" ", b"\n", first, count) for j in (4, 9, 0)]
+        assert f.read_columns([4, 9, 0], first, count, delimiter=b" ") == want, (first, count)
+        for j in (0, 9):
+            got = f.field_ints(j, first, count, delimiter=b" ")
+            assert got.dtype == np.int64 and got.tolist() == [fieldnum.word(v) for v in raw.field_values(j, b" ", b"\n", first, count)], (j, first, count)
+    assert f.read_columns([4], k, 1, delimiter=b" ") == [[b"." + n256]]                             # across 2^32
+    assert any(start > CUT for start, _ in raw.field_spans(4, b" ")[t2_line + 1:t2_line + 41])
+    with pytest.raises(ValueError):
+        f.where_field(4, values=[b"." + n256], first=k - 700, count=1_400, delimiter=b" ")
+    # the field of line k that holds byte 2^32 under the delimiter b"k"
+    j, (start, size) = next((j, span) for j, span in ((j, raw.field_spans(j, b"k")[k]) for j in range(12)) if span[0] <= CUT < span[0] + span[1])
+    value = raw.slice(start, start + size)
+    assert start < CUT < start + size <= start + 256 and value in n256 and raw.field_values(j, b"k", b"\n", k, 1) == [value]
+    window = raw.field_values(j, b"k", b"\n", k - 700, 1_400)
+    assert [k - 700 + i for i, v in enumerate(window) if v == value] == [k]
+    got = f.where_field(j, values=[value], first=k - 700, count=1_400, delimiter=b"k")
+    assert got.dtype == np.uint64 and got.tolist() == [k]
+    numbers, lines = f.select_lines(j, values=[value, b"never"], first=k - 700, count=1_400, delimiter=b"k")
+    assert numbers.tolist() == [k] and lines == [raw.slice(bounds[k][0], bounds[k][1] + 1)]
+    assert f.where_field(j, values=[value], invert=True, first=k - 2, count=5, delimiter=b"k").tolist() == [k - 2, k - 1, k + 1, k + 2]
+    assert f.count_where_field(j, values=[value], invert=True, first=k - 2, count=5, delimiter=b"k") == 4
+    # five values of T2's lines, counted over the whole file in one pass: from the groups and their spans, so that the field
+    # of 4.3 GB is never sliced
+    values = []
+    for v in raw.field_values(3, b" ", b"\n", t2_line + 1, 400):
+        if v is not None and v not in values and len(values) < 5:
+            values.append(v)
+    lines, counts, missing, spans = raw.field_groups(3, b" ")
+    want = sum(count for count, (start, size) in zip(counts, spans) if 0 <= size <= 256 and raw.slice(start, start + size) in values)
+    assert len(values) == 5 and want > 100
+    assert f.count_where_field(3, values=values, delimiter=b" ") == want
+    # sums per key in T2
+    first, count = t2_line + 1, 5_000
+    lines, counts, missing, _ = raw.field_groups(3, b" ", b"\n", 0, first, count)
+    keys = raw.field_values(3, b" ", b"\n", first, count)
+    words = [fieldnum.word(v) for v in raw.field_values(0, b" ", b"\n", first, count)]
+    groups = {}
+    for key, word in zip(keys, words):
+        if key is not None:
+            g = groups.setdefault(key, {"numbers": 0, "sum": 0, "min": fieldnum.NOT_A_NUMBER, "max": fieldnum.NOT_A_NUMBER})
+            if word not in (fieldnum.NOT_A_NUMBER, fieldnum.MISSING):
+                g["min"] = word if g["numbers"] == 0 else min(g["min"], word)
+                g["max"] = word if g["numbers"] == 0 else max(g["max"], word)
+                g["numbers"] += 1
+                g["sum"] += word
+    got = f.sum_by_field(3, 0, first, count, delimiter=b" ")
+    assert (got[0].tolist(), got[1].tolist(), got[6]) == (lines, counts, missing) and len(lines) == len(groups) > 100
+    ordered = [groups[keys[line - first]] for line in lines]
+    assert got[2].tolist() == [g["numbers"] for g in ordered] and got[3] == [g["sum"] for g in ordered]
+    assert got[4].tolist() == [g["min"] for g in ordered] and got[5].tolist() == [g["max"] for g in ordered]
+
+
 def test_reader_one_line_of_more_than_4_gib(native, far, far_path):
     """Under a delimiter that is in no text the whole file is one unterminated line of more than 2^32 bytes: its hash is
     composed on the host from every launch's (h, x^len), its field 0 has a size above 2^32 and the same key."""
