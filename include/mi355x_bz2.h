@@ -23,6 +23,19 @@
  * No exceptions cross this ABI: every reference throw site on the path has a status code below; the host-side
  * scheduler turns a non-OK status back into the reference's behaviour (prefetch failures are silent, on-demand
  * failures surface from read(); src/core/BlockFetcher.hpp:305, 424-432).
+ *
+ * Threads.  A mi355x_bz2_ctx and a mi355x_bz2_reader are each used by ONE thread at a time: their calls are not
+ * serialised against one another, and a result held between a step-1 call and its take belongs to the calls of that
+ * one thread.  Different contexts and readers on different threads are independent of one another, also on the same
+ * device, also while one of them is created or destroyed under another's batch in flight: what they share -- per
+ * device the chain that orders their walks, the count of live contexts from which every batch takes its lane layout
+ * and its crowd mode, and the once-per-device kernel attributes -- is guarded inside the library; the distinct-lines and
+ * group-by calls sort on the null stream, which the threads of a process share, each call in device memory of its own
+ * that it allocates and frees; and every entry point sets the calling thread's current HIP device itself.  The number
+ * of live contexts changes a batch's launch plan and never its result.  mi355x_bz2_find_magic, the status and name
+ * functions and mi355x_bz2_warmup may be called from any thread.  The MI355X_BZ2_* environment switches are read with
+ * getenv while the library runs (per batch, per reader launch): the environment must not be changed while another
+ * thread is inside the library.  tests/test_gpu_threads.py pins all of this.
  */
 #ifndef MI355X_BZ2_H
 #define MI355X_BZ2_H

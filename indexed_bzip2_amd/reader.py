@@ -9,6 +9,15 @@ BZ2Reader that the reference selects for 1 -- the stream CRC of every end-of-str
 (BZ2Reader.hpp:406-416); 0 = as much as the machine wants (reference: all cores; here: the default batch of 512
 blocks); N > 1 = N blocks per GPU batch, no stream-CRC check (ParallelBZ2Reader never checks it).  There is no CPU
 reader: every value decodes on the GPU.
+
+Threads: a reader (like a Decoder, and a mi355x_bz2_ctx in C) is used by one thread at a time -- its calls are not
+serialised against one another, and the buffered position and a held result belong to that one caller.  Different readers
+on different threads are independent, on the same GPU too: open one per worker thread.  The functions of buffers.py
+(decompress, decompress_many, decompress_many_to_tensor, compress, compress_many) may be called from any thread; they
+take turns on the device's kept context behind a lock.  The MI355X_BZ2_* environment switches are read while the library
+runs, so os.environ must not be changed while another thread is inside it.  The *_to_tensor calls need torch's HIP
+runtime to be the first in the process (import torch and touch the GPU before the first reader), on whichever thread.
+tests/test_gpu_threads.py pins this.
 """
 import ctypes
 import builtins
