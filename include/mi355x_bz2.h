@@ -503,6 +503,24 @@ int mi355x_bz2_match_fields( mi355x_bz2_ctx* ctx, const uint8_t* values, const u
                              uint64_t seed, const uint64_t* keys_device, const uint64_t* starts_device,
                              const int64_t* sizes_device, uint64_t n, uint64_t base, uint64_t* flags_device );
 
+/* Does a field match a regular expression: the predicate of mi355x_bz2_reader_field_matches_regex over columns that are in
+ * device memory already.  The field is to the pattern what a line's content is to _match_lines: a line MATCHES iff it has
+ * the field and the table of `re` (mi355x_bz2_regex_compile: its syntax, its refusals, its IGNORE_CASE flag), run from
+ * state 0 over the field's bytes, reaches state 1 or ends in a state that accepts at the end.  `^` and `$` anchor to the
+ * field's ends (awk '$3 ~ /^GET$/'); an empty field that is present matches iff state 0 accepts at the end; a missing
+ * field never matches; a field may have any size.  For a field without the byte 0x0A this is Python's re.search( pattern,
+ * field, re.DOTALL ); Python's `$` also matches in front of a trailing 0x0A, the table's does not.
+ *   _match_fields_regex  starts_device[n] (uint64) and sizes_device[n] (int64; DEVICE memory) are what _field_spans wrote
+ *                     for n lines of the last batch's output; `base` is what takes a start back to an offset in that
+ *                     output, as for _gather_fields.  flags_device[n] (uint64, DEVICE memory) receives 1 for a line that
+ *                     matches and 0 for every other; nothing is written at or beyond n.  A line with a size < 0 gives 0;
+ *                     so does one whose span does not lie inside the output, which is never read.  No batch may be in
+ *                     flight.  The call returns when everything is written.  k_field_regex: one lane per line, which
+ *                     stops at the first byte after which the answer is known -- state 1, or the state from which no
+ *                     match can follow --, so that an anchored prefix costs a few bytes per line. */
+int mi355x_bz2_match_fields_regex( mi355x_bz2_ctx* ctx, const mi355x_bz2_regex* re, const uint64_t* starts_device,
+                                   const int64_t* sizes_device, uint64_t n, uint64_t base, uint64_t* flags_device );
+
 /* The hash of field `field` of every line: the KEY of a line is mi355x_bz2_line_hash's hash (same seed, same base) of
  * content.split( dl )[field], the field mi355x_bz2_field_spans finds; a line with fewer fields has the key
  * MI355X_BZ2_FIELD_MISSING = 2^61 - 1, the hash's modulus, which no hash takes; an empty field is present and hashes
@@ -1036,6 +1054,24 @@ int mi355x_bz2_reader_select_lines( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl
                                     const uint32_t* value_sizes, uint32_t n_values, uint64_t seed, int has_lo, int64_t lo,
                                     int has_hi, int64_t hi, int invert, uint64_t first, uint64_t count, uint64_t max_lines,
                                     int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
+
+/* ---- lines selected by a regular expression on a field (mi355x_bz2_match_fields_regex says when a field matches): a
+ * third predicate beside the values and the range above, with the same `invert`, the same line range and the same holds.
+ *   _field_matches_regex  as _field_matches, with `re` (mi355x_bz2_regex_compile; a pattern it refuses never gets here) in
+ *                     place of the values: each launch runs mi355x_bz2_field_spans' kernels and k_field_regex over its
+ *                     resident blocks, every needed block decoded ONCE, then one rocPRIM select over the flags.  A line
+ *                     that crosses a launch seam and the unterminated tail are known by start and size only: an empty
+ *                     field is decided at once, the bytes of the others are fetched by one _read_ranges-like call -- at
+ *                     most launches + 1 fields, the only second decode -- and the table is run on the host.  The line
+ *                     numbers are held as _field_matches holds them: _take_field_matches gives them, and the next
+ *                     _field_matches / _field_in_range / _field_matches_regex / _select_lines(_regex) releases them.
+ *   _select_lines_regex  as _select_lines: the result is held as grep's, _take_grep + _take_line_ranges. */
+int mi355x_bz2_reader_field_matches_regex( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field,
+                                           const mi355x_bz2_regex* re, int invert, uint64_t first, uint64_t count,
+                                           uint64_t limit, int keep_on_device, uint64_t* n_selected, uint64_t* n_matching );
+int mi355x_bz2_reader_select_lines_regex( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field,
+                                          const mi355x_bz2_regex* re, int invert, uint64_t first, uint64_t count,
+                                          uint64_t max_lines, int keep_on_device, uint64_t* n_lines, uint64_t* total_bytes );
 
 /* blockOffsets() (forces a full decode) / availableBlockOffsets(): two-call protocol -- pass capacity 0 to get the
  * count in *n, then call again with arrays of that size.                         :339-363 */

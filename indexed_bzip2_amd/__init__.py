@@ -28,8 +28,9 @@ field_ints_to_tensor give field j of every line as an int64 (parse_field_number 
 [+-]?[0-9]{1,18}, not awk's strtod; FIELD_NOT_A_NUMBER and FIELD_NUMBER_MISSING otherwise), sum_by_field sums one column
 per value of another on the GPU from one decode, exactly, and value_sums adds the keys (`awk '{s[$1]+=$3}'`).  And which
 rows: where_field, where_field_to_tensor and count_where_field select the lines whose field j is byte for byte one of a set
-of values, or whose number lies in a range (`awk -F'\t' '$3 == "GET"'`, `awk '$5 >= 500'`, a semi-join), invert=True the
-others; select_lines and select_lines_to_tensor bring those lines as grep brings its own.
+of values, or whose number lies in a range (`awk -F'\t' '$3 == "GET"'`, `awk '$5 >= 500'`, a semi-join), or, with
+regex=pattern, whose field matches a regular expression of grep_regex's kind, anchored to the field's ends (`awk -F'\t'
+'$3 ~ /^GET$/'`), invert=True the others; select_lines and select_lines_to_tensor bring those lines as grep brings its own.
 """
 __version__ = "0.1.0"
 

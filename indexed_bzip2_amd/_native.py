@@ -234,6 +234,13 @@ SYMBOLS = [
                                                        ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
                                                        ctypes.c_int64, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64,
                                                        ctypes.c_int, _u64p, _u64p]),
+    ("mi355x_bz2_match_fields_regex", ctypes.c_int, [_vp, _vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp]),
+    ("mi355x_bz2_reader_field_matches_regex", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, _vp, ctypes.c_int,
+                                                              ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                                              _u64p, _u64p]),
+    ("mi355x_bz2_reader_select_lines_regex", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, _vp, ctypes.c_int,
+                                                             ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int,
+                                                             _u64p, _u64p]),
     ("mi355x_bz2_read_stream_header", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64]),
     ("mi355x_bz2_reader_open_path", ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
     ("mi355x_bz2_reader_open_fd", ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.c_int32, ctypes.POINTER(_vp)]),
@@ -1137,6 +1144,29 @@ class Decoder:
             self._check(lib().mi355x_bz2_match_fields(self._h, data, value_sizes, n_values, seed, d_keys, d_starts, d_sizes, n,
                                                       int(base) % 2**64, d_flags))
         _with_device_copies("match_fields", hosts, call)
+        return flags[:room]
+
+    def match_fields_regex(self, regex, starts, sizes, base=0, room=None):
+        """k_field_regex: does the field of every line match `regex` (compile_regex, or a pattern to compile)?  The field
+        is to the pattern what a line's content is to match_lines: `^` and `$` anchor to the field's ends.  starts and
+        sizes are field_spans' two arrays for n lines of the last batch's output; start - base is a field's offset in that
+        output -> flags: a numpy uint64 array of `room` words (default: n) that were all ones before the call, of which
+        the call writes the first n: 1 where the line matches, 0 elsewhere (a size < 0, a span outside the output)."""
+        import numpy as np
+        if not isinstance(regex, CompiledRegex):
+            regex = compile_regex(regex)
+        starts = np.ascontiguousarray(starts, dtype=np.uint64)
+        sizes = np.ascontiguousarray(sizes, dtype=np.int64)
+        if starts.ndim != 1 or starts.shape != sizes.shape:
+            raise ValueError("starts and sizes must be one-dimensional and equally long")
+        n = int(starts.size)
+        room = n if room is None else max(int(room), n)
+        flags = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
+        hosts = [np.resize(starts, max(1, n)), np.resize(sizes, max(1, n)), flags]
+
+        def call(d_starts, d_sizes, d_flags):
+            self._check(lib().mi355x_bz2_match_fields_regex(self._h, regex._h, d_starts, d_sizes, n, int(base) % 2**64, d_flags))
+        _with_device_copies("match_fields_regex", hosts, call)
         return flags[:room]
 
     def output_device_ptr(self) -> int:

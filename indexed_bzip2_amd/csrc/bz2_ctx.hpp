@@ -14,6 +14,7 @@
 #include "../../include/mi355x_bz2.h"
 #include "bz2_fieldhash.hpp"
 #include "bz2_fieldmatch.hpp"
+#include "bz2_fieldregex.hpp"
 #include "bz2_fieldnum.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
@@ -108,6 +109,13 @@ int fieldNumbersOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent,
  * values and 0 elsewhere. */
 int matchFieldsOutput( mi355x_bz2_ctx* ctx, const bz2gpu::ValueTable& table, const uint64_t* dKeys, const uint64_t* dStarts,
                        const int64_t* dSizes, uint64_t n, uint64_t srcOffset, uint64_t fileOffset, uint64_t* dFlags );
+
+/** The reader's regular-expression match on a field in one launch: mi355x_bz2_match_fields_regex over the n lines whose
+ * starts and sizes fieldSpansOutput wrote for an extent that begins at `srcOffset` of the last batch's output and at
+ * `fileOffset` of the decoded file.  dFlags[0, n), device memory, receives 1 where the field matches (bz2_fieldregex.hpp)
+ * and 0 elsewhere. */
+int matchFieldsRegexOutput( mi355x_bz2_ctx* ctx, const bz2gpu::Regex& regex, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n,
+                            uint64_t srcOffset, uint64_t fileOffset, uint64_t* dFlags );
 
 /** Device memory that is nobody's context's (bz2_distinct.hip): the reader's line hashes.  device < 0: the current one.
  * allocate returns nullptr with *error set.  The copies wait for their completion; deviceToHost with dstIsDevice copies

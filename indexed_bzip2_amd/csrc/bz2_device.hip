@@ -36,6 +36,7 @@
 #include "bz2_fieldhash.hip.h"
 #include "bz2_fieldnum.hip.h"
 #include "bz2_fieldmatch.hip.h"
+#include "bz2_fieldregex.hip.h"
 #include "bz2_fieldcols.hip.h"
 #include "bz2_stage1.hip.h"
 #include "bz2_hscan.hip.h"
@@ -50,6 +51,7 @@
 #include "bz2_fieldhash.hpp"
 #include "bz2_fieldnum.hpp"
 #include "bz2_fieldmatch.hpp"
+#include "bz2_fieldregex.hpp"
 #include "bz2_fieldcols.hpp"
 
 using namespace bz2gpu;

@@ -1,7 +1,8 @@
 /**
  * bz2_queries.hip.h -- the host side of the calls that read a finished batch's output: gather, count / find / rank of a
  * byte, search for a string or a set of strings, regular expressions, line hashes, field spans, field columns, field
- * hashes, field numbers and field matches, their mi355x::*Output forms for the reader and their extern "C" entry points.  Part of bz2_device.hip's
+ * hashes, field numbers, field matches and field matches by a regular expression, their mi355x::*Output forms for the
+ * reader and their extern "C" entry points.  Part of bz2_device.hip's
  * translation unit (the context's layout names device record types), included below the context's definition and HIP_TRY.
  *
  * Every launcher but gatherPieces (millions of one-tile pieces, a plain loop) has the same shape: refuseQuery, the tiles
@@ -1074,6 +1075,41 @@ matchFields( mi355x_bz2_ctx* c, const char* what, const ValueTable& table, const
     return MI355X_BZ2_OK;
 }
 
+/**
+ * mi355x_bz2_match_fields_regex and the reader's launches.  The n lines' starts and sizes are in device memory already --
+ * the field-span passes wrote them --, so only the table and acceptsAtEnd go up: once per call of this launcher, which for
+ * the reader is once per resident stretch, as matchFields sends its image (at most 16 KiB + 64 B, and the dead state is
+ * found anew, 64 x 256 comparisons at the most; neither is kept on the context).  k_field_regex writes dFlags[0, n), one
+ * word per line.  A start counts from `base`, modulo 2^64, as for matchFields.
+ */
+static_assert( REGEX_STATES == REGEX_MAX_STATES, "regexDeadState's `none` is a state that k_field_regex never reaches" );
+
+int
+matchFieldsRegex( mi355x_bz2_ctx* c, const char* what, const Regex& regex, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n,
+                  uint64_t base, uint64_t* dFlags )
+{
+    const std::scoped_lock lock( c->mutex );
+    const bool compiled = regex.n >= 2 && regex.n <= REGEX_MAX_STATES && regex.transitions.size() == (size_t)regex.n * 256
+                          && regex.acceptsAtEnd.size() == regex.n;
+    if ( const int status = refuseQuery( c, what, nullptr, 0, compiled ? "" : "not a compiled regular expression" ) ) return status;
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    HIP_TRY( c, hipSetDevice( c->device ) );
+    const FieldRegexLayout l = layFieldRegex( regex.n, REGEX_STATES );
+    if ( const int status = growLineStaging( c, l.bytes, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    std::memset( h, 0, l.bytes );
+    std::memcpy( h + l.tableAt, regex.transitions.data(), (size_t)regex.n * 256 );
+    std::memcpy( h + l.acceptsAt, regex.acceptsAtEnd.data(), regex.n );
+    HIP_TRY( c, hipMemcpyAsync( d, h, l.bytes, hipMemcpyHostToDevice, c->stream ) );
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( n + FIELDREGEX_THREADS - 1 ) / FIELDREGEX_THREADS, FIELDREGEX_BLOCKS );
+    hipLaunchKernelGGL( k_field_regex, dim3( blocks ), dim3( FIELDREGEX_THREADS ), 0, c->stream, d + l.tableAt, d + l.acceptsAt, regex.n,
+                        regexDeadState( regex ), dStarts, dSizes, n, c->dOut, c->outSize, base, dFlags );
+    HIP_TRY( c, hipGetLastError() );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    return MI355X_BZ2_OK;
+}
+
 /** The set of a C ABI call, checked: false with lastError set if it breaks a limit or `flags` has an unknown bit. */
 bool
 takeSet( mi355x_bz2_ctx* c, const char* what, const uint8_t* patterns, const uint32_t* sizes, uint32_t n, uint32_t flags,
@@ -1237,6 +1273,17 @@ mi355x::matchFieldsOutput( mi355x_bz2_ctx* c, const bz2gpu::ValueTable& table, c
     }
     /* modulo 2^64, as gatherFieldsOutput has it */
     return matchFields( c, "field_matches", table, dKeys, dStarts, dSizes, n, fileOffset - srcOffset, dFlags );
+}
+
+int
+mi355x::matchFieldsRegexOutput( mi355x_bz2_ctx* c, const bz2gpu::Regex& regex, const uint64_t* dStarts, const int64_t* dSizes, uint64_t n,
+                                uint64_t srcOffset, uint64_t fileOffset, uint64_t* dFlags )
+{
+    if ( c == nullptr || ( n > 0 && ( dStarts == nullptr || dSizes == nullptr || dFlags == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    /* modulo 2^64, as gatherFieldsOutput has it */
+    return matchFieldsRegex( c, "field_matches_regex", regex, dStarts, dSizes, n, fileOffset - srcOffset, dFlags );
 }
 
 int
@@ -1413,6 +1460,16 @@ mi355x_bz2_match_fields( mi355x_bz2_ctx* c, const uint8_t* values, const uint32_
         return MI355X_BZ2_ERR_DEVICE;
     }
     return matchFields( c, "match_fields", table, keysDevice, startsDevice, sizesDevice, n, base, flagsDevice );
+}
+
+int
+mi355x_bz2_match_fields_regex( mi355x_bz2_ctx* c, const mi355x_bz2_regex* re, const uint64_t* startsDevice, const int64_t* sizesDevice,
+                               uint64_t n, uint64_t base, uint64_t* flagsDevice )
+{
+    if ( c == nullptr || re == nullptr || ( n > 0 && ( startsDevice == nullptr || sizesDevice == nullptr || flagsDevice == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return matchFieldsRegex( c, "match_fields_regex", re->dfa, startsDevice, sizesDevice, n, base, flagsDevice );
 }
 
 int

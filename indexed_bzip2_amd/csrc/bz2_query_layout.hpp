@@ -189,6 +189,20 @@ layFieldMatch( uint64_t imageBytes )
     return { r.add( imageBytes, 16 ), r.size() };
 }
 
+/* match_fields_regex over lines whose columns are in device memory already, under an automaton of `states` states
+ * (bz2_regex.hpp): [table, 256 bytes per state][acceptsAtEnd, `maxStates` bytes, zero behind the states] up, nothing down;
+ * nothing for the kernel alone */
+struct FieldRegexLayout
+{
+    uint64_t tableAt, acceptsAt, bytes;
+};
+inline FieldRegexLayout
+layFieldRegex( uint64_t states, uint64_t maxStates )
+{
+    Regions r;
+    return { r.add( states * 256, 16 ), r.add( maxStates, 16 ), r.size() };
+}
+
 /* field_hashes for field `field`: field_spans' and hash_lines' lists side by side, since both first passes run as they
  * are: [tiles][field spans][hash spans] up, [field summaries][hash summaries][tail hashes, 16 bytes per span]
  * [head positions][head hashes, field + 1 per span each] down; [field tile summaries][hash tile summaries][chunk places]

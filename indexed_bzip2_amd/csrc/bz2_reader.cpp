@@ -1485,6 +1485,40 @@ struct FieldMatchQuery
     static const bz2gpu::FieldKey& tail( const bz2gpu::StitchedFieldHashes& stitched ) { return stitched.tail; }
 };
 
+/* field_matches_regex: field_spans' two columns and a flag per line, from ONE decode: behind the field-span pass, while the
+ * stretch is resident, k_field_regex runs the automaton over the fields of the lines written (matchFieldsRegexOutput).  The
+ * stretch and the stitcher are field_spans': a line that crosses a seam and the tail get the flag 0 here, and
+ * StreamReader::fieldMatchesRegex decides them from their bytes. */
+struct FieldRegexQuery
+{
+    static constexpr size_t COLUMNS = 3;        /* starts, sizes (int64), flags */
+    using Stretch = bz2gpu::FieldStretch;
+    uint8_t nl, dl;
+    uint32_t field;
+    const bz2gpu::Regex* regex;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, field, place.skip, place.take,
+                                            to[0], reinterpret_cast<int64_t*>( to[1] ), &stretch.summary ) );
+        const uint64_t closed = stretch.summary.count;
+        const uint64_t written = closed > place.skip ? std::min( closed - place.skip, place.take ) : 0;
+        checkDevice( ctx, matchFieldsRegexOutput( ctx, *regex, to[0], reinterpret_cast<const int64_t*>( to[1] ), written, piece.src,
+                                                  piece.fileOffset, to[2] ) );
+        return closed;
+    }
+
+    template<typename Patch>
+    auto stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const { return bz2gpu::stitchFields( stretches, field, patch ); }
+
+    static std::array<uint64_t, COLUMNS> words( const bz2gpu::FieldSpan& span ) { return { span.start, (uint64_t)span.size, 0 }; }
+    static const bz2gpu::FieldSpan& tail( const bz2gpu::StitchedFields& stitched ) { return stitched.tail; }
+};
+
 /* ------------------------------------------------------------------------------------------------ the reader */
 class StreamReader
 {
@@ -2543,6 +2577,64 @@ public:
         holdSelectedLines( what, predicate, n, first, limit, keepOnDevice, nSelected, nMatching );
     }
 
+    /** mi355x_bz2_reader_field_matches_regex: the lines of [first, first + count) whose field matches the automaton
+     * (bz2_fieldregex.hpp), or with `invert` the others.  lineColumns with FieldRegexQuery: every block is decoded once, the
+     * field-span pass and k_field_regex run over each resident stretch.  The lines that cross a launch seam and the
+     * unterminated tail come from the stitcher as ( start, size ) without bytes: an empty field is decided by
+     * acceptsAtEnd[0], the bytes of the others are fetched by ONE readRanges call -- a second decode of their blocks, at
+     * most launches + 1 of them -- and decided by fieldRegexHolds on the host.  Then bz2_distinct.hip's selectLines over the
+     * flags; the first `limit` numbers are held. */
+    void
+    fieldMatchesRegex( uint8_t nl, uint8_t dl, uint32_t field, const bz2gpu::Regex& regex, bool invert, uint64_t first, uint64_t count,
+                       uint64_t limit, bool keepOnDevice, uint64_t* nSelected, uint64_t* nMatching,
+                       const char* what = "field_matches_regex" )
+    {
+        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, std::string( what ) + ": " + refused );
+        const auto& index = lineIndex( nl );
+        dropHeldLines();
+        m_fieldMatches.reset();
+        uint64_t n = 0;
+        std::vector<std::pair<uint64_t, std::array<uint64_t, FieldRegexQuery::COLUMNS> > > patched;
+        const auto held = lineColumns( FieldRegexQuery{ nl, dl, field, &regex }, what, index, first, count, false, &n, &patched );
+        std::vector<uint64_t> hits, at, offsets, sizes;
+        uint64_t bytes = 0;
+        for ( const auto& [line, words] : patched ) {
+            const auto size = (int64_t)words[1];
+            if ( size < 0 ) continue;
+            if ( size == 0 ) {
+                if ( regex.acceptsAtEnd[bz2gpu::REGEX_START] != 0 ) hits.push_back( line );
+                continue;
+            }
+            at.push_back( line );
+            offsets.push_back( words[0] );
+            sizes.push_back( words[1] );
+            bytes += words[1];
+        }
+        if ( !at.empty() ) {
+            std::vector<uint8_t> fetched( (size_t)bytes );
+            std::vector<uint64_t> nRead( at.size() );
+            readRanges( offsets.data(), sizes.data(), at.size(), fetched.data(), false, nRead.data() );
+            if ( nRead != sizes ) fail( MI355X_BZ2_ERR_LOGIC, std::string( what ) + ": a patched field lies behind the end of the file" );
+            uint64_t from = 0;
+            for ( size_t i = 0; i < at.size(); ++i ) {
+                if ( bz2gpu::fieldRegexHolds( regex, fetched.data() + from, (int64_t)sizes[i] ) ) hits.push_back( at[i] );
+                from += sizes[i];
+            }
+        }
+        std::string why;
+        const uint64_t one = 1;
+        for ( const auto line : hits ) {
+            if ( !hostToDevice( m_device, held.column<uint64_t>( 2 ) + line, &one, sizeof( one ), &why ) ) {
+                fail( MI355X_BZ2_ERR_DEVICE, std::string( what ) + ": " + why );
+            }
+        }
+        LinePredicate predicate;
+        predicate.dFlags = held.column<const uint64_t>( 2 );
+        predicate.invert = invert;
+        holdSelectedLines( what, predicate, n, first, limit, keepOnDevice, nSelected, nMatching );
+    }
+
     /** mi355x_bz2_reader_take_field_matches: the first min( capacity, held ) line numbers; they stay held. */
     void
     takeFieldMatches( void* numbers, uint64_t capacity, bool dstIsDevice )
@@ -2671,7 +2763,7 @@ private:
 
     /** The result of a per-line column query, in device memory of the reader's own: up to four columns of n 8-byte words
      * -- hashes; starts and sizes; keys, starts and sizes; numbers, starts and sizes; keys, starts, sizes and values; keys,
-     * starts, sizes and flags.  An empty result has no memory. */
+     * starts, sizes and flags; starts, sizes and flags.  An empty result has no memory. */
     struct HeldColumns
     {
         struct Release { void operator()( void* pointer ) const { deviceRelease( pointer ); } };
@@ -2890,7 +2982,7 @@ private:
         } );
     }
 
-    /** What line_hashes, field_spans, field_hashes, field_numbers, field_sums and field_matches do, given the `query` (the
+    /** What line_hashes, field_spans, field_hashes, field_numbers, field_sums, field_matches and field_matches_regex do, given the `query` (the
      * structs in front of the reader):
      * the launches of planLineHashes for lines [first, first + count), each doing its stretches on the context that
      * decoded them, straight into device columns that are allocated before anything is launched and in which every
@@ -3144,7 +3236,7 @@ private:
     std::optional<std::vector<FieldGroup> > m_fieldGroups;    /* between field_groups and the next call of its family */
     std::optional<HeldColumns> m_fieldNumbers;                /* between field_numbers and the next call of its family */
     std::optional<std::vector<FieldSumGroup> > m_fieldSums;   /* between field_sums and the next call of its family */
-    std::optional<HeldFieldMatches> m_fieldMatches;           /* between field_matches / field_in_range and the next of the two */
+    std::optional<HeldFieldMatches> m_fieldMatches;           /* between field_matches / field_in_range / field_matches_regex and the next of them */
     std::optional<std::vector<uint64_t> > m_distinct;  /* between distinct_lines (with numbers) and the next of the two */
 };
 }  // namespace mi355x
@@ -3736,6 +3828,33 @@ mi355x_bz2_reader_select_lines( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, ui
                 reader.fieldInRange( nl, dl, field, range, invert != 0, first, count, limit, false, nSelected, nMatching, "select_lines" );
             }, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
         }
+    } );
+}
+
+int
+mi355x_bz2_reader_field_matches_regex( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const mi355x_bz2_regex* re,
+                                       int invert, uint64_t first, uint64_t count, uint64_t limit, int keepOnDevice,
+                                       uint64_t* nSelected, uint64_t* nMatching )
+{
+    if ( re == nullptr || nSelected == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        uint64_t matching = 0;
+        reader.fieldMatchesRegex( nl, dl, field, re->dfa, invert != 0, first, count, limit, keepOnDevice != 0, nSelected, &matching );
+        if ( nMatching != nullptr ) *nMatching = matching;
+    } );
+}
+
+int
+mi355x_bz2_reader_select_lines_regex( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, const mi355x_bz2_regex* re,
+                                      int invert, uint64_t first, uint64_t count, uint64_t maxLines, int keepOnDevice,
+                                      uint64_t* nLines, uint64_t* totalBytes )
+{
+    if ( re == nullptr || nLines == nullptr || totalBytes == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.selectLines( [&] ( uint64_t limit, uint64_t* nSelected, uint64_t* nMatching ) {
+            reader.fieldMatchesRegex( nl, dl, field, re->dfa, invert != 0, first, count, limit, false, nSelected, nMatching,
+                                      "select_lines_regex" );
+        }, nl, maxLines, keepOnDevice != 0, nLines, totalBytes );
     } );
 }
 

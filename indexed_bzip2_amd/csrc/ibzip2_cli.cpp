@@ -49,9 +49,10 @@ struct Options
     std::vector<uint32_t> cutFields;            /* --cut-fields: not empty iff given */
     bool sumByField{ false };
     bool whereField{ false }, whereEquals{ false }, whereInFile{ false }, whereBetween{ false }, invertMatch{ false };
+    bool whereMatches{ false };
     bool hasLow{ false }, hasHigh{ false };
     int64_t low{ 0 }, high{ 0 };
-    std::string equals, valueFile;
+    std::string equals, valueFile, matches;
     unsigned field{ 0 }, valueField{ 0 };
     uint8_t fieldDelimiter{ '\t' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
@@ -165,6 +166,12 @@ printHelp()
         "      --between arg             With --where-field: given LO,HI (either side may be empty: open), the field\n"
         "                                must be a number n with LO <= n <= HI (awk '$5 >= 500 && $5 <= 599'). A\n"
         "                                number is [+-]?[0-9]{1,18} from end to end, not awk's strtod.\n"
+        "      --matches arg             With --where-field: the field must match the given regular expression, the\n"
+        "                                fourth alternative beside --equals, --in-file and --between (awk -F'\\t'\n"
+        "                                '$7 ~ /^\\/api\\//'). The syntax is --grep-regex's; the field is to the pattern\n"
+        "                                what the line is to --grep-regex: ^ and $ anchor to the field's ends, and a\n"
+        "                                line without field N does not match. --ignore-case applies, within\n"
+        "                                --where-field with --matches only.\n"
         "      --invert-match            With --where-field: print the lines that are NOT selected (grep -v), those\n"
         "                                without field N included.\n"
         "      --count-matches-file arg  As --count-matches, for every line of the given file at once: one count per\n"
@@ -207,6 +214,8 @@ printHelp()
         "  ibzip2-mi355x --sum-by-field 0,2 file.tsv.bz2\n\n"
         "Print the rows whose fifth column is a 5xx status, with their line numbers:\n"
         "  ibzip2-mi355x --where-field 4 --between 500,599 --line-number file.tsv.bz2\n\n"
+        "Print the rows whose seventh column starts with /api/v and a digit:\n"
+        "  ibzip2-mi355x --where-field 6 --matches '^/api/v[0-9]' file.tsv.bz2\n\n"
         "Print the lines that start with a date and report an error:\n"
         "  ibzip2-mi355x --grep-regex '^[0-9]{4}-[0-9]{2}-[0-9]{2} .*(ERROR|FATAL)' file.bz2\n";
 }
@@ -435,6 +444,7 @@ parseArguments( int argc, char** argv, Options& o )
                 }
                 o.whereBetween = true;
             }
+            else if ( name == "matches" ) { if ( !need( o.matches ) ) return 1; o.whereMatches = true; }
             else if ( name == "invert-match" ) o.invertMatch = true;
             else if ( name == "field-delimiter" ) {
                 if ( !need( value ) || !parseByte( value, o.fieldDelimiter ) || o.fieldDelimiter == '\n' ) {
@@ -654,8 +664,17 @@ main( int argc, char** argv )
                      "'--count-by-field' or '--sum-by-field'\n";
         return 1;
     }
-    if ( o.whereField && (int)o.whereEquals + (int)o.whereInFile + (int)o.whereBetween != 1 ) {
+    /* --matches is named only where it was given: the sentence below it is older than --matches, and its bytes are kept */
+    if ( o.whereField && o.whereMatches && ( o.whereEquals || o.whereInFile || o.whereBetween ) ) {
+        std::cerr << "Option '--where-field' needs exactly one of '--equals', '--in-file', '--between' and '--matches'\n";
+        return 1;
+    }
+    if ( o.whereField && !o.whereMatches && (int)o.whereEquals + (int)o.whereInFile + (int)o.whereBetween != 1 ) {
         std::cerr << "Option '--where-field' needs exactly one of '--equals', '--in-file' and '--between'\n";
+        return 1;
+    }
+    if ( !o.whereField && o.whereMatches ) {
+        std::cerr << "Option '--matches' needs '--where-field'\n";
         return 1;
     }
     if ( !o.whereField && ( o.whereEquals || o.whereInFile || o.whereBetween || o.invertMatch ) ) {
@@ -666,7 +685,8 @@ main( int argc, char** argv )
         std::cerr << "Option '--line-number' needs '--grep' or '--grep-file'\n";
         return 1;
     }
-    if ( o.ignoreCase && !o.grep && !o.grepFile && !o.countMatches && !o.countMatchesFile && !o.grepRegex ) {
+    /* also accepted with --grep-regex and with --where-field --matches; the sentence's bytes are kept as they were */
+    if ( o.ignoreCase && !o.grep && !o.grepFile && !o.countMatches && !o.countMatchesFile && !o.grepRegex && !o.whereMatches ) {
         std::cerr << "Option '--ignore-case' needs '--grep', '--grep-file', '--count-matches' or '--count-matches-file'\n";
         return 1;
     }
@@ -1013,6 +1033,17 @@ main( int argc, char** argv )
                 return 1;
             }
         }
+        mi355x_bz2_regex* regex = nullptr;
+        if ( o.whereMatches ) {
+            /* before anything is opened, as --grep-regex has it */
+            char why[512];
+            if ( mi355x_bz2_regex_compile( reinterpret_cast<const uint8_t*>( o.matches.data() ), o.matches.size(), searchFlags, &regex,
+                                           why, sizeof( why ) ) != MI355X_BZ2_OK ) {
+                std::cerr << "Invalid regular expression: " << why << "\n";
+                return 1;
+            }
+        }
+        const std::unique_ptr<mi355x_bz2_regex, void ( * )( mi355x_bz2_regex* )> regexOwner( regex, mi355x_bz2_regex_free );
         Input in;
         if ( !in.open( o.input ) ) {
             std::cerr << "Could not open '" << o.input << "'\n";
@@ -1029,10 +1060,13 @@ main( int argc, char** argv )
             return 1;
         }
         uint64_t nLines = 0, total = 0;
-        rc = mi355x_bz2_reader_select_lines( reader, '\n', o.fieldDelimiter, o.field, reinterpret_cast<const uint8_t*>( values.data() ),
-                                             valueSizes.data(), (uint32_t)std::min<size_t>( valueSizes.size(), 0xFFFFFFFFu ), o.seed,
-                                             o.hasLow ? 1 : 0, o.low, o.hasHigh ? 1 : 0, o.high, o.invertMatch ? 1 : 0, 0, ~uint64_t( 0 ),
-                                             ~uint64_t( 0 ), 0, &nLines, &total );
+        rc = o.whereMatches
+             ? mi355x_bz2_reader_select_lines_regex( reader, '\n', o.fieldDelimiter, o.field, regex, o.invertMatch ? 1 : 0, 0, ~uint64_t( 0 ),
+                                                     ~uint64_t( 0 ), 0, &nLines, &total )
+             : mi355x_bz2_reader_select_lines( reader, '\n', o.fieldDelimiter, o.field, reinterpret_cast<const uint8_t*>( values.data() ),
+                                               valueSizes.data(), (uint32_t)std::min<size_t>( valueSizes.size(), 0xFFFFFFFFu ), o.seed,
+                                               o.hasLow ? 1 : 0, o.low, o.hasHigh ? 1 : 0, o.high, o.invertMatch ? 1 : 0, 0, ~uint64_t( 0 ),
+                                               ~uint64_t( 0 ), 0, &nLines, &total );
         std::vector<uint64_t> numbers( nLines ), sizes( nLines );
         std::vector<char> bytes( total );
         if ( rc == MI355X_BZ2_OK ) rc = mi355x_bz2_reader_take_grep( reader, numbers.data(), sizes.data(), nLines );

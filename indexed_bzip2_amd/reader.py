@@ -920,19 +920,38 @@ class _IndexedBzip2FileParallel:
     # that is present, never a missing one.  It matches between=(lo, hi) iff N.parse_field_number(field) is a number n with
     # lo <= n <= hi; None is an open side; a field that is no number and a missing one never match.  invert=True selects
     # the complement within the line range (`grep -v`).  The key under `seed` only filters in front of the comparison of
-    # the bytes: the answer does not depend on it.  No quoting, no escaping: not a CSV parser
-    def _where_arguments(self, field, values, between, invert, first, count, limit, delimiter, newline, seed):
-        if (values is None) == (between is None):
-            raise ValueError("exactly one of values and between must be given")
+    # the bytes: the answer does not depend on it.  It matches regex=pattern (keyword only; bytes-like, or compiled by
+    # compile_regex) iff it has the field and the pattern's table, run over the field's bytes, matches: the field is to the
+    # pattern what a line's content is to grep_regex, so `^` and `$` anchor to the field's ends (`awk '$3 ~ /^GET$/'`), an
+    # empty field that is present matches iff the pattern matches the empty string, a missing field never matches, and a
+    # field may have any size.  For a field without the byte 0x0A that is re.search(pattern, field, re.DOTALL), with
+    # ignore_case=True re.IGNORECASE too; Python's `$` also matches in front of a trailing b"\n", the table's does not.
+    # `seed` is ignored with regex.  No quoting, no escaping: not a CSV parser
+    def _where_arguments(self, field, values, between, invert, first, count, limit, delimiter, newline, seed, regex=None,
+                         ignore_case=False):
+        if regex is None:
+            if ignore_case:
+                raise ValueError("ignore_case needs regex")
+            if (values is None) == (between is None):
+                raise ValueError("exactly one of values and between must be given")
+        elif values is not None or between is not None:
+            raise ValueError("exactly one of values, between and regex must be given")
         nl, dl, field, first, count, seed = self._field_hash_arguments(field, first, count, delimiter, newline, seed)
-        predicate = N.value_set(values) if values is not None else N.number_range(between)
+        if regex is not None:
+            predicate = (self._regex(regex, ignore_case),)      # a ValueError for a pattern outside the syntax
+        else:
+            predicate = N.value_set(values) if values is not None else N.number_range(between)
         return nl, dl, field, first, count, seed, predicate, 1 if invert else 0, self._line_limit(limit)
 
     def _where_field(self, arguments, limit, keep):
-        """mi355x_bz2_reader_field_matches or _field_in_range -> (the numbers held, the lines that match)."""
+        """mi355x_bz2_reader_field_matches, _field_in_range or _field_matches_regex -> (the numbers held, the lines that
+        match)."""
         nl, dl, field, first, count, seed, predicate, invert, _ = arguments
         held, matching = ctypes.c_uint64(), ctypes.c_uint64()
-        if len(predicate) == 3:
+        if len(predicate) == 1:
+            self._check(N.lib().mi355x_bz2_reader_field_matches_regex(self._h, nl, dl, field, predicate[0]._h, invert, first, count,
+                                                                       limit, keep, ctypes.byref(held), ctypes.byref(matching)))
+        elif len(predicate) == 3:
             data, sizes, k = predicate
             self._check(N.lib().mi355x_bz2_reader_field_matches(self._h, nl, dl, field, data, sizes, k, seed, invert, first, count, limit,
                                                                  keep, ctypes.byref(held), ctypes.byref(matching)))
@@ -942,16 +961,24 @@ class _IndexedBzip2FileParallel:
         return held.value, matching.value
 
     def where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
-                    newline=b"\n", seed=0):
+                    newline=b"\n", seed=0, *,
+                    regex=None, ignore_case=False):
         """The numbers of the lines of [first, first + count) whose field `field` is one of `values` (1 to 1 024 bytes
         objects of 0 to 256 bytes, at most 16 384 bytes in total) or whose number lies in between=(lo, hi) -> numpy uint64,
-        ascending, numbered in the file, at most `limit` of them (None: all).  Exactly one of values and between.  The
+        ascending, numbered in the file, at most `limit` of them (None: all).  The
         numbers index the arrays of read_columns, field_ints and field_hashes over the same line range (less `first`).
         Every needed block is decoded once; the predicate is evaluated and its flags are compacted on the GPU, and 8 bytes
         per selected line come back.  Two different values with the same key under `seed` are refused: pass another seed.
-        Not a CSV parser.  Positionless."""
+        Or, keyword only, regex=pattern (bytes-like, or compiled by compile_regex; ignore_case=True folds ASCII letters):
+        the lines whose field matches it, `awk -F'\\t' '$7 ~ /^\\/api\\//'`.  The field is to the pattern what the line's
+        content is to grep_regex: `^` and `$` anchor to the field's ends, a field of any size is walked, a missing field
+        never matches, an empty one matches iff the pattern matches the empty string.  For a field without b"\\n" that is
+        re.search(pattern, field, re.DOTALL); Python's `$` also matches in front of a trailing b"\\n", this one does not.
+        The syntax and the refusals (a ValueError before anything is launched) are compile_regex's; a GPU lane stops at
+        the first byte after which the answer is known, so an anchored prefix costs a few bytes per line.  Exactly one of
+        values, between and regex; `seed` is ignored with regex.  Not a CSV parser.  Positionless."""
         import numpy as np
-        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed, regex, ignore_case)
         n, _ = self._where_field(arguments, arguments[-1], 0)
         out = np.empty(n, dtype=np.uint64)
         if n:
@@ -959,11 +986,12 @@ class _IndexedBzip2FileParallel:
         return out
 
     def where_field_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                              delimiter=b"\t", newline=b"\n", seed=0):
+                              delimiter=b"\t", newline=b"\n", seed=0, *,
+                              regex=None, ignore_case=False):
         """where_field as a torch.int64 tensor on the reader's device; the numbers never pass through the host.  Less
         `first`, it indexes the tensors of read_columns_to_tensor, field_ints_to_tensor and field_hashes_to_tensor."""
         import torch
-        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed, regex, ignore_case)
         dev = self._device_index()
         n, _ = self._where_field(arguments, arguments[-1], 1)
         out = torch.empty(n, dtype=torch.int64, device=f"cuda:{dev}")
@@ -973,9 +1001,10 @@ class _IndexedBzip2FileParallel:
         return out
 
     def count_where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                          delimiter=b"\t", newline=b"\n", seed=0):
+                          delimiter=b"\t", newline=b"\n", seed=0, *,
+                          regex=None, ignore_case=False):
         """len(where_field(...)) without the numbers: nothing per line leaves the GPU, 8 bytes come back."""
-        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed, regex, ignore_case)
         _, matching = self._where_field(arguments, 0, 0)
         return min(matching, arguments[-1])
 
@@ -985,26 +1014,33 @@ class _IndexedBzip2FileParallel:
         nl, dl, field, first, count, seed, predicate, invert, limit = arguments
         if limit == 0:
             return np.empty(0, dtype=np.uint64), [], 0
-        if len(predicate) == 3:
-            data, sizes, k = predicate
-            bounds = (0, 0, 0, 0)
-        else:
-            data, sizes, k, bounds = None, None, 0, predicate
         n, total = ctypes.c_uint64(), ctypes.c_uint64()
-        self._check(N.lib().mi355x_bz2_reader_select_lines(self._h, nl, dl, field, data, sizes, k, seed, *bounds, invert, first, count,
-                                                            limit, 1 if on_device else 0, ctypes.byref(n), ctypes.byref(total)))
+        if len(predicate) == 1:
+            self._check(N.lib().mi355x_bz2_reader_select_lines_regex(self._h, nl, dl, field, predicate[0]._h, invert, first, count,
+                                                                      limit, 1 if on_device else 0, ctypes.byref(n),
+                                                                      ctypes.byref(total)))
+        else:
+            if len(predicate) == 3:
+                data, sizes, k = predicate
+                bounds = (0, 0, 0, 0)
+            else:
+                data, sizes, k, bounds = None, None, 0, predicate
+            self._check(N.lib().mi355x_bz2_reader_select_lines(self._h, nl, dl, field, data, sizes, k, seed, *bounds, invert, first,
+                                                                count, limit, 1 if on_device else 0, ctypes.byref(n),
+                                                                ctypes.byref(total)))
         numbers = (ctypes.c_uint64 * max(1, n.value))()
         sizes = (ctypes.c_uint64 * max(1, n.value))()
         self._check(N.lib().mi355x_bz2_reader_take_grep(self._h, numbers, sizes, n.value))
         return (np.frombuffer(numbers, dtype=np.uint64, count=n.value).copy(), [sizes[i] for i in range(n.value)], total.value)
 
     def select_lines(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
-                     newline=b"\n", seed=0):
+                     newline=b"\n", seed=0, *,
+                     regex=None, ignore_case=False):
         """The lines where_field selects -> (numbers, lines) as grep returns them: the line numbers (numpy uint64,
         ascending) and one bytes object per line, whole and with its delimiter, at most `limit` lines (None: all).  The
         selection, then the lines themselves in a second pass over the blocks that hold them.  Releases line ranges held
         by earlier calls.  Positionless."""
-        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed, regex, ignore_case)
         numbers, sizes, total = self._select_lines(arguments, False)
         if arguments[-1] == 0:
             return numbers, []
@@ -1019,11 +1055,12 @@ class _IndexedBzip2FileParallel:
         return numbers, lines
 
     def select_lines_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                               delimiter=b"\t", newline=b"\n", seed=0):
+                               delimiter=b"\t", newline=b"\n", seed=0, *,
+                               regex=None, ignore_case=False):
         """select_lines into ONE contiguous torch.uint8 tensor on the reader's device -> (numbers, data, offsets) as
         grep_to_tensor returns them: line i is ``data[offsets[i]:offsets[i + 1]]``."""
         import torch
-        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        arguments = self._where_arguments(field, values, between, invert, first, count, limit, delimiter, newline, seed, regex, ignore_case)
         dev = self._device_index()
         numbers, sizes, total = self._select_lines(arguments, True)
         data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
@@ -1342,29 +1379,39 @@ class IndexedBzip2File(io.BufferedReader):
         return self._open_reader().field_ints_to_tensor(field, first, count, delimiter, newline)
 
     def where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
-                    newline=b"\n", seed=0):
+                    newline=b"\n", seed=0, *,
+                    regex=None, ignore_case=False):
         """See _IndexedBzip2FileParallel.where_field."""
-        return self._open_reader().where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        return self._open_reader().where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed,
+                                              regex=regex, ignore_case=ignore_case)
 
     def where_field_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                              delimiter=b"\t", newline=b"\n", seed=0):
+                              delimiter=b"\t", newline=b"\n", seed=0, *,
+                              regex=None, ignore_case=False):
         """See _IndexedBzip2FileParallel.where_field_to_tensor."""
-        return self._open_reader().where_field_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        return self._open_reader().where_field_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed,
+                                                        regex=regex, ignore_case=ignore_case)
 
     def count_where_field(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                          delimiter=b"\t", newline=b"\n", seed=0):
+                          delimiter=b"\t", newline=b"\n", seed=0, *,
+                          regex=None, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_where_field."""
-        return self._open_reader().count_where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        return self._open_reader().count_where_field(field, values, between, invert, first, count, limit, delimiter, newline, seed,
+                                                    regex=regex, ignore_case=ignore_case)
 
     def select_lines(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None, delimiter=b"\t",
-                     newline=b"\n", seed=0):
+                     newline=b"\n", seed=0, *,
+                     regex=None, ignore_case=False):
         """See _IndexedBzip2FileParallel.select_lines."""
-        return self._open_reader().select_lines(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        return self._open_reader().select_lines(field, values, between, invert, first, count, limit, delimiter, newline, seed,
+                                               regex=regex, ignore_case=ignore_case)
 
     def select_lines_to_tensor(self, field, values=None, between=None, invert=False, first=0, count=None, limit=None,
-                               delimiter=b"\t", newline=b"\n", seed=0):
+                               delimiter=b"\t", newline=b"\n", seed=0, *,
+                               regex=None, ignore_case=False):
         """See _IndexedBzip2FileParallel.select_lines_to_tensor."""
-        return self._open_reader().select_lines_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed)
+        return self._open_reader().select_lines_to_tensor(field, values, between, invert, first, count, limit, delimiter, newline, seed,
+                                                         regex=regex, ignore_case=ignore_case)
 
     def sum_by_field(self, key_field, value_field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """See _IndexedBzip2FileParallel.sum_by_field."""
