@@ -463,6 +463,35 @@ int mi355x_bz2_field_spans( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spa
                             uint32_t field, mi355x_bz2_field_summary* summaries, uint64_t* head_positions,
                             uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
 
+/* Field `field` of every line when fields may be quoted.  quote = one more byte, quote != nl and quote != dl.  Within a
+ * line's content every quote byte toggles "inside quotes" and the content is parted at the dl bytes that lie OUTSIDE
+ * quotes: a doubled quote inside a quoted field toggles twice and needs no rule of its own; an unbalanced quote makes
+ * the rest of the line one field.  The nl always closes the line and resets the state: a quoted field cannot hold an nl,
+ * and lines and their numbers are _field_spans'.  That parts the line into RAW fields; presence and "missing" are
+ * _field_spans'.  The CONTENT of a raw field of 2 bytes or more whose first and last bytes are both quote is the raw
+ * field without these two; any other raw field is its own content.  Doubled quotes inside stay doubled: spans of the
+ * data are reported, no byte is rewritten.  No backslash escapes.
+ *   _field_spans_quoted  _field_spans with these differences.  quote == nl or quote == dl is
+ *                     MI355X_BZ2_ERR_INVALID_ARGUMENT, before anything is launched.  starts_device[] and sizes_device[]
+ *                     receive CONTENT spans, the first closed line of a span computed as if the span were entered at a
+ *                     line start outside quotes.  The summaries are RAW, not trimmed, and know both ways a span can be
+ *                     entered: head_delims[h] and head_positions[( i * 2 + h ) * ( field + 1 ) + k], k < head_delims[h],
+ *                     are the counted dl bytes in front of first_nl when the span is entered outside ( h = 0 ) and inside
+ *                     ( h = 1 ) quotes (host memory, room for n * 2 * ( field + 1 ); may be NULL); head_quote_parity =
+ *                     the parity of the quote bytes in front of first_nl (of all of them without an nl); the tail
+ *                     members are those of a span entered outside quotes (behind an nl a line starts outside), and
+ *                     tail_in_quote = the parity of the quote bytes from tail_start on.  bz2_fieldquote.hpp:
+ *                     stitchQuotedFields.  k_field_chunks_quoted, k_field_link_quoted, k_scan_tiles,
+ *                     k_field_emit_quoted, k_field_sizes, k_field_unquote. */
+typedef struct mi355x_bz2_quoted_field_summary
+{
+    uint64_t count, first_nl, tail_start, tail_field_start, tail_field_end;
+    uint32_t head_delims[2], tail_delims, has_delimiter, tail_non_empty, head_quote_parity, tail_in_quote, reserved;
+} mi355x_bz2_quoted_field_summary;
+int mi355x_bz2_field_spans_quoted( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl,
+                                   uint8_t quote, uint32_t field, mi355x_bz2_quoted_field_summary* summaries,
+                                   uint64_t* head_positions, uint64_t* starts_device, int64_t* sizes_device, uint64_t capacity );
+
 /* A column of fields as bytes: the fields that _field_spans found, packed back to back in the order of their lines.
  *   _gather_fields_tile_bytes  the bytes of the destination one GPU workgroup writes: of interest to tests and tuning.
  *   _gather_fields    starts_device[n] (uint64) and sizes_device[n] (int64; both DEVICE memory) are n spans as
@@ -951,6 +980,22 @@ int mi355x_bz2_reader_field_columns( mi355x_bz2_reader* r, uint8_t nl, uint8_t d
                                      uint64_t* total_bytes );
 int mi355x_bz2_reader_take_field_column( mi355x_bz2_reader* r, uint32_t column, void* data, void* offsets, void* sizes,
                                          int dst_is_device );
+
+/* ---- quoted fields (mi355x_bz2_field_spans_quoted says what a quoted field is: every quote byte toggles, a dl inside
+ * quotes does not part, the nl always closes the line, the content loses its enclosing pair, doubled quotes stay doubled).
+ *   _field_spans_quoted    _field_spans with the CONTENT of the fields under `quote`; quote == nl or quote == dl is
+ *                     MI355X_BZ2_ERR_INVALID_ARGUMENT, before anything is launched.  Each launch runs
+ *                     mi355x_bz2_field_spans_quoted's kernels.  The lines the host patches -- one per launch seam, and
+ *                     the tail -- come out of the stitcher raw: the first and last byte of each that has 2 bytes or more
+ *                     are fetched in ONE call of _read_ranges' path, and the pair is taken off on the host.  Held and
+ *                     taken as _field_spans' result: _take_field_spans serves both.
+ *   _field_columns_quoted  _field_columns likewise, its fix-ups trimmed the same way before the offsets are scanned;
+ *                     _take_field_column serves both. */
+int mi355x_bz2_reader_field_spans_quoted( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first,
+                                          uint64_t count, int keep_on_device, uint64_t* n_lines, uint8_t quote );
+int mi355x_bz2_reader_field_columns_quoted( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t n_fields,
+                                            uint64_t first, uint64_t count, int keep_on_device, uint64_t* n_lines,
+                                            uint64_t* total_bytes, uint8_t quote );
 
 /* ---- field hashes and groups (mi355x_bz2_field_hashes says what the key of a line is).
  *   _field_hashes     the keys of lines [first, first + count), count clipped at the last line; *n_lines = their number.

@@ -21,7 +21,9 @@ of at most L bytes collide for at most L of the 2^61 bases a seed selects, and a
 And what a line holds: field_spans and field_spans_to_tensor say where field j of every line lies when the line is split at
 a delimiter byte exactly as bytes.split splits it (size -1 where a line has fewer fields), read_fields and
 read_fields_to_tensor bring those bytes and nothing else (`cut -f`, `awk -F`); there is no quoting or escaping, this is not
-a CSV parser.  And how often each value of a column occurs: field_hashes and field_hashes_to_tensor give the hash of
+a CSV parser -- unless quote=b'"' is given to field_spans, read_fields or read_columns: then a delimiter inside quotes does
+not split the line and a field comes back without its enclosing pair of quotes (doubled quotes inside stay doubled, and a
+newline still ends every line).  And how often each value of a column occurs: field_hashes and field_hashes_to_tensor give the hash of
 field j of every line (FIELD_MISSING, 2^61 - 1, where a line has no such field), count_by_field groups the lines by it on
 the GPU and value_counts adds the values (`cut -f3 | sort | uniq -c | sort -rn`).  And how much: field_ints and
 field_ints_to_tensor give field j of every line as an int64 (parse_field_number says which bytes are a number:

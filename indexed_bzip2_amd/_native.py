@@ -196,6 +196,13 @@ SYMBOLS = [
     ("mi355x_bz2_field_chunk_bytes", ctypes.c_uint32, []),
     ("mi355x_bz2_field_spans", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
                                                ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_field_spans_quoted", ctypes.c_int, [_vp, ctypes.POINTER(ByteSpan), ctypes.c_uint32, ctypes.c_uint8, ctypes.c_uint8,
+                                                      ctypes.c_uint8, ctypes.c_uint32, _vp, _vp, _vp, _vp, ctypes.c_uint64]),
+    ("mi355x_bz2_reader_field_spans_quoted", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
+                                                             ctypes.c_uint64, ctypes.c_int, _u64p, ctypes.c_uint8]),
+    ("mi355x_bz2_reader_field_columns_quoted", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, _u32p, ctypes.c_uint32,
+                                                               ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int, _u64p, _u64p,
+                                                               ctypes.c_uint8]),
     ("mi355x_bz2_gather_fields_tile_bytes", ctypes.c_uint32, []),
     ("mi355x_bz2_gather_fields", ctypes.c_int, [_vp, _vp, _vp, ctypes.c_uint64, ctypes.c_uint64, _vp, _vp, ctypes.c_uint64, _u64p]),
     ("mi355x_bz2_reader_field_spans", ctypes.c_int, [_vp, ctypes.c_uint8, ctypes.c_uint8, ctypes.c_uint32, ctypes.c_uint64,
@@ -471,6 +478,14 @@ class FieldSummary(ctypes.Structure):
                 ("tail_delims", ctypes.c_uint32), ("has_delimiter", ctypes.c_uint32), ("tail_non_empty", ctypes.c_uint32)]
 
 
+class QuotedFieldSummary(ctypes.Structure):
+    """mi355x_bz2_quoted_field_summary"""
+    _fields_ = [("count", ctypes.c_uint64), ("first_nl", ctypes.c_uint64), ("tail_start", ctypes.c_uint64),
+                ("tail_field_start", ctypes.c_uint64), ("tail_field_end", ctypes.c_uint64), ("head_delims", ctypes.c_uint32 * 2),
+                ("tail_delims", ctypes.c_uint32), ("has_delimiter", ctypes.c_uint32), ("tail_non_empty", ctypes.c_uint32),
+                ("head_quote_parity", ctypes.c_uint32), ("tail_in_quote", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 def field_chunk_bytes():
     """The bytes of a span that one GPU lane walks in field_spans (mi355x_bz2_field_chunk_bytes)."""
     return int(lib().mi355x_bz2_field_chunk_bytes())
@@ -644,6 +659,19 @@ def _field_summary_dict(s, heads):
             "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
             "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
             "tail_non_empty": bool(s.tail_non_empty)}
+
+
+def _quoted_field_summary_dict(s, heads, cap):
+    """_field_summary_dict for a QuotedFieldSummary; `heads` starts at the span's two lists of `cap` head positions."""
+    none = 2**64 - 1
+    return {"count": int(s.count), "has_delimiter": bool(s.has_delimiter),
+            "first_nl": None if s.first_nl == none else int(s.first_nl),
+            "head_positions": [[int(v) for v in heads[h * cap:h * cap + s.head_delims[h]]] for h in (0, 1)],
+            "head_quote_parity": bool(s.head_quote_parity),
+            "tail_start": int(s.tail_start), "tail_delims": int(s.tail_delims),
+            "tail_field_start": None if s.tail_field_start == none else int(s.tail_field_start),
+            "tail_field_end": None if s.tail_field_end == none else int(s.tail_field_end),
+            "tail_in_quote": bool(s.tail_in_quote), "tail_non_empty": bool(s.tail_non_empty)}
 
 
 class Decoder:
@@ -973,24 +1001,40 @@ class Decoder:
                 "tail_non_empty": bool(s.tail_non_empty), "count": int(s.count)} for s in summaries[:len(spans)]]
         return out, hashes[:room]
 
-    def field_spans(self, spans, field, delimiter=b"\t", newline=b"\n", capacity=None, room=None):
+    def field_spans(self, spans, field, delimiter=b"\t", newline=b"\n", capacity=None, room=None, *, quote=None):
         """k_field_chunks, k_field_link, k_scan_tiles, k_field_emit, k_field_sizes: the summary for field `field` of every
         span [(offset, size)] of the last batch's output, read as a stretch of lines that a line may enter and leave, and
         where the field lies in the lines the spans close -> (summaries, starts, sizes): one dict per span (count,
         has_delimiter, first_nl, head_positions, tail_start, tail_delims, tail_field_start, tail_field_end,
         tail_non_empty; None for a position the span does not reach) and two numpy arrays, uint64 and int64, of `room`
         values (default: capacity) that were all ones before the call and of which the call may write the first
-        `capacity` (None: as many as there are closed lines).  A start is an offset in the output."""
+        `capacity` (None: as many as there are closed lines).  A start is an offset in the output.
+
+        With quote (one byte, not the delimiter or the newline) mi355x_bz2_field_spans_quoted: k_field_chunks_quoted,
+        k_field_link_quoted, k_scan_tiles, k_field_emit_quoted, k_field_sizes, k_field_unquote.  starts and sizes are the
+        fields' contents; a summary is raw and has head_positions as a pair of lists, the span entered outside and inside
+        quotes, and head_quote_parity and tail_in_quote besides."""
         import numpy as np
         nl, dl, field = _field_query_arguments(newline, delimiter, field)
+        if quote is not None:
+            if not isinstance(quote, (bytes, bytearray, memoryview)):
+                raise ValueError("quote must be exactly one byte that differs from delimiter and newline")
+            quote = bytes(quote)
+            if len(quote) != 1 or quote[0] in (nl, dl):
+                raise ValueError("quote must be exactly one byte that differs from delimiter and newline")
+        lists = 1 if quote is None else 2
         spans = [(int(o), int(n)) for o, n in spans]
         arr = (ByteSpan * max(1, len(spans)))(*[ByteSpan(o, n) for o, n in spans])
-        summaries = (FieldSummary * max(1, len(spans)))()
-        heads = np.zeros(max(1, len(spans) * (field + 1)), dtype=np.uint64)
+        summaries = ((FieldSummary if quote is None else QuotedFieldSummary) * max(1, len(spans)))()
+        heads = np.zeros(max(1, len(spans) * lists * (field + 1)), dtype=np.uint64)
 
         def call(starts, sizes, capacity):
-            self._check(lib().mi355x_bz2_field_spans(self._h, arr, len(spans), nl, dl, field, summaries, heads.ctypes.data,
-                                                     starts, sizes, capacity))
+            if quote is None:
+                self._check(lib().mi355x_bz2_field_spans(self._h, arr, len(spans), nl, dl, field, summaries, heads.ctypes.data,
+                                                         starts, sizes, capacity))
+            else:
+                self._check(lib().mi355x_bz2_field_spans_quoted(self._h, arr, len(spans), nl, dl, quote[0], field, summaries,
+                                                                heads.ctypes.data, starts, sizes, capacity))
         if capacity is None:
             call(None, None, 0)
             capacity = sum(s.count for s in summaries[:len(spans)])
@@ -998,7 +1042,10 @@ class Decoder:
         starts = np.full(max(1, room), 2**64 - 1, dtype=np.uint64)
         sizes = np.full(max(1, room), -1 - 2**62, dtype=np.int64)
         _with_device_copies("field_spans", [starts, sizes], lambda *device: call(*device, capacity))
-        out = [_field_summary_dict(s, heads[i * (field + 1):]) for i, s in enumerate(summaries[:len(spans)])]
+        if quote is None:
+            out = [_field_summary_dict(s, heads[i * (field + 1):]) for i, s in enumerate(summaries[:len(spans)])]
+        else:
+            out = [_quoted_field_summary_dict(s, heads[2 * i * (field + 1):], field + 1) for i, s in enumerate(summaries[:len(spans)])]
         return out, starts[:room], sizes[:room]
 
     def gather_fields(self, starts, sizes, base=0, room=None, capacity=None, dst=True, fill=0xA5, misalign=0):

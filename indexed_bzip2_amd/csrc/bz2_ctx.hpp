@@ -16,6 +16,7 @@
 #include "bz2_fieldmatch.hpp"
 #include "bz2_fieldregex.hpp"
 #include "bz2_fieldnum.hpp"
+#include "bz2_fieldquote.hpp"
 #include "bz2_fields.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_regex.hpp"
@@ -77,6 +78,12 @@ int hashLinesOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, ui
  * dStarts[0, ...) and dSizes[0, ...), device memory, the starts as offsets in the file. */
 int fieldSpansOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
                       uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes, bz2gpu::FieldSummary* summary );
+
+/** fieldSpansOutput under a quote: mi355x_bz2_field_spans_quoted with `extent` as its one span.  dStarts and dSizes receive
+ * the fields' contents; *summary is raw and knows both entry hypotheses (bz2_fieldquote.hpp). */
+int fieldSpansQuotedOutput( mi355x_bz2_ctx* ctx, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                            uint8_t quote, uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes,
+                            bz2gpu::QuotedFieldSummary* summary );
 
 /** The reader's gather in one launch: mi355x_bz2_gather_fields over the n spans that fieldSpansOutput wrote for an extent
  * that begins at `srcOffset` of the last batch's output and at `fileOffset` of the decoded file.  When the total is known,

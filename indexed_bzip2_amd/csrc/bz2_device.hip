@@ -33,6 +33,7 @@
 #include "bz2_regex.hip.h"
 #include "bz2_linehash.hip.h"
 #include "bz2_fields.hip.h"
+#include "bz2_fieldquote.hip.h"
 #include "bz2_fieldhash.hip.h"
 #include "bz2_fieldnum.hip.h"
 #include "bz2_fieldmatch.hip.h"
@@ -48,6 +49,7 @@
 #include "bz2_regex.hpp"
 #include "bz2_linehash.hpp"
 #include "bz2_fields.hpp"
+#include "bz2_fieldquote.hpp"
 #include "bz2_fieldhash.hpp"
 #include "bz2_fieldnum.hpp"
 #include "bz2_fieldmatch.hpp"

@@ -749,6 +749,93 @@ fieldSpans( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spa
     return MI355X_BZ2_OK;
 }
 
+static_assert( sizeof( QuotedFieldSpanSummary ) == 64, "16-byte aligned in layQuotedFields" );
+
+/**
+ * mi355x_bz2_field_spans_quoted and the reader's launches: fieldSpans with the quoted twins of its kernels
+ * (bz2_fieldquote.hip.h), the head positions of both entry hypotheses, 2 * ( field + 1 ) per span, and k_field_unquote
+ * behind k_field_sizes, which turns the raw fields of the closed lines into their contents.
+ */
+int
+fieldSpansQuoted( mi355x_bz2_ctx* c, const char* what, const mi355x_bz2_byte_span* spans, const uint64_t* bases, uint32_t n, uint8_t nl,
+                  uint8_t dl, uint8_t quote, uint32_t field, mi355x_bz2_quoted_field_summary* summaries, uint64_t* headPositions,
+                  uint64_t skip, uint64_t capacity, uint64_t* dStarts, int64_t* dSizes )
+{
+    const std::scoped_lock lock( c->mutex );
+    const auto why = quotedFieldArgumentsError( nl, dl, quote, field );
+    if ( !why.empty() ) return refuse( c, what, why );
+    if ( const int status = refuseQuery( c, what, spans, n ) ) return status;
+    if ( n == 0 ) return MI355X_BZ2_OK;
+    const auto firstTile = firstTiles( spans, n, COUNT_TILE, 1 );
+    const uint64_t nTiles = firstTile.back(), slots = nTiles * FIELD_THREADS, cap = (uint64_t)field + 1;
+    if ( slots > 0x7FFFFFFFu ) return refuse( c, what, "too many spans" );
+    HIP_TRY( c, hipSetDevice( c->device ) );
+
+    const FieldLayout l = layQuotedFields( QUERY_SIZES, sizeof( QuotedFieldSpanSummary ), nTiles, n, field );
+    if ( const int status = growLineStaging( c, l.tileSummariesAt, l.bytes ) ) return status;
+    uint8_t* const h = c->hSearch.bytes;
+    uint8_t* const d = c->dSearch.bytes;
+    writeCountTiles( at<CountTile>( h, l.tilesAt ), spans, n, COUNT_TILE, 1 );
+    uint64_t bytesInSpans = 0;
+    for ( uint32_t s = 0; s < n; ++s ) {
+        const uint64_t base = bases != nullptr ? bases[s] : spans[s].offset;
+        at<FieldSpanTiles>( h, l.spansAt )[s] = { firstTile[s], firstTile[s + 1] - firstTile[s], base };
+        bytesInSpans += spans[s].size;
+    }
+    const auto* const dTiles = at<const CountTile>( d, l.tilesAt );
+    const auto* const dSpans = at<const FieldSpanTiles>( d, l.spansAt );
+    auto* const dSummaries = at<QuotedFieldSpanSummary>( d, l.resultsAt );
+    auto* const dTileSummaries = at<FieldTile>( d, l.tileSummariesAt );
+    auto* const dPlaces = at<uint64_t>( d, l.placesAt );
+    auto* const dPrefixes = at<uint32_t>( d, l.prefixesAt );
+    auto* const dCounts = at<uint32_t>( d, l.countsAt );
+    HIP_TRY( c, hipMemcpyAsync( d, h, l.resultsAt, hipMemcpyHostToDevice, c->stream ) );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_field_chunks_quoted, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, (uint32_t)quote, (uint32_t)cap, dPrefixes, dCounts, dTileSummaries );
+        HIP_TRY( c, hipGetLastError() );
+    }
+    hipLaunchKernelGGL( k_field_link_quoted, dim3( n ), dim3( FIELD_THREADS ), 0, c->stream, dSpans, dTileSummaries, dSummaries, field );
+    HIP_TRY( c, hipGetLastError() );
+    if ( nTiles > 0 ) {
+        hipLaunchKernelGGL( k_scan_tiles, dim3( 1 ), dim3( SCAN_THREADS ), 0, c->stream, dCounts, (uint32_t)slots, dPlaces );
+        HIP_TRY( c, hipGetLastError() );
+        hipLaunchKernelGGL( k_field_emit_quoted, dim3( (uint32_t)nTiles ), dim3( FIELD_THREADS ), 0, c->stream, dTiles, c->dOut,
+                            (uint32_t)nl, (uint32_t)dl, (uint32_t)quote, field, dSpans, dPrefixes, dTileSummaries, dPlaces, dSummaries,
+                            at<uint64_t>( d, l.headsAt ), skip, capacity, dStarts, dSizes );
+        HIP_TRY( c, hipGetLastError() );
+        /* a span closes at most one line per byte */
+        const uint64_t most = std::min( capacity, bytesInSpans );
+        if ( most > 0 ) {
+            const uint32_t blocks = (uint32_t)std::min<uint64_t>( ( most + FIELD_SIZES_THREADS - 1 ) / FIELD_SIZES_THREADS, FIELD_SIZES_BLOCKS );
+            hipLaunchKernelGGL( k_field_sizes, dim3( blocks ), dim3( FIELD_SIZES_THREADS ), 0, c->stream, dPlaces, dCounts, slots,
+                                skip, capacity, dStarts, dSizes );
+            HIP_TRY( c, hipGetLastError() );
+            static_assert( FIELD_UNQUOTE_THREADS == FIELD_SIZES_THREADS && FIELD_UNQUOTE_BLOCKS == FIELD_SIZES_BLOCKS );
+            hipLaunchKernelGGL( k_field_unquote, dim3( blocks ), dim3( FIELD_UNQUOTE_THREADS ), 0, c->stream, dTiles, nTiles, dSpans, n,
+                                dPlaces, dCounts, slots, c->dOut, (uint32_t)quote, skip, capacity, dStarts, dSizes );
+            HIP_TRY( c, hipGetLastError() );
+        }
+    }
+    HIP_TRY( c, hipMemcpyAsync( h + l.resultsAt, d + l.resultsAt, l.tileSummariesAt - l.resultsAt, hipMemcpyDeviceToHost, c->stream ) );
+    HIP_TRY( c, hipStreamSynchronize( c->stream ) );
+    for ( uint32_t i = 0; i < n; ++i ) {
+        const auto& from = at<const QuotedFieldSpanSummary>( h, l.resultsAt )[i];
+        summaries[i] = { from.count, from.firstNl, from.tailStart, from.tailFieldStart, from.tailFieldEnd,
+                         { from.headDelims[0], from.headDelims[1] }, from.tailDelims, ( from.info & FIELD_HAS_DELIMITER ) != 0 ? 1u : 0u,
+                         ( from.info & FIELD_TAIL_NON_EMPTY ) != 0 ? 1u : 0u, from.headQuoteParity,
+                         ( from.info & FIELD_TAIL_IN_QUOTE ) != 0 ? 1u : 0u, 0u };
+        if ( headPositions != nullptr ) {
+            for ( uint32_t hypothesis = 0; hypothesis < 2; ++hypothesis ) {
+                const uint64_t first = ( 2 * (uint64_t)i + hypothesis ) * cap;
+                std::copy_n( at<const uint64_t>( h, l.headsAt ) + first, std::min<uint64_t>( from.headDelims[hypothesis], cap ),
+                             headPositions + first );
+            }
+        }
+    }
+    return MI355X_BZ2_OK;
+}
+
 static_assert( sizeof( FieldColumnCheck ) == 24 && FIELDCOL_TILE == FIELD_COLUMN_TILE_BYTES, "the layout's check; the host's constant" );
 
 /**
@@ -1216,6 +1303,39 @@ mi355x::fieldSpansOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent,
 }
 
 int
+mi355x::fieldSpansQuotedOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
+                                uint8_t quote, uint32_t field, uint64_t skip, uint64_t take, uint64_t* dStarts, int64_t* dSizes,
+                                bz2gpu::QuotedFieldSummary* summary )
+{
+    if ( c == nullptr || summary == nullptr || field > FIELD_MAX || ( take > 0 && ( dStarts == nullptr || dSizes == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    mi355x_bz2_quoted_field_summary s{};
+    const size_t cap = (size_t)field + 1;
+    std::vector<uint64_t> heads( 2 * cap );
+    const int status = fieldSpansQuoted( c, "field_spans", &extent, &fileOffset, 1, nl, dl, quote, field, &s, heads.data(), skip, take,
+                                         dStarts, dSizes );
+    *summary = bz2gpu::emptyQuotedFieldSummary( field );
+    if ( status != MI355X_BZ2_OK ) return status;
+    summary->size = extent.size;
+    summary->hasDelimiter = s.has_delimiter != 0;
+    summary->tailNonEmpty = s.tail_non_empty != 0;
+    summary->count = s.count;
+    summary->firstNl = s.first_nl;
+    for ( size_t hypothesis = 0; hypothesis < 2; ++hypothesis ) {
+        const auto first = heads.begin() + hypothesis * cap;
+        summary->headPositions[hypothesis].assign( first, first + std::min<size_t>( s.head_delims[hypothesis], cap ) );
+    }
+    summary->headQuoteParity = s.head_quote_parity != 0;
+    summary->tailStart = s.tail_start;
+    summary->tailDelims = s.tail_delims;
+    summary->tailFieldStart = s.tail_field_start;
+    summary->tailFieldEnd = s.tail_field_end;
+    summary->tailInQuote = s.tail_in_quote != 0;
+    return status;
+}
+
+int
 mi355x::fieldHashesOutput( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span& extent, uint64_t fileOffset, uint8_t nl, uint8_t dl,
                            uint32_t field, uint64_t x, uint64_t skip, uint64_t take, uint64_t* dKeys, uint64_t* dStarts,
                            int64_t* dSizes, bz2gpu::FieldHashSummary* summary )
@@ -1420,6 +1540,19 @@ mi355x_bz2_field_spans( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, ui
     }
     return fieldSpans( c, "field_spans", spans, nullptr, n, nl, dl, field, summaries, headPositions, 0, capacity, startsDevice,
                        sizesDevice );
+}
+
+int
+mi355x_bz2_field_spans_quoted( mi355x_bz2_ctx* c, const mi355x_bz2_byte_span* spans, uint32_t n, uint8_t nl, uint8_t dl, uint8_t quote,
+                               uint32_t field, mi355x_bz2_quoted_field_summary* summaries, uint64_t* headPositions,
+                               uint64_t* startsDevice, int64_t* sizesDevice, uint64_t capacity )
+{
+    if ( c == nullptr || ( n > 0 && ( spans == nullptr || summaries == nullptr ) )
+         || ( capacity > 0 && ( startsDevice == nullptr || sizesDevice == nullptr ) ) ) {
+        return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    }
+    return fieldSpansQuoted( c, "field_spans_quoted", spans, nullptr, n, nl, dl, quote, field, summaries, headPositions, 0, capacity,
+                             startsDevice, sizesDevice );
 }
 
 int

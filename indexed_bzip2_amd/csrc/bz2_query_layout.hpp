@@ -157,6 +157,18 @@ layFields( const QuerySizes& s, uint64_t nTiles, uint64_t n, uint64_t field )
              r.add( slots * 4 ), r.size() };
 }
 
+/* field_spans_quoted for field `field`: field_spans' lists with a summary of `summaryBytes` and the head positions of both
+ * entry hypotheses, 2 * ( field + 1 ) per span */
+inline FieldLayout
+layQuotedFields( const QuerySizes& s, uint64_t summaryBytes, uint64_t nTiles, uint64_t n, uint64_t field )
+{
+    const uint64_t slots = nTiles * s.chunksPerTile;
+    Regions r;
+    return { r.add( nTiles * s.countTile ), r.add( n * s.fieldSpan, 16 ), r.add( n * summaryBytes, 16 ),
+             r.add( n * 2 * ( field + 1 ) * 8, 16 ), r.add( nTiles * s.fieldTile, 16 ), r.add( slots * 8, 16 ), r.add( slots * 4 ),
+             r.add( slots * 4 ), r.size() };
+}
+
 /* field_numbers for field `field`: field_spans' lists, and for k_field_texts where every span lies in the output and the
  * texts of 20 bytes it writes: [tiles][spans][extents, 16 bytes per span] up, [span summaries][head positions, field + 1 per
  * span][head texts, field + 1 per span][tail texts, one per span] down;

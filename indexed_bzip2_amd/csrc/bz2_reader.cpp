@@ -1281,6 +1281,33 @@ struct FieldSpanQuery
     static const bz2gpu::FieldSpan& tail( const bz2gpu::StitchedFields& stitched ) { return stitched.tail; }
 };
 
+/** FieldSpanQuery under a quote: the launches write contents, the stitcher's patches and tail are raw fields, which the
+ * reader trims (StreamReader::quotedContents). */
+struct QuotedFieldSpanQuery
+{
+    static constexpr size_t COLUMNS = 2;        /* starts, sizes (int64) */
+    using Stretch = bz2gpu::QuotedFieldStretch;
+    uint8_t nl, dl, quote;
+    uint32_t field;
+
+    static uint64_t& size( Stretch& stretch ) { return stretch.summary.size; }
+
+    uint64_t
+    pass( mi355x_bz2_ctx* ctx, const ColumnPiece& piece, const bz2gpu::ColumnPlace& place, const std::array<uint64_t*, COLUMNS>& to,
+          Stretch& stretch ) const
+    {
+        checkDevice( ctx, fieldSpansQuotedOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, quote, field, place.skip,
+                                                  place.take, to[0], reinterpret_cast<int64_t*>( to[1] ), &stretch.summary ) );
+        return stretch.summary.count;
+    }
+
+    template<typename Patch>
+    auto stitch( const std::vector<Stretch>& stretches, const Patch& patch ) const { return bz2gpu::stitchQuotedFields( stretches, field, patch ); }
+
+    static std::array<uint64_t, COLUMNS> words( const bz2gpu::FieldSpan& span ) { return { span.start, (uint64_t)span.size }; }
+    static const bz2gpu::FieldSpan& tail( const bz2gpu::StitchedFields& stitched ) { return stitched.tail; }
+};
+
 struct FieldHashQuery
 {
     static constexpr size_t COLUMNS = 3;        /* keys, starts, sizes (int64) */
@@ -2170,14 +2197,61 @@ public:
 
     /** mi355x_bz2_reader_field_spans: lineColumns with fieldSpansOutput and stitchFields, a column of starts and one of sizes. */
     void
-    fieldSpans( uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines )
+    fieldSpans( uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines,
+                std::optional<uint8_t> quote = std::nullopt )
     {
-        const auto refused = bz2gpu::fieldArgumentsError( nl, dl, field );
+        const auto refused = quote ? bz2gpu::quotedFieldArgumentsError( nl, dl, *quote, field ) : bz2gpu::fieldArgumentsError( nl, dl, field );
         if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, "field_spans: " + refused );
         const auto& index = lineIndex( nl );
         dropHeldLines();
         m_fields.reset();
-        m_fields = lineColumns( FieldSpanQuery{ nl, dl, field }, "field_spans", index, first, count, keepOnDevice, nLines );
+        if ( !quote ) {
+            m_fields = lineColumns( FieldSpanQuery{ nl, dl, field }, "field_spans", index, first, count, keepOnDevice, nLines );
+            return;
+        }
+        /* mi355x_bz2_reader_field_spans_quoted: the launches wrote contents; the patched lines are raw */
+        std::vector<std::pair<uint64_t, std::array<uint64_t, 2> > > patched;
+        auto held = lineColumns( QuotedFieldSpanQuery{ nl, dl, *quote, field }, "field_spans", index, first, count, keepOnDevice, nLines,
+                                 &patched );
+        std::vector<bz2gpu::FieldSpan> fields;
+        for ( const auto& [line, words] : patched ) fields.push_back( { words[0], (int64_t)words[1] } );
+        quotedContents( fields, *quote, "field_spans" );
+        std::string why;
+        for ( size_t i = 0; i < fields.size(); ++i ) {
+            const auto words = QuotedFieldSpanQuery::words( fields[i] );
+            if ( words == patched[i].second ) continue;
+            for ( size_t c = 0; c < words.size(); ++c ) {
+                if ( !hostToDevice( m_device, held.column<uint64_t>( c ) + patched[i].first, &words[c], sizeof( words[c] ), &why ) ) {
+                    fail( MI355X_BZ2_ERR_DEVICE, "field_spans: " + why );
+                }
+            }
+        }
+        m_fields = std::move( held );
+    }
+
+    /** The raw fields `fields` of the decoded file become their contents under `quote` (bz2_fieldquote.hpp): the first and
+     * last byte of each that has 2 bytes or more are fetched in one call of readRanges.  These are the lines the stitchers
+     * patch -- one per launch seam, and the tail -- so the blocks that hold them are the only ones decoded again. */
+    void
+    quotedContents( std::vector<bz2gpu::FieldSpan>& fields, uint8_t quote, const std::string& what )
+    {
+        std::vector<uint64_t> offsets, sizes;
+        for ( const auto& field : fields ) {
+            if ( field.size < 2 ) continue;
+            offsets.insert( offsets.end(), { field.start, field.start + (uint64_t)field.size - 1 } );
+            sizes.insert( sizes.end(), { 1, 1 } );
+        }
+        if ( offsets.empty() ) return;
+        std::vector<uint8_t> ends( offsets.size() );
+        std::vector<uint64_t> nRead( offsets.size() );
+        readRanges( offsets.data(), sizes.data(), offsets.size(), ends.data(), false, nRead.data() );
+        if ( nRead != sizes ) fail( MI355X_BZ2_ERR_LOGIC, what + ": a patched field lies behind the end of the file" );
+        size_t at = 0;
+        for ( auto& field : fields ) {
+            if ( field.size < 2 ) continue;
+            field = bz2gpu::quotedFieldContent( field, ends[at], ends[at + 1], quote );
+            at += 2;
+        }
     }
 
     /** mi355x_bz2_reader_take_field_spans. */
@@ -2199,7 +2273,7 @@ public:
      */
     void
     fieldColumns( uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t nFields, uint64_t first, uint64_t count, bool keepOnDevice,
-                  uint64_t* nLines, uint64_t* totals )
+                  uint64_t* nLines, uint64_t* totals, std::optional<uint8_t> quote = std::nullopt )
     {
         const std::string what = "field_columns";
         if ( nFields == 0 || nFields > bz2gpu::FIELD_COLUMNS_MAX ) {
@@ -2207,9 +2281,29 @@ public:
                                                    + ", not " + std::to_string( nFields ) );
         }
         for ( uint32_t f = 0; f < nFields; ++f ) {
-            const auto refused = bz2gpu::fieldArgumentsError( nl, dl, fields[f] );
+            const auto refused = quote ? bz2gpu::quotedFieldArgumentsError( nl, dl, *quote, fields[f] )
+                                       : bz2gpu::fieldArgumentsError( nl, dl, fields[f] );
             if ( !refused.empty() ) fail( MI355X_BZ2_ERR_INVALID_ARGUMENT, what + ": " + refused );
         }
+        /* mi355x_bz2_reader_field_columns_quoted: the same path with the quoted pass and stitcher, and the patched lines'
+         * raw fields trimmed (quotedContents) before anything is made of their sizes */
+        if ( quote ) {
+            const uint8_t q = *quote;
+            fieldColumnsBy( [nl, dl, q] ( uint32_t field ) { return QuotedFieldSpanQuery{ nl, dl, q, field }; }, quote, what, nl, fields,
+                            nFields, first, count, keepOnDevice, nLines, totals );
+        } else {
+            fieldColumnsBy( [nl, dl] ( uint32_t field ) { return FieldSpanQuery{ nl, dl, field }; }, quote, what, nl, fields, nFields, first,
+                            count, keepOnDevice, nLines, totals );
+        }
+    }
+
+    /** fieldColumns for the span query that queryOf( field ) names. */
+    template<typename QueryOf>
+    void
+    fieldColumnsBy( const QueryOf& queryOf, std::optional<uint8_t> quote, const std::string& what, uint8_t nl, const uint32_t* fields,
+                    uint32_t nFields, uint64_t first, uint64_t count, bool keepOnDevice, uint64_t* nLines, uint64_t* totals )
+    {
+        using Stretch = typename decltype( queryOf( 0u ) )::Stretch;
         const auto& index = lineIndex( nl );
         dropHeldLines();
         m_fieldColumns.reset();
@@ -2236,7 +2330,7 @@ public:
         /* a stretch's offsets are local to it and have one more entry than it has lines: stretch k's lie k entries further
          * on than its lines, so that no two stretches share one; the final offsets overwrite them */
         std::vector<Memory> starts( nFields );
-        std::vector<std::vector<bz2gpu::FieldStretch> > stretches( nFields, std::vector<bz2gpu::FieldStretch>( nStretches ) );
+        std::vector<std::vector<Stretch> > stretches( nFields, std::vector<Stretch>( nStretches ) );
         std::vector<std::vector<bz2gpu::ColumnStretch> > packed( nFields, std::vector<bz2gpu::ColumnStretch>( nStretches ) );
         for ( uint32_t f = 0; f < nFields; ++f ) {
             starts[f] = allocate( plan.count * sizeof( uint64_t ) );
@@ -2255,8 +2349,7 @@ public:
                 auto* const dStarts = static_cast<uint64_t*>( starts[f].get() ) + place.at;
                 auto* const dSizes = static_cast<int64_t*>( column.sizes.get() ) + place.at;
                 auto& summary = stretches[f][k].summary;
-                checkDevice( ctx, fieldSpansOutput( ctx, { piece.src, piece.size }, piece.fileOffset, nl, dl, fields[f], place.skip, place.take,
-                                                    dStarts, dSizes, &summary ) );
+                (void)queryOf( fields[f] ).pass( ctx, piece, place, { dStarts, reinterpret_cast<uint64_t*>( dSizes ) }, stretches[f][k] );
                 if ( summary.count != stretches[0][k].summary.count ) {
                     fail( MI355X_BZ2_ERR_LOGIC, what + ": the passes over one stretch count different lines" );
                 }
@@ -2277,10 +2370,10 @@ public:
         const uint64_t wantedClosed = plan.wantedClosed();
         uint64_t lines = 0;
         std::string why;
+        std::vector<std::vector<bz2gpu::ColumnPatch> > patchesOf( nFields );
         for ( uint32_t f = 0; f < nFields; ++f ) {
-            auto& column = held.columns[f];
-            std::vector<bz2gpu::ColumnPatch> patches;
-            const auto stitched = bz2gpu::stitchFields( stretches[f], fields[f], [&] ( uint64_t k, const bz2gpu::FieldSpan& field ) {
+            auto& patches = patchesOf[f];
+            const auto stitched = queryOf( fields[f] ).stitch( stretches[f], [&] ( uint64_t k, const bz2gpu::FieldSpan& field ) {
                 const uint64_t line = plan.firstClosed + k;
                 if ( line >= first && line - first < wantedClosed ) patches.push_back( { line - first, field.start, field.size } );
             } );
@@ -2288,6 +2381,26 @@ public:
             if ( plan.reachesEnd && stitched.hasTail ) patches.push_back( { n++, stitched.tail.start, stitched.tail.size } );
             if ( f > 0 && n != lines ) fail( MI355X_BZ2_ERR_LOGIC, what + ": the stitchers disagree about the lines" );
             lines = n;
+        }
+        if ( quote ) {
+            /* the raw fields of all columns' patched lines in one call */
+            std::vector<bz2gpu::FieldSpan> raw;
+            for ( const auto& patches : patchesOf ) {
+                for ( const auto& patch : patches ) raw.push_back( { patch.start, patch.size } );
+            }
+            quotedContents( raw, *quote, what );
+            size_t at = 0;
+            for ( auto& patches : patchesOf ) {
+                for ( auto& patch : patches ) {
+                    patch.start = raw[at].start;
+                    patch.size = raw[at++].size;
+                }
+            }
+        }
+        for ( uint32_t f = 0; f < nFields; ++f ) {
+            auto& column = held.columns[f];
+            const auto& patches = patchesOf[f];
+            const uint64_t n = lines;
             auto* const dSizes = static_cast<int64_t*>( column.sizes.get() );
             for ( const auto& patch : patches ) {
                 if ( !hostToDevice( m_device, dSizes + patch.line, &patch.size, sizeof( patch.size ), &why ) ) fail( MI355X_BZ2_ERR_DEVICE, what + ": " + why );
@@ -3689,6 +3802,30 @@ mi355x_bz2_reader_field_columns( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, c
     std::fill_n( totalBytes, std::min<uint32_t>( nFields, bz2gpu::FIELD_COLUMNS_MAX ), uint64_t( 0 ) );
     return guarded( r, [&] ( mi355x::StreamReader& reader ) {
         reader.fieldColumns( nl, dl, fields, nFields, first, count, keepOnDevice != 0, nLines, totalBytes );
+    } );
+}
+
+int
+mi355x_bz2_reader_field_spans_quoted( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, uint32_t field, uint64_t first, uint64_t count,
+                                      int keepOnDevice, uint64_t* nLines, uint8_t quote )
+{
+    if ( nLines == nullptr ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldSpans( nl, dl, field, first, count, keepOnDevice != 0, nLines, quote );
+    } );
+}
+
+int
+mi355x_bz2_reader_field_columns_quoted( mi355x_bz2_reader* r, uint8_t nl, uint8_t dl, const uint32_t* fields, uint32_t nFields,
+                                        uint64_t first, uint64_t count, int keepOnDevice, uint64_t* nLines, uint64_t* totalBytes,
+                                        uint8_t quote )
+{
+    if ( nLines == nullptr || totalBytes == nullptr || ( nFields > 0 && fields == nullptr ) ) return MI355X_BZ2_ERR_INVALID_ARGUMENT;
+    *nLines = 0;
+    std::fill_n( totalBytes, std::min<uint32_t>( nFields, bz2gpu::FIELD_COLUMNS_MAX ), uint64_t( 0 ) );
+    return guarded( r, [&] ( mi355x::StreamReader& reader ) {
+        reader.fieldColumns( nl, dl, fields, nFields, first, count, keepOnDevice != 0, nLines, totalBytes, quote );
     } );
 }
 

@@ -55,6 +55,8 @@ struct Options
     std::string equals, valueFile, matches;
     unsigned field{ 0 }, valueField{ 0 };
     uint8_t fieldDelimiter{ '\t' };
+    bool hasFieldQuote{ false };                /* --field-quote */
+    uint8_t fieldQuote{ '"' };
     std::string input, output, listCompressedPath, listOffsetsPath, pattern, patternFile, regex;
     bool hasOutput{ false };
     unsigned finderParallelism{ 1 }, decoderParallelism{ 0 }, bufferSize{ 0 };
@@ -135,6 +137,11 @@ printHelp()
         "                                fields, and the GPU packs each field's bytes. This is not a CSV parser.\n"
         "      --field-delimiter arg     With --cut-field: the byte between fields, as itself (',') or as \\t, \\0 or\n"
         "                                \\xHH; not the newline. (default: \\t)\n"
+        "      --field-quote arg         With --cut-field or --cut-fields: the byte that quotes fields, given as for\n"
+        "                                --field-delimiter; not the newline or the delimiter. A delimiter between two\n"
+        "                                quote bytes does not split the line, and a field enclosed in a pair of quote\n"
+        "                                bytes prints without the pair; doubled quotes inside stay doubled, and a\n"
+        "                                newline always ends the line. (default: no quoting)\n"
         "      --count-by-field arg      Print how often every value of field N (as for --cut-field) occurs, one line\n"
         "                                'count<TAB>value' per distinct value, the most frequent first and values of\n"
         "                                equal count in the order of their first occurrence (cut -f | sort | uniq -c |\n"
@@ -453,6 +460,13 @@ parseArguments( int argc, char** argv, Options& o )
                 }
                 o.hasFieldDelimiter = true;
             }
+            else if ( name == "field-quote" ) {
+                if ( !need( value ) || !parseByte( value, o.fieldQuote ) || o.fieldQuote == '\n' ) {
+                    std::cerr << "Bad value for --field-quote\n";
+                    return 1;
+                }
+                o.hasFieldQuote = true;
+            }
             else if ( name == "grep-file" ) { if ( !need( o.patternFile ) ) return 1; o.grepFile = true; }
             else if ( name == "count-matches-file" ) { if ( !need( o.patternFile ) ) return 1; o.countMatchesFile = true; }
             else if ( name == "line-number" ) o.lineNumber = true;
@@ -734,6 +748,14 @@ main( int argc, char** argv )
         std::cerr << "Option '--field-delimiter' needs '--cut-field'\n";
         return 1;
     }
+    if ( o.hasFieldQuote && ( ( !o.cutField && o.cutFields.empty() ) || o.countByField || o.sumByField || o.whereField ) ) {
+        std::cerr << "Option '--field-quote' needs '--cut-field' or '--cut-fields' and no other field option\n";
+        return 1;
+    }
+    if ( o.hasFieldQuote && o.fieldQuote == o.fieldDelimiter ) {
+        std::cerr << "Bad value for --field-quote\n";
+        return 1;
+    }
     const uint32_t searchFlags = o.ignoreCase ? MI355X_BZ2_SEARCH_IGNORE_CASE : 0u;
     if ( o.version ) {
         std::cout << "ibzip2-mi355x, CLI to the MI355X bzip2 block decoder (C ABI version " << mi355x_bz2_abi_version()
@@ -852,7 +874,8 @@ main( int argc, char** argv )
         std::string bytes, text;
         for ( uint64_t first = 0; rc == MI355X_BZ2_OK; first += WINDOW ) {
             uint64_t n = 0;
-            rc = mi355x_bz2_reader_field_spans( reader, '\n', o.fieldDelimiter, o.field, first, WINDOW, 0, &n );
+            rc = o.hasFieldQuote ? mi355x_bz2_reader_field_spans_quoted( reader, '\n', o.fieldDelimiter, o.field, first, WINDOW, 0, &n, o.fieldQuote )
+                                 : mi355x_bz2_reader_field_spans( reader, '\n', o.fieldDelimiter, o.field, first, WINDOW, 0, &n );
             if ( rc != MI355X_BZ2_OK || n == 0 ) break;
             starts.resize( n );
             sizes.resize( n );
@@ -914,8 +937,10 @@ main( int argc, char** argv )
         std::string text;
         for ( uint64_t first = 0; rc == MI355X_BZ2_OK; first += WINDOW ) {
             uint64_t n = 0;
-            rc = mi355x_bz2_reader_field_columns( reader, '\n', o.fieldDelimiter, o.cutFields.data(), (uint32_t)nFields, first, WINDOW, 0, &n,
-                                                  totals.data() );
+            rc = o.hasFieldQuote ? mi355x_bz2_reader_field_columns_quoted( reader, '\n', o.fieldDelimiter, o.cutFields.data(), (uint32_t)nFields,
+                                                                           first, WINDOW, 0, &n, totals.data(), o.fieldQuote )
+                                 : mi355x_bz2_reader_field_columns( reader, '\n', o.fieldDelimiter, o.cutFields.data(), (uint32_t)nFields,
+                                                                    first, WINDOW, 0, &n, totals.data() );
             if ( rc != MI355X_BZ2_OK || n == 0 ) break;
             uint64_t total = 0;
             for ( size_t f = 0; f < nFields && rc == MI355X_BZ2_OK; ++f ) {

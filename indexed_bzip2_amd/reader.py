@@ -685,31 +685,57 @@ class _IndexedBzip2FileParallel:
         (count,), _ = self._u64([2**64 - 1 if count is None else count], "count")
         return nl, delimiter[0], field, first, count
 
-    def _field_spans(self, field, first, count, delimiter, newline, tensors):
-        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
-        L = N.lib()
-        return tuple(self._columns(lambda keep, n: L.mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, keep, n),
-                                   lambda *to: L.mi355x_bz2_reader_take_field_spans(self._h, *to), ("uint64", "int64"), tensors))
+    # -- quote=: None, or one byte that differs from `delimiter` and `newline`.  Within a line every quote byte toggles
+    # "inside quotes" and only the delimiters outside part the line, so a doubled quote inside a quoted field needs no rule
+    # of its own and an unbalanced quote makes the rest of the line one field.  `newline` ALWAYS ends the line and the quote
+    # state: a quoted field cannot hold a newline, and lines keep their numbers.  The field reported is the CONTENT: a raw
+    # field of 2 bytes or more whose first and last bytes are both the quote loses these two; `""` is the empty field, a
+    # lone `"` stays.  Doubled quotes inside stay doubled -- spans of the file come back, no byte is rewritten -- and there
+    # are no backslash escapes.  field_spans, read_fields, read_columns and their tensor forms take it
+    @staticmethod
+    def _quote_argument(quote, nl, dl):
+        if quote is None:
+            return None
+        if not isinstance(quote, (bytes, bytearray, memoryview)) or len(bytes(quote)) != 1:
+            raise ValueError("quote must be None or exactly one byte, e.g. b'\"'")
+        quote = bytes(quote)
+        if quote[0] == nl or quote[0] == dl:
+            raise ValueError("quote must differ from delimiter and newline")
+        return quote[0]
 
-    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def _field_spans(self, field, first, count, delimiter, newline, tensors, quote=None):
+        nl, dl, field, first, count = self._field_arguments(field, first, count, delimiter, newline)
+        q = self._quote_argument(quote, nl, dl)
+        L = N.lib()
+        if q is None:
+            launch = lambda keep, n: L.mi355x_bz2_reader_field_spans(self._h, nl, dl, field, first, count, keep, n)
+        else:
+            launch = lambda keep, n: L.mi355x_bz2_reader_field_spans_quoted(self._h, nl, dl, field, first, count, keep, n, q)
+        return tuple(self._columns(launch, lambda *to: L.mi355x_bz2_reader_take_field_spans(self._h, *to), ("uint64", "int64"), tensors))
+
+    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """Where field `field` (0-based, at most 1023) lies in lines [first, first + count) (count None: to the last
         line; clipped there) -> (starts numpy uint64, sizes numpy int64), one pair per line: data[start:start + size] ==
         content.split(delimiter)[field].  A line with fewer fields has size -1 and start = the offset at which its
         content ends.  No quoting, no escaping: `cut -f`, not a CSV parser.  Only the blocks that hold those lines are
         decoded, each once; the spans are computed on the GPU and 16 bytes per line come back.  Builds the line index
-        first if the reader does not hold one for `newline`.  Positionless."""
-        return self._field_spans(field, first, count, delimiter, newline, False)
+        first if the reader does not hold one for `newline`.  Positionless.
 
-    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+        With quote=b'"' (one byte, not `delimiter` or `newline`) delimiters inside quotes do not part the line and the
+        span is the field's content, without an enclosing pair of quotes; doubled quotes inside stay doubled, and
+        `newline` still ends every line: a quoted field cannot hold one."""
+        return self._field_spans(field, first, count, delimiter, newline, False, quote)
+
+    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """field_spans as two torch.int64 tensors (starts, sizes) on the reader's device; nothing passes through the
         host.  A start is below 2^63, so int64 holds it as it is."""
-        return self._field_spans(field, first, count, delimiter, newline, True)
+        return self._field_spans(field, first, count, delimiter, newline, True, quote)
 
-    def _read_fields(self, field, first, count, delimiter, newline, make):
+    def _read_fields(self, field, first, count, delimiter, newline, make, quote=None):
         """field_spans, then the existing read_ranges over the present fields; make(total) -> (destination, pointer,
         is_device).  Returns (sizes numpy int64, bounds numpy int64 of n + 1, destination)."""
         import numpy as np
-        starts, sizes = self.field_spans(field, first, count, delimiter, newline)
+        starts, sizes = self.field_spans(field, first, count, delimiter, newline, quote=quote)
         n = len(starts)
         lengths = np.maximum(sizes, 0).astype(np.uint64)
         bounds = np.zeros(n + 1, dtype=np.int64)
@@ -722,27 +748,28 @@ class _IndexedBzip2FileParallel:
                                                                n, dst, device, got.ctypes.data_as(u64p)))
         return sizes, bounds, out
 
-    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """Field `field` of lines [first, first + count) -> a list with one bytes object per line, content.split(
         delimiter)[field], and None where the line has no such field.  No quoting, no escaping: `cut -f`, not a CSV
         parser.  field_spans finds the fields on the GPU; then the blocks that hold them are decoded a second time and
         only the fields' bytes are copied out.  Positionless.  read_columns gives the same, for several fields, from one
-        decode."""
+        decode.  quote= as for field_spans: the fields' contents, their doubled quotes kept."""
         def make(total):
             out = bytearray(total)
             return out, ((ctypes.c_char * total).from_buffer(out) if total else None), 0
-        sizes, bounds, out = self._read_fields(field, first, count, delimiter, newline, make)
+        sizes, bounds, out = self._read_fields(field, first, count, delimiter, newline, make, quote)
         data = bytes(out)
         return [data[bounds[i]:bounds[i + 1]] if sizes[i] >= 0 else None for i in range(len(sizes))]
 
-    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """read_fields into ONE contiguous torch.uint8 tensor on the reader's device -> (data, offsets) as
         read_line_ranges_to_tensor shapes them: line i's field is ``data[offsets[i]:offsets[i + 1]]``, `offsets` an
         int64 CPU tensor of n + 1 boundaries; a missing field has size 0 (field_spans tells it from an empty one).  The
         fields' bytes never pass through the host.  read_columns_to_tensor gives the bytes from one decode, with offsets
         and sizes on the device."""
         import torch
-        self._field_arguments(field, first, count, delimiter, newline)      # refused before the GPU is touched
+        nl, dl, _, _, _ = self._field_arguments(field, first, count, delimiter, newline)    # refused before the GPU is touched
+        self._quote_argument(quote, nl, dl)
         dev = self._device_index()
 
         def make(total):
@@ -751,11 +778,11 @@ class _IndexedBzip2FileParallel:
                 # the new tensor's memory may still be in use by work queued on torch's stream: the gather comes after it
                 torch.cuda.current_stream(data.device).synchronize()
             return data, (ctypes.c_void_p(data.data_ptr()) if total else None), 1
-        _, bounds, data = self._read_fields(field, first, count, delimiter, newline, make)
+        _, bounds, data = self._read_fields(field, first, count, delimiter, newline, make, quote)
         return data, torch.from_numpy(bounds)
 
     # -- field columns: the bytes of several fields of every line from ONE decode, each column packed on the GPU
-    def _column_arguments(self, fields, first, count, delimiter, newline):
+    def _column_arguments(self, fields, first, count, delimiter, newline, quote=None):
         if isinstance(fields, (str, bytes, bytearray)):
             raise TypeError("fields must be a sequence of field numbers")
         fields = list(fields)
@@ -766,19 +793,23 @@ class _IndexedBzip2FileParallel:
         for field in fields:
             nl, dl, field, first_, count_ = self._field_arguments(field, first, count, delimiter, newline)
             checked.append(field)
-        return nl, dl, checked, first_, count_
+        return nl, dl, checked, first_, count_, self._quote_argument(quote, nl, dl)
 
-    def _field_columns(self, fields, first, count, delimiter, newline):
+    def _field_columns(self, fields, first, count, delimiter, newline, quote=None):
         """mi355x_bz2_reader_field_columns -> (the number of lines, the bytes of every column); the columns are held."""
-        nl, dl, fields, first, count = self._column_arguments(fields, first, count, delimiter, newline)
+        nl, dl, fields, first, count, q = self._column_arguments(fields, first, count, delimiter, newline, quote)
         numbers = (ctypes.c_uint32 * len(fields))(*fields)
         n = ctypes.c_uint64()
         totals = (ctypes.c_uint64 * len(fields))()
-        self._check(N.lib().mi355x_bz2_reader_field_columns(self._h, nl, dl, numbers, len(fields), first, count, 1, ctypes.byref(n),
-                                                            totals))
+        if q is None:
+            self._check(N.lib().mi355x_bz2_reader_field_columns(self._h, nl, dl, numbers, len(fields), first, count, 1, ctypes.byref(n),
+                                                                totals))
+        else:
+            self._check(N.lib().mi355x_bz2_reader_field_columns_quoted(self._h, nl, dl, numbers, len(fields), first, count, 1,
+                                                                       ctypes.byref(n), totals, q))
         return n.value, list(totals)
 
-    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """The fields `fields` (1 to 16 field numbers, each at most 1023; one may be named twice) of lines [first, first +
         count) -> a list with one (data, offsets, sizes) per entry of `fields`, all on the reader's device: `data` a
         torch.uint8 tensor of the field's bytes packed in line order, `offsets` torch.int64 of n + 1 boundaries and `sizes`
@@ -786,11 +817,11 @@ class _IndexedBzip2FileParallel:
         an empty slice where line i has fewer fields.  Every needed block is decoded once, whatever the number of fields
         -- but for the few blocks that hold a line crossing a launch seam --, the GPU copies the fields out of the launch
         that found them, and nothing per line passes through the host.  No quoting, no escaping: `cut -f1,4,6`, not a
-        CSV parser.  Positionless."""
+        CSV parser.  Positionless.  quote= as for field_spans: the fields' contents, their doubled quotes kept."""
         import torch
-        self._column_arguments(fields, first, count, delimiter, newline)    # refused before the GPU is touched
+        self._column_arguments(fields, first, count, delimiter, newline, quote)    # refused before the GPU is touched
         dev = self._device_index()
-        n, totals = self._field_columns(fields, first, count, delimiter, newline)
+        n, totals = self._field_columns(fields, first, count, delimiter, newline, quote)
         out = []
         for column, total in enumerate(totals):
             data = torch.empty(total, dtype=torch.uint8, device=f"cuda:{dev}")
@@ -804,11 +835,11 @@ class _IndexedBzip2FileParallel:
             out.append((data, offsets, sizes))
         return out
 
-    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """read_columns_to_tensor on the host -> a list with, per entry of `fields`, a list with one bytes object per line
         and None where the line has no such field: [read_fields(j, ...) for j in fields], from one decode."""
         import numpy as np
-        n, totals = self._field_columns(fields, first, count, delimiter, newline)
+        n, totals = self._field_columns(fields, first, count, delimiter, newline, quote)
         out = []
         for column, total in enumerate(totals):
             data = bytearray(total)
@@ -1346,13 +1377,13 @@ class IndexedBzip2File(io.BufferedReader):
         """See _IndexedBzip2FileParallel.first_occurrences."""
         return self._open_reader().first_occurrences(newline, seed)
 
-    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def field_spans(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.field_spans."""
-        return self._open_reader().field_spans(field, first, count, delimiter, newline)
+        return self._open_reader().field_spans(field, first, count, delimiter, newline, quote=quote)
 
-    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def field_spans_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.field_spans_to_tensor."""
-        return self._open_reader().field_spans_to_tensor(field, first, count, delimiter, newline)
+        return self._open_reader().field_spans_to_tensor(field, first, count, delimiter, newline, quote=quote)
 
     def field_hashes(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", seed=0):
         """See _IndexedBzip2FileParallel.field_hashes."""
@@ -1421,21 +1452,21 @@ class IndexedBzip2File(io.BufferedReader):
         """See _IndexedBzip2FileParallel.value_sums."""
         return self._open_reader().value_sums(key_field, value_field, limit, first, count, delimiter, newline, seed)
 
-    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_fields(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.read_fields."""
-        return self._open_reader().read_fields(field, first, count, delimiter, newline)
+        return self._open_reader().read_fields(field, first, count, delimiter, newline, quote=quote)
 
-    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_fields_to_tensor(self, field, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.read_fields_to_tensor."""
-        return self._open_reader().read_fields_to_tensor(field, first, count, delimiter, newline)
+        return self._open_reader().read_fields_to_tensor(field, first, count, delimiter, newline, quote=quote)
 
-    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_columns(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.read_columns."""
-        return self._open_reader().read_columns(fields, first, count, delimiter, newline)
+        return self._open_reader().read_columns(fields, first, count, delimiter, newline, quote=quote)
 
-    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n"):
+    def read_columns_to_tensor(self, fields, first=0, count=None, delimiter=b"\t", newline=b"\n", *, quote=None):
         """See _IndexedBzip2FileParallel.read_columns_to_tensor."""
-        return self._open_reader().read_columns_to_tensor(fields, first, count, delimiter, newline)
+        return self._open_reader().read_columns_to_tensor(fields, first, count, delimiter, newline, quote=quote)
 
     def count_matches_each(self, patterns, start=0, end=None, *, ignore_case=False):
         """See _IndexedBzip2FileParallel.count_matches_each."""
